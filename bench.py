@@ -6,12 +6,17 @@ one fused launch that writes the four defect residuals and every x-dependent Jac
 each vector (1 eval = the hot-path share of one objfunc + one sens call).  Inputs are
 resident in HBM when the timed region starts; outputs stay in HBM.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps of `value` (one timed region) and prints the line.  --full adds
+everything else: the cold and allocator-placement timed regions, the informational legs, `other_configs` and the
+`cpu_baseline` leg with its oracle spot check.  --dump-outputs DIR writes what the last timed step computed (a
+fixed, seeded sample of the batch's rows) as DIR/*.npy, float64.
 
 Multi-GPU: the path shards by independent decision vectors (replicas of the static problem, B
 vectors per rank, no data-path collective) -> "scaling": "weak".  Rank 0 prints ONE JSON line, with a per-rank `roofline`
-and the `cpu_baseline` leg (rank 0's host cores) at every N.
+and, under --full, the `cpu_baseline` leg (rank 0's host cores) at every N.
 """
 import argparse
 import json
@@ -64,6 +69,36 @@ def launch_ranks(n_gpus, argv, dry=False):
         raise SystemExit("bench.py --gpus %d: the child run reported n_gpus = %r" % (n_gpus, line.get("n_gpus")))
     print(lines[0])
     return 0
+
+
+def synthetic_batch(x0, M, B, seed):
+    """problem.synthetic_batch bit for bit, its rows drawn by up to 16 threads (numpy's fills and ufuncs release the GIL):
+    one thread takes 10 s and more at B = 65536, all of it outside the timed steps."""
+    from concurrent.futures import ThreadPoolExecutor
+    x0 = np.asarray(x0, dtype=np.float64)
+    X = np.tile(x0, (B, 1))
+
+    def rows(lo, hi):
+        for b in range(max(lo, 1), hi):
+            z = np.random.default_rng(seed + b).standard_normal(x0.size)
+            z[M:4 * M] = np.abs(z[M:4 * M])
+            X[b] *= 1.0 + 1e-6 * z
+    nt = max(1, min(16, len(os.sched_getaffinity(0)), B // 256))
+    chunk = -(-B // nt)
+    with ThreadPoolExecutor(nt) as ex:
+        list(ex.map(lambda i: rows(i * chunk, min(B, (i + 1) * chunk)), range(nt)))
+    return X
+
+
+DUMP_BYTES = 48 << 20     # --dump-outputs: what the sampled rows may take in all (the contract allows 64 MB)
+DUMP_SEED = 20261016
+
+
+def dump_rows(B, bytes_per_row):
+    """the fixed, seeded sample of batch rows --dump-outputs writes: row 0 (= x0) and as many others as DUMP_BYTES holds"""
+    n = int(max(1, min(B, DUMP_BYTES // max(bytes_per_row, 1))))
+    rest = np.sort(np.random.default_rng(DUMP_SEED).choice(B - 1, n - 1, replace=False)) + 1 if n > 1 else np.empty(0, np.int64)
+    return np.concatenate([[0], rest]).astype(np.int64)
 
 
 def cpu_model():
@@ -201,9 +236,18 @@ def main():
                     help="skip the short legs of the other BASELINE.json configurations (key `other_configs`; --no-extras skips them too)")
     ap.add_argument("--no-extras", action="store_true", help="skip the informational full-COO and B=1 legs")
     ap.add_argument("--dry-launcher", action="store_true", help="print the N-rank launcher command and exit (no GPU touched)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the cold and allocator-placement timed regions, the informational legs, other_configs and cpu_baseline "
+                         "(--no-extras / --no-other-configs / --no-cpu-baseline leave parts out); a plain run times `value` alone")
+    ap.add_argument("--dump-outputs", default=None, dest="dump_outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed to DIR/*.npy (float64): residual.npy [n][residual_rows] "
+                         "and jacobian_values.npy [n][jacobian_values_per_eval] (the compact x-dependent values) of a fixed, seeded "
+                         "sample of n batch rows (sample_rows.npy; row 0 = the unperturbed x0), rank 0's batch")
     a = ap.parse_args()
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if a.steps < 1:
+        raise SystemExit("--steps must be >= 1")
 
     # ---- N ranks: before torch is imported and before anything touches HIP ----
     world_env = os.environ.get("WORLD_SIZE")
@@ -250,7 +294,7 @@ def main():
 
     x0 = pack_x(xdict)
     shard = a.mode == "phase-shard" and world > 1
-    X = problem.synthetic_batch(x0, E.M, B, seed=20260313 + (0 if shard else rank * B))
+    X = synthetic_batch(x0, E.M, B, seed=20260313 + (0 if shard else rank * B))
     stream = torch.cuda.current_stream().cuda_stream  # the engine launches on torch's current stream
     dX = torch.from_numpy(X).to(dev)
     # [r6] Three timed regions: from an idle GPU (`value_cold`), steady state on the buffers as the allocator places them
@@ -343,29 +387,34 @@ def main():
         dist.all_reduce(we, op=dist.ReduceOp.MAX)
         w_extra = int(we.item())
     untimed(w_extra)
-    elapsed, kern_ms = timed(K)
-    all_ms += kern_ms * K
-    all_n += K
+    nan = float("nan")
+
+    def region():
+        """W warm-up steps, then the K timed steps -> (wall seconds, HIP-event ms per step)"""
+        nonlocal all_ms, all_n
+        untimed(W)
+        e, k = timed(K)
+        all_ms += k * K
+        all_n += K
+        return e, k
+    # A plain run times ONE region of K steps, `value`'s; --full times the cold and the allocator-placement regions too (NaN = not timed).
+    elapsed_cold, kern_ms_cold = nan, nan
+    if a.full:
+        elapsed_cold, kern_ms_cold = timed(K)
+        all_ms += kern_ms_cold * K
+        all_n += K
     # (2) `value`: the same K steps after ~0.25 s of untimed launches (same count on every rank) and W warm-up steps again -- the
     # steady state a batch workload lives in.
     n_settle = 0 if a.settle_ms <= 0 else min(5000, max(4, int(a.settle_ms / 1.0 * 16384 / B)))
     untimed(n_settle)
-    untimed(W)
-    elapsed_settled, kern_ms_settled = timed(K)
-    all_ms += kern_ms_settled * K
-    all_n += K
     # [r6] `value` is the STEADY-STATE figure (the second timed region), `value_cold` the first one.  The K timed steps right behind W
     # warm-up steps from an idle GPU sit inside the chip's start-up power / clock transient (19.1 against 20.8 M evals/s on one box);
     # rounds 4-5 reported that region as `value` -- and in round 5 some 300 placement launches had run in front of it, which made it
     # the steady-state figure in all but name (VERDICT r5 item 4).  Now the line says what it is: `warmup` = W as asked for,
     # `warmup_steps_run` = every launch in front of the timed region of `value`, `value_cold` = the contract read literally.
-    warm_total = W + w_probe + w_extra + K + n_settle + W
-    elapsed_cold, kern_ms_cold = elapsed, kern_ms
-    elapsed, kern_ms = elapsed_settled, kern_ms_settled
-    status = E.sync(stream)
     # [r6] buffer placement, after the contract's timed regions: the same K steps on the fastest of `--placement-tries` candidate
     # placements of jvar and of (x, res), W warm-up steps in front (informational; every rank does the same)
-    elapsed_placed, kern_ms_placed = float("nan"), float("nan")
+    elapsed_placed, kern_ms_placed = nan, nan
     do_place = a.placement_tries > 1 and not shard
     if do_place:
         # free memory first (VERDICT r5 item 9): a rank that cannot hold a second set of buffers beside the first makes EVERY rank skip
@@ -378,6 +427,10 @@ def main():
         if int(ok_t.item()) == 0:
             do_place = False
             placement = {"error": "placement skipped: %.1f GB free on rank %d, %.1f GB wanted for the candidate buffers" % (free_b / 1e9, rank, need / 1e9)}
+    # the allocator's placement: timed here under --full, and in a plain run when it is `value` (no placement)
+    elapsed_default, kern_ms_default = nan, nan
+    if a.full or not do_place:
+        elapsed_default, kern_ms_default = region()
     if do_place:
         from gelato_amd.placement import place_batch_buffers
         placed_ok = 1
@@ -395,38 +448,66 @@ def main():
             dist.all_reduce(ok_t, op=dist.ReduceOp.MIN)
             placed_ok = int(ok_t.item())
         if placed_ok:
-            untimed(W)
-            elapsed_placed, kern_ms_placed = timed(K)
-            all_ms += kern_ms_placed * K
-            all_n += K
-        elif placement is not None and "error" not in placement:
-            placement["error"] = "another rank could not place its buffers: the placed steps were not timed"
+            elapsed_placed, kern_ms_placed = region()
+        else:
+            if placement is not None and "error" not in placement:
+                placement["error"] = "another rank could not place its buffers: the placed steps were not timed"
+            if elapsed_default != elapsed_default:      # a plain run: the allocator's placement is `value` after all
+                elapsed_default, kern_ms_default = region()
+    default_timed = elapsed_default == elapsed_default
+    status = E.sync(stream)
     djv_ptr = 0 if djv is None else djv.data_ptr()
 
-    tmax = torch.tensor([elapsed, elapsed_cold, elapsed_placed], dtype=torch.float64, device=dev)
+    tmax = torch.tensor([elapsed_default, elapsed_cold, elapsed_placed], dtype=torch.float64, device=dev)
     if use_dist:
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
     T, T_cold, T_placed = float(tmax[0].item()), float(tmax[1].item()), float(tmax[2].item())
+    kern_ms = kern_ms_default
     # [r6] WHICH region is `value`.  On the allocator's placement the steady-state figure is one of two levels by the physical pages
     # the process happened to get (20.4 / 20.5 / 21.0 / 21.9 M evals/s in four calls, profiles/r06/boxes.json) -- and over N ranks the
     # slowest rank's level, i.e. almost always the slow one: a coin in the headline and a false scaling loss.  On placed buffers it
     # is 21.7-21.8 M every time.  So `value` is the PLACED steady-state figure when the placement ran (the K timed steps behind
     # `warmup_steps_run` launches, every one of them counted), `value_default_placement` the allocator's, `value_cold` the literal
     # W + K region from an idle GPU: all three in the line.  --placement-tries 1: `value` = `value_default_placement`.
-    T_default, kern_ms_default = T, kern_ms
+    T_default = T
     placed_used = T_placed == T_placed      # not NaN: every rank placed its buffers and timed the K steps on them
     if placed_used:
         T, kern_ms = T_placed, kern_ms_placed
-        warm_total += K + (placement.get("all_launches", 0) if isinstance(placement, dict) else 0) + W
+    warm_detail = {"cold_region_warmup": W + w_probe + w_extra, "cold_region_timed": K if a.full else 0, "settling_launches": n_settle,
+                   "default_placement_region": ((W + K) if default_timed else 0) if placed_used else W,
+                   "placement_candidate_launches": (placement.get("all_launches", 0) if (placed_used and isinstance(placement, dict)) else 0),
+                   "warmup_before_value": W}
+    warm_total = sum(warm_detail.values())
 
     if rank != 0:
         if use_dist:
             dist.destroy_process_group()
         return
 
+    dumped = None
+    if a.dump_outputs:
+        # what the last timed step wrote (nothing has launched since): a fixed, seeded sample of the batch's rows
+        rows = dump_rows(B, 8 * (E.nres + (0 if a.residual_only else E.V)))
+        ri = torch.from_numpy(rows).to(dev)
+        if shard:
+            r_t, j_t = shards.gather(dout[:, ri])
+            r_t = r_t.cpu().numpy()
+            j_t = None if a.residual_only else j_t.cpu().numpy()
+        else:
+            r_t = dres.index_select(0, ri).cpu().numpy()
+            j_t = None if djv is None else djv.index_select(0, ri).cpu().numpy()
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        arrays = {"residual": r_t, "sample_rows": rows.astype(np.float64)}
+        if j_t is not None:
+            arrays["jacobian_values"] = j_t
+        for name, arr in arrays.items():
+            np.save(os.path.join(a.dump_outputs, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
+        dumped = {"dir": os.path.abspath(a.dump_outputs), "files": sorted(n + ".npy" for n in arrays), "rows": int(rows.size), "of": B,
+                  "bytes": int(sum(v.size for v in arrays.values()) * 8)}
+
     # element 0 of what was just timed, kept for the oracle check inside the cpu_baseline leg
     gpu_first = None
-    if not a.no_cpu_baseline:
+    if a.full and not a.no_cpu_baseline:
         if shard:
             r_t, j_t = shards.gather(dout[:, :1])
             gpu_first = (r_t[0].cpu().numpy(), E.expand(j_t[0].cpu().numpy()))
@@ -473,24 +554,27 @@ def main():
     kname = "gel::eval_kernel<%s, %s, %s, %s>" % tuple("true" if v else "false" for v in (info[0], info[1], info[2], info[4]))
     if shard:   # a unit range always runs the split (latency) form, one decision vector per wavefront
         kname = "gel::eval_kernel<true, %s, true, false>" % ("true" if info[1] else "false")
+
+    def measured(v):
+        """a figure of a region this run did not time (NaN) -> null"""
+        return None if v != v else v
+
     out = {
         "metric": "residual+Jacobian evals/sec (and ms/eval), 6-phase x 64-node LGR mesh",
         "value": evals / T, "unit": "evals/s", "n_gpus": world, "steps": K, "warmup": W,
         "world_size": world, "collective_backend": ("nccl (RCCL over xGMI)" if use_dist else None),
         "warmup_steps_run": warm_total,
-        "warmup_steps_run_detail": {"cold_region_warmup": W + w_probe + w_extra, "cold_region_timed": K, "settling_launches": n_settle,
-                                    "default_placement_region": (W + K) if placed_used else W,
-                                    "placement_candidate_launches": (placement.get("all_launches", 0) if (placed_used and isinstance(placement, dict)) else 0),
-                                    "warmup_before_value": W},
+        "warmup_steps_run_detail": warm_detail, "full": bool(a.full),
         "value_is": ("steady state on placed buffers (gelato_amd/placement.py)" if placed_used else "steady state on the allocator's buffer placement"),
-        "value_default_placement": evals / T_default, "ms_per_step_default_placement": 1e3 * T_default / K,
+        "value_default_placement": measured(evals / T_default), "ms_per_step_default_placement": measured(1e3 * T_default / K),
         "ms_per_step": 1e3 * T / K, "ms_per_eval": 1e3 * T / (B * K), "higher_is_better": True,
         "scaling": "strong" if shard else "weak", "vs_baseline": None, "dtype": "f64", "data": "synthetic",
         # `value`: K timed steps in the settled power state (warmup_steps_run launches in front of them, W of them directly), on the
         # placed buffers when the placement ran; `value_default_placement`: the same on the buffers as the allocator placed them;
         # `value_cold`: the K timed steps right behind W (+ time-based, >= 40 ms) warm-up steps from an idle GPU -- inside the
-        # start-up power transient.  value_settled = value (the key of rounds 3-5, kept for comparisons)
-        "value_cold": evals / T_cold, "ms_per_step_cold": 1e3 * T_cold / K,
+        # start-up power transient.  value_settled = value (the key of rounds 3-5, kept for comparisons).  A plain run times `value`
+        # alone: the other two are null unless --full (or, without a placement, value_default_placement = value)
+        "value_cold": measured(evals / T_cold), "ms_per_step_cold": measured(1e3 * T_cold / K),
         "value_settled": evals / T, "ms_per_step_settled": 1e3 * T / K,
         "config": {"workload": a.workload + (" (residual only)" if a.residual_only else ""), "engine_flags": int(a.flags), "phases": int(S),
                    "nodes_per_phase": [int(n) for n in prob["num_nodes"]],
@@ -510,8 +594,10 @@ def main():
         placement["ms_per_step_placed"] = 1e3 * T_placed / K
         placement["kernel_ms_placed"] = kern_ms_placed
         placement["launches_before_value_placed"] = placement.get("all_launches", 0) + W
-        placement["value_placed_over_default"] = T_default / T_placed
+        placement["value_placed_over_default"] = measured(T_default / T_placed)
     out["build"] = build
+    if dumped is not None:
+        out["dump_outputs"] = dumped
     if not shard:
         # one launch = B evals on this rank; HIP events on the launch stream over the K timed launches
         stored = 8 * E.nres if a.residual_only else E.stored_bytes
@@ -546,9 +632,10 @@ def main():
                            # mean over EVERY launch of this kernel in this run up to here (placement candidates, warm-ups, both timed
                            # regions and the settling launches between them): what `rocprofv3 --kernel-trace --stats` of the run averages
                            "kernel_ms_mean_of_all_launches": all_ms / max(all_n, 1), "launches_so_far": all_n,
-                           "frac_cold": abytes / (kern_ms_cold * 1e-3) / 1e9 / HBM_PEAK_GBS, "kernel_ms_cold": kern_ms_cold,
+                           "frac_cold": measured(abytes / (kern_ms_cold * 1e-3) / 1e9 / HBM_PEAK_GBS), "kernel_ms_cold": measured(kern_ms_cold),
                            # frac / kernel_ms belong to `value` (placed buffers when the placement ran); the allocator's placement beside them
-                           "frac_default_placement": abytes / (kern_ms_default * 1e-3) / 1e9 / HBM_PEAK_GBS, "kernel_ms_default_placement": kern_ms_default,
+                           "frac_default_placement": measured(abytes / (kern_ms_default * 1e-3) / 1e9 / HBM_PEAK_GBS),
+                           "kernel_ms_default_placement": measured(kern_ms_default),
                            "frac_placed": (abytes / (kern_ms_placed * 1e-3) / 1e9 / HBM_PEAK_GBS) if kern_ms_placed == kern_ms_placed else None,
                            "kernel_ms_placed": kern_ms_placed if kern_ms_placed == kern_ms_placed else None,
                            "algorithmic_bytes_per_eval": a_min, "algorithmic_bytes_per_launch": abytes,
@@ -561,6 +648,9 @@ def main():
                                          "the limit the counters show nearer: 'mfma' = the fp64 datapath that v_mfma_f64 and vector fp64 "
                                          "share (fp64.pipe_busy) is busier than HBM is with the bytes that really move "
                                          "(hbm_frac_of_bytes_moved); see DESIGN.md 3.1"}
+    elif not a.full:
+        out["shard"] = {"step_ms": kern_ms, "units_per_rank": [c for _, c in shards.ranges], "slice_doubles_per_vector": shards.width,
+                        "note": "the kernel-only time of this rank's unit range and the roofline of it: --full"}
     else:
         # this rank's kernel alone (its unit range of all B vectors, split form, written into its slice of the exchange buffer):
         # HIP events over K launches without the collective
@@ -580,14 +670,14 @@ def main():
                            "frac": r_bytes / (k_ms * 1e-3) / 1e9 / HBM_PEAK_GBS, "traffic": None, "traffic_source": traffic_why,
                            "kernel": kname, "kernel_ms": k_ms, "rank": rank,
                            "algorithmic_bytes_per_launch": r_bytes, "owned_entries_per_vector": own}
-        out["shard"] = {"step_ms": kern_ms, "step_ms_cold": kern_ms_cold, "kernel_ms": k_ms,
+        out["shard"] = {"step_ms": kern_ms, "step_ms_cold": measured(kern_ms_cold), "kernel_ms": k_ms,
                         "exchange_ms": max(kern_ms - k_ms, 0.0), "pack_launches": 0, "unpack_launches": 0,
                         "units_per_rank": [c for _, c in shards.ranges], "slice_doubles_per_vector": shards.width,
                         "all_gather_bytes_received_per_rank_per_step": shards.bytes_received_per_vector() * B,
                         "note": "one step = this rank's unit range (split-form kernel writing straight into its slice of the exchange "
                                 "buffer) + ONE in-place all-gather; a consumer reads the buffer through gel_shard_plan's map"}
 
-    if not a.no_extras and not a.residual_only and not shard:
+    if a.full and not a.no_extras and not a.residual_only and not shard:
         # informational: materialise every COO value like the reference does (compact -> full expansion)
         try:
             Bf = min(B, 1024)
@@ -838,7 +928,7 @@ def main():
         except Exception as ex:  # noqa: BLE001
             out["defect_plus_aero"] = {"error": str(ex)[:300]}
 
-    if not a.no_other_configs and not a.no_extras and not shard and not a.residual_only and a.workload == "mixed-6x64" and a.flags == 0:
+    if a.full and not a.no_other_configs and not a.no_extras and not shard and not a.residual_only and a.workload == "mixed-6x64" and a.flags == 0:
         # The other BASELINE.json configurations in front of the driver, after the headline's timed region:
         # configs[1] 3 x 32 residual-only, configs[4] stress-12x128, dense-6x64 (maximum work), and the headline mesh in the
         # reference-literal form that re-runs the RHS chain on every perturbed column (GEL_FLAG_FD_RECOMPUTE).  Each leg: its own
@@ -923,7 +1013,7 @@ def main():
                       "frac_default_placement on the allocator's; after the headline's timed regions; %.1f s in all" % (LEG_DISTINCT, LEG_K, time.perf_counter() - t_legs))
         out["other_configs"] = oc
 
-    if not a.no_cpu_baseline:   # rank 0, at every N
+    if a.full and not a.no_cpu_baseline:   # rank 0, at every N
         out["cpu_baseline"] = cpu_baseline(prob, D, tau, X, gpu_first, residual_only=a.residual_only)
         # informational only (the roofline fraction is the kernel-quality figure): the GPU writes compact
         # Jacobian values, the scalar port materialises every COO value

@@ -1164,6 +1164,49 @@ def test_benchmark_batch_against_oracle_in_full():
     assert worst_j <= 1e-5, worst_j
 
 
+def test_bench_plain_run_line_and_dumped_outputs_against_oracle(tmp_path):
+    """A plain bench.py run (one timed region of --steps steps) in a fresh process: its result line, and the rows --dump-outputs
+    writes of what the last timed step computed -- every sampled row against the oracle on the same decision vector."""
+    import json
+    import os
+    import subprocess
+    import sys
+    from conftest import ROOT
+    from gelato_amd import problem
+    B, K = 2048, 3
+    out_dir = tmp_path / "outputs"
+    pr = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(K), "--warmup", "1",
+                         "--batch", str(B), "--placement-tries", "1", "--settle-ms", "0", "--dump-outputs", str(out_dir)],
+                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=240)
+    assert pr.returncode == 0, pr.stderr[-2000:]
+    lines = [ln for ln in pr.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]
+    assert len(lines) == 1
+    line = json.loads(lines[0])
+    assert line["steps"] == K and line["full"] is False and line["status"] == 0
+    assert line["ms_per_step"] > 0 and abs(line["value"] - B / (line["ms_per_step"] * 1e-3)) <= 1e-9 * line["value"]
+    for key in ("cpu_baseline", "other_configs", "full_coo_expand", "defect_plus_aero"):
+        assert key not in line, key
+    assert line["dump_outputs"]["bytes"] <= 64 * 10 ** 6
+    res, jv = np.load(out_dir / "residual.npy"), np.load(out_dir / "jacobian_values.npy")
+    rows = np.load(out_dir / "sample_rows.npy")
+    assert res.dtype == jv.dtype == rows.dtype == np.float64 and rows[0] == 0 and len(rows) == len(res) == len(jv) > 1
+    prob, x0, pdict = named_problem("mixed-6x64")
+    ps = pdict["ps_params"]
+    D = [ps.D(i) for i in range(pdict["num_sections"])]
+    tau = [ps.tau(i) for i in range(pdict["num_sections"])]
+    oracle = _setup()
+    from gelato_amd import Engine
+    E = Engine(prob, D=D, tau=tau)
+    P = oracle.Problem(prob, D=D, tau=tau)
+    assert res.shape[1] == E.nres and jv.shape[1] == E.V
+    X = problem.synthetic_batch(x0, E.M, B, seed=20260313)[rows.astype(np.int64)]
+    ores, ovals = P.eval_batch(X, nthreads=max(1, min(16, len(os.sched_getaffinity(0)))))
+    ov = ovals[:, E.var_index()]
+    bound = np.concatenate(list(dx_roundoff_bound(E, x0).values()))
+    assert np.max(np.abs(res - ores) - (1e-12 + 2 * bound + 1e-10 * np.abs(ores))) <= 0.0
+    assert np.max(np.abs(jv - ov) - 1e-6 * np.abs(ov)) <= 1e-5
+
+
 # --------------------------------------------------------------------------
 # the path's exp (the library's algorithm with scalar coefficient operands, csrc/gel_physics.h fexp) gives the library's bits
 # --------------------------------------------------------------------------

@@ -336,3 +336,36 @@ def test_bench_gpus_2_without_gpus_fails_loudly_instead_of_running_one_rank():
 def test_bench_rank_count_must_agree_with_gpus_flag():
     pr = _bench(["--gpus", "8"], env={"RANK": "0", "WORLD_SIZE": "1", "LOCAL_RANK": "0"})
     assert pr.returncode != 0 and "must agree" in pr.stderr and '"metric"' not in pr.stdout
+
+
+def test_bench_refuses_zero_timed_steps():
+    pr = _bench(["--steps", "0", "--warmup", "0"])
+    assert pr.returncode != 0 and "--steps must be >= 1" in pr.stderr and '"metric"' not in pr.stdout
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)          # module level: argparse / numpy only, nothing touches HIP
+    return m
+
+
+def test_bench_batch_generator_is_the_problem_generator_bit_for_bit():
+    """bench.py draws its rows on several threads: the batch must be problem.synthetic_batch's, bit for bit"""
+    from gelato_amd import pack_x, problem
+    _pd, _ud, _c, xdict = problem.make_problem("mixed-6x64")
+    x0 = pack_x(xdict)
+    bench = _bench_module()
+    for B, M, seed in ((1, 384, 20260313), (3, 384, 20260313), (1500, 384, 20260313 + 7), (777, 65, 5)):
+        assert np.array_equal(bench.synthetic_batch(x0, M, B, seed), problem.synthetic_batch(x0, M, B, seed=seed)), (B, M, seed)
+
+
+def test_bench_dump_sample_is_fixed_and_within_budget():
+    bench = _bench_module()
+    for B, per_row in ((65536, 8 * (11 * 384 + 26048)), (65536, 8 * 1056), (2048, 8 * 30000), (1, 8), (5, 8)):
+        rows = bench.dump_rows(B, per_row)
+        assert np.array_equal(rows, bench.dump_rows(B, per_row))                       # the same rows in every run
+        assert rows[0] == 0 and np.all(np.diff(rows) > 0) and rows[-1] < B             # x0 first, distinct, inside the batch
+        assert rows.size * per_row <= bench.DUMP_BYTES <= 64 * 10 ** 6 or rows.size == 1
+        assert rows.size == min(B, bench.DUMP_BYTES // per_row)
