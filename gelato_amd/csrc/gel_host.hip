@@ -127,6 +127,7 @@ struct HostPhase {
 struct gel_problem {
   int device = 0;
   bool fd_recompute = false;   // GEL_FLAG_FD_RECOMPUTE (or a step too long for the difference form): the reference's recomputing sweeps
+  bool exact = false;          // GEL_FLAG_EXACT_DEFECT_JAC: defect Jacobians by gel_kernels_exact.hip (residuals by the residual-only form)
   hipStream_t stream = nullptr;
   gel::ProblemDev dev{};
   std::vector<HostPhase> ph;
@@ -397,6 +398,22 @@ static void phase_columns(const gel_problem* p, int i, std::vector<int32_t>& col
       return fail(GEL_ERR_HIP, "host-only handle: nothing can be evaluated without a GPU (no CPU fallback)"); \
   } while (0)
 
+// The defect groups of B vectors: one launch of the fused kernel; on a handle created with GEL_FLAG_EXACT_DEFECT_JAC, a call with
+// derivatives is the residual-only launch of the fused kernel (when residuals are asked for) followed by the exact-Jacobian kernel.
+hipError_t launch_defects(const gel_problem* p, const gel::ProblemDev& dv, int B, const double* x, double* res, double* jvar,
+                          hipStream_t s) {
+  if (!p->exact || !jvar) return gel::launch_eval(dv, B, x, res, jvar, s);
+  if (res) {
+    const hipError_t e = gel::launch_eval(dv, B, x, res, nullptr, s);
+    if (e != hipSuccess) return e;
+  }
+  return gel::launch_eval_exact(dv, B, x, jvar, s);
+}
+#define NO_EXACT(p, what)                                                                                                   \
+  do {                                                                                                                      \
+    if ((p)->exact) return fail(GEL_ERR_ARG, what " has no exact-Jacobian form (handle created with GEL_FLAG_EXACT_DEFECT_JAC)"); \
+  } while (0)
+
 // calls moving less than this are served zero-copy out of the pinned staging buffers (run_host)
 constexpr size_t kZeroCopyBytes = (size_t)1 << 20;
 
@@ -543,16 +560,17 @@ int run_host(gel_problem* p, int B, const double* x, bool want_res, bool want_ja
     dv.flag = p->h_flag;
     // COO-direct output exists in the latency form only: a problem of more than 256 work items takes a cooperative form even for one
     // vector (gel::eval_form) and keeps the compact path
-    if (coo && B == 1 && want_jac && gel::eval_form(dv, 1, want_res, true).split) { dv.coo_full = p->h_full; dv.coo = p->d_coo; *coo_io = true; }
+    if (coo && !p->exact && B == 1 && want_jac && gel::eval_form(dv, 1, want_res, true).split) { dv.coo_full = p->h_full; dv.coo = p->d_coo; *coo_io = true; }
     dv.split_vel = 1;   // a whole evaluation: every part of every work item is in this launch
-    if (gel::eval_form(dv, B, want_res, want_jac).split) arm_done(p, dv);   // the latency form tells the host itself when its results are there
-    HIPCHK(gel::launch_eval(dv, B, xin, want_res ? (res_to ? res_to : p->h_res) : nullptr, want_jac ? p->h_jv : nullptr, p->stream));
+    // the latency form tells the host itself when its results are there (not when the exact kernel follows it)
+    if (!(p->exact && want_jac) && gel::eval_form(dv, B, want_res, want_jac).split) arm_done(p, dv);
+    HIPCHK(launch_defects(p, dv, B, xin, want_res ? (res_to ? res_to : p->h_res) : nullptr, want_jac ? p->h_jv : nullptr, p->stream));
     HIPCHK(wait_done(p, dv));
     if (*p->h_flag) { *p->h_flag = 0; return GEL_NONFINITE; }
     return GEL_OK;
   }
   HIPCHK(hipMemcpyAsync(p->d_x, xin, nx * 8, hipMemcpyHostToDevice, p->stream));
-  HIPCHK(gel::launch_eval(p->dev, B, p->d_x, want_res ? p->d_res : nullptr, want_jac ? p->d_jv : nullptr, p->stream));
+  HIPCHK(launch_defects(p, p->dev, B, p->d_x, want_res ? p->d_res : nullptr, want_jac ? p->d_jv : nullptr, p->stream));
   if (want_res) HIPCHK(hipMemcpyAsync(p->h_res, p->d_res, nr * 8, hipMemcpyDeviceToHost, p->stream));
   if (want_jac && nj) HIPCHK(hipMemcpyAsync(p->h_jv, p->d_jv, nj * 8, hipMemcpyDeviceToHost, p->stream));
   HIPCHK(hipMemcpyAsync(p->h_flag, p->d_flag, 4, hipMemcpyDeviceToHost, p->stream));
@@ -673,7 +691,7 @@ int run_host_pipelined(gel_problem* p, int B, const double* x, double* res, doub
     double* const hres = direct ? res + (size_t)first * nr : sl.h_res;
     double* const hjv = direct ? jvar + (size_t)first * nj : sl.h_jv;
     if (hipMemcpyAsync(sl.d_x, hx, (size_t)count * nv * 8, hipMemcpyHostToDevice, sl.stream) != hipSuccess ||
-        gel::launch_eval(dv, count, sl.d_x, res ? sl.d_res : nullptr, jvar ? sl.d_jv : nullptr, sl.stream) != hipSuccess ||
+        launch_defects(p, dv, count, sl.d_x, res ? sl.d_res : nullptr, jvar ? sl.d_jv : nullptr, sl.stream) != hipSuccess ||
         (res && hipMemcpyAsync(hres, sl.d_res, (size_t)count * nr * 8, hipMemcpyDeviceToHost, sl.stream) != hipSuccess) ||
         (jvar && nj && hipMemcpyAsync(hjv, sl.d_jv, (size_t)count * nj * 8, hipMemcpyDeviceToHost, sl.stream) != hipSuccess) ||
         hipMemcpyAsync(sl.h_flag, sl.d_flag, 4, hipMemcpyDeviceToHost, sl.stream) != hipSuccess) {
@@ -779,6 +797,11 @@ int gel_problem_create(const gel_problem_desc* d, gel_problem** out) {
       !d->engine_on || !d->attitude_hold || !d->wind_table || !d->ca_table || d->wind_rows < 2 || d->ca_rows < 2)
     return fail(GEL_ERR_ARG, "incomplete problem description");
   if (!(d->dx > 0.0)) return fail(GEL_ERR_ARG, "dx must be positive");
+  // the exact Jacobian fills the default compact layout (closed-form t0 / tf and quaternion slots); the aero rows it leaves to
+  // finite differences keep their difference form, which needs a step of at most 1 m
+  if ((d->flags & GEL_FLAG_EXACT_DEFECT_JAC) &&
+      ((d->flags & GEL_FLAG_FD_RECOMPUTE) || !(std::fabs(d->dx * d->unit_position) <= 1.0)))
+    return fail(GEL_ERR_ARG, "GEL_FLAG_EXACT_DEFECT_JAC cannot be combined with GEL_FLAG_FD_RECOMPUTE (nor with |dx * unit_position| > 1)");
   if (const char* why = gel::check_tables(d->wind_table, d->wind_rows, d->ca_table, d->ca_rows)) return fail(GEL_ERR_ARG, why);
   for (int i = 0; i < d->num_sections; i++)
     if (d->num_nodes[i] < 2) return fail(GEL_ERR_ARG, "every phase needs >= 2 LGR nodes (nodes_LGR requires n >= 2)");
@@ -799,6 +822,7 @@ int gel_problem_create(const gel_problem_desc* d, gel_problem** out) {
   // unless the caller asks for the reference's recomputing sweeps or the step dx * unit_position is beyond the 1 m the
   // truncated series of the difference form are sized for (the reference's own dx = 1e-8 gives 0.064 m).
   p->fd_recompute = ((d->flags & GEL_FLAG_FD_RECOMPUTE) != 0) || !(std::fabs(d->dx * d->unit_position) <= 1.0);
+  p->exact = (d->flags & GEL_FLAG_EXACT_DEFECT_JAC) != 0;
   p->barC20 = (d->barC20 == 0.0) ? -0.484165371736e-3 : d->barC20;
   const int S = d->num_sections;
   int N = 0;
@@ -1235,13 +1259,14 @@ int gel_eval_batch(gel_problem* p, int32_t B, const double* x, double* res, doub
 int gel_eval_batch_device(gel_problem* p, int32_t B, const double* d_x, double* d_res, double* d_jvar, void* stream) {
   if (!p || !d_x || B < 1 || (!d_res && !d_jvar)) return fail(GEL_ERR_ARG, "bad argument");
   NEED_DEVICE(p);
-  HIPCHK(gel::launch_eval(p->dev, B, d_x, d_res, d_jvar, stream ? (hipStream_t)stream : p->stream));
+  HIPCHK(launch_defects(p, p->dev, B, d_x, d_res, d_jvar, stream ? (hipStream_t)stream : p->stream));
   return GEL_OK;
 }
 
 int gel_eval_shard_units_device(gel_problem* p, int32_t B, const double* d_x, double* d_res, double* d_jvar,
                                 int32_t unit_begin, int32_t unit_count, void* stream) {
   if (!p || !d_x || B < 1 || !d_jvar) return fail(GEL_ERR_ARG, "bad argument (the unit form always writes Jacobian values)");
+  NO_EXACT(p, "gel_eval_shard_units_device");
   NEED_DEVICE(p);
   const int32_t total = 4 * (int32_t)p->chunk_phase.size();
   if (unit_begin < 0 || unit_count < 0 || unit_begin + unit_count > total)
@@ -1396,6 +1421,7 @@ static int check_plan(const gel_problem* p, int32_t nranks, int64_t width) {
 int gel_eval_shard_packed_device(gel_problem* p, int32_t B, const double* d_x, double* d_out, int32_t rank, int32_t nranks_expected,
                                  int64_t width_expected, void* stream) {
   if (!p || !d_x || !d_out || B < 1) return fail(GEL_ERR_ARG, "bad argument");
+  NO_EXACT(p, "gel_eval_shard_packed_device");
   NEED_DEVICE(p);
   if (int rc = check_plan(p, nranks_expected, width_expected)) return rc;
   if (!p->d_unit_base) return fail(GEL_ERR_ARG, "gel_shard_plan has not been called on this handle");
@@ -1448,7 +1474,7 @@ int gel_eval_full_device(gel_problem* p, int32_t B, const double* d_x, double* d
   hipStream_t s = stream ? (hipStream_t)stream : p->stream;
   gel::ProblemDev dv = p->dev;
   dv.cached_out = 1;   // the compact values are read again by the update below: kept in the caches when the launch fits them
-  HIPCHK(gel::launch_eval(dv, B, d_x, d_res, d_jvar, s));
+  HIPCHK(launch_defects(p, dv, B, d_x, d_res, d_jvar, s));
   HIPCHK(gel::launch_update_full(p->dims.total_nnz, p->dims.num_var_entries, p->nvar_entries, B, p->d_vdst, p->d_vsrc,
                                  p->nvar_lines, p->d_vline, p->d_src, p->d_cval, d_jvar, d_jfull, s));
   return GEL_OK;
@@ -1905,6 +1931,7 @@ int gel_aero_record_map(const gel_problem* p, int32_t kind, int32_t var, int64_t
 int gel_eval_batch_aero_device(gel_problem* p, int32_t B, const double* d_x, double* d_res, double* d_jvar, double* d_aero,
                                void* stream) {
   if (!p || !d_x || B < 1 || !d_res || !d_jvar || !d_aero) return fail(GEL_ERR_ARG, "bad argument");
+  NO_EXACT(p, "gel_eval_batch_aero_device");
   NEED_DEVICE(p);
   if (p->aero_nodes.empty()) return fail(GEL_ERR_ARG, "no aero path constraints configured (gel_aero_configure)");
   hipStream_t s = stream ? (hipStream_t)stream : p->stream;
@@ -2226,7 +2253,11 @@ int gel_eval_callback(gel_problem* p, const double* x, const gel_callback_io* io
   const bool fused = io->res || want_jac;
   // GEL_CB_MODE=3 (measurement switch): the three launches of rounds 1-2, back to back on the handle's stream (compact path)
   static const int cb_mode = [] { const char* e = getenv("GEL_CB_MODE"); return e ? atoi(e) : 0; }();
-  const bool coo = want_jac && cb_mode != 3 && coo_direct(p);
+  // exact handle with derivatives: the defect part is split out of the one-launch form -- the residual-only launch and the exact
+  // kernel (launch_defects), then the row table and the aero kinds in launches of their own -- so that no forward-difference
+  // sweep of the defect groups runs (nor flags a value that is then replaced)
+  const bool split_exact = p->exact && want_jac;
+  const bool coo = want_jac && cb_mode != 3 && !p->exact && coo_direct(p);
   if (coo) {
     if ((rc = ensure_full(p))) return rc;
     dv.coo_full = p->h_full; dv.coo = p->d_coo;
@@ -2242,8 +2273,8 @@ int gel_eval_callback(gel_problem* p, const double* x, const gel_callback_io* io
       out.con[k] = (io->aero_con[k] && n) ? p->h_aero + off_c[k] : nullptr;
       out.jac[k] = (out.con[k] && io->aero_jac[k]) ? p->h_aero + off_j[k] : nullptr;
     }
-  if (cb_mode == 3 || !fused) {
-    if (fused) HIPCHK(gel::launch_eval(dv, 1, xin, res_to, want_jac ? p->h_jv : nullptr, p->stream));
+  if (cb_mode == 3 || !fused || split_exact) {
+    if (fused) HIPCHK(launch_defects(p, dv, 1, xin, res_to, want_jac ? p->h_jv : nullptr, p->stream));
     if (rows) HIPCHK(gel::launch_rows(dv, (int)nlin, p->d_lin_rows, (int)nfn, p->d_fn_rows, 1, xin, p->h_rows,
                                       io->rows_jfn ? p->h_rows + R : nullptr, p->stream));
     if (aero) HIPCHK(gel::launch_aero(dv, (int)p->aero_nodes.size(), p->d_aero_nodes, 1, xin, out, p->stream));

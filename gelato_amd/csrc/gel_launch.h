@@ -16,6 +16,8 @@ hipError_t launch_eval(const ProblemDev& P, int B, const double* d_x, double* d_
 // defect groups + the aero rows of the aerodynamic phases' nodes 1 .. n in ONE launch (gel_eval_kernel.h, AERO instantiation)
 bool eval_aero_fusable(const ProblemDev& P, int B);
 hipError_t launch_eval_aero(const ProblemDev& P, int B, const double* d_x, double* d_res, double* d_jvar, hipStream_t s);
+// exact Jacobian of the defect groups (gel_kernels_exact.hip, GEL_FLAG_EXACT_DEFECT_JAC): the compact values only, no residuals
+hipError_t launch_eval_exact(const ProblemDev& P, int B, const double* d_x, double* d_jvar, hipStream_t s);
 hipError_t launch_expand(long long nnz, long long V, int B, const double* cval, const int32_t* src,
                          const double* d_jvar, double* d_full, hipStream_t s);
 // x-dependent entries only, into a full COO buffer that holds the constants (launch_fill_full lays them down)

@@ -87,7 +87,8 @@ class Engine:
             d.D, d.tau = None, None
         d.device = device
         self.flags = int(flags)
-        d.flags = int(flags)  # 0, or GEL_FLAG_DX_MFMA (1) / GEL_FLAG_DX_VALU (2) to force the D.X path, GEL_FLAG_NO_PACK (4), GEL_FLAG_FD_RECOMPUTE (8)
+        d.flags = int(flags)  # 0, or GEL_FLAG_DX_MFMA (1) / GEL_FLAG_DX_VALU (2) to force the D.X path, GEL_FLAG_NO_PACK (4), GEL_FLAG_FD_RECOMPUTE (8),
+        # GEL_FLAG_EXACT_DEFECT_JAC (32, _lib): the defect groups' Jacobians exact to rounding instead of forward differences
         h = C.c_void_p()
         check(L.gel_problem_create(C.byref(d), C.byref(h)))
         self._h = h

@@ -70,6 +70,28 @@ extern "C" {
                               phases are written in closed form +-f_c unit_t/2 (the RHS does not depend on t; the reference's two
                               sweeps only add rounding noise, <= 2e-6 measured).  Both forms meet the stated tolerance against
                               the reference's values; with the flag set the compact layout keeps separate t0 / tf slots. */
+#define GEL_FLAG_EXACT_DEFECT_JAC 32 /* opt-in: every x-dependent entry of the reference's pattern for the four defect groups'
+                              Jacobians (equality_jac_dynamics_{mass,position,velocity,quaternion}) is the analytic derivative of the
+                              residual the handle computes, formed in fp64 forward mode (value plus tangent along each variable) --
+                              exact to rounding, where the default is the reference's forward difference.  dx is ignored for these
+                              groups.  Exact ON THE REFERENCE'S PATTERN: where the pattern has no slot for a dependence, none is
+                              added -- a phase with reference_area < 0 depends on velocity through the aerodynamic force, but the
+                              reference's pattern holds only D there (no velocity sweep, lib/con_dynamics.py:403), and so does this.
+                              The aero path constraints' gradients (gel_eval_aero*, the callback's aero part) and the node-function
+                              rows (gel_rows_*, the callback's row table) STAY forward differences with dx.
+                              Residuals are bit-identical to a handle without the flag (the fused kernel's residual-only form runs
+                              first; the exact kernel then writes the compact Jacobian: two launches per evaluation; gel_eval_callback
+                              runs them, then the row table and the aero kinds, in launches of their own).  Pattern,
+                              constants, compact layout and gather map are those of the default layout.  Evaluates through
+                              gel_eval_residual / _jacobian, gel_eval, gel_eval_batch, gel_eval_batch_device, gel_eval_full_device and
+                              gel_eval_callback; gel_eval_batch_aero_device and gel_eval_shard_* return GEL_ERR_ARG, and so does
+                              gel_problem_create for GEL_FLAG_FD_RECOMPUTE | GEL_FLAG_EXACT_DEFECT_JAC (or |dx * unit_position| > 1),
+                              also on a host-only handle.  Conventions where the value is not differentiable -- the derivative of
+                              the branch the value took: the table interval used (0 where interp clamps, x <= xp[0] included), the
+                              atmosphere layer and the 86 km geopotential switch, the gravity r < b clamp; air-relative speed 0:
+                              d|v_air| = 0 (the force's derivative is 0 there); polar axis p = 0: the partials of p and of the
+                              longitude are 0.  A non-finite entry it writes makes the call return GEL_NONFINITE (gel_sync for the
+                              device forms). */
 
 #define GEL_NUM_GROUPS 4
 #define GEL_NUM_BLOCKS 13
