@@ -10,6 +10,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <functional>
+#include <memory>
 #include <string>
 #include <thread>
 #include <vector>
@@ -31,6 +32,62 @@ int fail(int code, const std::string& msg) {
     if (_e != hipSuccess)                                                                    \
       return fail(GEL_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));           \
   } while (0)
+
+// The only owners of device and pinned memory in this file: an array frees its block in its destructor (and when it is
+// moved onto).  reserve() only grows: the old block goes first, and a failed allocation leaves the array empty with
+// capacity 0 -- never a stale pointer.  upload() sizes the array for at least one element and copies the host data in.
+template <class T, bool Pinned>
+class HipArray {
+ public:
+  HipArray() = default;
+  HipArray(HipArray&& o) noexcept : p_(o.p_), cap_(o.cap_) { o.p_ = nullptr; o.cap_ = 0; }
+  HipArray& operator=(HipArray&& o) noexcept {
+    if (this != &o) { reset(); std::swap(p_, o.p_); std::swap(cap_, o.cap_); }
+    return *this;
+  }
+  ~HipArray() { reset(); }
+  T* get() const { return p_; }
+  hipError_t reserve(size_t n) {
+    if (cap_ >= n) return hipSuccess;
+    reset();
+    void* q = nullptr;
+    const hipError_t e = Pinned ? hipHostMalloc(&q, n * sizeof(T)) : hipMalloc(&q, n * sizeof(T));
+    if (e == hipSuccess) { p_ = static_cast<T*>(q); cap_ = n; }
+    return e;
+  }
+  hipError_t upload(const T* h, size_t n) {
+    if (const hipError_t e = reserve(std::max<size_t>(1, n))) return e;
+    if (!n) return hipSuccess;
+    if (Pinned) { std::memcpy(p_, h, n * sizeof(T)); return hipSuccess; }
+    return hipMemcpy(p_, h, n * sizeof(T), hipMemcpyHostToDevice);
+  }
+  hipError_t upload(const std::vector<T>& h) { return upload(h.data(), h.size()); }
+
+ private:
+  void reset() {
+    if (p_) (void)(Pinned ? hipHostFree((void*)p_) : hipFree((void*)p_));
+    p_ = nullptr;
+    cap_ = 0;
+  }
+  T* p_ = nullptr;
+  size_t cap_ = 0;  // elements
+};
+template <class T> using DeviceArray = HipArray<T, false>;
+template <class T> using PinnedArray = HipArray<T, true>;
+
+// A stream, created on demand; its destructor lets the work on it finish, then destroys it.
+class Stream {
+ public:
+  Stream() = default;
+  Stream(Stream&& o) noexcept : s_(o.s_) { o.s_ = nullptr; }
+  Stream& operator=(Stream&& o) noexcept { std::swap(s_, o.s_); return *this; }
+  ~Stream() { if (s_) { hipStreamSynchronize(s_); hipStreamDestroy(s_); } }
+  hipStream_t get() const { return s_; }
+  hipError_t create() { return s_ ? hipSuccess : hipStreamCreate(&s_); }
+
+ private:
+  hipStream_t s_ = nullptr;
+};
 
 // ---------------------------------------------------------------------------
 // LGR nodes / differentiation matrix.
@@ -128,7 +185,8 @@ struct gel_problem {
   int device = 0;
   bool fd_recompute = false;   // GEL_FLAG_FD_RECOMPUTE (or a step too long for the difference form): the reference's recomputing sweeps
   bool exact = false;          // GEL_FLAG_EXACT_DEFECT_JAC: defect Jacobians by gel_kernels_exact.hip (residuals by the residual-only form)
-  hipStream_t stream = nullptr;
+  bool aero_fused = true;      // GEL_AERO_FUSED (read when the handle is created): 0 = gel_eval_batch_aero_device by the two kernels
+  Stream stream;
   gel::ProblemDev dev{};
   std::vector<HostPhase> ph;
   gel_dims dims{};
@@ -146,98 +204,102 @@ struct gel_problem {
   std::vector<int32_t> shard_begin;  // [nranks + 1]
   std::vector<int64_t> unit_base;    // [4 * nchunks]
   int64_t shard_width = 0;
-  int64_t* d_unit_base = nullptr;
-  int64_t* d_shard_pos = nullptr;    // [11N + V]: rank * width + offset of every res entry, then of every compact value
-  // aero path constraints: kind 0 = AOA_max, 1 = dynamic_pressure_max, 2 = Q_alpha_max
-  std::vector<gel::AeroRowDev> aero_rows[3];
-  std::vector<gel::AeroNodeDev> aero_nodes;                   // the constrained state nodes, shared by the kinds
-  gel::AeroNodeDev* d_aero_nodes = nullptr;
-  // gel_eval_batch_aero_device (defect groups + aero rows, one output record per vector): the record's layout, the per-phase
-  // records of the rows the fused kernel's lanes write, and the constrained nodes they do not reach (state node 0 of a phase,
-  // phases without aerodynamics) -- left to aero_wide_kernel
-  int64_t aero_ld = 0, aero_off_con[2][3] = {{0, 0, 0}, {0, 0, 0}}, aero_off_jac[2][3] = {{0, 0, 0}, {0, 0, 0}};
-  std::vector<gel::AeroRowDev> aero_part_rows[2][3];          // the rows of part A (the lanes') and part B (the rest), per kind
-  std::vector<int32_t> aero_part_of[3];                       // per row of a kind: part | (row inside the part) << 1
-  std::vector<int64_t> aero_partA_base[3];                    // per row of part A: first double of its spec's block in the record
-  int64_t aero_partA_len = 0;                                 // doubles of part A (part B's sections follow)
-  int64_t aero_dump = 0;                                      // first double of the dump area at the end of part A
-  std::vector<gel::AeroNodeDev> aero_part_nodes[2];
-  std::vector<gel::AeroPhaseDev> aero_ph;
-  gel::AeroPhaseDev* d_aero_ph = nullptr;
-  gel::AeroNodeDev* d_aero_part_nodes[2] = {nullptr, nullptr};
-  double *d_aero_x = nullptr, *d_aero_out = nullptr;          // working set of large host-buffer calls
-  size_t d_aero_x_cap = 0, d_aero_out_cap = 0;                // doubles
+  DeviceArray<int64_t> d_unit_base;
+  DeviceArray<int64_t> d_shard_pos;  // [11N + V]: rank * width + offset of every res entry, then of every compact value
+  // aero path constraints, host tables and their device copies: gel_aero_configure builds a whole new set and
+  // swaps it in, so a call that fails leaves the previous one in place
+  struct Aero {
+    std::vector<gel::AeroRowDev> rows[3];                   // kind 0 = AOA_max, 1 = dynamic_pressure_max, 2 = Q_alpha_max
+    std::vector<gel::AeroNodeDev> nodes;                    // the constrained state nodes, shared by the kinds
+    // gel_eval_batch_aero_device (defect groups + aero rows, one output record per vector): the record's layout, the per-phase
+    // records of the rows the fused kernel's lanes write, and the constrained nodes they do not reach (state node 0 of a phase,
+    // phases without aerodynamics) -- left to aero_wide_kernel
+    int64_t ld = 0, off_con[2][3] = {{0, 0, 0}, {0, 0, 0}}, off_jac[2][3] = {{0, 0, 0}, {0, 0, 0}};
+    std::vector<gel::AeroRowDev> part_rows[2][3];           // the rows of part A (the lanes') and part B (the rest), per kind
+    std::vector<int32_t> part_of[3];                        // per row of a kind: part | (row inside the part) << 1
+    std::vector<int64_t> partA_base[3];                     // per row of part A: first double of its spec's block in the record
+    int64_t partA_len = 0;                                  // doubles of part A (part B's sections follow)
+    int64_t dump = 0;                                       // first double of the dump area at the end of part A
+    std::vector<gel::AeroNodeDev> part_nodes[2];
+    std::vector<gel::AeroPhaseDev> ph;
+    DeviceArray<gel::AeroNodeDev> d_nodes, d_part_nodes[2];
+    DeviceArray<gel::AeroPhaseDev> d_ph;
+  } aero;
+  DeviceArray<double> d_aero_x, d_aero_out;                 // working set of large host-buffer calls
   // device buffers (static)
-  gel::PhaseDev* d_phases = nullptr;
-  int32_t* d_node_phase = nullptr;
-  int4* d_chunks = nullptr;         // work items in phase order (what gel_chunk_phase / shard ranges index)
-  int4* d_chunks_sorted = nullptr;  // the same items, dearest phase type first (whole launches)
-  double* d_Dsw = nullptr;          // D per work item in the feed order of v_mfma_f64_16x16x4_f64
-  double* d_Dst = nullptr;          // the same, row-tile major (one wavefront per row tile)
-  double* d_Dt = nullptr;
-  double* d_tau = nullptr;
-  double* d_tables = nullptr;
-  double* d_cval = nullptr;
-  int32_t* d_src = nullptr;
-  int32_t *d_vdst = nullptr, *d_vsrc = nullptr;   // the x-dependent entries of the gather map: destination (ascending), signed source
+  DeviceArray<gel::PhaseDev> d_phases;
+  DeviceArray<int32_t> d_node_phase;
+  DeviceArray<int4> d_chunks;         // work items in phase order (what gel_chunk_phase / shard ranges index)
+  DeviceArray<int4> d_chunks_sorted;  // the same items, dearest phase type first (whole launches)
+  DeviceArray<double> d_Dsw;          // D per work item in the feed order of v_mfma_f64_16x16x4_f64
+  DeviceArray<double> d_Dst;          // the same, row-tile major (one wavefront per row tile)
+  DeviceArray<double> d_Dt, d_tau, d_tables, d_cval;
+  DeviceArray<int32_t> d_src;
+  DeviceArray<int32_t> d_vdst, d_vsrc;   // the x-dependent entries of the gather map: destination (ascending), signed source
   int32_t nvar_entries = 0;
-  int32_t* d_vline = nullptr;     // the 64-byte lines (index / 8) of a value vector that hold an x-dependent entry
+  DeviceArray<int32_t> d_vline;   // the 64-byte lines (index / 8) of a value vector that hold an x-dependent entry
   int32_t nvar_lines = 0;
   // COO-direct output of the one-vector latency path (gel_eval_kernel.h "COO-DIRECT"): first entry of the eight groups of runs per
   // phase; the runs of the gather map that are left to the host (dense velocity / quaternion blocks); the engine's own full value
   // array in pinned host memory (constants laid down once; the kernel and the host scatter rewrite the x-dependent entries)
   std::vector<int32_t> coo_tab;   // [8 * S]; empty: the mode is not available for this problem
   std::vector<Run> rest_runs;
-  int32_t* d_coo = nullptr;
-  double* h_full = nullptr;
-  double* cb_res = nullptr;       // pinned residual vector a caller may name as its own output (gel_pinned_buffers): no copy then
-  double* cb_x[2] = {nullptr, nullptr};   // two pinned decision-vector buffers a caller may fill in turn and pass as x: read in place
-  int32_t* d_flag = nullptr;
+  DeviceArray<int32_t> d_coo;
+  PinnedArray<double> h_full;
+  PinnedArray<double> cb_res;     // pinned residual vector a caller may name as its own output (gel_pinned_buffers): no copy then
+  PinnedArray<double> cb_x[2];    // two pinned decision-vector buffers a caller may fill in turn and pass as x: read in place
+  DeviceArray<int32_t> d_flag;
   // B = 1 / small-batch working set
   int capB = 0;
-  double *d_x = nullptr, *d_res = nullptr, *d_jv = nullptr;
-  double *h_x = nullptr, *h_res = nullptr, *h_jv = nullptr;  // pinned
-  int32_t* h_flag = nullptr;                                  // pinned
+  DeviceArray<double> d_x, d_res, d_jv;
+  PinnedArray<double> h_x, h_res, h_jv;
+  PinnedArray<int32_t> h_flag;
   // gel_jac_fd working set: kept between calls; the residuals of all num_vars + 1 perturbed vectors are
   // re-used while x stays the same (the four groups are asked for one after the other)
-  double *jfd_x = nullptr, *jfd_Xp = nullptr, *jfd_res = nullptr, *jfd_J = nullptr;
-  size_t jfd_J_cap = 0;                                       // doubles
+  DeviceArray<double> jfd_x, jfd_Xp, jfd_res, jfd_J;
   // every phase as its own one-phase problem (gel_jac_fd differences phase by phase)
-  gel::PhaseDev* d_subphases = nullptr;                       // [S] the phase records with ua = xa = 0
-  int4* d_subchunks = nullptr;                                // the phase-ordered work items with phase index 0
-  int32_t* d_colmap = nullptr;                                // per phase: local column -> global column
+  DeviceArray<gel::PhaseDev> d_subphases;                     // [S] the phase records with ua = xa = 0
+  DeviceArray<int4> d_subchunks;                              // the phase-ordered work items with phase index 0
+  DeviceArray<int32_t> d_colmap;                              // per phase: local column -> global column
   std::vector<int32_t> sub_chunk0, sub_nchunks, sub_col0;     // [S] first work item, work items, first colmap entry
   std::vector<size_t> sub_res0;                               // [S] first double of the phase's residuals in jfd_res
   std::vector<double> jfd_last_x;                             // empty = nothing cached
-  int32_t* d_done = nullptr;                                  // self-signalling one-vector launches (ProblemDev::done_flag): device counter,
-  volatile int32_t* h_done = nullptr;                         // pinned host word, sequence number of the last armed launch
+  DeviceArray<int32_t> d_done;                                // self-signalling one-vector launches (ProblemDev::done_flag): device counter,
+  PinnedArray<volatile int32_t> h_done;                       // pinned host word, sequence number of the last armed launch
   int32_t done_seq = 0;
   long long done_ema_us = 100;                                // running estimate of a self-signalling launch's wait (sets the spin budget)
   int jfd_status = GEL_OK;
   // knot / terminal / user rows (gel_rows_configure)
   std::vector<gel::LinRowDev> lin_rows;
   std::vector<gel::FnRowDev> fn_rows;
-  gel::LinRowDev* d_lin_rows = nullptr;
-  gel::FnRowDev* d_fn_rows = nullptr;
-  double* h_rows = nullptr;                                   // pinned outputs of small gel_rows_eval calls: con | jfn
-  size_t h_rows_cap = 0;                                      // doubles
-  double *d_rows_x = nullptr, *d_rows_out = nullptr;          // working set of large host-buffer calls
-  size_t d_rows_x_cap = 0, d_rows_out_cap = 0;                // doubles
-  double* h_aero = nullptr;                                   // pinned outputs of small gel_eval_aero calls
-  size_t h_aero_cap = 0;                                      // doubles
+  DeviceArray<gel::LinRowDev> d_lin_rows;
+  DeviceArray<gel::FnRowDev> d_fn_rows;
+  PinnedArray<double> h_rows;                                 // pinned outputs of small gel_rows_eval calls: con | jfn
+  DeviceArray<double> d_rows_x, d_rows_out;                   // working set of large host-buffer calls
+  PinnedArray<double> h_aero;                                 // pinned outputs of small gel_eval_aero calls
   // large host batches (gel_eval_batch): two staging slots of kPipeEvals decision vectors each, every
   // slot with its own stream, so that PCIe in, kernel, PCIe out and the host copies of neighbouring
   // sub-batches overlap
   struct Slot {
-    double *d_x = nullptr, *d_res = nullptr, *d_jv = nullptr;
-    double *h_x = nullptr, *h_res = nullptr, *h_jv = nullptr;  // pinned
-    int32_t *d_flag = nullptr, *h_flag = nullptr;
-    hipStream_t stream = nullptr;
+    DeviceArray<double> d_x, d_res, d_jv;
+    PinnedArray<double> h_x, h_res, h_jv;
+    DeviceArray<int32_t> d_flag;
+    PinnedArray<int32_t> h_flag;
+    Stream stream;
     int64_t first = 0;  // sub-batch in flight: [first, first + count)
     int count = 0;
     bool res = false, jac = false;
   } slot[2];
   int pipe_evals = 0;  // capacity of a slot (0 = not allocated)
+
+  // Nothing may still run on the handle's streams when its memory goes: the device is made current and every stream is
+  // drained first; then the members free themselves.  A host-only handle owns no device resource and makes no HIP call.
+  ~gel_problem() {
+    if (device == GEL_DEVICE_NONE) return;
+    hipSetDevice(device);
+    for (hipStream_t s : {stream.get(), slot[0].stream.get(), slot[1].stream.get()})
+      if (s) hipStreamSynchronize(s);
+  }
 };
 
 namespace {
@@ -373,13 +435,6 @@ int64_t phase_block_nnz(const HostPhase& h, int blk) {
   }
 }
 
-template <class T>
-int upload(T** d, const std::vector<T>& h) {
-  HIPCHK(hipMalloc((void**)d, std::max<size_t>(1, h.size()) * sizeof(T)));
-  if (!h.empty()) HIPCHK(hipMemcpy(*d, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-  return GEL_OK;
-}
-
 // global column of every local column of phase i as a one-phase problem: [mass n+1 | pos 3(n+1) | vel 3(n+1) | quat 4(n+1) | u 2n | t0 tf]
 static void phase_columns(const gel_problem* p, int i, std::vector<int32_t>& colmap) {
   const HostPhase& h = p->ph[i];
@@ -421,20 +476,10 @@ int ensure_capacity(gel_problem* p, int B) {
   NEED_DEVICE(p);
   if (B <= p->capB) return GEL_OK;
   HIPCHK(hipSetDevice(p->device));
-  // release first and forget the old capacity: a failed allocation below must not leave freed pointers behind
-  hipFree(p->d_x); hipFree(p->d_res); hipFree(p->d_jv);
-  if (p->h_x) hipHostFree(p->h_x);
-  if (p->h_res) hipHostFree(p->h_res);
-  if (p->h_jv) hipHostFree(p->h_jv);
-  p->d_x = p->d_res = p->d_jv = p->h_x = p->h_res = p->h_jv = nullptr;
-  p->capB = 0;
+  p->capB = 0;   // until every buffer below has grown
   const size_t nx = (size_t)B * p->dims.num_vars, nr = (size_t)B * 11 * p->dims.N, nj = (size_t)B * std::max<int64_t>(1, p->dims.num_var_entries);
-  HIPCHK(hipMalloc((void**)&p->d_x, nx * 8));
-  HIPCHK(hipMalloc((void**)&p->d_res, nr * 8));
-  HIPCHK(hipMalloc((void**)&p->d_jv, nj * 8));
-  HIPCHK(hipHostMalloc((void**)&p->h_x, nx * 8));
-  HIPCHK(hipHostMalloc((void**)&p->h_res, nr * 8));
-  HIPCHK(hipHostMalloc((void**)&p->h_jv, nj * 8));
+  HIPCHK(p->d_x.reserve(nx)); HIPCHK(p->d_res.reserve(nr)); HIPCHK(p->d_jv.reserve(nj));
+  HIPCHK(p->h_x.reserve(nx)); HIPCHK(p->h_res.reserve(nr)); HIPCHK(p->h_jv.reserve(nj));
   p->capB = B;
   return GEL_OK;
 }
@@ -452,9 +497,9 @@ static bool done_flag_on() {
   return on;
 }
 static void arm_done(gel_problem* p, gel::ProblemDev& dv) {
-  if (!p->d_done || !p->h_done || !done_flag_on()) return;
-  dv.done_ctr = p->d_done;
-  dv.done_flag = const_cast<int32_t*>(p->h_done);
+  if (!p->d_done.get() || !p->h_done.get() || !done_flag_on()) return;
+  dv.done_ctr = p->d_done.get();
+  dv.done_flag = const_cast<int32_t*>(p->h_done.get());
   dv.done_seq = ++p->done_seq;
 }
 static hipError_t spin_wait(hipStream_t s);
@@ -475,7 +520,7 @@ static hipError_t wait_done(gel_problem* p, const gel::ProblemDev& dv) {
     const auto t0 = std::chrono::steady_clock::now();
     const auto budget = std::chrono::microseconds(std::min<long long>(5000, std::max<long long>(200, 8 * p->done_ema_us)));
     for (unsigned it = 1;; it++) {
-      if (*p->h_done == dv.done_seq) {
+      if (*p->h_done.get() == dv.done_seq) {
         std::atomic_thread_fence(std::memory_order_acquire);
         const long long us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
         p->done_ema_us = (3 * p->done_ema_us + us + 3) / 4;
@@ -486,7 +531,7 @@ static hipError_t wait_done(gel_problem* p, const gel::ProblemDev& dv) {
     }
     p->done_ema_us = std::min<long long>(5000, 2 * p->done_ema_us + 50);   // the wait outlasted the budget: a longer one next time
   }
-  return spin_wait(p->stream);
+  return spin_wait(p->stream.get());
 }
 
 static hipError_t spin_wait(hipStream_t s) {
@@ -500,23 +545,19 @@ static hipError_t spin_wait(hipStream_t s) {
 // The engine's own full COO value array and residual vector in pinned host memory (one-vector latency path): the constants are
 // laid down here, once; the COO-direct kernel and the host's scatter of the few entries left to it rewrite the x-dependent ones.
 int ensure_full(gel_problem* p) {
-  if (p->h_full && p->cb_res && p->cb_x[0] && p->cb_x[1]) return GEL_OK;
+  if (p->h_full.get() && p->cb_res.get() && p->cb_x[0].get() && p->cb_x[1].get()) return GEL_OK;
   HIPCHK(hipSetDevice(p->device));
   // each buffer on its own: a failed allocation leaves the others as they are and the next call tries again (no half-made set is
   // ever handed out: gel_pinned_buffers and the zero-copy checks only run after this function has returned GEL_OK)
-  if (!p->h_full) {
-    HIPCHK(hipHostMalloc((void**)&p->h_full, std::max<size_t>(1, p->cval.size()) * 8));
-    std::memcpy(p->h_full, p->cval.data(), p->cval.size() * 8);
-  }
-  if (!p->cb_res) HIPCHK(hipHostMalloc((void**)&p->cb_res, (size_t)11 * p->dims.N * 8));
-  for (int i = 0; i < 2; i++)
-    if (!p->cb_x[i]) HIPCHK(hipHostMalloc((void**)&p->cb_x[i], (size_t)p->dims.num_vars * 8));
+  if (!p->h_full.get()) HIPCHK(p->h_full.upload(p->cval));
+  HIPCHK(p->cb_res.reserve((size_t)11 * p->dims.N));
+  for (auto& b : p->cb_x) HIPCHK(b.reserve((size_t)p->dims.num_vars));
   return GEL_OK;
 }
 // GEL_NO_COO_DIRECT=1 (measurement switch): the compact layout + the host scatter of every x-dependent entry, as before round 5
 bool coo_direct(const gel_problem* p) {
   static const bool off = [] { const char* e = getenv("GEL_NO_COO_DIRECT"); return e && atoi(e) != 0; }();
-  return !off && !p->coo_tab.empty() && p->d_coo != nullptr;
+  return !off && !p->coo_tab.empty() && p->d_coo.get() != nullptr;
 }
 // After a COO-direct evaluation: the entries the kernel left to the host (the diagonal of the dense velocity block, the pairs of the
 // dense quaternion block: 11 of a node's 49 slots) go from the compact vector into the engine's array; a caller that brought its
@@ -525,16 +566,16 @@ void finish_full(gel_problem* p, double* vals_full, int fill) {
   auto rest = [&](double* out) {
     for (const gel_problem::Run& r : p->rest_runs) {
       double* d = out + r.dst0;
-      const double* v = p->h_jv + r.src0;
+      const double* v = p->h_jv.get() + r.src0;
       if (r.sign > 0) for (int64_t k = 0; k < r.len; k++) d[k * r.dstride] = v[k * r.sstride];
       else for (int64_t k = 0; k < r.len; k++) d[k * r.dstride] = -v[k * r.sstride];
     }
   };
-  rest(p->h_full);
-  if (vals_full == p->h_full) return;
+  rest(p->h_full.get());
+  if (vals_full == p->h_full.get()) return;
   if (fill) std::memcpy(vals_full, p->cval.data(), p->cval.size() * 8);
   for (int b : {3, 4, 5, 6, 8, 9, 11, 12})
-    std::memcpy(vals_full + p->block_off[b], p->h_full + p->block_off[b], (size_t)(p->block_off[b + 1] - p->block_off[b]) * 8);
+    std::memcpy(vals_full + p->block_off[b], p->h_full.get() + p->block_off[b], (size_t)(p->block_off[b + 1] - p->block_off[b]) * 8);
   rest(vals_full);
 }
 
@@ -548,36 +589,37 @@ int run_host(gel_problem* p, int B, const double* x, bool want_res, bool want_ja
   HIPCHK(hipSetDevice(p->device));
   const size_t nx = (size_t)B * p->dims.num_vars, nr = (size_t)B * 11 * p->dims.N, nj = (size_t)B * p->dims.num_var_entries;
   // a one-vector call whose x IS one of the handle's pinned decision-vector buffers (gel_pinned_buffers) is read in place
-  const bool x_pinned = B == 1 && p->cb_x[0] && (x == p->cb_x[0] || x == p->cb_x[1]);
-  if (!x_pinned) std::memcpy(p->h_x, x, nx * 8);
-  const double* const xin = x_pinned ? x : p->h_x;
+  const bool x_pinned = B == 1 && p->cb_x[0].get() && (x == p->cb_x[0].get() || x == p->cb_x[1].get());
+  if (!x_pinned) std::memcpy(p->h_x.get(), x, nx * 8);
+  const double* const xin = x_pinned ? x : p->h_x.get();
   if ((nx + (want_res ? nr : 0) + (want_jac ? nj : 0)) * 8 <= kZeroCopyBytes) {
     // Small calls (the optimiser's one-vector callbacks): the kernel reads x from and writes its results
     // to the pinned staging buffers itself -- one launch and one synchronise instead of launch + four
     // copy commands (measured 91 -> see DESIGN.md 5, B = 1).  The non-finite flag is a plain store of 1,
     // so it may live in host memory too.
     gel::ProblemDev dv = p->dev;
-    dv.flag = p->h_flag;
+    dv.flag = p->h_flag.get();
     // COO-direct output exists in the latency form only: a problem of more than 256 work items takes a cooperative form even for one
     // vector (gel::eval_form) and keeps the compact path
-    if (coo && !p->exact && B == 1 && want_jac && gel::eval_form(dv, 1, want_res, true).split) { dv.coo_full = p->h_full; dv.coo = p->d_coo; *coo_io = true; }
+    if (coo && !p->exact && B == 1 && want_jac && gel::eval_form(dv, 1, want_res, true).split) { dv.coo_full = p->h_full.get(); dv.coo = p->d_coo.get(); *coo_io = true; }
     dv.split_vel = 1;   // a whole evaluation: every part of every work item is in this launch
     // the latency form tells the host itself when its results are there (not when the exact kernel follows it)
     if (!(p->exact && want_jac) && gel::eval_form(dv, B, want_res, want_jac).split) arm_done(p, dv);
-    HIPCHK(launch_defects(p, dv, B, xin, want_res ? (res_to ? res_to : p->h_res) : nullptr, want_jac ? p->h_jv : nullptr, p->stream));
+    HIPCHK(launch_defects(p, dv, B, xin, want_res ? (res_to ? res_to : p->h_res.get()) : nullptr, want_jac ? p->h_jv.get() : nullptr, p->stream.get()));
     HIPCHK(wait_done(p, dv));
-    if (*p->h_flag) { *p->h_flag = 0; return GEL_NONFINITE; }
+    if (*p->h_flag.get()) { *p->h_flag.get() = 0; return GEL_NONFINITE; }
     return GEL_OK;
   }
-  HIPCHK(hipMemcpyAsync(p->d_x, xin, nx * 8, hipMemcpyHostToDevice, p->stream));
-  HIPCHK(launch_defects(p, p->dev, B, p->d_x, want_res ? p->d_res : nullptr, want_jac ? p->d_jv : nullptr, p->stream));
-  if (want_res) HIPCHK(hipMemcpyAsync(p->h_res, p->d_res, nr * 8, hipMemcpyDeviceToHost, p->stream));
-  if (want_jac && nj) HIPCHK(hipMemcpyAsync(p->h_jv, p->d_jv, nj * 8, hipMemcpyDeviceToHost, p->stream));
-  HIPCHK(hipMemcpyAsync(p->h_flag, p->d_flag, 4, hipMemcpyDeviceToHost, p->stream));
-  HIPCHK(hipStreamSynchronize(p->stream));
-  if (want_res && res_to) std::memcpy(res_to, p->h_res, nr * 8);
-  if (*p->h_flag) {
-    HIPCHK(hipMemsetAsync(p->d_flag, 0, 4, p->stream));
+  hipStream_t s = p->stream.get();
+  HIPCHK(hipMemcpyAsync(p->d_x.get(), xin, nx * 8, hipMemcpyHostToDevice, s));
+  HIPCHK(launch_defects(p, p->dev, B, p->d_x.get(), want_res ? p->d_res.get() : nullptr, want_jac ? p->d_jv.get() : nullptr, s));
+  if (want_res) HIPCHK(hipMemcpyAsync(p->h_res.get(), p->d_res.get(), nr * 8, hipMemcpyDeviceToHost, s));
+  if (want_jac && nj) HIPCHK(hipMemcpyAsync(p->h_jv.get(), p->d_jv.get(), nj * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(p->h_flag.get(), p->d_flag.get(), 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (want_res && res_to) std::memcpy(res_to, p->h_res.get(), nr * 8);
+  if (*p->h_flag.get()) {
+    HIPCHK(hipMemsetAsync(p->d_flag.get(), 0, 4, s));
     return GEL_NONFINITE;
   }
   return GEL_OK;
@@ -602,8 +644,6 @@ void par_copy(void* dst, const void* src, size_t bytes) {
   for (auto& t : th) t.join();
 }
 
-void free_slots(gel_problem* p);
-
 int ensure_slots(gel_problem* p) {
   NEED_DEVICE(p);
   if (p->pipe_evals) return GEL_OK;
@@ -611,39 +651,23 @@ int ensure_slots(gel_problem* p) {
   const size_t per_eval = 8 * (size_t)std::max<int64_t>(p->dims.num_var_entries, 1);
   const int cap = (int)std::max<size_t>(1, kPipeBytes / per_eval);
   const size_t nx = (size_t)cap * p->dims.num_vars, nr = (size_t)cap * 11 * p->dims.N, nj = (size_t)cap * std::max<int64_t>(1, p->dims.num_var_entries);
-  for (auto& sl : p->slot) {
-    const bool ok = hipMalloc((void**)&sl.d_x, nx * 8) == hipSuccess && hipMalloc((void**)&sl.d_res, nr * 8) == hipSuccess &&
-                    hipMalloc((void**)&sl.d_jv, nj * 8) == hipSuccess && hipMalloc((void**)&sl.d_flag, 4) == hipSuccess &&
-                    hipMemset(sl.d_flag, 0, 4) == hipSuccess && hipHostMalloc((void**)&sl.h_x, nx * 8) == hipSuccess &&
-                    hipHostMalloc((void**)&sl.h_res, nr * 8) == hipSuccess && hipHostMalloc((void**)&sl.h_jv, nj * 8) == hipSuccess &&
-                    hipHostMalloc((void**)&sl.h_flag, 4) == hipSuccess && hipStreamCreate(&sl.stream) == hipSuccess;
-    if (!ok) {
-      free_slots(p);   // nothing half-allocated survives: the next call starts from scratch instead of leaking
-      return fail(GEL_ERR_ALLOC, "staging slots: allocation failed");
-    }
-    *sl.h_flag = 0;
-    sl.count = 0;
+  gel_problem::Slot fresh[2];   // all or nothing: a failure frees what was made, and the next call starts from scratch
+  for (auto& sl : fresh) {
+    const bool ok = sl.d_x.reserve(nx) == hipSuccess && sl.d_res.reserve(nr) == hipSuccess && sl.d_jv.reserve(nj) == hipSuccess &&
+                    sl.d_flag.reserve(1) == hipSuccess && hipMemset(sl.d_flag.get(), 0, 4) == hipSuccess &&
+                    sl.h_x.reserve(nx) == hipSuccess && sl.h_res.reserve(nr) == hipSuccess && sl.h_jv.reserve(nj) == hipSuccess &&
+                    sl.h_flag.reserve(1) == hipSuccess && sl.stream.create() == hipSuccess;
+    if (!ok) return fail(GEL_ERR_ALLOC, "staging slots: allocation failed");
+    *sl.h_flag.get() = 0;
   }
+  for (int i = 0; i < 2; i++) p->slot[i] = std::move(fresh[i]);
   p->pipe_evals = cap;
   return GEL_OK;
 }
 
-void free_slots(gel_problem* p) {
-  for (auto& sl : p->slot) {
-    if (sl.stream) { hipStreamSynchronize(sl.stream); hipStreamDestroy(sl.stream); }
-    hipFree(sl.d_x); hipFree(sl.d_res); hipFree(sl.d_jv); hipFree(sl.d_flag);
-    if (sl.h_x) hipHostFree(sl.h_x);
-    if (sl.h_res) hipHostFree(sl.h_res);
-    if (sl.h_jv) hipHostFree(sl.h_jv);
-    if (sl.h_flag) hipHostFree(sl.h_flag);
-    sl = gel_problem::Slot{};
-  }
-  p->pipe_evals = 0;
-}
-
 // B evals from / to pageable host arrays in sub-batches: while sub-batch i runs (H2D, kernel, D2H on its
 // slot's stream), the host retires sub-batch i-1 of the other slot (pinned -> caller) and stages i+1.
-// Is this host pointer page-locked memory the runtime knows (hipHostMalloc / hipHostRegister, e.g. a torch tensor made with
+// Is this host pointer page-locked memory the runtime knows (its own pinned allocations or hipHostRegister, e.g. a torch tensor made with
 // pin_memory = True)?  Then the copy engines read and write it directly and the staging copy through the handle's slots is skipped.
 static bool is_pinned(const void* ptr) {
   if (!ptr) return false;
@@ -665,15 +689,15 @@ int run_host_pipelined(gel_problem* p, int B, const double* x, double* res, doub
   int status = GEL_OK;
   auto retire = [&](gel_problem::Slot& sl) -> int {
     if (!sl.count) return GEL_OK;
-    HIPCHK(hipStreamSynchronize(sl.stream));
-    if (*sl.h_flag) {
-      *sl.h_flag = 0;
-      HIPCHK(hipMemsetAsync(sl.d_flag, 0, 4, sl.stream));
+    HIPCHK(hipStreamSynchronize(sl.stream.get()));
+    if (*sl.h_flag.get()) {
+      *sl.h_flag.get() = 0;
+      HIPCHK(hipMemsetAsync(sl.d_flag.get(), 0, 4, sl.stream.get()));
       status = GEL_NONFINITE;
     }
     if (!direct) {
-      if (sl.res) par_copy(res + (size_t)sl.first * nr, sl.h_res, (size_t)sl.count * nr * 8);
-      if (sl.jac && nj) par_copy(jvar + (size_t)sl.first * nj, sl.h_jv, (size_t)sl.count * nj * 8);
+      if (sl.res) par_copy(res + (size_t)sl.first * nr, sl.h_res.get(), (size_t)sl.count * nr * 8);
+      if (sl.jac && nj) par_copy(jvar + (size_t)sl.first * nj, sl.h_jv.get(), (size_t)sl.count * nj * 8);
     }
     sl.count = 0;
     return GEL_OK;
@@ -683,18 +707,19 @@ int run_host_pipelined(gel_problem* p, int B, const double* x, double* res, doub
     if ((rc = retire(sl))) break;
     const int64_t first = (int64_t)i * cap;
     const int count = (int)std::min<int64_t>(cap, B - first);
-    if (!direct) par_copy(sl.h_x, x + (size_t)first * nv, (size_t)count * nv * 8);
+    if (!direct) par_copy(sl.h_x.get(), x + (size_t)first * nv, (size_t)count * nv * 8);
     sl.first = first; sl.count = count; sl.res = res != nullptr; sl.jac = jvar != nullptr;
     gel::ProblemDev dv = p->dev;
-    dv.flag = sl.d_flag;
-    const double* const hx = direct ? x + (size_t)first * nv : sl.h_x;
-    double* const hres = direct ? res + (size_t)first * nr : sl.h_res;
-    double* const hjv = direct ? jvar + (size_t)first * nj : sl.h_jv;
-    if (hipMemcpyAsync(sl.d_x, hx, (size_t)count * nv * 8, hipMemcpyHostToDevice, sl.stream) != hipSuccess ||
-        launch_defects(p, dv, count, sl.d_x, res ? sl.d_res : nullptr, jvar ? sl.d_jv : nullptr, sl.stream) != hipSuccess ||
-        (res && hipMemcpyAsync(hres, sl.d_res, (size_t)count * nr * 8, hipMemcpyDeviceToHost, sl.stream) != hipSuccess) ||
-        (jvar && nj && hipMemcpyAsync(hjv, sl.d_jv, (size_t)count * nj * 8, hipMemcpyDeviceToHost, sl.stream) != hipSuccess) ||
-        hipMemcpyAsync(sl.h_flag, sl.d_flag, 4, hipMemcpyDeviceToHost, sl.stream) != hipSuccess) {
+    dv.flag = sl.d_flag.get();
+    const double* const hx = direct ? x + (size_t)first * nv : sl.h_x.get();
+    double* const hres = direct ? res + (size_t)first * nr : sl.h_res.get();
+    double* const hjv = direct ? jvar + (size_t)first * nj : sl.h_jv.get();
+    hipStream_t s = sl.stream.get();
+    if (hipMemcpyAsync(sl.d_x.get(), hx, (size_t)count * nv * 8, hipMemcpyHostToDevice, s) != hipSuccess ||
+        launch_defects(p, dv, count, sl.d_x.get(), res ? sl.d_res.get() : nullptr, jvar ? sl.d_jv.get() : nullptr, s) != hipSuccess ||
+        (res && hipMemcpyAsync(hres, sl.d_res.get(), (size_t)count * nr * 8, hipMemcpyDeviceToHost, s) != hipSuccess) ||
+        (jvar && nj && hipMemcpyAsync(hjv, sl.d_jv.get(), (size_t)count * nj * 8, hipMemcpyDeviceToHost, s) != hipSuccess) ||
+        hipMemcpyAsync(sl.h_flag.get(), sl.d_flag.get(), 4, hipMemcpyDeviceToHost, s) != hipSuccess) {
       rc = fail(GEL_ERR_HIP, "pipelined batch: enqueue failed");
       break;
     }
@@ -814,7 +839,7 @@ int gel_problem_create(const gel_problem_desc* d, gel_problem** out) {
     if (d->device < 0 || d->device >= ndev) return fail(GEL_ERR_ARG, "device ordinal out of range");
   }
 
-  gel_problem* p = new gel_problem();
+  std::unique_ptr<gel_problem> p(new gel_problem());   // released to the caller on success only
   p->device = d->device;
   p->um = d->unit_mass; p->up = d->unit_position; p->uv = d->unit_velocity; p->uu = d->unit_u; p->ut = d->unit_t;
   p->dx = d->dx;
@@ -823,6 +848,8 @@ int gel_problem_create(const gel_problem_desc* d, gel_problem** out) {
   // truncated series of the difference form are sized for (the reference's own dx = 1e-8 gives 0.064 m).
   p->fd_recompute = ((d->flags & GEL_FLAG_FD_RECOMPUTE) != 0) || !(std::fabs(d->dx * d->unit_position) <= 1.0);
   p->exact = (d->flags & GEL_FLAG_EXACT_DEFECT_JAC) != 0;
+  const char* fused = std::getenv("GEL_AERO_FUSED");
+  p->aero_fused = !(fused && fused[0] == '0');
   p->barC20 = (d->barC20 == 0.0) ? -0.484165371736e-3 : d->barC20;
   const int S = d->num_sections;
   int N = 0;
@@ -896,7 +923,7 @@ int gel_problem_create(const gel_problem_desc* d, gel_problem** out) {
     refs.push_back({slot, f, kind, 0});
   });
   for (int64_t s = 0; s < V; s++)
-    if (p->var_idx[(size_t)s] < 0) { delete p; return fail(GEL_ERR_ARG, "internal: compact slot without a COO entry"); }
+    if (p->var_idx[(size_t)s] < 0) return fail(GEL_ERR_ARG, "internal: compact slot without a COO entry");
   {
     // The gather map as constant-stride runs for the host scatter.  A per-node slot is used once or twice (a t0
     // column and its negated tf column): its k-th use over consecutive nodes is one run.  A phase scalar is used
@@ -970,12 +997,12 @@ int gel_problem_create(const gel_problem_desc* d, gel_problem** out) {
     for (int j0 = 0; j0 < p->ph[i].n; j0 += 64) p->chunk_phase.push_back(i);
   if (p->device == GEL_DEVICE_NONE) {
     p->dev.nchunks = (int32_t)p->chunk_phase.size();
-    *out = p;
+    *out = p.release();
     return GEL_OK;
   }
 
   // device side
-  if (hipSetDevice(p->device) != hipSuccess) { delete p; return fail(GEL_ERR_HIP, "hipSetDevice failed"); }
+  if (hipSetDevice(p->device) != hipSuccess) return fail(GEL_ERR_HIP, "hipSetDevice failed");
   std::vector<gel::PhaseDev> dph(S);
   std::vector<int32_t> node_phase(N);
   std::vector<double> Dt, tau;
@@ -1032,34 +1059,21 @@ int gel_problem_create(const gel_problem_desc* d, gel_problem** out) {
   // the phase-ordered list serves shard launches over ARBITRARY work-item ranges: no runs there
   std::vector<int4> shard_chunks = chunks;
   for (int4& c : shard_chunks) c.w = 1;
-  int rc = GEL_OK;
-  if ((rc = upload(&p->d_chunks, shard_chunks)) || (rc = upload(&p->d_chunks_sorted, sorted_chunks)) || (rc = upload(&p->d_Dsw, Dsw)) || (rc = upload(&p->d_Dst, Dst)) || (rc = upload(&p->d_phases, dph)) || (rc = upload(&p->d_node_phase, node_phase)) || (rc = upload(&p->d_Dt, Dt)) ||
-      (rc = upload(&p->d_tau, tau)) || (rc = upload(&p->d_tables, tables)) || (rc = upload(&p->d_cval, p->cval)) ||
-      (rc = upload(&p->d_src, p->src))) {
-    gel_problem_destroy(p);
-    return rc;
-  }
+  HIPCHK(p->d_chunks.upload(shard_chunks)); HIPCHK(p->d_chunks_sorted.upload(sorted_chunks)); HIPCHK(p->d_Dsw.upload(Dsw));
+  HIPCHK(p->d_Dst.upload(Dst)); HIPCHK(p->d_phases.upload(dph)); HIPCHK(p->d_node_phase.upload(node_phase)); HIPCHK(p->d_Dt.upload(Dt));
+  HIPCHK(p->d_tau.upload(tau)); HIPCHK(p->d_tables.upload(tables)); HIPCHK(p->d_cval.upload(p->cval)); HIPCHK(p->d_src.upload(p->src));
   {
     std::vector<int32_t> vdst, vsrc;
     for (size_t i = 0; i < p->src.size(); i++)
       if (p->src[i] != -1) { vdst.push_back((int32_t)i); vsrc.push_back(p->src[i]); }
     p->nvar_entries = (int32_t)vdst.size();
-    if (!vdst.empty() && ((rc = upload(&p->d_vdst, vdst)) || (rc = upload(&p->d_vsrc, vsrc)))) {
-      gel_problem_destroy(p);
-      return rc;
-    }
+    if (!vdst.empty()) { HIPCHK(p->d_vdst.upload(vdst)); HIPCHK(p->d_vsrc.upload(vsrc)); }
     std::vector<int32_t> vline;
     for (int32_t d : vdst)
       if (vline.empty() || vline.back() != d / 8) vline.push_back(d / 8);
     p->nvar_lines = (int32_t)vline.size();
-    if (!vline.empty() && (rc = upload(&p->d_vline, vline))) {
-      gel_problem_destroy(p);
-      return rc;
-    }
-    if (!p->coo_tab.empty() && (rc = upload(&p->d_coo, p->coo_tab))) {
-      gel_problem_destroy(p);
-      return rc;
-    }
+    if (!vline.empty()) HIPCHK(p->d_vline.upload(vline));
+    if (!p->coo_tab.empty()) HIPCHK(p->d_coo.upload(p->coo_tab));
   }
   {
     // one-phase sub-problems for the phase-by-phase forward difference (gel_jac_fd)
@@ -1075,26 +1089,20 @@ int gel_problem_create(const gel_problem_desc* d, gel_problem** out) {
       p->sub_nchunks.push_back(cnt);
       c0 += cnt;
       p->sub_col0.push_back((int32_t)colmap.size());
-      phase_columns(p, i, colmap);
+      phase_columns(p.get(), i, colmap);
     }
-    if ((rc = upload(&p->d_subphases, sub)) || (rc = upload(&p->d_subchunks, subchunks)) || (rc = upload(&p->d_colmap, colmap))) {
-      gel_problem_destroy(p);
-      return rc;
-    }
+    HIPCHK(p->d_subphases.upload(sub)); HIPCHK(p->d_subchunks.upload(subchunks)); HIPCHK(p->d_colmap.upload(colmap));
   }
-  if (hipMalloc((void**)&p->d_flag, 4) != hipSuccess || hipMemset(p->d_flag, 0, 4) != hipSuccess ||
-      hipMalloc((void**)&p->d_done, 4) != hipSuccess || hipMemset(p->d_done, 0, 4) != hipSuccess ||
-      hipHostMalloc((void**)&p->h_done, 4) != hipSuccess ||
-      hipHostMalloc((void**)&p->h_flag, 4) != hipSuccess || hipStreamCreate(&p->stream) != hipSuccess) {
-    gel_problem_destroy(p);
+  if (p->d_flag.reserve(1) != hipSuccess || hipMemset(p->d_flag.get(), 0, 4) != hipSuccess ||
+      p->d_done.reserve(1) != hipSuccess || hipMemset(p->d_done.get(), 0, 4) != hipSuccess || p->h_done.reserve(1) != hipSuccess ||
+      p->h_flag.reserve(1) != hipSuccess || p->stream.create() != hipSuccess)
     return fail(GEL_ERR_HIP, "device allocation failed");
-  }
-  *p->h_flag = 0;
+  *p->h_flag.get() = 0;
   gel::ProblemDev& dv = p->dev;
   dv.S = S; dv.N = N; dv.M = M; dv.nvars = dm.num_vars; dv.Kw = d->wind_rows; dv.Kc = d->ca_rows; dv.V = V;
-  dv.phases = p->d_phases; dv.node_phase = p->d_node_phase; dv.Dt = p->d_Dt; dv.tau = p->d_tau; dv.tables = p->d_tables;
-  dv.flag = p->d_flag;
-  dv.nchunks = (int32_t)chunks.size(); dv.chunks = p->d_chunks_sorted; dv.Dsw = p->d_Dsw; dv.Dst = p->d_Dst;
+  dv.phases = p->d_phases.get(); dv.node_phase = p->d_node_phase.get(); dv.Dt = p->d_Dt.get(); dv.tau = p->d_tau.get();
+  dv.tables = p->d_tables.get(); dv.flag = p->d_flag.get();
+  dv.nchunks = (int32_t)chunks.size(); dv.chunks = p->d_chunks_sorted.get(); dv.Dsw = p->d_Dsw.get(); dv.Dst = p->d_Dst.get();
   dv.park_off = (int32_t)((tables.size() + 1) / 2 * 2);
   {
     // D.X path.  fp64 MFMA and fp64 VALU instructions share the SIMD's fp64 datapath on this part (measured: their busy
@@ -1121,34 +1129,11 @@ int gel_problem_create(const gel_problem_desc* d, gel_problem** out) {
   }
   dv.um = p->um; dv.up = p->up; dv.uv = p->uv; dv.uu = p->uu; dv.ut = p->ut; dv.dx = p->dx; dv.barC20 = p->barC20;
   dv.inv_uv = 1.0 / p->uv; dv.inv_dx = 1.0 / p->dx; dv.kpt = p->uv * p->ut / 2.0 / p->up; dv.hT = p->ut * 0.5;
-  *out = p;
+  *out = p.release();
   return GEL_OK;
 }
 
 int gel_problem_destroy(gel_problem* p) {
-  if (!p) return GEL_OK;
-  if (p->device == GEL_DEVICE_NONE) { delete p; return GEL_OK; }
-  hipSetDevice(p->device);
-  if (p->stream) { hipStreamSynchronize(p->stream); hipStreamDestroy(p->stream); }
-  hipFree(p->d_phases); hipFree(p->d_node_phase); hipFree(p->d_chunks); hipFree(p->d_chunks_sorted); hipFree(p->d_Dsw); hipFree(p->d_Dst); hipFree(p->d_Dt); hipFree(p->d_tau); hipFree(p->d_tables);
-  hipFree(p->d_vdst); hipFree(p->d_vsrc); hipFree(p->d_vline); hipFree(p->d_coo);
-  if (p->h_full) hipHostFree(p->h_full);
-  if (p->cb_res) hipHostFree(p->cb_res);
-  for (int i = 0; i < 2; i++) if (p->cb_x[i]) hipHostFree(p->cb_x[i]);
-  hipFree(p->d_cval); hipFree(p->d_src); hipFree(p->d_flag); hipFree(p->d_unit_base); hipFree(p->d_shard_pos);
-  hipFree(p->d_aero_nodes); hipFree(p->d_aero_x); hipFree(p->d_aero_out); hipFree(p->d_aero_ph); hipFree(p->d_aero_part_nodes[0]); hipFree(p->d_aero_part_nodes[1]);
-  free_slots(p);
-  hipFree(p->d_x); hipFree(p->d_res); hipFree(p->d_jv);
-  if (p->h_x) hipHostFree(p->h_x);
-  if (p->h_res) hipHostFree(p->h_res);
-  if (p->h_jv) hipHostFree(p->h_jv);
-  if (p->h_flag) hipHostFree(p->h_flag);
-  if (p->h_aero) hipHostFree(p->h_aero);
-  if (p->h_rows) hipHostFree(p->h_rows);
-  hipFree(p->d_lin_rows); hipFree(p->d_fn_rows); hipFree(p->d_rows_x); hipFree(p->d_rows_out);
-  hipFree(p->jfd_x); hipFree(p->jfd_Xp); hipFree(p->jfd_res); hipFree(p->jfd_J);
-  hipFree(p->d_done); if (p->h_done) hipHostFree(const_cast<int32_t*>(p->h_done));
-  hipFree(p->d_subphases); hipFree(p->d_subchunks); hipFree(p->d_colmap);
   delete p;
   return GEL_OK;
 }
@@ -1210,19 +1195,19 @@ int gel_pinned_buffers(gel_problem* p, double** res, double** vals_full, double*
   if (!p) return fail(GEL_ERR_ARG, "null argument");
   NEED_DEVICE(p);
   if (int rc = ensure_full(p)) return rc;
-  if (res) *res = p->cb_res;
-  if (vals_full) *vals_full = p->h_full;
-  if (x0) *x0 = p->cb_x[0];
-  if (x1) *x1 = p->cb_x[1];
+  if (res) *res = p->cb_res.get();
+  if (vals_full) *vals_full = p->h_full.get();
+  if (x0) *x0 = p->cb_x[0].get();
+  if (x1) *x1 = p->cb_x[1].get();
   return GEL_OK;
 }
 
 int gel_eval_residual(gel_problem* p, const double* x, double* res) {
   if (!p || !x || !res) return fail(GEL_ERR_ARG, "null argument");
-  const bool own = p->cb_res && res == p->cb_res;   // the caller named the handle's pinned vector: the kernel writes it, no copy
-  const int rc = run_host(p, 1, x, true, false, own ? p->cb_res : nullptr);
+  const bool own = p->cb_res.get() && res == p->cb_res.get();   // the caller named the handle's pinned vector: the kernel writes it, no copy
+  const int rc = run_host(p, 1, x, true, false, own ? p->cb_res.get() : nullptr);
   if (rc < 0) return rc;
-  if (!own) std::memcpy(res, p->h_res, (size_t)11 * p->dims.N * 8);
+  if (!own) std::memcpy(res, p->h_res.get(), (size_t)11 * p->dims.N * 8);
   return rc;
 }
 
@@ -1235,12 +1220,12 @@ int gel_eval(gel_problem* p, const double* x, double* res, double* vals_full, in
   NEED_DEVICE(p);
   bool coo = coo_direct(p);
   if (coo) { if (int rc0 = ensure_full(p)) return rc0; }
-  const bool own = res && p->cb_res && res == p->cb_res;
-  const int rc = run_host(p, 1, x, res != nullptr, true, own ? p->cb_res : nullptr, &coo);
+  const bool own = res && p->cb_res.get() && res == p->cb_res.get();
+  const int rc = run_host(p, 1, x, res != nullptr, true, own ? p->cb_res.get() : nullptr, &coo);
   if (rc < 0) return rc;
-  if (res && !own) std::memcpy(res, p->h_res, (size_t)11 * p->dims.N * 8);
+  if (res && !own) std::memcpy(res, p->h_res.get(), (size_t)11 * p->dims.N * 8);
   if (coo) finish_full(p, vals_full, fill_constants);
-  else scatter_full(p, p->h_jv, vals_full, fill_constants);
+  else scatter_full(p, p->h_jv.get(), vals_full, fill_constants);
   return rc;
 }
 
@@ -1251,15 +1236,15 @@ int gel_eval_batch(gel_problem* p, int32_t B, const double* x, double* res, doub
   if ((size_t)B * 8 * (size_t)std::max<int64_t>(p->dims.num_var_entries, 1) > kPipeBytes) return run_host_pipelined(p, B, x, res, jvar);
   const int rc = run_host(p, B, x, res != nullptr, jvar != nullptr);
   if (rc < 0) return rc;
-  if (res) std::memcpy(res, p->h_res, (size_t)B * 11 * p->dims.N * 8);
-  if (jvar) std::memcpy(jvar, p->h_jv, (size_t)B * p->dims.num_var_entries * 8);
+  if (res) std::memcpy(res, p->h_res.get(), (size_t)B * 11 * p->dims.N * 8);
+  if (jvar) std::memcpy(jvar, p->h_jv.get(), (size_t)B * p->dims.num_var_entries * 8);
   return rc;
 }
 
 int gel_eval_batch_device(gel_problem* p, int32_t B, const double* d_x, double* d_res, double* d_jvar, void* stream) {
   if (!p || !d_x || B < 1 || (!d_res && !d_jvar)) return fail(GEL_ERR_ARG, "bad argument");
   NEED_DEVICE(p);
-  HIPCHK(launch_defects(p, p->dev, B, d_x, d_res, d_jvar, stream ? (hipStream_t)stream : p->stream));
+  HIPCHK(launch_defects(p, p->dev, B, d_x, d_res, d_jvar, stream ? (hipStream_t)stream : p->stream.get()));
   return GEL_OK;
 }
 
@@ -1273,11 +1258,11 @@ int gel_eval_shard_units_device(gel_problem* p, int32_t B, const double* d_x, do
     return fail(GEL_ERR_ARG, "unit range out of bounds");
   if (unit_count == 0) return GEL_OK;
   gel::ProblemDev dv = p->dev;
-  dv.chunks = p->d_chunks;  // unit ids refer to the phase-ordered list
+  dv.chunks = p->d_chunks.get();  // unit ids refer to the phase-ordered list
   dv.chunk0 = 0;
   dv.unit0 = unit_begin;
   dv.nunits = unit_count;
-  HIPCHK(gel::launch_eval(dv, B, d_x, d_res, d_jvar, stream ? (hipStream_t)stream : p->stream));
+  HIPCHK(gel::launch_eval(dv, B, d_x, d_res, d_jvar, stream ? (hipStream_t)stream : p->stream.get()));
   return GEL_OK;
 }
 
@@ -1391,21 +1376,20 @@ int gel_shard_plan(gel_problem* p, int32_t nranks, const int32_t* unit_begin, in
   }
   for (int64_t v : pos)
     if (v < 0) return fail(GEL_ERR_ARG, "shard plan: an output entry without an owner (internal)");
+  // the device copies first: a failure leaves the previous plan in place, on the host and on the device
+  DeviceArray<int64_t> d_base, d_pos;
+  if (p->device != GEL_DEVICE_NONE) {
+    HIPCHK(hipSetDevice(p->device));
+    HIPCHK(d_base.upload(base)); HIPCHK(d_pos.upload(pos));
+  }
+  p->d_unit_base = std::move(d_base);
+  p->d_shard_pos = std::move(d_pos);
   p->shard_begin.assign(unit_begin, unit_begin + nranks + 1);
   p->unit_base = base;
   p->shard_width = w;
   *width = w;
   if (res_pos) std::memcpy(res_pos, pos.data(), sizeof(int64_t) * 11 * (size_t)N);
   if (jvar_pos) std::memcpy(jvar_pos, pos.data() + (size_t)11 * N, sizeof(int64_t) * (size_t)V);
-  if (p->device >= 0) {
-    HIPCHK(hipSetDevice(p->device));
-    hipFree(p->d_unit_base); hipFree(p->d_shard_pos);
-    p->d_unit_base = nullptr; p->d_shard_pos = nullptr;
-    HIPCHK(hipMalloc(&p->d_unit_base, sizeof(int64_t) * (size_t)nunits));
-    HIPCHK(hipMemcpy(p->d_unit_base, base.data(), sizeof(int64_t) * (size_t)nunits, hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc(&p->d_shard_pos, sizeof(int64_t) * pos.size()));
-    HIPCHK(hipMemcpy(p->d_shard_pos, pos.data(), sizeof(int64_t) * pos.size(), hipMemcpyHostToDevice));
-  }
   return GEL_OK;
 }
 
@@ -1424,20 +1408,20 @@ int gel_eval_shard_packed_device(gel_problem* p, int32_t B, const double* d_x, d
   NO_EXACT(p, "gel_eval_shard_packed_device");
   NEED_DEVICE(p);
   if (int rc = check_plan(p, nranks_expected, width_expected)) return rc;
-  if (!p->d_unit_base) return fail(GEL_ERR_ARG, "gel_shard_plan has not been called on this handle");
+  if (!p->d_unit_base.get()) return fail(GEL_ERR_ARG, "gel_shard_plan has not been called on this handle");
   const int nranks = (int)p->shard_begin.size() - 1;
   if (rank < 0 || rank >= nranks) return fail(GEL_ERR_ARG, "rank outside the plan");
   const int32_t u0 = p->shard_begin[rank], cnt = p->shard_begin[rank + 1] - u0;
   if (cnt == 0) return GEL_OK;
   gel::ProblemDev dv = p->dev;
-  dv.chunks = p->d_chunks;  // unit ids refer to the phase-ordered list
+  dv.chunks = p->d_chunks.get();  // unit ids refer to the phase-ordered list
   dv.chunk0 = 0;
   dv.unit0 = u0;
   dv.nunits = cnt;
   dv.shard_width = p->shard_width;
-  dv.unit_base = p->d_unit_base;
+  dv.unit_base = p->d_unit_base.get();
   double* slice = d_out + (size_t)rank * (size_t)B * (size_t)p->shard_width;
-  HIPCHK(gel::launch_eval(dv, B, d_x, slice, slice, stream ? (hipStream_t)stream : p->stream));
+  HIPCHK(gel::launch_eval(dv, B, d_x, slice, slice, stream ? (hipStream_t)stream : p->stream.get()));
   return GEL_OK;
 }
 
@@ -1446,58 +1430,58 @@ int gel_shard_unpack_device(gel_problem* p, int32_t B, const double* d_out, doub
   if (!p || !d_out || B < 1 || (!d_res && !d_jvar)) return fail(GEL_ERR_ARG, "bad argument");
   NEED_DEVICE(p);
   if (int rc = check_plan(p, nranks_expected, width_expected)) return rc;
-  if (!p->d_shard_pos) return fail(GEL_ERR_ARG, "gel_shard_plan has not been called on this handle");
-  HIPCHK(gel::launch_shard_unpack(11 * p->dims.N, p->dims.num_var_entries, p->shard_width, B, p->d_shard_pos, d_out, d_res, d_jvar,
-                                  stream ? (hipStream_t)stream : p->stream));
+  if (!p->d_shard_pos.get()) return fail(GEL_ERR_ARG, "gel_shard_plan has not been called on this handle");
+  HIPCHK(gel::launch_shard_unpack(11 * p->dims.N, p->dims.num_var_entries, p->shard_width, B, p->d_shard_pos.get(), d_out, d_res, d_jvar,
+                                  stream ? (hipStream_t)stream : p->stream.get()));
   return GEL_OK;
 }
 
 int gel_fill_full_device(gel_problem* p, int32_t B, double* d_jfull, void* stream) {
   if (!p || !d_jfull || B < 1) return fail(GEL_ERR_ARG, "bad argument");
   NEED_DEVICE(p);
-  HIPCHK(gel::launch_fill_full(p->dims.total_nnz, B, p->d_cval, d_jfull, stream ? (hipStream_t)stream : p->stream));
+  HIPCHK(gel::launch_fill_full(p->dims.total_nnz, B, p->d_cval.get(), d_jfull, stream ? (hipStream_t)stream : p->stream.get()));
   return GEL_OK;
 }
 
 int gel_update_full_device(gel_problem* p, int32_t B, const double* d_jvar, double* d_jfull, void* stream) {
   if (!p || !d_jvar || !d_jfull || B < 1) return fail(GEL_ERR_ARG, "bad argument");
   NEED_DEVICE(p);
-  HIPCHK(gel::launch_update_full(p->dims.total_nnz, p->dims.num_var_entries, p->nvar_entries, B, p->d_vdst, p->d_vsrc,
-                                 p->nvar_lines, p->d_vline, p->d_src, p->d_cval, d_jvar, d_jfull,
-                                 stream ? (hipStream_t)stream : p->stream));
+  HIPCHK(gel::launch_update_full(p->dims.total_nnz, p->dims.num_var_entries, p->nvar_entries, B, p->d_vdst.get(), p->d_vsrc.get(),
+                                 p->nvar_lines, p->d_vline.get(), p->d_src.get(), p->d_cval.get(), d_jvar, d_jfull,
+                                 stream ? (hipStream_t)stream : p->stream.get()));
   return GEL_OK;
 }
 
 int gel_eval_full_device(gel_problem* p, int32_t B, const double* d_x, double* d_res, double* d_jvar, double* d_jfull, void* stream) {
   if (!p || !d_x || !d_jvar || !d_jfull || B < 1) return fail(GEL_ERR_ARG, "bad argument");
   NEED_DEVICE(p);
-  hipStream_t s = stream ? (hipStream_t)stream : p->stream;
+  hipStream_t s = stream ? (hipStream_t)stream : p->stream.get();
   gel::ProblemDev dv = p->dev;
   dv.cached_out = 1;   // the compact values are read again by the update below: kept in the caches when the launch fits them
   HIPCHK(launch_defects(p, dv, B, d_x, d_res, d_jvar, s));
-  HIPCHK(gel::launch_update_full(p->dims.total_nnz, p->dims.num_var_entries, p->nvar_entries, B, p->d_vdst, p->d_vsrc,
-                                 p->nvar_lines, p->d_vline, p->d_src, p->d_cval, d_jvar, d_jfull, s));
+  HIPCHK(gel::launch_update_full(p->dims.total_nnz, p->dims.num_var_entries, p->nvar_entries, B, p->d_vdst.get(), p->d_vsrc.get(),
+                                 p->nvar_lines, p->d_vline.get(), p->d_src.get(), p->d_cval.get(), d_jvar, d_jfull, s));
   return GEL_OK;
 }
 
 int gel_expand_full_device(gel_problem* p, int32_t B, const double* d_jvar, double* d_jfull, void* stream) {
   if (!p || !d_jvar || !d_jfull || B < 1) return fail(GEL_ERR_ARG, "bad argument");
   NEED_DEVICE(p);
-  HIPCHK(gel::launch_expand(p->dims.total_nnz, p->dims.num_var_entries, B, p->d_cval, p->d_src, d_jvar, d_jfull,
-                            stream ? (hipStream_t)stream : p->stream));
+  HIPCHK(gel::launch_expand(p->dims.total_nnz, p->dims.num_var_entries, B, p->d_cval.get(), p->d_src.get(), d_jvar, d_jfull,
+                            stream ? (hipStream_t)stream : p->stream.get()));
   return GEL_OK;
 }
 
 int gel_sync(gel_problem* p, void* stream) {
   if (!p) return fail(GEL_ERR_ARG, "null argument");
   NEED_DEVICE(p);
-  hipStream_t s = stream ? (hipStream_t)stream : p->stream;
-  HIPCHK(hipMemcpyAsync(p->h_flag, p->d_flag, 4, hipMemcpyDeviceToHost, s));
+  hipStream_t s = stream ? (hipStream_t)stream : p->stream.get();
+  HIPCHK(hipMemcpyAsync(p->h_flag.get(), p->d_flag.get(), 4, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
-  if (*p->h_flag) {
-    HIPCHK(hipMemsetAsync(p->d_flag, 0, 4, s));
+  if (*p->h_flag.get()) {
+    HIPCHK(hipMemsetAsync(p->d_flag.get(), 0, 4, s));
     HIPCHK(hipStreamSynchronize(s));
-    *p->h_flag = 0;
+    *p->h_flag.get() = 0;
     return GEL_NONFINITE;
   }
   return GEL_OK;
@@ -1507,7 +1491,7 @@ int gel_sync(gel_problem* p, void* stream) {
 // working set: x, the perturbed local vectors of the LARGEST phase (reused phase after phase), the residuals of every phase's
 // perturbed vectors (kept while x stays the same: the four groups are asked for one after the other)
 static int jfd_allocate(gel_problem* p) {
-  if (p->jfd_x) return GEL_OK;
+  if (p->jfd_x.get()) return GEL_OK;
   const size_t nv = (size_t)p->dims.num_vars;
   size_t xp_max = 0, res_tot = 0;
   p->sub_res0.clear();
@@ -1517,12 +1501,10 @@ static int jfd_allocate(gel_problem* p) {
     p->sub_res0.push_back(res_tot);
     res_tot += (nloc + 1) * 11 * n;
   }
-  if (hipMalloc((void**)&p->jfd_x, nv * 8) != hipSuccess || hipMalloc((void**)&p->jfd_Xp, xp_max * 8) != hipSuccess ||
-      hipMalloc((void**)&p->jfd_res, res_tot * 8) != hipSuccess) {
-    hipFree(p->jfd_x); hipFree(p->jfd_Xp); hipFree(p->jfd_res);
-    p->jfd_x = p->jfd_Xp = p->jfd_res = nullptr;   // all or nothing: a later call must not find a partial set
+  DeviceArray<double> jx, jxp, jres;   // all or nothing: a later call must not find a partial set
+  if (jx.reserve(nv) != hipSuccess || jxp.reserve(xp_max) != hipSuccess || jres.reserve(res_tot) != hipSuccess)
     return fail(GEL_ERR_ALLOC, "gel_jac_fd: device allocation failed");
-  }
+  p->jfd_x = std::move(jx); p->jfd_Xp = std::move(jxp); p->jfd_res = std::move(jres);
   return GEL_OK;
 }
 
@@ -1532,10 +1514,10 @@ static int jfd_evaluate(gel_problem* p, const double* d_x, hipStream_t s) {
     const int n = p->ph[i].n, nloc = 13 * n + 13;
     gel::ProblemDev dv = p->dev;   // the phase as a one-phase problem: same tables, D, tau; local index space
     dv.S = 1; dv.N = n; dv.M = n + 1; dv.nvars = nloc; dv.V = 0;
-    dv.phases = p->d_subphases + i;
-    dv.chunks = p->d_subchunks + p->sub_chunk0[i]; dv.nchunks = p->sub_nchunks[i]; dv.chunk0 = 0;
-    HIPCHK(gel::launch_perturb_local(nloc, p->dx, d_x, p->d_colmap + p->sub_col0[i], p->jfd_Xp, s));
-    HIPCHK(gel::launch_eval(dv, nloc + 1, p->jfd_Xp, p->jfd_res + p->sub_res0[i], nullptr, s));
+    dv.phases = p->d_subphases.get() + i;
+    dv.chunks = p->d_subchunks.get() + p->sub_chunk0[i]; dv.nchunks = p->sub_nchunks[i]; dv.chunk0 = 0;
+    HIPCHK(gel::launch_perturb_local(nloc, p->dx, d_x, p->d_colmap.get() + p->sub_col0[i], p->jfd_Xp.get(), s));
+    HIPCHK(gel::launch_eval(dv, nloc + 1, p->jfd_Xp.get(), p->jfd_res.get() + p->sub_res0[i], nullptr, s));
   }
   return GEL_OK;
 }
@@ -1553,11 +1535,11 @@ static int jfd_quotients(gel_problem* p, int group, int blocks, double* d_J, hip
     const int n = p->ph[i].n, nloc = 13 * n + 13;
     const int roff_loc = (group == 0) ? 0 : (group == 1) ? n : (group == 2) ? 4 * n : 7 * n;
     if (blocks)
-      HIPCHK(gel::launch_quotient_local(nloc, 11 * n, roff_loc, w * n, p->dx, p->jfd_res + p->sub_res0[i], d_J + off, (long long)nloc, 0,
+      HIPCHK(gel::launch_quotient_local(nloc, 11 * n, roff_loc, w * n, p->dx, p->jfd_res.get() + p->sub_res0[i], d_J + off, (long long)nloc, 0,
                                         nullptr, s));
     else
-      HIPCHK(gel::launch_quotient_local(nloc, 11 * n, roff_loc, w * n, p->dx, p->jfd_res + p->sub_res0[i], d_J, (long long)nv,
-                                        w * p->ph[i].ua, p->d_colmap + p->sub_col0[i], s));
+      HIPCHK(gel::launch_quotient_local(nloc, 11 * n, roff_loc, w * n, p->dx, p->jfd_res.get() + p->sub_res0[i], d_J, (long long)nv,
+                                        w * p->ph[i].ua, p->d_colmap.get() + p->sub_col0[i], s));
     off += (size_t)w * n * nloc;
   }
   *count = blocks ? off : nrows * nv;
@@ -1579,39 +1561,34 @@ static int jfd_host(gel_problem* p, int32_t group, const double* x, double* J, i
   if ((rc = jfd_allocate(p))) return rc;
   const size_t nv = (size_t)p->dims.num_vars, nrows = (size_t)p->dims.num_rows[group];
   const size_t need = blocks ? jfd_block_doubles(p, group) : nrows * nv;
-  if (p->jfd_J_cap < need) {
-    hipFree(p->jfd_J);
-    p->jfd_J = nullptr; p->jfd_J_cap = 0;
-    HIPCHK(hipMalloc((void**)&p->jfd_J, need * 8));
-    p->jfd_J_cap = need;
-  }
+  HIPCHK(p->jfd_J.reserve(need));
   // the perturbed evaluations -- unless the same x was just differenced
   if (p->jfd_last_x.size() != nv || std::memcmp(p->jfd_last_x.data(), x, nv * 8) != 0) {
     p->jfd_last_x.clear();
-    HIPCHK(hipMemcpyAsync(p->jfd_x, x, nv * 8, hipMemcpyHostToDevice, p->stream));
-    if ((rc = jfd_evaluate(p, p->jfd_x, p->stream))) return rc;
-    HIPCHK(hipMemcpyAsync(p->h_flag, p->d_flag, 4, hipMemcpyDeviceToHost, p->stream));
-    HIPCHK(hipStreamSynchronize(p->stream));
+    HIPCHK(hipMemcpyAsync(p->jfd_x.get(), x, nv * 8, hipMemcpyHostToDevice, p->stream.get()));
+    if ((rc = jfd_evaluate(p, p->jfd_x.get(), p->stream.get()))) return rc;
+    HIPCHK(hipMemcpyAsync(p->h_flag.get(), p->d_flag.get(), 4, hipMemcpyDeviceToHost, p->stream.get()));
+    HIPCHK(hipStreamSynchronize(p->stream.get()));
     p->jfd_status = GEL_OK;
-    if (*p->h_flag) { *p->h_flag = 0; HIPCHK(hipMemsetAsync(p->d_flag, 0, 4, p->stream)); p->jfd_status = GEL_NONFINITE; }
+    if (*p->h_flag.get()) { *p->h_flag.get() = 0; HIPCHK(hipMemsetAsync(p->d_flag.get(), 0, 4, p->stream.get())); p->jfd_status = GEL_NONFINITE; }
     p->jfd_last_x.assign(x, x + nv);
   }
   size_t total = 0;
-  if ((rc = jfd_quotients(p, group, blocks, p->jfd_J, p->stream, &total))) return rc;
-  HIPCHK(hipStreamSynchronize(p->stream));
+  if ((rc = jfd_quotients(p, group, blocks, p->jfd_J.get(), p->stream.get(), &total))) return rc;
+  HIPCHK(hipStreamSynchronize(p->stream.get()));
   // J -> caller through the two pinned slots: D2H of piece i+1 overlaps the host copy of piece i
   const size_t piece = (size_t)p->pipe_evals * (size_t)std::max<int64_t>(p->dims.num_var_entries, 1);
   size_t pend_off[2] = {0, 0}, pend_n[2] = {0, 0};
   for (size_t off = 0, i = 0; off < total || pend_n[0] || pend_n[1]; i++) {
     gel_problem::Slot& sl = p->slot[i & 1];
     if (pend_n[i & 1]) {
-      HIPCHK(hipStreamSynchronize(sl.stream));
-      par_copy(J + pend_off[i & 1], sl.h_jv, pend_n[i & 1] * 8);
+      HIPCHK(hipStreamSynchronize(sl.stream.get()));
+      par_copy(J + pend_off[i & 1], sl.h_jv.get(), pend_n[i & 1] * 8);
       pend_n[i & 1] = 0;
     }
     if (off < total) {
       const size_t n = std::min(piece, total - off);
-      HIPCHK(hipMemcpyAsync(sl.h_jv, p->jfd_J + off, n * 8, hipMemcpyDeviceToHost, sl.stream));
+      HIPCHK(hipMemcpyAsync(sl.h_jv.get(), p->jfd_J.get() + off, n * 8, hipMemcpyDeviceToHost, sl.stream.get()));
       pend_off[i & 1] = off; pend_n[i & 1] = n;
       off += n;
     }
@@ -1652,7 +1629,7 @@ int gel_jac_fd_device(gel_problem* p, int32_t group, const double* d_x, double* 
   HIPCHK(hipSetDevice(p->device));
   int rc = jfd_allocate(p);
   if (rc) return rc;
-  hipStream_t s = stream ? (hipStream_t)stream : p->stream;
+  hipStream_t s = stream ? (hipStream_t)stream : p->stream.get();
   p->jfd_last_x.clear();   // the residuals kept for gel_jac_fd's host callers are overwritten
   if ((rc = jfd_evaluate(p, d_x, s))) return rc;
   size_t total = 0;
@@ -1661,15 +1638,6 @@ int gel_jac_fd_device(gel_problem* p, int32_t group, const double* d_x, double* 
 
 // --------------------------- RHS / point hooks ---------------------------
 namespace {
-struct DevBuf {
-  double* p = nullptr;
-  ~DevBuf() { if (p) hipFree(p); }
-  int put(const double* h, size_t n) {
-    HIPCHK(hipMalloc((void**)&p, std::max<size_t>(1, n) * 8));
-    if (h && n) HIPCHK(hipMemcpy(p, h, n * 8, hipMemcpyHostToDevice));
-    return GEL_OK;
-  }
-};
 int need_device() {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
@@ -1688,15 +1656,13 @@ int gel_dynamics_velocity(int32_t n, const double* mass_e, const double* pos_e, 
   if (rc) return rc;
   if (const char* why = gel::check_tables(wind, Kw, ca, Kc)) return fail(GEL_ERR_ARG, why);
   const std::vector<double> tables = gel::build_tables(wind, Kw, ca, Kc);
-  DevBuf m, r, v, q, tt, tb, o;
-  if ((rc = m.put(mass_e, n)) || (rc = r.put(pos_e, 3 * (size_t)n)) || (rc = v.put(vel_e, 3 * (size_t)n)) ||
-      (rc = q.put(quat, 4 * (size_t)n)) || (rc = tt.put(t, n)) || (rc = tb.put(tables.data(), tables.size())) ||
-      (rc = o.put(nullptr, 3 * (size_t)n)))
-    return rc;
+  DeviceArray<double> m, r, v, q, tt, tb, o;
+  HIPCHK(m.upload(mass_e, n)); HIPCHK(r.upload(pos_e, 3 * (size_t)n)); HIPCHK(v.upload(vel_e, 3 * (size_t)n));
+  HIPCHK(q.upload(quat, 4 * (size_t)n)); HIPCHK(tt.upload(t, n)); HIPCHK(tb.upload(tables)); HIPCHK(o.reserve(3 * (size_t)n));
   if (barC20 == 0.0) barC20 = -0.484165371736e-3;
-  HIPCHK(gel::launch_rhs_vel(true, n, m.p, r.p, v.p, q.p, tt.p, tb.p, Kw, Kc, param[0], param[2], param[4], units[0],
-                             units[1], units[2], barC20, o.p, nullptr));
-  HIPCHK(hipMemcpy(out, o.p, 3 * (size_t)n * 8, hipMemcpyDeviceToHost));
+  HIPCHK(gel::launch_rhs_vel(true, n, m.get(), r.get(), v.get(), q.get(), tt.get(), tb.get(), Kw, Kc, param[0], param[2], param[4],
+                             units[0], units[1], units[2], barC20, o.get(), nullptr));
+  HIPCHK(hipMemcpy(out, o.get(), 3 * (size_t)n * 8, hipMemcpyDeviceToHost));
   return GEL_OK;
 }
 
@@ -1706,14 +1672,12 @@ int gel_dynamics_velocity_NoAir(int32_t n, const double* mass_e, const double* p
   if (n == 0) return GEL_OK;
   int rc = need_device();
   if (rc) return rc;
-  DevBuf m, r, q, o;
-  if ((rc = m.put(mass_e, n)) || (rc = r.put(pos_e, 3 * (size_t)n)) || (rc = q.put(quat, 4 * (size_t)n)) ||
-      (rc = o.put(nullptr, 3 * (size_t)n)))
-    return rc;
+  DeviceArray<double> m, r, q, o;
+  HIPCHK(m.upload(mass_e, n)); HIPCHK(r.upload(pos_e, 3 * (size_t)n)); HIPCHK(q.upload(quat, 4 * (size_t)n)); HIPCHK(o.reserve(3 * (size_t)n));
   if (barC20 == 0.0) barC20 = -0.484165371736e-3;
-  HIPCHK(gel::launch_rhs_vel(false, n, m.p, r.p, nullptr, q.p, nullptr, nullptr, 0, 0, param[0], 0.0, 0.0, units[0],
-                             units[1], units[2], barC20, o.p, nullptr));
-  HIPCHK(hipMemcpy(out, o.p, 3 * (size_t)n * 8, hipMemcpyDeviceToHost));
+  HIPCHK(gel::launch_rhs_vel(false, n, m.get(), r.get(), nullptr, q.get(), nullptr, nullptr, 0, 0, param[0], 0.0, 0.0, units[0],
+                             units[1], units[2], barC20, o.get(), nullptr));
+  HIPCHK(hipMemcpy(out, o.get(), 3 * (size_t)n * 8, hipMemcpyDeviceToHost));
   return GEL_OK;
 }
 
@@ -1722,24 +1686,12 @@ int gel_dynamics_quaternion(int32_t n, const double* quat, const double* u_e, do
   if (n == 0) return GEL_OK;
   int rc = need_device();
   if (rc) return rc;
-  DevBuf q, u, o;
-  if ((rc = q.put(quat, 4 * (size_t)n)) || (rc = u.put(u_e, 2 * (size_t)n)) || (rc = o.put(nullptr, 4 * (size_t)n))) return rc;
-  HIPCHK(gel::launch_rhs_quat(n, q.p, u.p, unit_u, o.p, nullptr));
-  HIPCHK(hipMemcpy(out, o.p, 4 * (size_t)n * 8, hipMemcpyDeviceToHost));
+  DeviceArray<double> q, u, o;
+  HIPCHK(q.upload(quat, 4 * (size_t)n)); HIPCHK(u.upload(u_e, 2 * (size_t)n)); HIPCHK(o.reserve(4 * (size_t)n));
+  HIPCHK(gel::launch_rhs_quat(n, q.get(), u.get(), unit_u, o.get(), nullptr));
+  HIPCHK(hipMemcpy(out, o.get(), 4 * (size_t)n * 8, hipMemcpyDeviceToHost));
   return GEL_OK;
 }
-
-namespace {
-// grows a device or pinned buffer; on failure the buffer is gone and its capacity is 0 (never a stale pointer)
-int grow(double** buf, size_t* cap, size_t need, bool pinned) {
-  if (*cap >= need) return GEL_OK;
-  if (*buf) { if (pinned) hipHostFree(*buf); else hipFree(*buf); }
-  *buf = nullptr; *cap = 0;
-  HIPCHK(pinned ? hipHostMalloc((void**)buf, need * 8) : hipMalloc((void**)buf, need * 8));
-  *cap = need;
-  return GEL_OK;
-}
-}  // namespace
 
 // ------------------ aero path constraints (lib/con_aero.py) ------------------
 int gel_aero_configure(gel_problem* p, int32_t kind, int32_t nspec, const int32_t* phase, const int32_t* range_all,
@@ -1758,46 +1710,43 @@ int gel_aero_configure(gel_problem* p, int32_t kind, int32_t nspec, const int32_
     const int row0 = (int)rows.size();
     for (int k = 0; k < nk; k++) rows.push_back(gel::AeroRowDev{phase[s], k, nk, row0, limit[s]});
   }
-  p->aero_rows[kind] = rows;
+  // the whole new configuration in a local, swapped in only once everything has succeeded: a failed call leaves the old one in
+  // place, on the host and on the device
+  gel_problem::Aero a;
+  for (int kd = 0; kd < 3; kd++) a.rows[kd] = (kd == kind) ? rows : p->aero.rows[kd];
   // the union of the constrained state nodes over the three kinds, in (phase, node) order
-  std::vector<gel::AeroNodeDev> nodes;
   for (int i = 0; i + 1 < (int)p->ph.size(); i++)
     for (int k = 0; k <= p->ph[i].n; k++) {
       gel::AeroNodeDev nd{i, k, {-1, -1, -1}, {0, 0, 0}, {0, 0, 0}, k, {1.0, 1.0, 1.0}};
       bool any = false;
       for (int kd = 0; kd < 3; kd++) {
-        const auto& A = p->aero_rows[kd];
+        const auto& A = a.rows[kd];
         for (size_t r = 0; r < A.size(); r++)
           if (A[r].phase == i && A[r].k == k) {
             nd.row[kd] = (int32_t)r; nd.nk[kd] = A[r].nk; nd.row0[kd] = A[r].row0; nd.limit[kd] = A[r].limit;
             any = true;
           }
       }
-      if (any) nodes.push_back(nd);
+      if (any) a.nodes.push_back(nd);
     }
-  p->aero_nodes = nodes;
   // ---- the per-vector record of gel_eval_batch_aero_device: two parts, each in gel_eval_aero_all's layout for ITS rows.
   //      Part A: nodes 1 .. n of the aerodynamic phases' "all nodes" specs -- what the fused kernel's lanes can write, a spec's row of
   //      a column n doubles long.  Part B: every other row.  Every section starts on a multiple of eight doubles.
   auto fusable = [&](const gel::AeroRowDev& r) { return p->ph[r.phase].air && r.nk == p->ph[r.phase].n + 1 && r.k >= 1; };
-  for (int part = 0; part < 2; part++)
-    for (int kd = 0; kd < 3; kd++) {
-      p->aero_part_rows[part][kd].clear();
-      p->aero_part_of[kd].assign(p->aero_rows[kd].size(), 0);
-    }
   for (int kd = 0; kd < 3; kd++) {
-    const auto& A = p->aero_rows[kd];
+    const auto& A = a.rows[kd];
+    a.part_of[kd].assign(A.size(), 0);
     for (size_t r0 = 0; r0 < A.size(); r0 += A[r0].nk) {
       // the spec's rows of part A and of part B, each a spec of its own there
-      int rowA0 = (int)p->aero_part_rows[0][kd].size(), rowB0 = (int)p->aero_part_rows[1][kd].size(), nA = 0, nB = 0;
+      int rowA0 = (int)a.part_rows[0][kd].size(), rowB0 = (int)a.part_rows[1][kd].size(), nA = 0, nB = 0;
       for (int k = 0; k < A[r0].nk; k++) (fusable(A[r0 + k]) ? nA : nB)++;
       int iA = 0, iB = 0;
       for (int k = 0; k < A[r0].nk; k++) {
         const bool fa = fusable(A[r0 + k]);
         gel::AeroRowDev q = A[r0 + k];
         q.nk = fa ? nA : nB; q.row0 = fa ? rowA0 : rowB0;
-        p->aero_part_of[kd][r0 + k] = (fa ? 0 : 1) | ((fa ? rowA0 + iA : rowB0 + iB) << 1);   // part, row inside the part
-        p->aero_part_rows[fa ? 0 : 1][kd].push_back(q);
+        a.part_of[kd][r0 + k] = (fa ? 0 : 1) | ((fa ? rowA0 + iA : rowB0 + iB) << 1);   // part, row inside the part
+        a.part_rows[fa ? 0 : 1][kd].push_back(q);
         (fa ? iA : iB)++;
       }
     }
@@ -1806,43 +1755,42 @@ int gel_aero_configure(gel_problem* p, int32_t kind, int32_t nspec, const int32_
   auto pad8 = [](int64_t v) { return (v + 7) / 8 * 8; };
   // part A, spec-major (gel_device.h AeroPhaseDev): one block of 13 n doubles per (kind, phase) spec
   for (int kd = 0; kd < 3; kd++) {
-    const auto& A = p->aero_part_rows[0][kd];
-    p->aero_partA_base[kd].assign(A.size(), 0);
+    const auto& A = a.part_rows[0][kd];
+    a.partA_base[kd].assign(A.size(), 0);
     for (size_t r0 = 0; r0 < A.size(); r0 += A[r0].nk) {
-      for (int k = 0; k < A[r0].nk; k++) p->aero_partA_base[kd][r0 + k] = off;
+      for (int k = 0; k < A[r0].nk; k++) a.partA_base[kd][r0 + k] = off;
       off = pad8(off + (int64_t)(p->fd_recompute ? gel::kAeroSpecColsWithT : gel::kAeroSpecCols) * A[r0].nk);
     }
   }
   {   // the dump area: where the lanes' stores of a kind their phase does not have go (AeroPhaseDev::base)
     int nmax = 0;
     for (const auto& h : p->ph) nmax = std::max(nmax, h.n);
-    p->aero_dump = off;
+    a.dump = off;
     off = pad8(off + (int64_t)gel::kAeroSpecColsWithT * nmax);
   }
-  p->aero_partA_len = off;
+  a.partA_len = off;
   // part B: gel_eval_aero_all's layout for its rows
-  for (int kd = 0; kd < 3; kd++) { p->aero_off_con[1][kd] = off; off = pad8(off + (int64_t)p->aero_part_rows[1][kd].size()); }
-  for (int kd = 0; kd < 3; kd++) { p->aero_off_jac[1][kd] = off; off = pad8(off + (int64_t)p->aero_part_rows[1][kd].size() * ((kd == 1) ? 8 : 12)); }
-  for (int kd = 0; kd < 3; kd++) { p->aero_off_con[0][kd] = 0; p->aero_off_jac[0][kd] = 0; }
-  p->aero_ld = off;
+  for (int kd = 0; kd < 3; kd++) { a.off_con[1][kd] = off; off = pad8(off + (int64_t)a.part_rows[1][kd].size()); }
+  for (int kd = 0; kd < 3; kd++) { a.off_jac[1][kd] = off; off = pad8(off + (int64_t)a.part_rows[1][kd].size() * ((kd == 1) ? 8 : 12)); }
+  for (int kd = 0; kd < 3; kd++) { a.off_con[0][kd] = 0; a.off_jac[0][kd] = 0; }
+  a.ld = off;
   // node tables of the two parts.  Part A: row0 = first double of the spec's block in the record, row = the constraint value's place
   // (block + node), ko = the node's place in a column's row; part B: the ordinary tables of its own rows
   for (int part = 0; part < 2; part++) {
-    auto& nodes_p = p->aero_part_nodes[part];
-    nodes_p.clear();
-    for (const auto& nd0 : p->aero_nodes) {
+    auto& nodes_p = a.part_nodes[part];
+    for (const auto& nd0 : a.nodes) {
       gel::AeroNodeDev nd = nd0;
       bool any = false;
       for (int kd = 0; kd < 3; kd++) {
         nd.row[kd] = -1;
         if (nd0.row[kd] < 0) continue;
-        const int32_t po = p->aero_part_of[kd][nd0.row[kd]];
+        const int32_t po = a.part_of[kd][nd0.row[kd]];
         if ((po & 1) != part) continue;
-        const auto& q = p->aero_part_rows[part][kd][po >> 1];
+        const auto& q = a.part_rows[part][kd][po >> 1];
         nd.ko = (po >> 1) - q.row0;
         nd.nk[kd] = q.nk;
         if (part == 0) {
-          nd.row0[kd] = (int32_t)p->aero_partA_base[kd][po >> 1];
+          nd.row0[kd] = (int32_t)a.partA_base[kd][po >> 1];
           nd.row[kd] = nd.row0[kd] + nd.ko;
         } else {
           nd.row[kd] = po >> 1; nd.row0[kd] = q.row0;
@@ -1853,43 +1801,38 @@ int gel_aero_configure(gel_problem* p, int32_t kind, int32_t nspec, const int32_
     }
   }
   // per-phase records of part A for the fused kernel's lanes
-  p->aero_ph.assign(p->ph.size(), gel::AeroPhaseDev{});
+  a.ph.assign(p->ph.size(), gel::AeroPhaseDev{});
   for (size_t i = 0; i < p->ph.size(); i++) {
-    gel::AeroPhaseDev& a = p->aero_ph[i];
-    for (int kd = 0; kd < 3; kd++) { a.il[kd] = 0.0; a.ilx[kd] = 0.0; a.base[kd] = (int32_t)(8 * p->aero_dump); }
+    gel::AeroPhaseDev& q = a.ph[i];
+    for (int kd = 0; kd < 3; kd++) { q.il[kd] = 0.0; q.ilx[kd] = 0.0; q.base[kd] = (int32_t)(8 * a.dump); }
     for (int kd = 0; kd < 3; kd++) {
-      const auto& A = p->aero_part_rows[0][kd];
+      const auto& A = a.part_rows[0][kd];
       for (size_t r0 = 0; r0 < A.size(); r0 += A[r0].nk) {
         if (A[r0].phase != (int)i) continue;
-        a.kinds |= 1 << kd;
-        a.base[kd] = (int32_t)(8 * p->aero_partA_base[kd][r0]);
-        a.il[kd] = 1.0 / A[r0].limit;            // the kernels' frcp(limit): the correctly rounded quotient
-        a.ilx[kd] = a.il[kd] * p->dev.inv_dx;
+        q.kinds |= 1 << kd;
+        q.base[kd] = (int32_t)(8 * a.partA_base[kd][r0]);
+        q.il[kd] = 1.0 / A[r0].limit;            // the kernels' frcp(limit): the correctly rounded quotient
+        q.ilx[kd] = q.il[kd] * p->dev.inv_dx;
       }
     }
   }
-  if (8 * p->aero_ld >= (int64_t)1 << 31) return fail(GEL_ERR_ARG, "aero record too long for 32-bit byte offsets");
+  if (8 * a.ld >= (int64_t)1 << 31) return fail(GEL_ERR_ARG, "aero record too long for 32-bit byte offsets");
   if (p->device != GEL_DEVICE_NONE) {
     HIPCHK(hipSetDevice(p->device));
-    HIPCHK(hipStreamSynchronize(p->stream));
-    hipFree(p->d_aero_nodes); hipFree(p->d_aero_ph);
-    p->d_aero_nodes = nullptr; p->d_aero_ph = nullptr;
-    hipFree(p->d_aero_part_nodes[0]); hipFree(p->d_aero_part_nodes[1]);
-    p->d_aero_part_nodes[0] = p->d_aero_part_nodes[1] = nullptr;
-    int rc = upload(&p->d_aero_nodes, p->aero_nodes);
-    if (rc) return rc;
-    if ((rc = upload(&p->d_aero_ph, p->aero_ph))) return rc;
+    HIPCHK(a.d_nodes.upload(a.nodes)); HIPCHK(a.d_ph.upload(a.ph));
     for (int part = 0; part < 2; part++)
-      if (!p->aero_part_nodes[part].empty() && (rc = upload(&p->d_aero_part_nodes[part], p->aero_part_nodes[part]))) return rc;
+      if (!a.part_nodes[part].empty()) HIPCHK(a.d_part_nodes[part].upload(a.part_nodes[part]));
+    HIPCHK(hipStreamSynchronize(p->stream.get()));   // launches in flight still read the old tables
   }
+  p->aero = std::move(a);
   return GEL_OK;
 }
 
 int gel_aero_record_layout(const gel_problem* p, int64_t* width, int64_t* off_con, int64_t* off_jac) {
   if (!p || !width || !off_con || !off_jac) return fail(GEL_ERR_ARG, "bad argument");
-  *width = p->aero_ld;
+  *width = p->aero.ld;
   for (int part = 0; part < 2; part++)
-    for (int k = 0; k < 3; k++) { off_con[3 * part + k] = p->aero_off_con[part][k]; off_jac[3 * part + k] = p->aero_off_jac[part][k]; }
+    for (int k = 0; k < 3; k++) { off_con[3 * part + k] = p->aero.off_con[part][k]; off_jac[3 * part + k] = p->aero.off_jac[part][k]; }
   return GEL_OK;
 }
 
@@ -1897,14 +1840,14 @@ int gel_aero_record_layout(const gel_problem* p, int64_t* width, int64_t* off_co
 // velocity / quaternion / t block of the gradient values (in the order of gel_aero_pattern)
 int gel_aero_record_map(const gel_problem* p, int32_t kind, int32_t var, int64_t* idx) {
   if (!p || kind < 0 || kind > 2 || var < -1 || var > 3 || !idx) return fail(GEL_ERR_ARG, "bad argument");
-  const auto& A = p->aero_rows[kind];
+  const auto& A = p->aero.rows[kind];
   const int nq = (kind == 1) ? 0 : 4;
   int64_t o = 0;
   if (var == -1) {
     for (size_t r = 0; r < A.size(); r++) {
-      const int32_t po = p->aero_part_of[kind][r];
-      if (po & 1) idx[o++] = p->aero_off_con[1][kind] + (po >> 1);
-      else idx[o++] = p->aero_partA_base[kind][po >> 1] + ((po >> 1) - p->aero_part_rows[0][kind][po >> 1].row0);
+      const int32_t po = p->aero.part_of[kind][r];
+      if (po & 1) idx[o++] = p->aero.off_con[1][kind] + (po >> 1);
+      else idx[o++] = p->aero.partA_base[kind][po >> 1] + ((po >> 1) - p->aero.part_rows[0][kind][po >> 1].row0);
     }
     return GEL_OK;
   }
@@ -1914,14 +1857,14 @@ int gel_aero_record_map(const gel_problem* p, int32_t kind, int32_t var, int64_t
   for (size_t r0 = 0; r0 < A.size(); r0 += A[r0].nk)
     for (int64_t j = 0; j < w; j++)
       for (int k = 0; k < A[r0].nk; k++) {     // the reference's emission order: spec, column, node (gel_aero_pattern)
-        const int32_t po = p->aero_part_of[kind][r0 + k];
+        const int32_t po = p->aero.part_of[kind][r0 + k];
         const int part = po & 1;
-        const auto& q = p->aero_part_rows[part][kind][po >> 1];
-        const int64_t R = (int64_t)p->aero_part_rows[part][kind].size();
+        const auto& q = p->aero.part_rows[part][kind][po >> 1];
+        const int64_t R = (int64_t)p->aero.part_rows[part][kind].size();
         const int64_t ko = (po >> 1) - q.row0;
-        if (part == 1) idx[o++] = p->aero_off_jac[1][kind] + bo * R + w * q.row0 + j * q.nk + ko;
+        if (part == 1) idx[o++] = p->aero.off_jac[1][kind] + bo * R + w * q.row0 + j * q.nk + ko;
         else if (var == 3 && !p->fd_recompute) idx[o++] = -1;      // an exact zero, not stored (AeroPhaseDev)
-        else idx[o++] = p->aero_partA_base[kind][po >> 1] + (((var == 0) ? 1 : ((var == 1) ? 4 : ((var == 2) ? 7 : 11))) + j) * q.nk + ko;
+        else idx[o++] = p->aero.partA_base[kind][po >> 1] + (((var == 0) ? 1 : ((var == 1) ? 4 : ((var == 2) ? 7 : 11))) + j) * q.nk + ko;
       }
   return GEL_OK;
 }
@@ -1933,33 +1876,32 @@ int gel_eval_batch_aero_device(gel_problem* p, int32_t B, const double* d_x, dou
   if (!p || !d_x || B < 1 || !d_res || !d_jvar || !d_aero) return fail(GEL_ERR_ARG, "bad argument");
   NO_EXACT(p, "gel_eval_batch_aero_device");
   NEED_DEVICE(p);
-  if (p->aero_nodes.empty()) return fail(GEL_ERR_ARG, "no aero path constraints configured (gel_aero_configure)");
-  hipStream_t s = stream ? (hipStream_t)stream : p->stream;
+  if (p->aero.nodes.empty()) return fail(GEL_ERR_ARG, "no aero path constraints configured (gel_aero_configure)");
+  hipStream_t s = stream ? (hipStream_t)stream : p->stream.get();
   gel::AeroLaunchOut out[2];
   for (int part = 0; part < 2; part++)
     for (int k = 0; k < 3; k++) {   // part A (spec-major): every pointer is the record itself
-      out[part].nrows[k] = (int32_t)p->aero_part_rows[part][k].size();
-      out[part].con[k] = out[part].nrows[k] ? d_aero + p->aero_off_con[part][k] : nullptr;
-      out[part].jac[k] = out[part].nrows[k] ? d_aero + p->aero_off_jac[part][k] : nullptr;
+      out[part].nrows[k] = (int32_t)p->aero.part_rows[part][k].size();
+      out[part].con[k] = out[part].nrows[k] ? d_aero + p->aero.off_con[part][k] : nullptr;
+      out[part].jac[k] = out[part].nrows[k] ? d_aero + p->aero.off_jac[part][k] : nullptr;
     }
   // GEL_AERO_FUSED=0: the two kernels one after the other (same record, same bits)
-  const char* e = std::getenv("GEL_AERO_FUSED");
-  const bool fused = gel::eval_aero_fusable(p->dev, B) && !p->aero_part_nodes[0].empty() && !(e && e[0] == '0');
+  const bool fused = p->aero_fused && gel::eval_aero_fusable(p->dev, B) && !p->aero.part_nodes[0].empty();
   if (fused) {
     gel::ProblemDev dv = p->dev;
-    dv.aero_ph = p->d_aero_ph; dv.aero_out = d_aero; dv.aero_ld = p->aero_ld;
+    dv.aero_ph = p->aero.d_ph.get(); dv.aero_out = d_aero; dv.aero_ld = p->aero.ld;
     HIPCHK(gel::launch_eval_aero(dv, B, d_x, d_res, d_jvar, s));
   } else {
     HIPCHK(gel::launch_eval(p->dev, B, d_x, d_res, d_jvar, s));
-    HIPCHK(gel::launch_aero(p->dev, (int)p->aero_part_nodes[0].size(), p->d_aero_part_nodes[0], B, d_x, out[0], s, p->aero_ld, true));
+    HIPCHK(gel::launch_aero(p->dev, (int)p->aero.part_nodes[0].size(), p->aero.d_part_nodes[0].get(), B, d_x, out[0], s, p->aero.ld, true));
   }
-  HIPCHK(gel::launch_aero_wide(p->dev, (int)p->aero_part_nodes[1].size(), p->d_aero_part_nodes[1], B, d_x, out[1], p->aero_ld, s));
+  HIPCHK(gel::launch_aero_wide(p->dev, (int)p->aero.part_nodes[1].size(), p->aero.d_part_nodes[1].get(), B, d_x, out[1], p->aero.ld, s));
   return GEL_OK;
 }
 
 int gel_aero_dims(const gel_problem* p, int32_t kind, int32_t* nrows, int64_t* nnz4) {
   if (!p || kind < 0 || kind > 2 || !nrows || !nnz4) return fail(GEL_ERR_ARG, "bad argument");
-  const int64_t R = (int64_t)p->aero_rows[kind].size();
+  const int64_t R = (int64_t)p->aero.rows[kind].size();
   *nrows = (int32_t)R;
   nnz4[0] = 3 * R; nnz4[1] = 3 * R; nnz4[2] = (kind == 1) ? 0 : 4 * R; nnz4[3] = 2 * R;
   return GEL_OK;
@@ -1968,7 +1910,7 @@ int gel_aero_dims(const gel_problem* p, int32_t kind, int32_t* nrows, int64_t* n
 int gel_aero_pattern(const gel_problem* p, int32_t kind, int32_t var, int32_t* rows, int32_t* cols) {
   // emission order of inequality_jac_max_*: con_aero.py:437-463
   if (!p || kind < 0 || kind > 2 || var < 0 || var > 3 || !rows || !cols) return fail(GEL_ERR_ARG, "bad argument");
-  const auto& A = p->aero_rows[kind];
+  const auto& A = p->aero.rows[kind];
   int64_t o = 0;
   for (size_t r0 = 0; r0 < A.size(); r0 += A[r0].nk) {
     const int nk = A[r0].nk, i = A[r0].phase, xa = p->ph[i].xa, iRow = (int)r0;
@@ -1985,7 +1927,7 @@ int gel_aero_pattern(const gel_problem* p, int32_t kind, int32_t var, int32_t* r
 }
 
 namespace {
-size_t aero_jac_len(const gel_problem* p, int kind) { return p->aero_rows[kind].size() * ((kind == 1) ? 8 : 12); }
+size_t aero_jac_len(const gel_problem* p, int kind) { return p->aero.rows[kind].size() * ((kind == 1) ? 8 : 12); }
 }  // namespace
 
 int gel_eval_aero_all_device(gel_problem* p, int32_t B, const double* d_x, double* const* d_con, double* const* d_jac,
@@ -1994,23 +1936,23 @@ int gel_eval_aero_all_device(gel_problem* p, int32_t B, const double* d_x, doubl
   NEED_DEVICE(p);
   gel::AeroLaunchOut out;
   for (int k = 0; k < 3; k++) {
-    out.nrows[k] = (int32_t)p->aero_rows[k].size();
+    out.nrows[k] = (int32_t)p->aero.rows[k].size();
     out.con[k] = out.nrows[k] ? d_con[k] : nullptr;
     out.jac[k] = (out.con[k] && d_jac) ? d_jac[k] : nullptr;
   }
-  HIPCHK(gel::launch_aero(p->dev, (int)p->aero_nodes.size(), p->d_aero_nodes, B, d_x, out, stream ? (hipStream_t)stream : p->stream));
+  HIPCHK(gel::launch_aero(p->dev, (int)p->aero.nodes.size(), p->aero.d_nodes.get(), B, d_x, out, stream ? (hipStream_t)stream : p->stream.get()));
   return GEL_OK;
 }
 
 int gel_eval_aero_all(gel_problem* p, int32_t B, const double* x, double* const* con, double* const* jac) {
   if (!p || B < 1 || !x || !con) return fail(GEL_ERR_ARG, "bad argument");
   NEED_DEVICE(p);
-  if (p->aero_nodes.empty()) return GEL_OK;
+  if (p->aero.nodes.empty()) return GEL_OK;
   HIPCHK(hipSetDevice(p->device));
   // one contiguous output area: con[0] | jac[0] | con[1] | jac[1] | con[2] | jac[2] (only what was asked for)
   size_t off_c[3], off_j[3], total = 0;
   for (int k = 0; k < 3; k++) {
-    const size_t R = p->aero_rows[k].size();
+    const size_t R = p->aero.rows[k].size();
     off_c[k] = total; total += (con[k] && R) ? (size_t)B * R : 0;
     off_j[k] = total; total += (con[k] && R && jac && jac[k]) ? (size_t)B * aero_jac_len(p, k) : 0;
   }
@@ -2021,40 +1963,41 @@ int gel_eval_aero_all(gel_problem* p, int32_t B, const double* x, double* const*
   double* base;
   if (zero_copy) {
     // the optimiser's callback: x and every output in pinned host memory, one launch + one synchronise
-    if ((rc = ensure_capacity(p, B)) || (rc = grow(&p->h_aero, &p->h_aero_cap, total, true))) return rc;
-    std::memcpy(p->h_x, x, nx * 8);
-    base = p->h_aero;
+    if ((rc = ensure_capacity(p, B))) return rc;
+    HIPCHK(p->h_aero.reserve(total));
+    std::memcpy(p->h_x.get(), x, nx * 8);
+    base = p->h_aero.get();
   } else {
-    if ((rc = grow(&p->d_aero_x, &p->d_aero_x_cap, nx, false)) || (rc = grow(&p->d_aero_out, &p->d_aero_out_cap, total, false))) return rc;
-    HIPCHK(hipMemcpyAsync(p->d_aero_x, x, nx * 8, hipMemcpyHostToDevice, p->stream));
-    base = p->d_aero_out;
+    HIPCHK(p->d_aero_x.reserve(nx)); HIPCHK(p->d_aero_out.reserve(total));
+    HIPCHK(hipMemcpyAsync(p->d_aero_x.get(), x, nx * 8, hipMemcpyHostToDevice, p->stream.get()));
+    base = p->d_aero_out.get();
   }
   gel::AeroLaunchOut out;
   for (int k = 0; k < 3; k++) {
-    const size_t R = p->aero_rows[k].size();
+    const size_t R = p->aero.rows[k].size();
     out.nrows[k] = (int32_t)R;
     out.con[k] = (con[k] && R) ? base + off_c[k] : nullptr;
     out.jac[k] = (out.con[k] && jac && jac[k]) ? base + off_j[k] : nullptr;
   }
   gel::ProblemDev dv = p->dev;
-  if (zero_copy) dv.flag = p->h_flag;
-  HIPCHK(gel::launch_aero(dv, (int)p->aero_nodes.size(), p->d_aero_nodes, B, zero_copy ? p->h_x : p->d_aero_x, out, p->stream));
+  if (zero_copy) dv.flag = p->h_flag.get();
+  HIPCHK(gel::launch_aero(dv, (int)p->aero.nodes.size(), p->aero.d_nodes.get(), B, zero_copy ? p->h_x.get() : p->d_aero_x.get(), out, p->stream.get()));
   if (!zero_copy) {
     for (int k = 0; k < 3; k++) {
-      if (out.con[k]) HIPCHK(hipMemcpyAsync(con[k], out.con[k], (size_t)B * p->aero_rows[k].size() * 8, hipMemcpyDeviceToHost, p->stream));
-      if (out.jac[k]) HIPCHK(hipMemcpyAsync(jac[k], out.jac[k], (size_t)B * aero_jac_len(p, k) * 8, hipMemcpyDeviceToHost, p->stream));
+      if (out.con[k]) HIPCHK(hipMemcpyAsync(con[k], out.con[k], (size_t)B * p->aero.rows[k].size() * 8, hipMemcpyDeviceToHost, p->stream.get()));
+      if (out.jac[k]) HIPCHK(hipMemcpyAsync(jac[k], out.jac[k], (size_t)B * aero_jac_len(p, k) * 8, hipMemcpyDeviceToHost, p->stream.get()));
     }
-    HIPCHK(hipMemcpyAsync(p->h_flag, p->d_flag, 4, hipMemcpyDeviceToHost, p->stream));
+    HIPCHK(hipMemcpyAsync(p->h_flag.get(), p->d_flag.get(), 4, hipMemcpyDeviceToHost, p->stream.get()));
   }
-  HIPCHK(hipStreamSynchronize(p->stream));
+  HIPCHK(hipStreamSynchronize(p->stream.get()));
   if (zero_copy)
     for (int k = 0; k < 3; k++) {
-      if (out.con[k]) std::memcpy(con[k], out.con[k], (size_t)B * p->aero_rows[k].size() * 8);
+      if (out.con[k]) std::memcpy(con[k], out.con[k], (size_t)B * p->aero.rows[k].size() * 8);
       if (out.jac[k]) std::memcpy(jac[k], out.jac[k], (size_t)B * aero_jac_len(p, k) * 8);
     }
-  if (*p->h_flag) {
-    *p->h_flag = 0;
-    if (!zero_copy) HIPCHK(hipMemsetAsync(p->d_flag, 0, 4, p->stream));
+  if (*p->h_flag.get()) {
+    *p->h_flag.get() = 0;
+    if (!zero_copy) HIPCHK(hipMemsetAsync(p->d_flag.get(), 0, 4, p->stream.get()));
     return GEL_NONFINITE;
   }
   return GEL_OK;
@@ -2078,21 +2021,24 @@ int gel_rows_configure(gel_problem* p, int32_t nlin, const gel_linear_row* lin, 
     if (fn[i].fn < 0 || fn[i].fn > 15 || fn[i].node < 0 || fn[i].node >= p->dims.M || !(fn[i].p[0] != 0.0) ||
         fn[i].tcol < -1 || fn[i].tcol > p->dims.S || (fn[i].fn >= 9 && fn[i].tcol < 0) || (fn[i].mode & ~15) || (fn[i].mode & 3) > 1)
       return fail(GEL_ERR_ARG, "node-function row: unknown function or mode, node / time column out of range, or zero scale");
-  p->lin_rows.resize(nlin);
-  p->fn_rows.resize(nfn);
-  for (int i = 0; i < nlin; i++) p->lin_rows[i] = gel::LinRowDev{lin[i].idx0, lin[i].idx1 < 0 ? -1 : lin[i].idx1, lin[i].coef0, lin[i].coef1, lin[i].c0};
+  // the new tables in locals, swapped in only once everything has succeeded: a failed call leaves the old ones in place
+  std::vector<gel::LinRowDev> lin_rows(nlin);
+  std::vector<gel::FnRowDev> fn_rows(nfn);
+  for (int i = 0; i < nlin; i++) lin_rows[i] = gel::LinRowDev{lin[i].idx0, lin[i].idx1 < 0 ? -1 : lin[i].idx1, lin[i].coef0, lin[i].coef1, lin[i].c0};
   for (int i = 0; i < nfn; i++) {
-    gel::FnRowDev& d = p->fn_rows[i];
+    gel::FnRowDev& d = fn_rows[i];
     d.fn = fn[i].fn; d.node = fn[i].node; d.tcol = fn[i].tcol; d.mode = fn[i].mode;
     for (int k = 0; k < 8; k++) d.p[k] = fn[i].p[k];
   }
-  if (p->device == GEL_DEVICE_NONE) return GEL_OK;
-  HIPCHK(hipSetDevice(p->device));
-  HIPCHK(hipStreamSynchronize(p->stream));
-  hipFree(p->d_lin_rows); hipFree(p->d_fn_rows);
-  p->d_lin_rows = nullptr; p->d_fn_rows = nullptr;
-  int rc = GEL_OK;
-  if ((rc = upload(&p->d_lin_rows, p->lin_rows)) || (rc = upload(&p->d_fn_rows, p->fn_rows))) return rc;
+  DeviceArray<gel::LinRowDev> d_lin;
+  DeviceArray<gel::FnRowDev> d_fn;
+  if (p->device != GEL_DEVICE_NONE) {
+    HIPCHK(hipSetDevice(p->device));
+    HIPCHK(d_lin.upload(lin_rows)); HIPCHK(d_fn.upload(fn_rows));
+    HIPCHK(hipStreamSynchronize(p->stream.get()));   // launches in flight still read the old tables
+  }
+  p->lin_rows = std::move(lin_rows); p->fn_rows = std::move(fn_rows);
+  p->d_lin_rows = std::move(d_lin); p->d_fn_rows = std::move(d_fn);
   return GEL_OK;
 }
 
@@ -2106,8 +2052,8 @@ int gel_rows_dims(const gel_problem* p, int32_t* nlin, int32_t* nfn) {
 int gel_rows_eval_device(gel_problem* p, int32_t B, const double* d_x, double* d_con, double* d_jfn, void* stream) {
   if (!p || B < 1 || !d_x || !d_con) return fail(GEL_ERR_ARG, "bad argument");
   NEED_DEVICE(p);
-  HIPCHK(gel::launch_rows(p->dev, (int)p->lin_rows.size(), p->d_lin_rows, (int)p->fn_rows.size(), p->d_fn_rows, B, d_x,
-                          d_con, d_jfn, stream ? (hipStream_t)stream : p->stream));
+  HIPCHK(gel::launch_rows(p->dev, (int)p->lin_rows.size(), p->d_lin_rows.get(), (int)p->fn_rows.size(), p->d_fn_rows.get(), B, d_x,
+                          d_con, d_jfn, stream ? (hipStream_t)stream : p->stream.get()));
   return GEL_OK;
 }
 
@@ -2122,27 +2068,28 @@ int gel_rows_eval(gel_problem* p, int32_t B, const double* x, double* con, doubl
   int rc;
   if ((nx + nc + nj) * 8 <= kZeroCopyBytes) {
     // the optimiser's callback: the kernel reads x from and writes to pinned host memory, one launch + one synchronise
-    if ((rc = ensure_capacity(p, B)) || (rc = grow(&p->h_rows, &p->h_rows_cap, nc + nj + 1, true))) return rc;
-    std::memcpy(p->h_x, x, nx * 8);
+    if ((rc = ensure_capacity(p, B))) return rc;
+    HIPCHK(p->h_rows.reserve(nc + nj + 1));
+    std::memcpy(p->h_x.get(), x, nx * 8);
     gel::ProblemDev dv = p->dev;
-    dv.flag = p->h_flag;
-    HIPCHK(gel::launch_rows(dv, (int)p->lin_rows.size(), p->d_lin_rows, (int)nf, p->d_fn_rows, B, p->h_x, p->h_rows,
-                            jfn ? p->h_rows + nc : nullptr, p->stream));
-    HIPCHK(hipStreamSynchronize(p->stream));
-    std::memcpy(con, p->h_rows, nc * 8);
-    if (jfn) std::memcpy(jfn, p->h_rows + nc, nj * 8);
-    if (*p->h_flag) { *p->h_flag = 0; return GEL_NONFINITE; }
+    dv.flag = p->h_flag.get();
+    HIPCHK(gel::launch_rows(dv, (int)p->lin_rows.size(), p->d_lin_rows.get(), (int)nf, p->d_fn_rows.get(), B, p->h_x.get(), p->h_rows.get(),
+                            jfn ? p->h_rows.get() + nc : nullptr, p->stream.get()));
+    HIPCHK(hipStreamSynchronize(p->stream.get()));
+    std::memcpy(con, p->h_rows.get(), nc * 8);
+    if (jfn) std::memcpy(jfn, p->h_rows.get() + nc, nj * 8);
+    if (*p->h_flag.get()) { *p->h_flag.get() = 0; return GEL_NONFINITE; }
     return GEL_OK;
   }
-  if ((rc = grow(&p->d_rows_x, &p->d_rows_x_cap, nx, false)) || (rc = grow(&p->d_rows_out, &p->d_rows_out_cap, nc + nj + 1, false))) return rc;
-  HIPCHK(hipMemcpyAsync(p->d_rows_x, x, nx * 8, hipMemcpyHostToDevice, p->stream));
-  HIPCHK(gel::launch_rows(p->dev, (int)p->lin_rows.size(), p->d_lin_rows, (int)nf, p->d_fn_rows, B, p->d_rows_x,
-                          p->d_rows_out, jfn ? p->d_rows_out + nc : nullptr, p->stream));
-  HIPCHK(hipMemcpyAsync(con, p->d_rows_out, nc * 8, hipMemcpyDeviceToHost, p->stream));
-  if (jfn) HIPCHK(hipMemcpyAsync(jfn, p->d_rows_out + nc, nj * 8, hipMemcpyDeviceToHost, p->stream));
-  HIPCHK(hipMemcpyAsync(p->h_flag, p->d_flag, 4, hipMemcpyDeviceToHost, p->stream));
-  HIPCHK(hipStreamSynchronize(p->stream));
-  if (*p->h_flag) { *p->h_flag = 0; HIPCHK(hipMemsetAsync(p->d_flag, 0, 4, p->stream)); return GEL_NONFINITE; }
+  HIPCHK(p->d_rows_x.reserve(nx)); HIPCHK(p->d_rows_out.reserve(nc + nj + 1));
+  HIPCHK(hipMemcpyAsync(p->d_rows_x.get(), x, nx * 8, hipMemcpyHostToDevice, p->stream.get()));
+  HIPCHK(gel::launch_rows(p->dev, (int)p->lin_rows.size(), p->d_lin_rows.get(), (int)nf, p->d_fn_rows.get(), B, p->d_rows_x.get(),
+                          p->d_rows_out.get(), jfn ? p->d_rows_out.get() + nc : nullptr, p->stream.get()));
+  HIPCHK(hipMemcpyAsync(con, p->d_rows_out.get(), nc * 8, hipMemcpyDeviceToHost, p->stream.get()));
+  if (jfn) HIPCHK(hipMemcpyAsync(jfn, p->d_rows_out.get() + nc, nj * 8, hipMemcpyDeviceToHost, p->stream.get()));
+  HIPCHK(hipMemcpyAsync(p->h_flag.get(), p->d_flag.get(), 4, hipMemcpyDeviceToHost, p->stream.get()));
+  HIPCHK(hipStreamSynchronize(p->stream.get()));
+  if (*p->h_flag.get()) { *p->h_flag.get() = 0; HIPCHK(hipMemsetAsync(p->d_flag.get(), 0, 4, p->stream.get())); return GEL_NONFINITE; }
   return GEL_OK;
 }
 
@@ -2158,20 +2105,19 @@ int gel_output_table(gel_problem* p, const double* x, const double* tx_res, doub
   for (size_t i = 0; i < p->ph.size(); i++)
     for (int k = 0; k <= p->ph[i].n; k++) sec[(size_t)p->ph[i].xa + k] = (int32_t)i;
   const size_t nx = (size_t)p->dims.num_vars, no = (size_t)M * gel::kOutputColumns;
-  int rc;
   // one scratch buffer: x | tx | out | node sections (as doubles' worth of bytes)
   const size_t words = nx + (size_t)M + no + ((size_t)M + 1) / 2;
-  if ((rc = grow(&p->d_rows_x, &p->d_rows_x_cap, words, false))) return rc;
-  double* d_x = p->d_rows_x;
+  HIPCHK(p->d_rows_x.reserve(words));
+  double* d_x = p->d_rows_x.get();
   double* d_tx = d_x + nx;
   double* d_out = d_tx + M;
   int32_t* d_sec = reinterpret_cast<int32_t*>(d_out + no);
-  HIPCHK(hipMemcpyAsync(d_x, x, nx * 8, hipMemcpyHostToDevice, p->stream));
-  HIPCHK(hipMemcpyAsync(d_tx, tx_res, (size_t)M * 8, hipMemcpyHostToDevice, p->stream));
-  HIPCHK(hipMemcpyAsync(d_sec, sec.data(), (size_t)M * 4, hipMemcpyHostToDevice, p->stream));
-  HIPCHK(gel::launch_output(p->dev, M, d_x, d_tx, d_sec, launch_lat_deg, launch_lon_deg, d_out, p->stream));
-  HIPCHK(hipMemcpyAsync(out, d_out, no * 8, hipMemcpyDeviceToHost, p->stream));
-  HIPCHK(hipStreamSynchronize(p->stream));
+  HIPCHK(hipMemcpyAsync(d_x, x, nx * 8, hipMemcpyHostToDevice, p->stream.get()));
+  HIPCHK(hipMemcpyAsync(d_tx, tx_res, (size_t)M * 8, hipMemcpyHostToDevice, p->stream.get()));
+  HIPCHK(hipMemcpyAsync(d_sec, sec.data(), (size_t)M * 4, hipMemcpyHostToDevice, p->stream.get()));
+  HIPCHK(gel::launch_output(p->dev, M, d_x, d_tx, d_sec, launch_lat_deg, launch_lon_deg, d_out, p->stream.get()));
+  HIPCHK(hipMemcpyAsync(out, d_out, no * 8, hipMemcpyDeviceToHost, p->stream.get()));
+  HIPCHK(hipStreamSynchronize(p->stream.get()));
   return GEL_OK;
 }
 
@@ -2236,19 +2182,19 @@ int gel_eval_callback(gel_problem* p, const double* x, const gel_callback_io* io
   size_t off_c[3], off_j[3], atotal = 0;
   bool aero = false;
   for (int k = 0; k < 3; k++) {
-    const size_t n = p->aero_rows[k].size();
+    const size_t n = p->aero.rows[k].size();
     off_c[k] = atotal; atotal += (io->aero_con[k] && n) ? n : 0;
     off_j[k] = atotal; atotal += (io->aero_con[k] && n && io->aero_jac[k]) ? aero_jac_len(p, k) : 0;
     aero = aero || (io->aero_con[k] && n);
   }
-  if (rows && (rc = grow(&p->h_rows, &p->h_rows_cap, R + 7 * nfn + 1, true))) return rc;
-  if (aero && (rc = grow(&p->h_aero, &p->h_aero_cap, atotal, true))) return rc;
-  const bool x_pinned = p->cb_x[0] && (x == p->cb_x[0] || x == p->cb_x[1]);
-  if (!x_pinned) std::memcpy(p->h_x, x, (size_t)p->dims.num_vars * 8);
-  const double* const xin = x_pinned ? x : p->h_x;
+  if (rows) HIPCHK(p->h_rows.reserve(R + 7 * nfn + 1));
+  if (aero) HIPCHK(p->h_aero.reserve(atotal));
+  const bool x_pinned = p->cb_x[0].get() && (x == p->cb_x[0].get() || x == p->cb_x[1].get());
+  if (!x_pinned) std::memcpy(p->h_x.get(), x, (size_t)p->dims.num_vars * 8);
+  const double* const xin = x_pinned ? x : p->h_x.get();
   // everything reads x from and writes to pinned host memory: no copy commands
   gel::ProblemDev dv = p->dev;
-  dv.flag = p->h_flag;
+  dv.flag = p->h_flag.get();
   const bool want_jac = io->vals_full != nullptr;
   const bool fused = io->res || want_jac;
   // GEL_CB_MODE=3 (measurement switch): the three launches of rounds 1-2, back to back on the handle's stream (compact path)
@@ -2260,48 +2206,48 @@ int gel_eval_callback(gel_problem* p, const double* x, const gel_callback_io* io
   const bool coo = want_jac && cb_mode != 3 && !p->exact && coo_direct(p);
   if (coo) {
     if ((rc = ensure_full(p))) return rc;
-    dv.coo_full = p->h_full; dv.coo = p->d_coo;
+    dv.coo_full = p->h_full.get(); dv.coo = p->d_coo.get();
   }
   dv.split_vel = 1;   // a whole evaluation: every part of every work item is in this launch
-  const bool own_res = io->res && p->cb_res && io->res == p->cb_res;
-  double* const res_to = own_res ? p->cb_res : p->h_res;
+  const bool own_res = io->res && p->cb_res.get() && io->res == p->cb_res.get();
+  double* const res_to = own_res ? p->cb_res.get() : p->h_res.get();
   gel::AeroLaunchOut out;
   if (aero)
     for (int k = 0; k < 3; k++) {
-      const size_t n = p->aero_rows[k].size();
+      const size_t n = p->aero.rows[k].size();
       out.nrows[k] = (int32_t)n;
-      out.con[k] = (io->aero_con[k] && n) ? p->h_aero + off_c[k] : nullptr;
-      out.jac[k] = (out.con[k] && io->aero_jac[k]) ? p->h_aero + off_j[k] : nullptr;
+      out.con[k] = (io->aero_con[k] && n) ? p->h_aero.get() + off_c[k] : nullptr;
+      out.jac[k] = (out.con[k] && io->aero_jac[k]) ? p->h_aero.get() + off_j[k] : nullptr;
     }
   if (cb_mode == 3 || !fused || split_exact) {
-    if (fused) HIPCHK(launch_defects(p, dv, 1, xin, res_to, want_jac ? p->h_jv : nullptr, p->stream));
-    if (rows) HIPCHK(gel::launch_rows(dv, (int)nlin, p->d_lin_rows, (int)nfn, p->d_fn_rows, 1, xin, p->h_rows,
-                                      io->rows_jfn ? p->h_rows + R : nullptr, p->stream));
-    if (aero) HIPCHK(gel::launch_aero(dv, (int)p->aero_nodes.size(), p->d_aero_nodes, 1, xin, out, p->stream));
+    if (fused) HIPCHK(launch_defects(p, dv, 1, xin, res_to, want_jac ? p->h_jv.get() : nullptr, p->stream.get()));
+    if (rows) HIPCHK(gel::launch_rows(dv, (int)nlin, p->d_lin_rows.get(), (int)nfn, p->d_fn_rows.get(), 1, xin, p->h_rows.get(),
+                                      io->rows_jfn ? p->h_rows.get() + R : nullptr, p->stream.get()));
+    if (aero) HIPCHK(gel::launch_aero(dv, (int)p->aero.nodes.size(), p->aero.d_nodes.get(), 1, xin, out, p->stream.get()));
   } else {
     // ONE launch: defect groups, aero kinds and row table as workgroup ranges of one grid (gel_kernels.hip callback_kernel)
     arm_done(p, dv);
-    HIPCHK(gel::launch_callback(dv, want_jac, xin, res_to, want_jac ? p->h_jv : nullptr,
-                                aero ? (int)p->aero_nodes.size() : 0, p->d_aero_nodes, aero ? &out : nullptr,
-                                (int)nlin, p->d_lin_rows, (int)nfn, p->d_fn_rows, rows ? p->h_rows : nullptr,
-                                (rows && io->rows_jfn) ? p->h_rows + R : nullptr, p->stream));
+    HIPCHK(gel::launch_callback(dv, want_jac, xin, res_to, want_jac ? p->h_jv.get() : nullptr,
+                                aero ? (int)p->aero.nodes.size() : 0, p->aero.d_nodes.get(), aero ? &out : nullptr,
+                                (int)nlin, p->d_lin_rows.get(), (int)nfn, p->d_fn_rows.get(), rows ? p->h_rows.get() : nullptr,
+                                (rows && io->rows_jfn) ? p->h_rows.get() + R : nullptr, p->stream.get()));
   }
   HIPCHK(wait_done(p, dv));   // the ONE wait of the callback: the kernel's own word where it signals, else the runtime's synchronise
-  if (io->res && !own_res) std::memcpy(io->res, p->h_res, (size_t)11 * p->dims.N * 8);
+  if (io->res && !own_res) std::memcpy(io->res, p->h_res.get(), (size_t)11 * p->dims.N * 8);
   if (want_jac) {
     if (coo) finish_full(p, io->vals_full, io->fill_constants);
-    else scatter_full(p, p->h_jv, io->vals_full, io->fill_constants);
+    else scatter_full(p, p->h_jv.get(), io->vals_full, io->fill_constants);
   }
   if (rows) {
-    std::memcpy(io->rows_con, p->h_rows, R * 8);
-    if (io->rows_jfn) std::memcpy(io->rows_jfn, p->h_rows + R, 7 * nfn * 8);
+    std::memcpy(io->rows_con, p->h_rows.get(), R * 8);
+    if (io->rows_jfn) std::memcpy(io->rows_jfn, p->h_rows.get() + R, 7 * nfn * 8);
   }
   if (aero)
     for (int k = 0; k < 3; k++) {
-      if (out.con[k]) std::memcpy(io->aero_con[k], out.con[k], p->aero_rows[k].size() * 8);
+      if (out.con[k]) std::memcpy(io->aero_con[k], out.con[k], p->aero.rows[k].size() * 8);
       if (out.jac[k]) std::memcpy(io->aero_jac[k], out.jac[k], aero_jac_len(p, k) * 8);
     }
-  if (*p->h_flag) { *p->h_flag = 0; return GEL_NONFINITE; }
+  if (*p->h_flag.get()) { *p->h_flag.get() = 0; return GEL_NONFINITE; }
   return GEL_OK;
 }
 
@@ -2328,10 +2274,10 @@ int gel_point_eval(int32_t kind, int32_t n, const double* in, const double* aux,
     hax = ext.data(); naux = ext.size();
   }
   else { aux_rows = 0; }
-  DevBuf i, a, o;
-  if ((rc = i.put(in, (size_t)n * nin[kind])) || (rc = a.put(hax, naux)) || (rc = o.put(nullptr, (size_t)n * nout[kind]))) return rc;
-  HIPCHK(gel::launch_point(kind, n, i.p, a.p, aux_rows, o.p, nullptr));
-  HIPCHK(hipMemcpy(out, o.p, (size_t)n * nout[kind] * 8, hipMemcpyDeviceToHost));
+  DeviceArray<double> i, a, o;
+  HIPCHK(i.upload(in, (size_t)n * nin[kind])); HIPCHK(a.upload(hax, naux)); HIPCHK(o.reserve((size_t)n * nout[kind]));
+  HIPCHK(gel::launch_point(kind, n, i.get(), a.get(), aux_rows, o.get(), nullptr));
+  HIPCHK(hipMemcpy(out, o.get(), (size_t)n * nout[kind] * 8, hipMemcpyDeviceToHost));
   return GEL_OK;
 }
 

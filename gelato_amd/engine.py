@@ -37,8 +37,28 @@ def pack_x(xdict, out=None):
     return np.concatenate([np.asarray(xdict[k], dtype=np.float64).ravel() for k in XKEYS], out=out)
 
 
+class _Handle:
+    """The one owner of a C problem handle: close() destroys it (once), and so does the collector when the last holder goes --
+    the Engine, or a pinned view of the handle's memory that outlives it.  It refers to nothing else, so reference counting
+    frees it."""
+
+    def __init__(self, ptr):
+        self.ptr = ptr
+
+    def close(self):
+        if self.ptr:
+            ptr, self.ptr = self.ptr, None
+            lib().gel_problem_destroy(ptr)
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 class _PinnedView(np.ndarray):
-    """numpy view of the handle's pinned host memory that keeps its Engine alive (attribute _engine on the base view)"""
+    """numpy view of the handle's pinned host memory that keeps the handle alive (attribute _owner on the base view)"""
 
 
 class Engine:
@@ -91,7 +111,8 @@ class Engine:
         # GEL_FLAG_EXACT_DEFECT_JAC (32, _lib): the defect groups' Jacobians exact to rounding instead of forward differences
         h = C.c_void_p()
         check(L.gel_problem_create(C.byref(d), C.byref(h)))
-        self._h = h
+        self._owner = _Handle(h)
+        self._h = h   # the raw pointer every call passes (self._owner holds the handle)
         dims = GelDims()
         check(L.gel_problem_dims(h, C.byref(dims)))
         self.S, self.N, self.M, self.nvars = dims.S, dims.N, dims.M, dims.num_vars
@@ -116,20 +137,16 @@ class Engine:
 
     # ------------------------------------------------------------------
     def close(self):
-        if getattr(self, "_h", None):
-            lib().gel_problem_destroy(self._h)
+        """Destroys the handle now.  Without close(), it goes when neither the engine nor a pinned view of it is left."""
+        owner = self.__dict__.get("_owner")
+        if owner is not None:
+            owner.close()
             self._h = None
             # the pinned buffers died with the handle: drop the views this object handed out of them (arrays a caller still holds
             # point at freed memory, like any view of a closed resource)
             self.__dict__.pop("_pinned", None)
             self.__dict__.pop("_cb_out", None)
             self._vals = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     # ------------------------------------------------------------------
     def D(self, i):
@@ -217,11 +234,13 @@ class Engine:
             r, v, x0, x1 = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
             check(lib().gel_pinned_buffers(self._h, C.byref(r), C.byref(v), C.byref(x0), C.byref(x1)))
             dp = C.POINTER(C.c_double)
-            # the views hold a reference to this engine (every slice of them reaches it through .base): the pinned memory is
-            # freed by close(), and a garbage-collected engine closes itself -- not while one of these arrays is alive
+            # the views hold a reference to the handle's owner, not to this engine (every slice of them reaches it through .base):
+            # the pinned memory is freed by close(), or once the engine and every one of these arrays are gone
+            owner = self._owner
+
             def view(ptr, n):
                 a = np.ctypeslib.as_array(C.cast(ptr, dp), shape=(n,)).view(_PinnedView)
-                a._engine = self
+                a._owner = owner
                 return a
             res = view(r, self.nres)
             vals = view(v, max(self.total_nnz, 1))[:self.total_nnz]

@@ -443,6 +443,7 @@ def test_fused_aero_rows_take_the_recomputing_fallback_like_the_aero_kernel(monk
     import torch
     from gelato_amd import Engine, con_dynamics, pack_x, problem
     pdict, unitdict, _c, xdict = problem.make_problem("mixed-6x64")
+    monkeypatch.setenv("GEL_AERO_FUSED", "1")   # read when the handle is created
     E = Engine(con_dynamics.problem_arrays(pdict, unitdict))
     S = pdict["num_sections"]
     for kind, lim in zip(KINDS, (0.2, 4.0e4, 5.0e3)):
@@ -469,7 +470,6 @@ def test_fused_aero_rows_take_the_recomputing_fallback_like_the_aero_kernel(monk
     s = torch.cuda.current_stream().cuda_stream
     B = len(X)
     dX = torch.from_numpy(X).to(dev)
-    monkeypatch.setenv("GEL_AERO_FUSED", "1")
     width, ocon, ojac = E.aero_record_layout()
     r1 = torch.empty((B, E.nres), dtype=torch.float64, device=dev)
     j1 = torch.empty((B, E.V), dtype=torch.float64, device=dev)
