@@ -16,6 +16,7 @@ GEL_OK, GEL_NONFINITE = 0, 1
 # gel_problem_desc.flags (include/gelato_amd.h)
 GEL_FLAG_FD_RECOMPUTE = 8
 GEL_FLAG_EXACT_DEFECT_JAC = 32   # defect-group Jacobians exact to rounding (forward mode) instead of forward differences
+GEL_FLAG_EXACT_AERO_JAC = 64     # aero path constraints' gradients exact to rounding (forward mode) instead of forward differences
 NUM_BLOCKS = 13
 
 _dp = C.POINTER(C.c_double)
@@ -134,7 +135,7 @@ def build(force=False):
     src_dir = os.path.join(_HERE, "csrc")
     if force and os.path.exists(SO_PATH):
         os.remove(SO_PATH)
-    subprocess.check_call(["make", "-s", "-j4", "-C", src_dir])   # four translation units (kernels, the AERO instantiation, the exact Jacobian, host side)
+    subprocess.check_call(["make", "-s", "-j5", "-C", src_dir])   # five translation units (kernels, the AERO instantiation, the two exact Jacobians, host side)
     if not os.path.exists(SO_PATH):
         raise RuntimeError("building %s failed" % SO_PATH)
     _write_build_info()

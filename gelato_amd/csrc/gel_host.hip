@@ -185,6 +185,7 @@ struct gel_problem {
   int device = 0;
   bool fd_recompute = false;   // GEL_FLAG_FD_RECOMPUTE (or a step too long for the difference form): the reference's recomputing sweeps
   bool exact = false;          // GEL_FLAG_EXACT_DEFECT_JAC: defect Jacobians by gel_kernels_exact.hip (residuals by the residual-only form)
+  bool exact_aero = false;     // GEL_FLAG_EXACT_AERO_JAC: aero gradients by gel_kernels_exact_aero.hip (values by the values-only aero launch)
   bool aero_fused = true;      // GEL_AERO_FUSED (read when the handle is created): 0 = gel_eval_batch_aero_device by the two kernels
   Stream stream;
   gel::ProblemDev dev{};
@@ -463,6 +464,22 @@ hipError_t launch_defects(const gel_problem* p, const gel::ProblemDev& dv, int B
     if (e != hipSuccess) return e;
   }
   return gel::launch_eval_exact(dv, B, x, jvar, s);
+}
+// The aero kinds of B vectors (launch_aero's outputs and addressing); on a handle created with GEL_FLAG_EXACT_AERO_JAC, a call with
+// gradients is the values-only aero launch followed by the exact aero kernel (same outputs: the constraint values bit-identical).
+// wide: the records' part B (launch_aero_wide); ld / spec_major: the records of gel_eval_batch_aero_device.
+hipError_t launch_aero_kinds(const gel_problem* p, const gel::ProblemDev& dv, int nnodes, const gel::AeroNodeDev* nodes, int B,
+                             const double* x, const gel::AeroLaunchOut& out, hipStream_t s, long long ld = 0, bool spec_major = false,
+                             bool wide = false) {
+  const bool jac = out.jac[0] || out.jac[1] || out.jac[2];
+  if (!p->exact_aero || !jac) return wide ? gel::launch_aero_wide(dv, nnodes, nodes, B, x, out, ld, s)
+                                          : gel::launch_aero(dv, nnodes, nodes, B, x, out, s, ld, spec_major);
+  gel::AeroLaunchOut vals = out;
+  for (int k = 0; k < 3; k++) vals.jac[k] = nullptr;
+  const hipError_t e = wide ? gel::launch_aero_wide(dv, nnodes, nodes, B, x, vals, ld, s)
+                            : gel::launch_aero(dv, nnodes, nodes, B, x, vals, s, ld, spec_major);
+  if (e != hipSuccess) return e;
+  return gel::launch_aero_exact(dv, nnodes, nodes, B, x, out, s, ld, !wide && spec_major);
 }
 #define NO_EXACT(p, what)                                                                                                   \
   do {                                                                                                                      \
@@ -827,6 +844,10 @@ int gel_problem_create(const gel_problem_desc* d, gel_problem** out) {
   if ((d->flags & GEL_FLAG_EXACT_DEFECT_JAC) &&
       ((d->flags & GEL_FLAG_FD_RECOMPUTE) || !(std::fabs(d->dx * d->unit_position) <= 1.0)))
     return fail(GEL_ERR_ARG, "GEL_FLAG_EXACT_DEFECT_JAC cannot be combined with GEL_FLAG_FD_RECOMPUTE (nor with |dx * unit_position| > 1)");
+  // the exact aero gradients fill the default layout (t columns as exact zeros, no t columns in the records' part A)
+  if ((d->flags & GEL_FLAG_EXACT_AERO_JAC) &&
+      ((d->flags & GEL_FLAG_FD_RECOMPUTE) || !(std::fabs(d->dx * d->unit_position) <= 1.0)))
+    return fail(GEL_ERR_ARG, "GEL_FLAG_EXACT_AERO_JAC cannot be combined with GEL_FLAG_FD_RECOMPUTE (nor with |dx * unit_position| > 1)");
   if (const char* why = gel::check_tables(d->wind_table, d->wind_rows, d->ca_table, d->ca_rows)) return fail(GEL_ERR_ARG, why);
   for (int i = 0; i < d->num_sections; i++)
     if (d->num_nodes[i] < 2) return fail(GEL_ERR_ARG, "every phase needs >= 2 LGR nodes (nodes_LGR requires n >= 2)");
@@ -848,6 +869,7 @@ int gel_problem_create(const gel_problem_desc* d, gel_problem** out) {
   // truncated series of the difference form are sized for (the reference's own dx = 1e-8 gives 0.064 m).
   p->fd_recompute = ((d->flags & GEL_FLAG_FD_RECOMPUTE) != 0) || !(std::fabs(d->dx * d->unit_position) <= 1.0);
   p->exact = (d->flags & GEL_FLAG_EXACT_DEFECT_JAC) != 0;
+  p->exact_aero = (d->flags & GEL_FLAG_EXACT_AERO_JAC) != 0;
   const char* fused = std::getenv("GEL_AERO_FUSED");
   p->aero_fused = !(fused && fused[0] == '0');
   p->barC20 = (d->barC20 == 0.0) ? -0.484165371736e-3 : d->barC20;
@@ -1874,7 +1896,8 @@ int gel_aero_record_map(const gel_problem* p, int32_t kind, int32_t var, int64_t
 int gel_eval_batch_aero_device(gel_problem* p, int32_t B, const double* d_x, double* d_res, double* d_jvar, double* d_aero,
                                void* stream) {
   if (!p || !d_x || B < 1 || !d_res || !d_jvar || !d_aero) return fail(GEL_ERR_ARG, "bad argument");
-  NO_EXACT(p, "gel_eval_batch_aero_device");
+  if (p->exact && !p->exact_aero)   // the exact defect Jacobian has no fused form with the FORWARD-DIFFERENCE aero rows
+    return fail(GEL_ERR_ARG, "gel_eval_batch_aero_device has no exact-Jacobian form (handle created with GEL_FLAG_EXACT_DEFECT_JAC)");
   NEED_DEVICE(p);
   if (p->aero.nodes.empty()) return fail(GEL_ERR_ARG, "no aero path constraints configured (gel_aero_configure)");
   hipStream_t s = stream ? (hipStream_t)stream : p->stream.get();
@@ -1886,8 +1909,13 @@ int gel_eval_batch_aero_device(gel_problem* p, int32_t B, const double* d_x, dou
       out[part].jac[k] = out[part].nrows[k] ? d_aero + p->aero.off_jac[part][k] : nullptr;
     }
   // GEL_AERO_FUSED=0: the two kernels one after the other (same record, same bits)
-  const bool fused = p->aero_fused && gel::eval_aero_fusable(p->dev, B) && !p->aero.part_nodes[0].empty();
-  if (fused) {
+  // GEL_FLAG_EXACT_AERO_JAC: the defect groups as gel_eval_batch_device forms them (launch_defects), then both parts of the record by
+  // the values-only aero launches and the exact aero kernel; the fused AERO instantiation is not used
+  const bool fused = !p->exact_aero && p->aero_fused && gel::eval_aero_fusable(p->dev, B) && !p->aero.part_nodes[0].empty();
+  if (p->exact_aero) {
+    HIPCHK(launch_defects(p, p->dev, B, d_x, d_res, d_jvar, s));
+    HIPCHK(launch_aero_kinds(p, p->dev, (int)p->aero.part_nodes[0].size(), p->aero.d_part_nodes[0].get(), B, d_x, out[0], s, p->aero.ld, true));
+  } else if (fused) {
     gel::ProblemDev dv = p->dev;
     dv.aero_ph = p->aero.d_ph.get(); dv.aero_out = d_aero; dv.aero_ld = p->aero.ld;
     HIPCHK(gel::launch_eval_aero(dv, B, d_x, d_res, d_jvar, s));
@@ -1895,7 +1923,7 @@ int gel_eval_batch_aero_device(gel_problem* p, int32_t B, const double* d_x, dou
     HIPCHK(gel::launch_eval(p->dev, B, d_x, d_res, d_jvar, s));
     HIPCHK(gel::launch_aero(p->dev, (int)p->aero.part_nodes[0].size(), p->aero.d_part_nodes[0].get(), B, d_x, out[0], s, p->aero.ld, true));
   }
-  HIPCHK(gel::launch_aero_wide(p->dev, (int)p->aero.part_nodes[1].size(), p->aero.d_part_nodes[1].get(), B, d_x, out[1], p->aero.ld, s));
+  HIPCHK(launch_aero_kinds(p, p->dev, (int)p->aero.part_nodes[1].size(), p->aero.d_part_nodes[1].get(), B, d_x, out[1], s, p->aero.ld, false, true));
   return GEL_OK;
 }
 
@@ -1940,7 +1968,7 @@ int gel_eval_aero_all_device(gel_problem* p, int32_t B, const double* d_x, doubl
     out.con[k] = out.nrows[k] ? d_con[k] : nullptr;
     out.jac[k] = (out.con[k] && d_jac) ? d_jac[k] : nullptr;
   }
-  HIPCHK(gel::launch_aero(p->dev, (int)p->aero.nodes.size(), p->aero.d_nodes.get(), B, d_x, out, stream ? (hipStream_t)stream : p->stream.get()));
+  HIPCHK(launch_aero_kinds(p, p->dev, (int)p->aero.nodes.size(), p->aero.d_nodes.get(), B, d_x, out, stream ? (hipStream_t)stream : p->stream.get()));
   return GEL_OK;
 }
 
@@ -1981,7 +2009,7 @@ int gel_eval_aero_all(gel_problem* p, int32_t B, const double* x, double* const*
   }
   gel::ProblemDev dv = p->dev;
   if (zero_copy) dv.flag = p->h_flag.get();
-  HIPCHK(gel::launch_aero(dv, (int)p->aero.nodes.size(), p->aero.d_nodes.get(), B, zero_copy ? p->h_x.get() : p->d_aero_x.get(), out, p->stream.get()));
+  HIPCHK(launch_aero_kinds(p, dv, (int)p->aero.nodes.size(), p->aero.d_nodes.get(), B, zero_copy ? p->h_x.get() : p->d_aero_x.get(), out, p->stream.get()));
   if (!zero_copy) {
     for (int k = 0; k < 3; k++) {
       if (out.con[k]) HIPCHK(hipMemcpyAsync(con[k], out.con[k], (size_t)B * p->aero.rows[k].size() * 8, hipMemcpyDeviceToHost, p->stream.get()));
@@ -2203,7 +2231,12 @@ int gel_eval_callback(gel_problem* p, const double* x, const gel_callback_io* io
   // kernel (launch_defects), then the row table and the aero kinds in launches of their own -- so that no forward-difference
   // sweep of the defect groups runs (nor flags a value that is then replaced)
   const bool split_exact = p->exact && want_jac;
-  const bool coo = want_jac && cb_mode != 3 && !p->exact && coo_direct(p);
+  // likewise on a GEL_FLAG_EXACT_AERO_JAC handle whose aero gradients are asked for: the values-only aero launch and the exact aero
+  // kernel (launch_aero_kinds) after the defect groups and the row table
+  bool aero_jac = false;
+  for (int k = 0; k < 3; k++) aero_jac = aero_jac || (io->aero_con[k] && io->aero_jac[k] && !p->aero.rows[k].empty());
+  const bool split_aero = p->exact_aero && aero_jac;
+  const bool coo = want_jac && cb_mode != 3 && !p->exact && !split_aero && coo_direct(p);
   if (coo) {
     if ((rc = ensure_full(p))) return rc;
     dv.coo_full = p->h_full.get(); dv.coo = p->d_coo.get();
@@ -2219,11 +2252,11 @@ int gel_eval_callback(gel_problem* p, const double* x, const gel_callback_io* io
       out.con[k] = (io->aero_con[k] && n) ? p->h_aero.get() + off_c[k] : nullptr;
       out.jac[k] = (out.con[k] && io->aero_jac[k]) ? p->h_aero.get() + off_j[k] : nullptr;
     }
-  if (cb_mode == 3 || !fused || split_exact) {
+  if (cb_mode == 3 || !fused || split_exact || split_aero) {
     if (fused) HIPCHK(launch_defects(p, dv, 1, xin, res_to, want_jac ? p->h_jv.get() : nullptr, p->stream.get()));
     if (rows) HIPCHK(gel::launch_rows(dv, (int)nlin, p->d_lin_rows.get(), (int)nfn, p->d_fn_rows.get(), 1, xin, p->h_rows.get(),
                                       io->rows_jfn ? p->h_rows.get() + R : nullptr, p->stream.get()));
-    if (aero) HIPCHK(gel::launch_aero(dv, (int)p->aero.nodes.size(), p->aero.d_nodes.get(), 1, xin, out, p->stream.get()));
+    if (aero) HIPCHK(launch_aero_kinds(p, dv, (int)p->aero.nodes.size(), p->aero.d_nodes.get(), 1, xin, out, p->stream.get()));
   } else {
     // ONE launch: defect groups, aero kinds and row table as workgroup ranges of one grid (gel_kernels.hip callback_kernel)
     arm_done(p, dv);

@@ -44,6 +44,11 @@ struct AeroLaunchOut { double* con[3]; double* jac[3]; int32_t nrows[3]; };
 hipError_t launch_aero(const ProblemDev& P, int nnodes, const AeroNodeDev* nodes, int B, const double* d_x,
                        const AeroLaunchOut& out, hipStream_t s, long long ld = 0, bool spec_major = false);
 
+// exact gradients of the aero kinds (gel_kernels_exact_aero.hip, GEL_FLAG_EXACT_AERO_JAC): out.jac only, in launch_aero's addressing
+// (ld = 0 dense arrays; ld != 0 records, spec_major part A or part B); the values come from a launch_aero without gradient outputs
+hipError_t launch_aero_exact(const ProblemDev& P, int nnodes, const AeroNodeDev* nodes, int B, const double* d_x,
+                             const AeroLaunchOut& out, hipStream_t s, long long ld = 0, bool spec_major = false);
+
 hipError_t launch_aero_wide(const ProblemDev& P, int nnodes, const AeroNodeDev* nodes, int B, const double* d_x,
                             const AeroLaunchOut& out, long long ld, hipStream_t s);
 

@@ -78,13 +78,15 @@ extern "C" {
                               added -- a phase with reference_area < 0 depends on velocity through the aerodynamic force, but the
                               reference's pattern holds only D there (no velocity sweep, lib/con_dynamics.py:403), and so does this.
                               The aero path constraints' gradients (gel_eval_aero*, the callback's aero part) and the node-function
-                              rows (gel_rows_*, the callback's row table) STAY forward differences with dx.
+                              rows (gel_rows_*, the callback's row table) STAY forward differences with dx; GEL_FLAG_EXACT_AERO_JAC
+                              (64) makes the aero part exact as well.
                               Residuals are bit-identical to a handle without the flag (the fused kernel's residual-only form runs
                               first; the exact kernel then writes the compact Jacobian: two launches per evaluation; gel_eval_callback
                               runs them, then the row table and the aero kinds, in launches of their own).  Pattern,
                               constants, compact layout and gather map are those of the default layout.  Evaluates through
                               gel_eval_residual / _jacobian, gel_eval, gel_eval_batch, gel_eval_batch_device, gel_eval_full_device and
-                              gel_eval_callback; gel_eval_batch_aero_device and gel_eval_shard_* return GEL_ERR_ARG, and so does
+                              gel_eval_callback; gel_eval_batch_aero_device (unless GEL_FLAG_EXACT_AERO_JAC is set as well) and
+                              gel_eval_shard_* return GEL_ERR_ARG, and so does
                               gel_problem_create for GEL_FLAG_FD_RECOMPUTE | GEL_FLAG_EXACT_DEFECT_JAC (or |dx * unit_position| > 1),
                               also on a host-only handle.  Conventions where the value is not differentiable -- the derivative of
                               the branch the value took: the table interval used (0 where interp clamps, x <= xp[0] included), the
@@ -92,6 +94,24 @@ extern "C" {
                               d|v_air| = 0 (the force's derivative is 0 there); polar axis p = 0: the partials of p and of the
                               longitude are 0.  A non-finite entry it writes makes the call return GEL_NONFINITE (gel_sync for the
                               device forms). */
+#define GEL_FLAG_EXACT_AERO_JAC 64 /* opt-in, independent of GEL_FLAG_EXACT_DEFECT_JAC (either alone or both): every gradient entry the
+                              aero path constraints write (angle of attack, dynamic pressure, q-alpha: inequality_jac_max_*) is the
+                              analytic derivative of con = 1 - f / limit with respect to the normalised position, velocity and
+                              quaternion (quaternion for alpha and q-alpha only), formed in fp64 forward mode -- exact to rounding,
+                              where the default is the reference's forward difference with dx.  The t0 / tf columns are exact zeros
+                              (the air-relative velocity does not depend on the Earth angle).  Dims, pattern, record layout and
+                              record map (gel_aero_dims / _pattern / _record_layout / _record_map) are those of the default.  The
+                              constraint values are bit-identical to a handle without the flag: the values-only aero launch runs
+                              first, then the exact kernel (gel_kernels_exact_aero.hip) writes the gradients.  Honoured by
+                              gel_eval_aero, gel_eval_aero_all, gel_eval_aero_all_device, gel_eval_callback (aero part in launches of
+                              its own) and gel_eval_batch_aero_device (defect groups as gel_eval_batch_device forms them, then both
+                              parts of the record; not the fused form).  gel_problem_create returns GEL_ERR_ARG for
+                              GEL_FLAG_FD_RECOMPUTE | GEL_FLAG_EXACT_AERO_JAC (or |dx * unit_position| > 1: the t columns are laid
+                              out differently there), also on a host-only handle.  Conventions: alpha's entries are 0 where its value
+                              is clamped to 0 (cos(alpha) > 1 or |v_air|^2 < 1e-12) and where the air velocity and the body axis are
+                              exactly parallel; the table-interval, atmosphere-layer, polar-axis and zero-air-speed conventions are
+                              those of GEL_FLAG_EXACT_DEFECT_JAC.  A non-finite entry it writes makes the call return GEL_NONFINITE
+                              (gel_sync for the device forms). */
 
 #define GEL_NUM_GROUPS 4
 #define GEL_NUM_BLOCKS 13
