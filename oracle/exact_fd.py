@@ -286,3 +286,162 @@ def aero_fd_truth(prob, x, spec):
                          float((ash - ac) / mpf("1e-3")), float((qsh - qc) / mpf("1e-3")), float(lat), float(alt)))
     keys = ("alpha", "q", "d_alpha", "d_q", "dalpha_dalt", "dq_dalt", "lat", "alt")
     return {k: np.array([row[i] for row in rows]) for i, k in enumerate(keys)}
+
+
+# ---- the other x-dependent entries of the default forward-difference Jacobian: NoAir velocity phases, the quaternion group,
+# ---- and the residuals of all four defect groups (tests/golden/make_exact_fd_groups.py, tests/test_exact_fd_groups.py) ----
+M_PI = mpf(3.141592653589793)          # the fp64 constant of src/pybind_dynamics.cpp:101, as an exact mpf
+
+
+def _split(prob, x):
+    nn = [int(v) for v in prob["num_nodes"]]
+    S, N = len(nn), sum(nn)
+    M = N + S
+    return (nn, x[:M], x[M:4 * M].reshape(-1, 3), x[4 * M:7 * M].reshape(-1, 3), x[7 * M:11 * M].reshape(-1, 4),
+            x[11 * M:11 * M + 2 * N].reshape(-1, 2), x[11 * M + 2 * N:])
+
+
+def rhs_noair(m_e, r_e, q, thrust, units, barC20):
+    """src/pybind_dynamics.cpp:73-92 on fp64 inputs (python floats); q exact mpf -> (acc / unit_vel [3], |T d / m| / unit_vel,
+    |g| / unit_vel) as mpf (max-norms: the magnitudes of the two terms whose roundings a fp64 run carries)"""
+    um, up, uv = units
+    m = f64(float(m_e) * float(um))                             # :78-79, rounded fp64 products
+    r = [f64(float(c) * float(up)) for c in r_e]
+    d = quatrot(conj(q), [mpf(1), mpf(0), mpf(0)])              # :85-86
+    g = gravity(r, barC20)                                      # :88
+    td = [thrust * d[i] / m for i in range(3)]
+    return ([(td[i] + g[i]) / uv for i in range(3)], max(abs(v) for v in td) / uv, max(abs(v) for v in g) / uv)
+
+
+def noair_fd_truth(prob, x, phase, barC20):
+    """Exact values of what the reference's velocity Jacobian of one phase WITHOUT aerodynamics (reference_area == 0) differences
+    (lib/con_dynamics.py:353-450 with dynamics() = dynamics_velocity_NoAir): f_c [n, 3] and the quotients
+    -(f_p - f_c)/dx (tf - to) unit_t / 2 of the mass (1), position (3) and quaternion (4) sweeps on exactly the fp64 inputs the
+    sweeps form (`+= dx`, then `* unit` rounded) -> dict: fc [n, 3], mass [n, 3], position [n, 3, 3], quaternion [n, 3, 4] (last
+    index = perturbed component), tmag, gmag [n] (max-norm of T d / m / unit_vel and of g / unit_vel at the node).  The velocity
+    block of such a phase is D alone and its t columns are the closed form +-f_c unit_t / 2 (:478-480)."""
+    nn, xm, xr, xv, xq, xu, xt = _split(prob, x)
+    um, up, uv = (f64(prob["units"][k]) for k in range(3))
+    ut = f64(prob["units"][4])
+    dx = float(prob["dx"])
+    xa, n = sum(nn[:phase]) + phase, nn[phase]
+    thrust = f64(prob["thrust"][phase])
+    scale = (f64(xt[phase + 1]) - f64(xt[phase])) * ut / 2
+    out = {"fc": np.zeros((n, 3)), "mass": np.zeros((n, 3)), "position": np.zeros((n, 3, 3)), "quaternion": np.zeros((n, 3, 4)),
+           "tmag": np.zeros(n), "gmag": np.zeros(n)}
+    for j in range(n):
+        k = xa + 1 + j
+        m0, r0, q0 = float(xm[k]), [float(v) for v in xr[k]], [float(v) for v in xq[k]]
+
+        def f(m=m0, r=r0, q=q0):
+            return rhs_noair(m, r, [f64(c) for c in q], thrust, (um, up, uv), barC20)[0]
+
+        fc, tmag, gmag = rhs_noair(m0, r0, [f64(c) for c in q0], thrust, (um, up, uv), barC20)
+
+        def quot(fp):
+            return [float(-(fp[i] - fc[i]) / f64(dx) * scale) for i in range(3)]
+
+        out["fc"][j] = [float(v) for v in fc]
+        out["tmag"][j], out["gmag"][j] = float(tmag), float(gmag)
+        out["mass"][j] = quot(f(m=m0 + dx))
+        for c in range(3):
+            rp = list(r0); rp[c] = rp[c] + dx
+            out["position"][j, :, c] = quot(f(r=rp))
+        for c in range(4):
+            qp = list(q0); qp[c] = qp[c] + dx
+            out["quaternion"][j, :, c] = quot(f(q=qp))
+    return out
+
+
+def quat_rate(q, u_e, uu):
+    """src/pybind_dynamics.cpp:94-106: d_quat = q (x) (0, 0, omega_y, omega_z) / 2 with omega = u * M_PI / 180 and u = u_e * unit_u
+    (a rounded fp64 product); q and u_e fp64 (python floats) -> 4 mpf"""
+    w = [f64(float(c) * float(uu)) * M_PI / 180 for c in u_e]
+    return [v / 2 for v in quatmult([f64(c) for c in q], [mpf(0), mpf(0), w[0], w[1]])]
+
+
+def quat_fd_truth(prob, x, phase):
+    """Exact values of what the reference's quaternion Jacobian of one free-attitude phase differences (lib/con_dynamics.py:569-613):
+    f_c [n, 4] and -(f_p - f_c)/dx (tf - to) unit_t / 2 for the quaternion (4) and u (2) sweeps -> dict: fc [n, 4],
+    quaternion [n, 4, 4], u [n, 4, 2] (last index = perturbed component).  d_quat is linear in q and in u, so each quotient is the
+    partial derivative times dl / dx, dl the step the reference really takes (fl(q + dx) - q; for u the difference of the two
+    rounded products fl(fl(u_e + dx) unit_u) - fl(u_e unit_u), over unit_u): evaluating the two sides exactly keeps that factor."""
+    nn, xm, xr, xv, xq, xu, xt = _split(prob, x)
+    uu, ut = float(prob["units"][3]), f64(prob["units"][4])
+    dx = float(prob["dx"])
+    ua, n = sum(nn[:phase]), nn[phase]
+    xa = ua + phase
+    scale = (f64(xt[phase + 1]) - f64(xt[phase])) * ut / 2
+    out = {"fc": np.zeros((n, 4)), "quaternion": np.zeros((n, 4, 4)), "u": np.zeros((n, 4, 2))}
+    for j in range(n):
+        q0, u0 = [float(v) for v in xq[xa + 1 + j]], [float(v) for v in xu[ua + j]]
+        fc = quat_rate(q0, u0, uu)
+
+        def quot(fp):
+            return [float(-(fp[i] - fc[i]) / f64(dx) * scale) for i in range(4)]
+
+        out["fc"][j] = [float(v) for v in fc]
+        for c in range(4):
+            qp = list(q0); qp[c] = qp[c] + dx
+            out["quaternion"][j, :, c] = quot(quat_rate(qp, u0, uu))
+        for c in range(2):
+            up_ = list(u0); up_[c] = up_[c] + dx
+            out["u"][j, :, c] = quot(quat_rate(q0, up_, uu))
+    return out
+
+
+def residual_truth(prob, x, phase, D, barC20):
+    """Exact residuals of the four defect groups of one phase on the fp64 D handed to the engine (D: [n, n + 1]) and the fp64 x:
+    D X - (tf - to) / 2 unit_t f, f exact (lib/con_dynamics.py:34-63 mass, :116-150 position, :216-289 velocity, :492-527
+    quaternion; hold / engine-off forms: differences to node 0) -> dict: mass [n], pos [n, 3], vel [n, 3], quat [n, 4]"""
+    nn, xm, xr, xv, xq, xu, xt = _split(prob, x)
+    um, up, uv, uu, ut = (f64(u) for u in prob["units"])
+    ua, n = sum(nn[:phase]), nn[phase]
+    xa = ua + phase
+    to, tf = float(xt[phase]), float(xt[phase + 1])
+    h = (f64(tf) - f64(to)) * ut / 2
+    Dm = [[f64(v) for v in row] for row in np.asarray(D, dtype=np.float64)]
+
+    def DX(col):      # col: [n + 1] of mpf -> [n] exact D . col
+        return [sum(Dm[j][k] * col[k] for k in range(n + 1)) for j in range(n)]
+
+    m = [f64(v) for v in xm[xa:xa + n + 1]]
+    if prob["engine_on"][phase]:
+        rh = -f64(prob["massflow"][phase]) / um * h           # :55-58
+        mass = [v - rh for v in DX(m)]
+    else:
+        mass = [v - m[0] for v in m[1:]]                      # :61
+    pos = np.zeros((n, 3)); vel = np.zeros((n, 3)); quat = np.zeros((n, 4))
+    for c in range(3):
+        dr = DX([f64(v) for v in xr[xa:xa + n + 1, c]])
+        for j in range(n):
+            pos[j, c] = float(dr[j] - f64(xv[xa + 1 + j, c]) * uv * h / up)   # :145-148
+    # velocity RHS per node: the NoAir form, or the aerodynamic one (as velocity_fd_truth evaluates it)
+    if prob["reference_area"][phase] == 0.0:
+        thrust = f64(prob["thrust"][phase])
+        fv = [rhs_noair(float(xm[xa + 1 + j]), [float(v) for v in xr[xa + 1 + j]], [f64(v) for v in xq[xa + 1 + j]], thrust,
+                        (um, up, uv), barC20)[0] for j in range(n)]
+    else:
+        tau = np.asarray(prob["tau"][phase], dtype=np.float64)
+        tn = tau * (tf - to) / 2 + (tf + to) / 2
+        wt, ct = np.asarray(prob["wind_table"]), np.asarray(prob["ca_table"])
+        wind = [[f64(v) for v in wt[:, c]] for c in range(3)]
+        ca = [[f64(v) for v in ct[:, c]] for c in range(2)]
+        args = (f64(prob["thrust"][phase]), f64(prob["reference_area"][phase]), f64(prob["nozzle_area"][phase]), wind, ca, (um, up, uv), barC20)
+        fv = [rhs_air(f64(xm[xa + 1 + j]), [f64(v) for v in xr[xa + 1 + j]], [f64(v) for v in xv[xa + 1 + j]],
+                      [f64(v) for v in xq[xa + 1 + j]], f64(tn[j]), *args) for j in range(n)]
+    for c in range(3):
+        dv = DX([f64(v) for v in xv[xa:xa + n + 1, c]])
+        for j in range(n):
+            vel[j, c] = float(dv[j] - fv[j][c] * h)
+    if prob["attitude_hold"][phase]:
+        for c in range(4):
+            for j in range(n):
+                quat[j, c] = float(f64(xq[xa + 1 + j, c]) - f64(xq[xa, c]))   # :521-522
+    else:
+        fq = [quat_rate([float(v) for v in xq[xa + 1 + j]], [float(v) for v in xu[ua + j]], float(prob["units"][3])) for j in range(n)]
+        for c in range(4):
+            dq = DX([f64(v) for v in xq[xa:xa + n + 1, c]])
+            for j in range(n):
+                quat[j, c] = float(dq[j] - fq[j][c] * h)
+    return {"mass": np.array([float(v) for v in mass]), "pos": pos, "vel": vel, "quat": quat}

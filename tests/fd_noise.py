@@ -263,3 +263,80 @@ def aero_first_order_truncation(terms, rows, limit, kind, t, dx):
         x = np.where(np.sin(a) > 0.0, np.cos(a) / (2.0 * np.sin(a)) * t, 0.0)
         d = x * (-t / (dx * limit)) * (1.0 if kind == "alpha" else q)
     return np.where(np.isfinite(d), d, 0.0)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# The rest of the default Jacobian (tests/test_exact_fd_groups.py, exact quotients in tests/golden/g21_exact_fd_groups.npz):
+#
+# NoAir velocity group (reference_area 0, src/pybind_dynamics.cpp:73-92: f = (T d(q) / m + g(r)) / unit_vel).
+#  * position sweeps, every form: gravity is recomputed at the perturbed point; each of its operations rounds independently in
+#    the two runs, and so does the sum with the unchanged thrust term -- the chain term of reference_bound_other with no aero
+#    term:  C_CHAIN eps (|T d / m| + |g|) / unit_vel  (tf - to) unit_t / 2 / dx;
+#  * mass and quaternion sweeps: the engine's default form is the closed form of the exact quotient (GEL_MASS_CLOSED,
+#    GEL_QUAT_CLOSED: a few roundings of the ENTRY, no difference): 1e-12 of the node's largest entry of the block; the
+#    recomputing form (flag 8) and the oracle difference two runs: the chain term above;
+#  * t columns: +-f_c unit_t / 2 in every form (lib/con_dynamics.py:478-480): 1e-12 + 1e-10 |.|.
+# Quaternion group (free attitude, :94-106: dq = q (x) (0, 0, w_y, w_z) / 2, w = u unit_u pi / 180).  With W = sum_i |q_i| (|w_y| +
+# |w_z|) / 2, the magnitude of the products a component of dq sums, and S = (tf - to) unit_t / 2:
+#  * recomputing form and oracle: two runs of a handful of products each, the perturbed one of magnitude W + |dl d(dq)/dl|:
+#    C_QUAT eps (W S / dx + |exact|)  (the second term: a u sweep from u = 0, where W = 0);
+#  * default form: six closed numbers (omega S / 2, unit_u (pi / 180) q_i S / 2) -- the PARTIAL derivative dS.  The reference's
+#    quotient is dS rho, rho = dl / dx the step it really takes over dx (q: fl(q + dx) - q; u: the difference of the two rounded
+#    products fl(fl(u + dx) unit_u) - fl(u unit_u), over unit_u), so  |entry - exact| <= |dS| |rho - 1| + C_QCLOSED eps |dS|
+#    (d2r = fl(pi / 180), S, the products: 6 roundings);  |dS| = |exact| / rho;
+#  * t columns: fq unit_t / 2, fq recomputed like the reference:  C_QUAT eps W unit_t / 2.
+# Residuals D X - S f, every group and form: (n + 1) eps |D| |X| (a dot product of n + 1 terms, any order or MFMA) + C_RES eps S F,
+# F the magnitude of the terms of f (mass: massflow / unit_mass; position: |v| unit_vel / unit_pos; velocity: |T d / m| + |g|
+# over unit_vel; quaternion: W); the hold / engine-off forms x_j - x_0: one rounding, eps |x_j - x_0|.
+# ---------------------------------------------------------------------------------------------------------------------------
+C_QUAT = 8.0
+C_QCLOSED = 8.0
+C_RES = 8.0
+CLOSED_REL = 1e-12
+
+
+def noair_chain_bound(tmag, gmag, scale):
+    """per node: position sweeps (every form); mass and quaternion sweeps of the recomputing form and of the oracle"""
+    return C_CHAIN * EPS * (np.asarray(tmag) + np.asarray(gmag)) * abs(scale)
+
+
+def closed_bound(exact):
+    """per entry of a block [n, rows, k]: 1e-12 of the node's largest exact entry"""
+    a = np.abs(exact)
+    return CLOSED_REL * a.reshape(len(a), -1).max(axis=1)[:, None, None] * np.ones_like(a)
+
+
+def t_column_bound(v):
+    return 1e-12 + 1e-10 * np.abs(v)
+
+
+def quat_magnitude(q, u, uu):
+    """q [n, 4], u [n, 2] (normalised) -> W [n] = sum |q_i| (|w_y| + |w_z|) / 2, w in rad"""
+    w = np.abs(np.asarray(u) * uu) * (np.pi / 180.0)
+    return np.abs(q).sum(axis=1) * w.sum(axis=1) / 2.0
+
+
+def quat_step_ratio(q, u, dx, uu):
+    """-> rho_q [n, 4], rho_u [n, 2]: the step each sweep of the reference really takes, over dx (exact differences in fp64)"""
+    q, u = np.asarray(q, dtype=np.float64), np.asarray(u, dtype=np.float64)
+    rq = ((q + dx) - q) / dx
+    ru = ((u + dx) * uu - u * uu) / (dx * uu)
+    return rq, ru
+
+
+def quat_closed_bound(exact, rho):
+    """exact [n, 4, k], rho [n, k] -> per entry: |dS| |rho - 1| + C_QCLOSED eps |dS|, dS = exact / rho"""
+    ds = np.abs(exact) / rho[:, None, :]
+    return ds * (np.abs(rho[:, None, :] - 1.0) + C_QCLOSED * EPS)
+
+
+def quat_chain_bound(W, scale, exact):
+    """W [n], exact [n, 4, k] -> per entry"""
+    return C_QUAT * EPS * (np.asarray(W)[:, None, None] * abs(scale) + np.abs(exact))
+
+
+def residual_bound(D, X, SF=0.0, diff=None):
+    """D [n, n + 1], X [n + 1, k] (or None: a difference form x_j - x_0 of X = diff) -> per row [n, k]"""
+    if diff is not None:
+        return EPS * np.abs(diff[1:] - diff[0])
+    return (D.shape[0] + 1) * EPS * (np.abs(D) @ np.abs(X)) + C_RES * EPS * np.abs(SF)

@@ -94,6 +94,22 @@ for name in ("g9_example", "g9_synthetic"):
                 out["aero_vs_exact"].append({"fixture": name, "kind": kind, "var": var, "who": who, "entries": int(vals.size),
                                              "entries_beyond_flat_tolerance_of_the_exact_quotient": int(np.count_nonzero(T.last_flat_excess > 0)),
                                              "worst_flat_excess": float(T.last_flat_excess.max())})
+# the NoAir velocity group, the quaternion group and the residuals against their exact quotients (G21), engine forms 0 and 8:
+# the largest |entry - exact| / derived bound per block (tests/test_exact_fd_groups.py asserts <= 1)
+import exact_fd_groups_truth as gx
+from gelato_amd import Engine
+out["groups_vs_exact"] = []
+for name in gx.STATES:
+    G, prob, x, P, D = gx.setup(name)
+    for flags in (0, 8):
+        E = Engine(prob, D=D, tau=prob["tau"], barC20=_orc.BARC20_CPP, flags=flags)
+        res, vals, rc = E.eval(x)
+        items = gx.checks(E.jac_dicts(vals), G, name, prob, x, D, "closed" if flags == 0 else "recompute")
+        items += gx.residual_checks(E.split_res(res), G, name, prob, x, D)
+        for block, ratio in gx.ratios(items).items():
+            err = max(float(np.abs(np.asarray(g) - e).max()) for lab, g, e, b in items if lab == block)
+            out["groups_vs_exact"].append({"fixture": name, "flags": flags, "block": block, "max_abs_err": err, "max_err_over_bound": ratio})
+        E.close()
 # summary
 dd = out["defect"]
 out["summary"] = {

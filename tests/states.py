@@ -176,3 +176,39 @@ def layer_break_state(n_max=None):
     x = np.concatenate([np.linspace(1.0, 0.5, n + 1), pos.ravel(), vel.ravel(), quat.ravel(),
                         2.0 * rng.standard_normal(2 * n), [10.0 / ut, 160.0 / ut]])
     return prob, x
+
+
+def noair_polar_state():
+    """Two phases without aerodynamics (reference_area 0), engine off (thrust 0, free attitude) then on (hold), 16 nodes each: nodes
+    ON the polar axis (x = y = 0 exactly, both poles), within millimetres .. metres of it, and elsewhere, at altitudes from 20 km
+    below the ellipsoid (below the polar radius: gravity's radius clamp) to 20,000 km.  The NoAir RHS (src/pybind_dynamics.cpp:73-92)
+    is thrust + J2 gravity: no geodetic conversion, no polar convention, so its quotients must hold there like anywhere."""
+    prob = _example_prob()
+    rng = np.random.default_rng(4242)
+    n = 16
+    S = 2
+    prob["num_nodes"] = np.array([n, n], dtype=np.int32)
+    prob["thrust"] = np.array([0.0, 30700.0])
+    prob["massflow"] = np.array([0.0, 9.8])
+    prob["reference_area"] = np.zeros(S)
+    prob["nozzle_area"] = np.zeros(S)
+    prob["engine_on"] = np.array([0, 1], dtype=np.int32)
+    prob["attitude_hold"] = np.array([0, 1], dtype=np.int32)
+    up, ut = prob["units"][1], prob["units"][4]
+    M = 2 * n + S
+    alt = np.tile([1e5, -20e3, -300.0, 0.0, 50.0, 100e3, 400e3, 1e6, 2e6, 5e6, 1e7, 2e7, -5e3, 30e3, 3e5, 3e6, 8e6], 2)
+    # colatitude from the +z axis, after node 0 of the phase (no sweep perturbs it): exactly 0 / pi (on the axis), 1e-12 .. 1e-6 rad
+    # (micrometres .. metres off it), then anywhere
+    colat = np.tile(np.concatenate([[0.7, 0.0, np.pi, 1e-12, 1e-9, np.pi - 1e-7, 1e-6], rng.uniform(0.0, np.pi, 10)]), 2)
+    lon = rng.uniform(-np.pi, np.pi, M)
+    a_e, b_e = 6378137.0, 6356752.314245
+    lat = np.pi / 2 - colat
+    R = (a_e * b_e / np.sqrt((b_e * np.cos(lat)) ** 2 + (a_e * np.sin(lat)) ** 2) + alt) / up
+    s = np.where((colat == 0.0) | (colat == np.pi), 0.0, np.sin(colat))
+    pos = np.column_stack([R * s * np.cos(lon), R * s * np.sin(lon), R * np.cos(colat)])
+    vel = rng.standard_normal((M, 3)) * 3.0
+    quat = rng.standard_normal((M, 4))
+    quat /= np.linalg.norm(quat, axis=1, keepdims=True)
+    x = np.concatenate([0.2 + rng.random(M), pos.ravel(), vel.ravel(), quat.ravel(), 2.0 * rng.standard_normal(2 * 2 * n),
+                        [10.0 / ut, 200.0 / ut, 900.0 / ut]])
+    return prob, x
