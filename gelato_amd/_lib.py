@@ -17,6 +17,7 @@ GEL_OK, GEL_NONFINITE = 0, 1
 GEL_FLAG_FD_RECOMPUTE = 8
 GEL_FLAG_EXACT_DEFECT_JAC = 32   # defect-group Jacobians exact to rounding (forward mode) instead of forward differences
 GEL_FLAG_EXACT_AERO_JAC = 64     # aero path constraints' gradients exact to rounding (forward mode) instead of forward differences
+GEL_FLAG_EXACT_ROWS_JAC = 128    # node-function rows' jfn (terminal, user, waypoint rows) exact to rounding instead of forward differences
 NUM_BLOCKS = 13
 
 _dp = C.POINTER(C.c_double)
@@ -135,7 +136,7 @@ def build(force=False):
     src_dir = os.path.join(_HERE, "csrc")
     if force and os.path.exists(SO_PATH):
         os.remove(SO_PATH)
-    subprocess.check_call(["make", "-s", "-j5", "-C", src_dir])   # five translation units (kernels, the AERO instantiation, the two exact Jacobians, host side)
+    subprocess.check_call(["make", "-s", "-j6", "-C", src_dir])   # six translation units (kernels, the AERO instantiation, the three exact Jacobians, host side)
     if not os.path.exists(SO_PATH):
         raise RuntimeError("building %s failed" % SO_PATH)
     _write_build_info()

@@ -19,7 +19,7 @@ non-finite output -> 1 (the reference hard-codes fail=False).
 """
 import numpy as np
 
-from ._lib import GEL_FLAG_EXACT_AERO_JAC, GEL_FLAG_EXACT_DEFECT_JAC
+from ._lib import GEL_FLAG_EXACT_AERO_JAC, GEL_FLAG_EXACT_DEFECT_JAC, GEL_FLAG_EXACT_ROWS_JAC
 from .engine import BLOCKS, Engine, _d, pack_x
 
 _KEY = "_gelato_amd"
@@ -67,6 +67,18 @@ def _aero_jacobian_flags(pdict):
     raise ValueError("pdict['aero_jacobian'] must be 'fd' or 'exact', not %r" % (how,))
 
 
+def _rows_jacobian_flags(pdict):
+    """pdict["rows_jacobian"]: "fd" (default: the reference's forward differences) or "exact" (analytic, fp64 forward mode) for the
+    Jacobians of the node-function rows (terminal orbit rows, device-form user constraints, waypoint / impact-point / antenna /
+    downrange rows)"""
+    how = pdict.get("rows_jacobian", "fd")
+    if how == "fd":
+        return 0
+    if how == "exact":
+        return GEL_FLAG_EXACT_ROWS_JAC
+    raise ValueError("pdict['rows_jacobian'] must be 'fd' or 'exact', not %r" % (how,))
+
+
 class _State:
     def __init__(self, pdict, unitdict):
         prob = problem_arrays(pdict, unitdict)
@@ -75,7 +87,7 @@ class _State:
         # D and tau are inputs of the path: whatever PSparams the caller put in pdict is used as is
         self.engine = Engine(prob, D=[ps.D(i) for i in range(S)], tau=[ps.tau(i) for i in range(S)],
                              barC20=float(pdict.get("barC20", 0.0)), device=int(pdict.get("device", 0)),
-                             flags=_defect_jacobian_flags(pdict) | _aero_jacobian_flags(pdict))
+                             flags=_defect_jacobian_flags(pdict) | _aero_jacobian_flags(pdict) | _rows_jacobian_flags(pdict))
         self.status = 0
         self._frame = None      # everything the device produced for the last xdict (one round trip)
         self._frame_sig = None

@@ -186,6 +186,7 @@ struct gel_problem {
   bool fd_recompute = false;   // GEL_FLAG_FD_RECOMPUTE (or a step too long for the difference form): the reference's recomputing sweeps
   bool exact = false;          // GEL_FLAG_EXACT_DEFECT_JAC: defect Jacobians by gel_kernels_exact.hip (residuals by the residual-only form)
   bool exact_aero = false;     // GEL_FLAG_EXACT_AERO_JAC: aero gradients by gel_kernels_exact_aero.hip (values by the values-only aero launch)
+  bool exact_rows = false;     // GEL_FLAG_EXACT_ROWS_JAC: node-function rows' jfn by gel_kernels_exact_rows.hip (values by rows_kernel)
   bool aero_fused = true;      // GEL_AERO_FUSED (read when the handle is created): 0 = gel_eval_batch_aero_device by the two kernels
   Stream stream;
   gel::ProblemDev dev{};
@@ -480,6 +481,16 @@ hipError_t launch_aero_kinds(const gel_problem* p, const gel::ProblemDev& dv, in
                             : gel::launch_aero(dv, nnodes, nodes, B, x, vals, s, ld, spec_major);
   if (e != hipSuccess) return e;
   return gel::launch_aero_exact(dv, nnodes, nodes, B, x, out, s, ld, !wide && spec_major);
+}
+// The row table of B vectors (launch_rows' outputs); on a handle created with GEL_FLAG_EXACT_ROWS_JAC, a call with jfn is rows_kernel
+// without the jfn output followed by the exact row kernel (the values bit-identical, no forward difference formed)
+hipError_t launch_rows_kinds(const gel_problem* p, const gel::ProblemDev& dv, int B, const double* x, double* con, double* jfn,
+                             hipStream_t s) {
+  const int nlin = (int)p->lin_rows.size(), nfn = (int)p->fn_rows.size();
+  if (!p->exact_rows || !jfn) return gel::launch_rows(dv, nlin, p->d_lin_rows.get(), nfn, p->d_fn_rows.get(), B, x, con, jfn, s);
+  const hipError_t e = gel::launch_rows(dv, nlin, p->d_lin_rows.get(), nfn, p->d_fn_rows.get(), B, x, con, nullptr, s);
+  if (e != hipSuccess) return e;
+  return gel::launch_rows_exact(dv, nfn, p->d_fn_rows.get(), B, x, jfn, s);
 }
 #define NO_EXACT(p, what)                                                                                                   \
   do {                                                                                                                      \
@@ -870,6 +881,7 @@ int gel_problem_create(const gel_problem_desc* d, gel_problem** out) {
   p->fd_recompute = ((d->flags & GEL_FLAG_FD_RECOMPUTE) != 0) || !(std::fabs(d->dx * d->unit_position) <= 1.0);
   p->exact = (d->flags & GEL_FLAG_EXACT_DEFECT_JAC) != 0;
   p->exact_aero = (d->flags & GEL_FLAG_EXACT_AERO_JAC) != 0;
+  p->exact_rows = (d->flags & GEL_FLAG_EXACT_ROWS_JAC) != 0;
   const char* fused = std::getenv("GEL_AERO_FUSED");
   p->aero_fused = !(fused && fused[0] == '0');
   p->barC20 = (d->barC20 == 0.0) ? -0.484165371736e-3 : d->barC20;
@@ -2080,8 +2092,7 @@ int gel_rows_dims(const gel_problem* p, int32_t* nlin, int32_t* nfn) {
 int gel_rows_eval_device(gel_problem* p, int32_t B, const double* d_x, double* d_con, double* d_jfn, void* stream) {
   if (!p || B < 1 || !d_x || !d_con) return fail(GEL_ERR_ARG, "bad argument");
   NEED_DEVICE(p);
-  HIPCHK(gel::launch_rows(p->dev, (int)p->lin_rows.size(), p->d_lin_rows.get(), (int)p->fn_rows.size(), p->d_fn_rows.get(), B, d_x,
-                          d_con, d_jfn, stream ? (hipStream_t)stream : p->stream.get()));
+  HIPCHK(launch_rows_kinds(p, p->dev, B, d_x, d_con, d_jfn, stream ? (hipStream_t)stream : p->stream.get()));
   return GEL_OK;
 }
 
@@ -2101,8 +2112,7 @@ int gel_rows_eval(gel_problem* p, int32_t B, const double* x, double* con, doubl
     std::memcpy(p->h_x.get(), x, nx * 8);
     gel::ProblemDev dv = p->dev;
     dv.flag = p->h_flag.get();
-    HIPCHK(gel::launch_rows(dv, (int)p->lin_rows.size(), p->d_lin_rows.get(), (int)nf, p->d_fn_rows.get(), B, p->h_x.get(), p->h_rows.get(),
-                            jfn ? p->h_rows.get() + nc : nullptr, p->stream.get()));
+    HIPCHK(launch_rows_kinds(p, dv, B, p->h_x.get(), p->h_rows.get(), jfn ? p->h_rows.get() + nc : nullptr, p->stream.get()));
     HIPCHK(hipStreamSynchronize(p->stream.get()));
     std::memcpy(con, p->h_rows.get(), nc * 8);
     if (jfn) std::memcpy(jfn, p->h_rows.get() + nc, nj * 8);
@@ -2111,8 +2121,8 @@ int gel_rows_eval(gel_problem* p, int32_t B, const double* x, double* con, doubl
   }
   HIPCHK(p->d_rows_x.reserve(nx)); HIPCHK(p->d_rows_out.reserve(nc + nj + 1));
   HIPCHK(hipMemcpyAsync(p->d_rows_x.get(), x, nx * 8, hipMemcpyHostToDevice, p->stream.get()));
-  HIPCHK(gel::launch_rows(p->dev, (int)p->lin_rows.size(), p->d_lin_rows.get(), (int)nf, p->d_fn_rows.get(), B, p->d_rows_x.get(),
-                          p->d_rows_out.get(), jfn ? p->d_rows_out.get() + nc : nullptr, p->stream.get()));
+  HIPCHK(launch_rows_kinds(p, p->dev, B, p->d_rows_x.get(), p->d_rows_out.get(), jfn ? p->d_rows_out.get() + nc : nullptr,
+                           p->stream.get()));
   HIPCHK(hipMemcpyAsync(con, p->d_rows_out.get(), nc * 8, hipMemcpyDeviceToHost, p->stream.get()));
   if (jfn) HIPCHK(hipMemcpyAsync(jfn, p->d_rows_out.get() + nc, nj * 8, hipMemcpyDeviceToHost, p->stream.get()));
   HIPCHK(hipMemcpyAsync(p->h_flag.get(), p->d_flag.get(), 4, hipMemcpyDeviceToHost, p->stream.get()));
@@ -2236,7 +2246,10 @@ int gel_eval_callback(gel_problem* p, const double* x, const gel_callback_io* io
   bool aero_jac = false;
   for (int k = 0; k < 3; k++) aero_jac = aero_jac || (io->aero_con[k] && io->aero_jac[k] && !p->aero.rows[k].empty());
   const bool split_aero = p->exact_aero && aero_jac;
-  const bool coo = want_jac && cb_mode != 3 && !p->exact && !split_aero && coo_direct(p);
+  // and on a GEL_FLAG_EXACT_ROWS_JAC handle whose row jfn is asked for: rows_kernel for the values, then the exact row kernel
+  // (launch_rows_kinds) -- no forward-difference sweep of the rows runs
+  const bool split_rows = p->exact_rows && rows && io->rows_jfn;
+  const bool coo = want_jac && cb_mode != 3 && !p->exact && !split_aero && !split_rows && coo_direct(p);
   if (coo) {
     if ((rc = ensure_full(p))) return rc;
     dv.coo_full = p->h_full.get(); dv.coo = p->d_coo.get();
@@ -2252,10 +2265,9 @@ int gel_eval_callback(gel_problem* p, const double* x, const gel_callback_io* io
       out.con[k] = (io->aero_con[k] && n) ? p->h_aero.get() + off_c[k] : nullptr;
       out.jac[k] = (out.con[k] && io->aero_jac[k]) ? p->h_aero.get() + off_j[k] : nullptr;
     }
-  if (cb_mode == 3 || !fused || split_exact || split_aero) {
+  if (cb_mode == 3 || !fused || split_exact || split_aero || split_rows) {
     if (fused) HIPCHK(launch_defects(p, dv, 1, xin, res_to, want_jac ? p->h_jv.get() : nullptr, p->stream.get()));
-    if (rows) HIPCHK(gel::launch_rows(dv, (int)nlin, p->d_lin_rows.get(), (int)nfn, p->d_fn_rows.get(), 1, xin, p->h_rows.get(),
-                                      io->rows_jfn ? p->h_rows.get() + R : nullptr, p->stream.get()));
+    if (rows) HIPCHK(launch_rows_kinds(p, dv, 1, xin, p->h_rows.get(), io->rows_jfn ? p->h_rows.get() + R : nullptr, p->stream.get()));
     if (aero) HIPCHK(launch_aero_kinds(p, dv, (int)p->aero.nodes.size(), p->aero.d_nodes.get(), 1, xin, out, p->stream.get()));
   } else {
     // ONE launch: defect groups, aero kinds and row table as workgroup ranges of one grid (gel_kernels.hip callback_kernel)

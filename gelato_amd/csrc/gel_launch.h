@@ -59,6 +59,9 @@ hipError_t launch_callback(const ProblemDev& P, bool want_jac, const double* d_x
                            int nlin, const LinRowDev* lin, int nfn, const FnRowDev* fr, double* d_con, double* d_jfn, hipStream_t s);
 hipError_t launch_rows(const ProblemDev& P, int nlin, const LinRowDev* lin, int nfn, const FnRowDev* fr, int B,
                        const double* d_x, double* d_con, double* d_jfn, hipStream_t s);
+// exact Jacobian of the node-function rows (gel_kernels_exact_rows.hip, GEL_FLAG_EXACT_ROWS_JAC): jfn [B][nfn][7] only, in
+// launch_rows' layout; the values come from a launch_rows without a jfn output
+hipError_t launch_rows_exact(const ProblemDev& P, int nfn, const FnRowDev* fr, int B, const double* d_x, double* d_jfn, hipStream_t s);
 
 // post-processing table (output_result.py): kOutputColumns values per state node, see include/gelato_amd.h
 constexpr int kOutputColumns = 34;

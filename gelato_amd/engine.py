@@ -110,6 +110,7 @@ class Engine:
         d.flags = int(flags)  # 0, or GEL_FLAG_DX_MFMA (1) / GEL_FLAG_DX_VALU (2) to force the D.X path, GEL_FLAG_NO_PACK (4), GEL_FLAG_FD_RECOMPUTE (8),
         # GEL_FLAG_EXACT_DEFECT_JAC (32, _lib): the defect groups' Jacobians exact to rounding instead of forward differences
         # GEL_FLAG_EXACT_AERO_JAC (64, _lib): the aero path constraints' gradients exact to rounding instead of forward differences
+        # GEL_FLAG_EXACT_ROWS_JAC (128, _lib): the node-function rows' jfn exact to rounding instead of forward differences
         h = C.c_void_p()
         check(L.gel_problem_create(C.byref(d), C.byref(h)))
         self._owner = _Handle(h)

@@ -79,7 +79,7 @@ extern "C" {
                               reference's pattern holds only D there (no velocity sweep, lib/con_dynamics.py:403), and so does this.
                               The aero path constraints' gradients (gel_eval_aero*, the callback's aero part) and the node-function
                               rows (gel_rows_*, the callback's row table) STAY forward differences with dx; GEL_FLAG_EXACT_AERO_JAC
-                              (64) makes the aero part exact as well.
+                              (64) makes the aero part exact as well, GEL_FLAG_EXACT_ROWS_JAC (128) the node-function rows.
                               Residuals are bit-identical to a handle without the flag (the fused kernel's residual-only form runs
                               first; the exact kernel then writes the compact Jacobian: two launches per evaluation; gel_eval_callback
                               runs them, then the row table and the aero kinds, in launches of their own).  Pattern,
@@ -111,7 +111,26 @@ extern "C" {
                               is clamped to 0 (cos(alpha) > 1 or |v_air|^2 < 1e-12) and where the air velocity and the body axis are
                               exactly parallel; the table-interval, atmosphere-layer, polar-axis and zero-air-speed conventions are
                               those of GEL_FLAG_EXACT_DEFECT_JAC.  A non-finite entry it writes makes the call return GEL_NONFINITE
-                              (gel_sync for the device forms). */
+                              (gel_sync for the device forms).  The node-function rows stay forward differences unless
+                              GEL_FLAG_EXACT_ROWS_JAC (128) is set as well. */
+#define GEL_FLAG_EXACT_ROWS_JAC 128 /* opt-in, combines with every other flag (GEL_FLAG_FD_RECOMPUTE included: the jfn layout does not
+                              depend on any flag): every jfn entry of a node-function row (gel_rows_configure: the terminal orbit
+                              rows, the device-form user constraints, the waypoint / impact-point / antenna / downrange rows) is
+                              s (df / dx_c) / p[0], s = -1 with mode & 8, for every value mode and for mode & 4 alike (their forward
+                              differences all approximate this quantity): the analytic derivative of the row's function with
+                              respect to the normalised column c (0..2 position, seed unit_position; 3..5 velocity, unit_velocity;
+                              6 the knot time, unit_t, where tcol >= 0), formed in fp64 forward mode -- exact to rounding, where
+                              the default is the forward difference with dx.  Columns the function does not read are exact zeros:
+                              column 6 of fn 0..8 and of rows with tcol < 0, the velocity columns of fn 9..11, 14 and 15.  The row
+                              values are bit-identical to a handle without the flag: rows_kernel runs without its jfn output, then
+                              the exact kernel (gel_kernels_exact_rows.hip) writes jfn.  Honoured by gel_rows_eval,
+                              gel_rows_eval_device and gel_eval_callback (the row table in launches of its own when rows_jfn is
+                              asked for).  Conventions where the value is not differentiable -- the derivative of the branch the
+                              value took: an impact point without a solution (the (0, 0) fill) has all seven entries 0; the
+                              inclination where c_z / |c| = +-1 exactly: 0; a norm at exactly 0 (|c|, e, |r|, |v|): its tangent is
+                              0; polar axis p = 0: the partials of p and of the longitude are 0; Vincenty with lon2 - lon1 == 0
+                              exactly: 0, otherwise the tangent carried through its loop, whose exit the value decides.  A
+                              non-finite entry it writes makes the call return GEL_NONFINITE (gel_sync for the device form). */
 
 #define GEL_NUM_GROUPS 4
 #define GEL_NUM_BLOCKS 13
