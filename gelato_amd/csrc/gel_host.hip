@@ -18,6 +18,7 @@
 #include "../../include/gelato_amd.h"
 #include "gel_device.h"
 #include "gel_launch.h"
+#include "gel_mesh.h"
 
 namespace {
 
@@ -170,6 +171,93 @@ int lgr_diffmat_ld(int n, std::vector<double>& D, std::vector<double>& tau_out) 
 }
 
 // ---------------------------------------------------------------------------
+// Collocation error estimate (gel_mesh_*): per phase of n nodes, on the fine grid sigma = the flipped LGR points
+// of n + 1 (sigma_0 = -1), the Lagrange bases of the phase's support tau_x = [-1, tau] (Lx) and of its collocation points tau
+// (Lu) at sigma_1 .. sigma_{n+1}, and the fine grid's Radau integration matrix I = (D^[:, 1:])^-1, D^ = lgr_diffmat(n + 1):
+// barycentric weights and Gauss-Jordan elimination in extended precision, rounded once.
+// ---------------------------------------------------------------------------
+std::vector<ld> bary_weights(const std::vector<ld>& t) {
+  std::vector<ld> w(t.size());
+  for (size_t i = 0; i < t.size(); i++) {
+    ld p = 1.0L;
+    for (size_t m = 0; m < t.size(); m++)
+      if (m != i) p *= (t[i] - t[m]);
+    w[i] = 1.0L / p;
+  }
+  return w;
+}
+// the Lagrange basis of support t (weights w) at z, second barycentric form; exactly 1 / 0 at a support point
+void lagrange_row(const std::vector<ld>& t, const std::vector<ld>& w, ld z, ld* out) {
+  for (size_t i = 0; i < t.size(); i++)
+    if (z == t[i]) {
+      for (size_t k = 0; k < t.size(); k++) out[k] = (k == i) ? 1.0L : 0.0L;
+      return;
+    }
+  ld sum = 0.0L;
+  for (size_t i = 0; i < t.size(); i++) { out[i] = w[i] / (z - t[i]); sum += out[i]; }
+  for (size_t i = 0; i < t.size(); i++) out[i] /= sum;
+}
+// sigma [P], Lx [P][n+1], Lu [P][n], I [P][P] (row-major, P = n + 1) of a phase whose collocation points are tau [n]
+int mesh_matrices_ld(const std::vector<double>& tau, std::vector<double>& out) {
+  const int n = (int)tau.size(), P = n + 1;
+  std::vector<ld> sg;
+  if (lgr_nodes_ld(P, sg)) return -1;
+  std::vector<ld> tx(P), tc(n);
+  tx[0] = -1.0L;
+  for (int k = 0; k < n; k++) tx[k + 1] = tc[k] = (ld)tau[k];
+  const std::vector<ld> wx = bary_weights(tx), wc = bary_weights(tc);
+  // D^ on the fine support s = [-1, sigma]: D^[k][i] = l_i'(s[k+1]); A = its columns 1 .. P, inverted in place
+  std::vector<ld> sup(P + 1);
+  sup[0] = -1.0L;
+  for (int k = 0; k < P; k++) sup[k + 1] = sg[k];
+  const std::vector<ld> ws = bary_weights(sup);
+  std::vector<ld> A((size_t)P * P), Inv((size_t)P * P, 0.0L);
+  for (int k = 0; k < P; k++) {
+    ld diag = 0.0L;
+    for (int i = 0; i <= P; i++) {
+      if (i == k + 1) continue;
+      const ld v = (ws[i] / ws[k + 1]) / (sup[k + 1] - sup[i]);
+      if (i > 0) A[(size_t)k * P + i - 1] = v;
+      diag -= v;
+    }
+    A[(size_t)k * P + k] = diag;
+    Inv[(size_t)k * P + k] = 1.0L;
+  }
+  for (int c = 0; c < P; c++) {   // Gauss-Jordan, partial pivoting
+    int piv = c;
+    for (int r = c + 1; r < P; r++)
+      if (fabsl(A[(size_t)r * P + c]) > fabsl(A[(size_t)piv * P + c])) piv = r;
+    if (!(fabsl(A[(size_t)piv * P + c]) > 0.0L)) return -1;
+    if (piv != c)
+      for (int k = 0; k < P; k++) { std::swap(A[(size_t)c * P + k], A[(size_t)piv * P + k]); std::swap(Inv[(size_t)c * P + k], Inv[(size_t)piv * P + k]); }
+    const ld ip = 1.0L / A[(size_t)c * P + c];
+    for (int k = 0; k < P; k++) { A[(size_t)c * P + k] *= ip; Inv[(size_t)c * P + k] *= ip; }
+    for (int r = 0; r < P; r++) {
+      if (r == c) continue;
+      const ld f = A[(size_t)r * P + c];
+      if (f == 0.0L) continue;
+      for (int k = 0; k < P; k++) { A[(size_t)r * P + k] -= f * A[(size_t)c * P + k]; Inv[(size_t)r * P + k] -= f * Inv[(size_t)c * P + k]; }
+    }
+  }
+  out.clear();
+  out.reserve((size_t)P * (1 + P + n + P));
+  for (int l = 0; l < P; l++) out.push_back((double)sg[l]);
+  std::vector<ld> row(P);
+  for (int l = 0; l < P; l++) {
+    lagrange_row(tx, wx, sg[l], row.data());
+    for (int i = 0; i < P; i++) out.push_back((double)row[i]);
+  }
+  for (int l = 0; l < P; l++) {
+    lagrange_row(tc, wc, sg[l], row.data());
+    for (int j = 0; j < n; j++) out.push_back((double)row[j]);
+  }
+  for (size_t k = 0; k < (size_t)P * P; k++) out.push_back((double)Inv[k]);
+  return 0;
+}
+// doubles of one phase's block in the host table: sigma | Lx | Lu | I
+inline size_t mesh_block_doubles(int n) { return (size_t)(n + 1) * (1 + (n + 1) + n + (n + 1)); }
+
+// ---------------------------------------------------------------------------
 struct HostPhase {
   int n, ua, xa;
   int air, air_fd, t_fd, q_fd, engine_on, hold;
@@ -279,6 +367,17 @@ struct gel_problem {
   PinnedArray<double> h_rows;                                 // pinned outputs of small gel_rows_eval calls: con | jfn
   DeviceArray<double> d_rows_x, d_rows_out;                   // working set of large host-buffer calls
   PinnedArray<double> h_aero;                                 // pinned outputs of small gel_eval_aero calls
+  // collocation error estimate (gel_mesh_*): per phase the host block sigma | Lx | Lu | I (row-major) at mesh_hoff[i], the device
+  // copy transposed (gel_mesh.h); none when a phase has more nodes than mesh_kernel's workgroup has lanes
+  std::vector<double> mesh_host;
+  std::vector<size_t> mesh_hoff;
+  std::vector<gel::MeshPhaseDev> mesh_ph;
+  int32_t mesh_npts = 0;
+  gel::MeshDev mesh_dev{};
+  DeviceArray<double> d_mesh_mat;
+  DeviceArray<gel::MeshPhaseDev> d_mesh_ph;
+  DeviceArray<double> d_mesh_x, d_mesh_out;                   // working set of large host-buffer calls
+  PinnedArray<double> h_mesh;                                 // pinned outputs of small gel_mesh_error calls: err | diff
   // large host batches (gel_eval_batch): two staging slots of kPipeEvals decision vectors each, every
   // slot with its own stream, so that PCIe in, kernel, PCIe out and the host copies of neighbouring
   // sub-batches overlap
@@ -1027,6 +1126,27 @@ int gel_problem_create(const gel_problem_desc* d, gel_problem** out) {
     }
   }
 
+  {
+    // collocation error estimate: every phase's block, built aside and committed once all are there (a phase that repeats an
+    // earlier one's n and tau repeats its block)
+    std::vector<double> mh, blk;
+    std::vector<size_t> hoff;
+    int32_t npts = 0;
+    bool fits = true;
+    for (int i = 0; i < S; i++) { npts += p->ph[i].n + 1; fits = fits && p->ph[i].n + 1 <= gel::kMeshMaxThreads; }
+    for (int i = 0; fits && i < S; i++) {
+      const HostPhase& h = p->ph[i];
+      int same = -1;
+      for (int j = 0; j < i; j++) if (p->ph[j].n == h.n && p->ph[j].tau == h.tau) { same = j; break; }
+      hoff.push_back(mh.size());
+      if (same >= 0) blk.assign(mh.begin() + hoff[same], mh.begin() + hoff[same] + mesh_block_doubles(h.n));
+      else if (mesh_matrices_ld(h.tau, blk)) return fail(GEL_ERR_ARG, "collocation error tables: singular integration matrix");
+      mh.insert(mh.end(), blk.begin(), blk.end());
+    }
+    p->mesh_host = std::move(mh);
+    p->mesh_hoff = std::move(hoff);
+    p->mesh_npts = npts;
+  }
   for (int i = 0; i < S; i++)
     for (int j0 = 0; j0 < p->ph[i].n; j0 += 64) p->chunk_phase.push_back(i);
   if (p->device == GEL_DEVICE_NONE) {
@@ -1163,6 +1283,34 @@ int gel_problem_create(const gel_problem_desc* d, gel_problem** out) {
   }
   dv.um = p->um; dv.up = p->up; dv.uv = p->uv; dv.uu = p->uu; dv.ut = p->ut; dv.dx = p->dx; dv.barC20 = p->barC20;
   dv.inv_uv = 1.0 / p->uv; dv.inv_dx = 1.0 / p->dx; dv.kpt = p->uv * p->ut / 2.0 / p->up; dv.hT = p->ut * 0.5;
+  if (!p->mesh_hoff.empty()) {
+    // the estimate's device tables: each phase's matrices transposed (point index fastest), LDS per workgroup of vpb vectors
+    std::vector<double> mat;
+    std::vector<gel::MeshPhaseDev> mph(S);
+    const size_t tab_lds = ((gel::staged_table_doubles(d->wind_rows, d->ca_rows) + 1) & ~(size_t)1);
+    int32_t pt0 = 0;
+    for (int i = 0; i < S; i++) {
+      const int n = p->ph[i].n, P = n + 1;
+      const double* hb = p->mesh_host.data() + p->mesh_hoff[i];
+      const double *sg = hb, *Lx = sg + P, *Lu = Lx + (size_t)P * P, *I = Lu + (size_t)P * n;
+      gel::MeshPhaseDev& q = mph[i];
+      q.n = n; q.vpb = gel::kMeshMaxThreads / P; q.pt0 = pt0; q.pad = 0;
+      pt0 += P;
+      q.lx = (int64_t)mat.size();
+      for (int k = 0; k < P; k++) for (int l = 0; l < P; l++) mat.push_back(Lx[(size_t)l * P + k]);
+      q.lu = (int64_t)mat.size();
+      for (int k = 0; k < n; k++) for (int l = 0; l < P; l++) mat.push_back(Lu[(size_t)l * n + k]);
+      q.it = (int64_t)mat.size();
+      for (int k = 0; k < P; k++) for (int l = 0; l < P; l++) mat.push_back(I[(size_t)l * P + k]);
+      q.sg = (int64_t)mat.size();
+      for (int l = 0; l < P; l++) mat.push_back(sg[l]);
+      q.lds = (int64_t)(8 * (tab_lds + (size_t)q.vpb * (11 * P + 2 * n + 11)));
+    }
+    HIPCHK(p->d_mesh_mat.upload(mat)); HIPCHK(p->d_mesh_ph.upload(mph));
+    p->mesh_ph = std::move(mph);
+    gel::MeshDev& md = p->mesh_dev;
+    md.S = S; md.npts = p->mesh_npts; md.ph = p->d_mesh_ph.get(); md.mat = p->d_mesh_mat.get(); md.vp = p->uv / p->up;
+  }
   *out = p.release();
   return GEL_OK;
 }
@@ -2128,6 +2276,73 @@ int gel_rows_eval(gel_problem* p, int32_t B, const double* x, double* con, doubl
   HIPCHK(hipMemcpyAsync(p->h_flag.get(), p->d_flag.get(), 4, hipMemcpyDeviceToHost, p->stream.get()));
   HIPCHK(hipStreamSynchronize(p->stream.get()));
   if (*p->h_flag.get()) { *p->h_flag.get() = 0; HIPCHK(hipMemsetAsync(p->d_flag.get(), 0, 4, p->stream.get())); return GEL_NONFINITE; }
+  return GEL_OK;
+}
+
+// ------------- collocation error estimate per section -------------
+#define NEED_MESH(p)                                                                                                   \
+  do {                                                                                                                 \
+    if ((p)->mesh_hoff.empty())                                                                                        \
+      return fail(GEL_ERR_ARG, "collocation error estimate: a phase has more than 511 nodes (one workgroup per point set)"); \
+  } while (0)
+
+int gel_mesh_dims(const gel_problem* p, int32_t* npts) {
+  if (!p || !npts) return fail(GEL_ERR_ARG, "null argument");
+  *npts = p->mesh_npts;
+  return GEL_OK;
+}
+
+int gel_mesh_matrices(const gel_problem* p, int32_t phase, double* sigma, double* Lx, double* Lu, double* I) {
+  if (!p || phase < 0 || phase >= p->dims.S) return fail(GEL_ERR_ARG, "bad argument");
+  NEED_MESH(p);
+  const int n = p->ph[phase].n, P = n + 1;
+  const double* hb = p->mesh_host.data() + p->mesh_hoff[phase];
+  if (sigma) std::memcpy(sigma, hb, (size_t)P * 8);
+  if (Lx) std::memcpy(Lx, hb + P, (size_t)P * P * 8);
+  if (Lu) std::memcpy(Lu, hb + P + (size_t)P * P, (size_t)P * n * 8);
+  if (I) std::memcpy(I, hb + P + (size_t)P * P + (size_t)P * n, (size_t)P * P * 8);
+  return GEL_OK;
+}
+
+int gel_mesh_error_device(gel_problem* p, int32_t B, const double* d_x, double* d_err, double* d_diff, void* stream) {
+  if (!p || B < 1 || !d_x || !d_err) return fail(GEL_ERR_ARG, "bad argument");
+  NEED_DEVICE(p);
+  NEED_MESH(p);
+  HIPCHK(gel::launch_mesh(p->dev, p->mesh_dev, p->mesh_ph.data(), B, d_x, d_err, d_diff, stream ? (hipStream_t)stream : p->stream.get()));
+  return GEL_OK;
+}
+
+int gel_mesh_error(gel_problem* p, int32_t B, const double* x, double* err, double* diff) {
+  if (!p || B < 1 || !x || !err) return fail(GEL_ERR_ARG, "bad argument");
+  NEED_DEVICE(p);
+  NEED_MESH(p);
+  HIPCHK(hipSetDevice(p->device));
+  const size_t nx = (size_t)B * p->dims.num_vars, ne = (size_t)B * p->dims.S * 4, nd = diff ? (size_t)B * p->mesh_npts * 11 : 0;
+  hipStream_t s = p->stream.get();
+  int rc;
+  if ((nx + ne + nd) * 8 <= kZeroCopyBytes) {
+    // a few vectors (after a solve): the kernel reads x from and writes to pinned host memory, one launch + one synchronise
+    if ((rc = ensure_capacity(p, B))) return rc;
+    HIPCHK(p->h_mesh.reserve(ne + nd));
+    std::memcpy(p->h_x.get(), x, nx * 8);
+    gel::ProblemDev dv = p->dev;
+    dv.flag = p->h_flag.get();
+    HIPCHK(gel::launch_mesh(dv, p->mesh_dev, p->mesh_ph.data(), B, p->h_x.get(), p->h_mesh.get(), diff ? p->h_mesh.get() + ne : nullptr, s));
+    HIPCHK(hipStreamSynchronize(s));
+    std::memcpy(err, p->h_mesh.get(), ne * 8);
+    if (diff) std::memcpy(diff, p->h_mesh.get() + ne, nd * 8);
+    if (*p->h_flag.get()) { *p->h_flag.get() = 0; return GEL_NONFINITE; }
+    return GEL_OK;
+  }
+  HIPCHK(p->d_mesh_x.reserve(nx)); HIPCHK(p->d_mesh_out.reserve(ne + nd));
+  HIPCHK(hipMemcpyAsync(p->d_mesh_x.get(), x, nx * 8, hipMemcpyHostToDevice, s));
+  HIPCHK(gel::launch_mesh(p->dev, p->mesh_dev, p->mesh_ph.data(), B, p->d_mesh_x.get(), p->d_mesh_out.get(),
+                          diff ? p->d_mesh_out.get() + ne : nullptr, s));
+  HIPCHK(hipMemcpyAsync(err, p->d_mesh_out.get(), ne * 8, hipMemcpyDeviceToHost, s));
+  if (diff) HIPCHK(hipMemcpyAsync(diff, p->d_mesh_out.get() + ne, nd * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(p->h_flag.get(), p->d_flag.get(), 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (*p->h_flag.get()) { *p->h_flag.get() = 0; HIPCHK(hipMemsetAsync(p->d_flag.get(), 0, 4, s)); return GEL_NONFINITE; }
   return GEL_OK;
 }
 

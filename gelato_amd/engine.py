@@ -659,6 +659,37 @@ class Engine:
         check(lib().gel_rows_eval_device(self._h, B, d_x, d_con, d_jfn or None, stream or None))
 
     # ------------------------------------------------------------------
+    # collocation error estimate per section (include/gelato_amd.h gel_mesh_*)
+    MESH_GROUPS = ("mass", "position", "velocity", "quaternion")
+
+    def mesh_npts(self):
+        """test points of the estimate: sum over phases of n + 1 (the rows of mesh_error's diff)"""
+        n = C.c_int32()
+        check(lib().gel_mesh_dims(self._h, C.byref(n)))
+        return int(n.value)
+
+    def mesh_matrices(self, phase):
+        """{"sigma" [n+1], "Lx" [n+1, n+1], "Lu" [n+1, n], "I" [n+1, n+1]} of one phase (works on host-only handles)"""
+        n = int(self.num_nodes[phase])
+        P = n + 1
+        out = {"sigma": np.zeros(P), "Lx": np.zeros((P, P)), "Lu": np.zeros((P, n)), "I": np.zeros((P, P))}
+        check(lib().gel_mesh_matrices(self._h, int(phase), _d(out["sigma"]), _d(out["Lx"]), _d(out["Lu"]), _d(out["I"])))
+        return out
+
+    def mesh_error(self, X, want_diff=False):
+        """X [B, nvars] (or [nvars]) -> (err [B, S, 4] (mass, position, velocity, quaternion), diff [B, npts, 11] | None, status)"""
+        X = _f64(X).reshape(-1, self.nvars)
+        B = X.shape[0]
+        err = np.empty((B, self.S, 4))
+        diff = np.empty((B, self.mesh_npts(), 11)) if want_diff else None
+        rc = check(lib().gel_mesh_error(self._h, B, _d(X), _d(err), _d(diff) if want_diff else None))
+        return err, diff, rc
+
+    def mesh_error_device(self, B, d_x, d_err, d_diff=0, stream=0):
+        """device buffers: d_err [B][S][4], d_diff [B][npts][11] or 0; status through sync()"""
+        check(lib().gel_mesh_error_device(self._h, int(B), d_x, d_err, d_diff or None, stream or None))
+
+    # ------------------------------------------------------------------
     def split_x(self, x):
         M, N, S = self.M, self.N, self.S
         o = np.cumsum([0, M, 3 * M, 3 * M, 4 * M, 2 * N, S + 1])

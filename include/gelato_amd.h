@@ -378,6 +378,32 @@ int gel_rows_dims(const gel_problem* p, int32_t* nlin, int32_t* nfn);
 int gel_rows_eval(gel_problem* p, int32_t B, const double* x, double* con, double* jfn /* or NULL */);
 int gel_rows_eval_device(gel_problem* p, int32_t B, const double* d_x, double* d_con, double* d_jfn /* or NULL */, void* stream);
 
+/* ---- collocation error estimate per section (the LGR mesh-error estimate of Garg et al. 2009 / GPOPS-II's ph method; DESIGN.md
+ *      3.9): is the trajectory accurate BETWEEN the nodes?  For phase s of n nodes, on its own tau (generated or desc.tau), with
+ *      the flipped LGR points sigma_1 .. sigma_{n+1} of n + 1 (sigma_{n+1} = +1, sigma_0 = -1):
+ *        X~(sigma_l) = sum_i Lx[l][i] X_i   (Lagrange basis on tau_x = [-1, tau], the n + 1 state nodes xa .. xa + n; X~(sigma_0) = X_0)
+ *        U~(sigma_l) = sum_j Lu[l][j] U_j   (Lagrange basis on tau, the n collocation nodes' u)
+ *        F_l = the right-hand side the phase's DEFECT ROWS impose, at (X~, U~, t(sigma_l) = sigma_l (tf - to)/2 + (tf + to)/2
+ *              normalised, as PSparams.time_nodes): mass -massflow/unit_mass with the engine on, else 0; position
+ *              X~_vel unit_v/unit_p; velocity dynamics_velocity (reference_area != 0) or _NoAir, / unit_v; quaternion
+ *              dynamics_quaternion, or 0 for a held attitude
+ *        X^(sigma_j) = X_0 + S sum_l I[j][l] F_l,  S = (tf - to) unit_t / 2,  I = (D^[:, 1:])^-1, D^ = gel_lgr_diffmat(n + 1)
+ *        e_{j,c} = |X^_c(sigma_j) - X~_c(sigma_j)| / (1 + max_{l=0..n+1} |X~_c(sigma_l)|)
+ *      over the 11 state components c (x's order: mass, position 3, velocity 3, quaternion 4).  The matrices are built at
+ *      gel_problem_create in extended precision (host-only handles included); phases of more than 511 nodes have none and the
+ *      gel_mesh_* calls but gel_mesh_dims refuse such a handle.  The flags of the handle do not change the estimate. ---- */
+/* npts = sum over phases of (n_s + 1): the test points, in phase order (the rows of diff) */
+int gel_mesh_dims(const gel_problem* p, int32_t* npts);
+/* phase's fine grid and matrices, row-major (P = n + 1); any pointer may be NULL */
+int gel_mesh_matrices(const gel_problem* p, int32_t phase, double* sigma /* [P] */, double* Lx /* [P][n+1] */,
+                      double* Lu /* [P][n] */, double* I /* [P][P] */);
+/* B decision vectors x [B][num_vars] -> err [B][S][4]: max of e over the test points and over the components of each group
+ * (mass, position, velocity, quaternion); diff (NULL: not wanted) [B][npts][11]: the signed X^ - X~ at every test point.  Returns
+ * GEL_NONFINITE when an output is NaN / Inf (the other vectors' outputs stay valid).  Host buffers; one device launch. */
+int gel_mesh_error(gel_problem* p, int32_t B, const double* x, double* err, double* diff /* or NULL */);
+/* the same on device buffers, asynchronous on `stream` (NULL = the handle's); status through gel_sync */
+int gel_mesh_error_device(gel_problem* p, int32_t B, const double* d_x, double* d_err, double* d_diff /* or NULL */, void* stream);
+
 /* ---- one optimiser callback = one device round trip: the four defect groups, the knot / terminal / user row table and the
  *      aero path constraints of ONE decision vector launched back to back on the handle's stream, one synchronise
  *      (what objfunc / sens of Trajectory_Optimization.py:194-312 need from the device).  Every output pointer may be
