@@ -123,6 +123,12 @@ SIGNATURES = {
     "gel_mesh_matrices": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, _dp, _dp]),
     "gel_mesh_error": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, _dp]),
     "gel_mesh_error_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gel_jac_matvec_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gel_jac_rmatvec_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gel_jac_matvec": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, _dp]),
+    "gel_jac_rmatvec": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, _dp]),
+    "gel_jac_products_host": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, _dp, C.c_int32]),
+    "gel_jac_products_info": (C.c_int, [C.c_void_p, _lp]),
     "gel_initial_guess": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, _dp, _dp]),
     "gel_output_table": (C.c_int, [C.c_void_p, _dp, _dp, C.c_double, C.c_double, _dp]),
     "gel_dynamics_velocity": (C.c_int, [C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int32, _dp, C.c_int32,
@@ -140,7 +146,7 @@ def build(force=False):
     src_dir = os.path.join(_HERE, "csrc")
     if force and os.path.exists(SO_PATH):
         os.remove(SO_PATH)
-    subprocess.check_call(["make", "-s", "-j7", "-C", src_dir])   # seven translation units (kernels, the AERO instantiation, the three exact Jacobians, the mesh error estimate, host side)
+    subprocess.check_call(["make", "-s", "-j8", "-C", src_dir])   # eight translation units (kernels, the AERO instantiation, the three exact Jacobians, the mesh error estimate, the Jacobian products, host side)
     if not os.path.exists(SO_PATH):
         raise RuntimeError("building %s failed" % SO_PATH)
     _write_build_info()

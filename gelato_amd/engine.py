@@ -690,6 +690,67 @@ class Engine:
         check(lib().gel_mesh_error_device(self._h, int(B), d_x, d_err, d_diff or None, stream or None))
 
     # ------------------------------------------------------------------
+    # Jacobian products from the compact values (include/gelato_amd.h gel_jac_*)
+    def _jac_product(self, fn, jvar, inp, nin, nout):
+        jvar, inp = _f64(jvar), _f64(inp)
+        lead = inp.shape[:-1]
+        if jvar.shape[-1] != self.V or inp.shape[-1] != nin or jvar.shape[:-1] != lead:
+            raise ValueError("jvar [..., %d] and the input [..., %d] must share their leading shape" % (self.V, nin))
+        B = int(np.prod(lead, dtype=np.int64)) if lead else 1
+        out = np.empty(lead + (nout,))
+        rc = check(fn(self._h, B, _d(jvar), _d(inp), _d(out)))
+        return out, rc
+
+    def jac_matvec(self, jvar, V):
+        """jvar [..., V], V [..., nvars] -> (y [..., 11N] = J v per vector, status)"""
+        return self._jac_product(lib().gel_jac_matvec, jvar, V, self.nvars, self.nres)
+
+    def jac_rmatvec(self, jvar, Lam):
+        """jvar [..., V], Lam [..., 11N] -> (g [..., nvars] = J^T lambda per vector, status)"""
+        return self._jac_product(lib().gel_jac_rmatvec, jvar, Lam, self.nres, self.nvars)
+
+    def jac_matvec_device(self, B, d_jvar, d_v, d_y, stream=0):
+        """device buffers: d_jvar [B][V], d_v [B][nvars] -> d_y [B][11N]; status through sync()"""
+        check(lib().gel_jac_matvec_device(self._h, int(B), d_jvar, d_v, d_y, stream or None))
+
+    def jac_rmatvec_device(self, B, d_jvar, d_lam, d_g, stream=0):
+        """device buffers: d_jvar [B][V], d_lam [B][11N] -> d_g [B][nvars]; status through sync()"""
+        check(lib().gel_jac_rmatvec_device(self._h, int(B), d_jvar, d_lam, d_g, stream or None))
+
+    def jac_products_host(self, jvar, inp, transpose=False):
+        """the same products in plain C++ on the host, from the same tables (works on host-only handles) -> (out, status)"""
+        t = int(bool(transpose))
+        return self._jac_product(lambda h, B, a, b, c: lib().gel_jac_products_host(h, B, a, b, c, t), jvar, inp,
+                                 self.nres if t else self.nvars, self.nvars if t else self.nres)
+
+    def jac_products_info(self):
+        """{"const_nnz", "var_entries", "max_row_nnz", "max_col_nnz"} of the operator tables"""
+        info = (C.c_int64 * 4)()
+        check(lib().gel_jac_products_info(self._h, info))
+        return dict(zip(("const_nnz", "var_entries", "max_row_nnz", "max_col_nnz"), (int(v) for v in info)))
+
+    def jac_operator(self, jvar_row):
+        """scipy.sparse.linalg.LinearOperator of shape (11N, nvars) for ONE vector's compact values; matvec / rmatvec run on the
+        device (scipy is imported here, not with the package)"""
+        from scipy.sparse.linalg import LinearOperator
+        jv = _f64(jvar_row).reshape(self.V).copy()
+
+        def mv(v):
+            return self.jac_matvec(jv, np.asarray(v, dtype=np.float64).reshape(self.nvars))[0]
+
+        def rmv(lam):
+            return self.jac_rmatvec(jv, np.asarray(lam, dtype=np.float64).reshape(self.nres))[0]
+
+        return LinearOperator((self.nres, self.nvars), matvec=mv, rmatvec=rmv, dtype=np.float64)
+
+    def merit_gradient(self, X):
+        """X [B, nvars] (or [nvars]) -> (phi [B] = 1/2 ||res||^2, g [B, nvars] = J^T res, status): one eval_batch, one product"""
+        X = _f64(X).reshape(-1, self.nvars)
+        res, jv, rc = self.eval_batch(X)
+        g, rc2 = self.jac_rmatvec(jv, res)
+        return 0.5 * np.einsum("bi,bi->b", res, res), g, max(rc, rc2)
+
+    # ------------------------------------------------------------------
     def split_x(self, x):
         M, N, S = self.M, self.N, self.S
         o = np.cumsum([0, M, 3 * M, 3 * M, 4 * M, 2 * N, S + 1])

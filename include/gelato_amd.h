@@ -404,6 +404,31 @@ int gel_mesh_error(gel_problem* p, int32_t B, const double* x, double* err, doub
 /* the same on device buffers, asynchronous on `stream` (NULL = the handle's); status through gel_sync */
 int gel_mesh_error_device(gel_problem* p, int32_t B, const double* d_x, double* d_err, double* d_diff /* or NULL */, void* stream);
 
+/* ---- batched Jacobian products from the compact values: y_b = J(x_b) v_b and g_b = J(x_b)^T lambda_b for the
+ *      four defect groups (the 13 COO blocks), where J(x_b) is exactly the matrix that gel_pattern_all + gel_const_values +
+ *      gel_full_source applied to jvar[b] define -- whatever the handle's flags put into jvar.  The full value array is never
+ *      formed.  Rows of y / lambda in the residual order [mass N | pos 3N | vel 3N | quat 4N]; columns of v / g in the packed
+ *      decision-vector order.  Every element of y and g is written by every call (a column without an entry gets 0.0).  A vector's
+ *      results depend neither on its neighbours in the batch nor on B, and are bit-identical run to run (no floating-point
+ *      atomics; every sum has a fixed order).  The operator tables are built by gel_problem_create from the same pattern walk
+ *      as the gather map (host-only handles included). ---- */
+/* device buffers, asynchronous on `stream` (NULL = the handle's); status through gel_sync: GEL_NONFINITE when some output is
+ * NaN / Inf (the other vectors' outputs stay valid).  gel_jac_rmatvec_device keeps per-phase partial sums of the time columns
+ * in a workspace of the handle: calls on one handle must not overlap on different streams. */
+int gel_jac_matvec_device(gel_problem* p, int32_t B, const double* d_jvar /* [B][V] */, const double* d_v /* [B][num_vars] */,
+                          double* d_y /* [B][11N] */, void* stream);
+int gel_jac_rmatvec_device(gel_problem* p, int32_t B, const double* d_jvar /* [B][V] */, const double* d_lam /* [B][11N] */,
+                           double* d_g /* [B][num_vars] */, void* stream);
+/* the same on host buffers (copy in, one launch, copy out, one synchronise); returns GEL_OK or GEL_NONFINITE */
+int gel_jac_matvec(gel_problem* p, int32_t B, const double* jvar, const double* v, double* y);
+int gel_jac_rmatvec(gel_problem* p, int32_t B, const double* jvar, const double* lam, double* g);
+/* plain C++ on the host from the SAME tables (works on GEL_DEVICE_NONE handles): transpose = 0: in = v, out = y; else in = lambda,
+ * out = g.  Returns GEL_OK or GEL_NONFINITE. */
+int gel_jac_products_host(const gel_problem* p, int32_t B, const double* jvar, const double* in, double* out, int32_t transpose);
+/* info [4]: non-zero constant entries, variable entries, largest non-zero count of a row, of a column (variable entries count
+ * as non-zero) */
+int gel_jac_products_info(const gel_problem* p, int64_t* info);
+
 /* ---- one optimiser callback = one device round trip: the four defect groups, the knot / terminal / user row table and the
  *      aero path constraints of ONE decision vector launched back to back on the handle's stream, one synchronise
  *      (what objfunc / sens of Trajectory_Optimization.py:194-312 need from the device).  Every output pointer may be
