@@ -50,6 +50,7 @@ class HipArray {
   }
   ~HipArray() { reset(); }
   T* get() const { return p_; }
+  size_t capacity() const { return cap_; }
   hipError_t reserve(size_t n) {
     if (cap_ >= n) return hipSuccess;
     reset();
@@ -279,6 +280,9 @@ struct gel_problem {
   bool exact_rows = false;     // GEL_FLAG_EXACT_ROWS_JAC: node-function rows' jfn by gel_kernels_exact_rows.hip (values by rows_kernel)
   bool aero_fused = true;      // GEL_AERO_FUSED (read when the handle is created): 0 = gel_eval_batch_aero_device by the two kernels
   Stream stream;
+  // The last caller-owned stream a device-form entry point was given (stream_of); gel_sync on it clears it again.  Whatever releases
+  // or replaces device memory that a device-form launch reads waits for this stream as well as for the handle's own (drain).
+  hipStream_t caller_stream = nullptr;
   gel::ProblemDev dev{};
   std::vector<HostPhase> ph;
   gel_dims dims{};
@@ -414,8 +418,8 @@ struct gel_problem {
   ~gel_problem() {
     if (device == GEL_DEVICE_NONE) return;
     hipSetDevice(device);
-    for (hipStream_t s : {stream.get(), slot[0].stream.get(), slot[1].stream.get()})
-      if (s) hipStreamSynchronize(s);
+    for (hipStream_t s : {stream.get(), slot[0].stream.get(), slot[1].stream.get(), caller_stream})
+      if (s) (void)hipStreamSynchronize(s);   // a caller's stream that is gone by now answers with an error: nothing runs on it
   }
 };
 
@@ -730,6 +734,27 @@ void jprod_host_op(const gel_problem& P, const gel::JprodOpDev& op, int64_t voff
   }
 }
 
+// The stream a device-form entry point launches on: the caller's (remembered for drain) or, for NULL, the handle's own.
+hipStream_t stream_of(gel_problem* p, void* stream) {
+  if (!stream) return p->stream.get();
+  return p->caller_stream = (hipStream_t)stream;
+}
+// Before device memory that launches read or write is released or replaced (a reconfiguration, a new shard plan, a workspace that
+// grows): wait for the handle's own stream AND for the last caller-owned stream, so that nothing in flight still uses the old block.
+hipError_t drain(gel_problem* p) {
+  if (p->stream.get())
+    if (const hipError_t e = hipStreamSynchronize(p->stream.get())) return e;
+  if (p->caller_stream)
+    if (const hipError_t e = hipStreamSynchronize(p->caller_stream)) return e;
+  return hipSuccess;
+}
+// A host-form call that found the device's non-finite flag set clears it and WAITS for the clear, as gel_sync does: a launch that
+// the caller enqueues on a stream of its own right after the return must not have its flag wiped by a memset that runs late.
+hipError_t clear_flag(gel_problem* p, hipStream_t s) {
+  if (const hipError_t e = hipMemsetAsync(p->d_flag.get(), 0, 4, s)) return e;
+  return hipStreamSynchronize(s);
+}
+
 #define NEED_DEVICE(p)                                                                              \
   do {                                                                                              \
     if ((p)->device == GEL_DEVICE_NONE)                                                             \
@@ -785,6 +810,7 @@ int ensure_capacity(gel_problem* p, int B) {
   NEED_DEVICE(p);
   if (B <= p->capB) return GEL_OK;
   HIPCHK(hipSetDevice(p->device));
+  HIPCHK(drain(p));   // the old staging blocks go: nothing in flight may still use them
   p->capB = 0;   // until every buffer below has grown
   const size_t nx = (size_t)B * p->dims.num_vars, nr = (size_t)B * 11 * p->dims.N, nj = (size_t)B * std::max<int64_t>(1, p->dims.num_var_entries);
   HIPCHK(p->d_x.reserve(nx)); HIPCHK(p->d_res.reserve(nr)); HIPCHK(p->d_jv.reserve(nj));
@@ -928,7 +954,8 @@ int run_host(gel_problem* p, int B, const double* x, bool want_res, bool want_ja
   HIPCHK(hipStreamSynchronize(s));
   if (want_res && res_to) std::memcpy(res_to, p->h_res.get(), nr * 8);
   if (*p->h_flag.get()) {
-    HIPCHK(hipMemsetAsync(p->d_flag.get(), 0, 4, s));
+    *p->h_flag.get() = 0;
+    HIPCHK(clear_flag(p, s));
     return GEL_NONFINITE;
   }
   return GEL_OK;
@@ -1612,7 +1639,7 @@ int gel_eval_batch(gel_problem* p, int32_t B, const double* x, double* res, doub
 int gel_eval_batch_device(gel_problem* p, int32_t B, const double* d_x, double* d_res, double* d_jvar, void* stream) {
   if (!p || !d_x || B < 1 || (!d_res && !d_jvar)) return fail(GEL_ERR_ARG, "bad argument");
   NEED_DEVICE(p);
-  HIPCHK(launch_defects(p, p->dev, B, d_x, d_res, d_jvar, stream ? (hipStream_t)stream : p->stream.get()));
+  HIPCHK(launch_defects(p, p->dev, B, d_x, d_res, d_jvar, stream_of(p, stream)));
   return GEL_OK;
 }
 
@@ -1630,7 +1657,7 @@ int gel_eval_shard_units_device(gel_problem* p, int32_t B, const double* d_x, do
   dv.chunk0 = 0;
   dv.unit0 = unit_begin;
   dv.nunits = unit_count;
-  HIPCHK(gel::launch_eval(dv, B, d_x, d_res, d_jvar, stream ? (hipStream_t)stream : p->stream.get()));
+  HIPCHK(gel::launch_eval(dv, B, d_x, d_res, d_jvar, stream_of(p, stream)));
   return GEL_OK;
 }
 
@@ -1749,6 +1776,7 @@ int gel_shard_plan(gel_problem* p, int32_t nranks, const int32_t* unit_begin, in
   if (p->device != GEL_DEVICE_NONE) {
     HIPCHK(hipSetDevice(p->device));
     HIPCHK(d_base.upload(base)); HIPCHK(d_pos.upload(pos));
+    HIPCHK(drain(p));   // launches in flight, on the handle's stream or on the caller's, still read the old plan
   }
   p->d_unit_base = std::move(d_base);
   p->d_shard_pos = std::move(d_pos);
@@ -1789,7 +1817,7 @@ int gel_eval_shard_packed_device(gel_problem* p, int32_t B, const double* d_x, d
   dv.shard_width = p->shard_width;
   dv.unit_base = p->d_unit_base.get();
   double* slice = d_out + (size_t)rank * (size_t)B * (size_t)p->shard_width;
-  HIPCHK(gel::launch_eval(dv, B, d_x, slice, slice, stream ? (hipStream_t)stream : p->stream.get()));
+  HIPCHK(gel::launch_eval(dv, B, d_x, slice, slice, stream_of(p, stream)));
   return GEL_OK;
 }
 
@@ -1800,14 +1828,14 @@ int gel_shard_unpack_device(gel_problem* p, int32_t B, const double* d_out, doub
   if (int rc = check_plan(p, nranks_expected, width_expected)) return rc;
   if (!p->d_shard_pos.get()) return fail(GEL_ERR_ARG, "gel_shard_plan has not been called on this handle");
   HIPCHK(gel::launch_shard_unpack(11 * p->dims.N, p->dims.num_var_entries, p->shard_width, B, p->d_shard_pos.get(), d_out, d_res, d_jvar,
-                                  stream ? (hipStream_t)stream : p->stream.get()));
+                                  stream_of(p, stream)));
   return GEL_OK;
 }
 
 int gel_fill_full_device(gel_problem* p, int32_t B, double* d_jfull, void* stream) {
   if (!p || !d_jfull || B < 1) return fail(GEL_ERR_ARG, "bad argument");
   NEED_DEVICE(p);
-  HIPCHK(gel::launch_fill_full(p->dims.total_nnz, B, p->d_cval.get(), d_jfull, stream ? (hipStream_t)stream : p->stream.get()));
+  HIPCHK(gel::launch_fill_full(p->dims.total_nnz, B, p->d_cval.get(), d_jfull, stream_of(p, stream)));
   return GEL_OK;
 }
 
@@ -1816,14 +1844,14 @@ int gel_update_full_device(gel_problem* p, int32_t B, const double* d_jvar, doub
   NEED_DEVICE(p);
   HIPCHK(gel::launch_update_full(p->dims.total_nnz, p->dims.num_var_entries, p->nvar_entries, B, p->d_vdst.get(), p->d_vsrc.get(),
                                  p->nvar_lines, p->d_vline.get(), p->d_src.get(), p->d_cval.get(), d_jvar, d_jfull,
-                                 stream ? (hipStream_t)stream : p->stream.get()));
+                                 stream_of(p, stream)));
   return GEL_OK;
 }
 
 int gel_eval_full_device(gel_problem* p, int32_t B, const double* d_x, double* d_res, double* d_jvar, double* d_jfull, void* stream) {
   if (!p || !d_x || !d_jvar || !d_jfull || B < 1) return fail(GEL_ERR_ARG, "bad argument");
   NEED_DEVICE(p);
-  hipStream_t s = stream ? (hipStream_t)stream : p->stream.get();
+  hipStream_t s = stream_of(p, stream);
   gel::ProblemDev dv = p->dev;
   dv.cached_out = 1;   // the compact values are read again by the update below: kept in the caches when the launch fits them
   HIPCHK(launch_defects(p, dv, B, d_x, d_res, d_jvar, s));
@@ -1836,23 +1864,24 @@ int gel_expand_full_device(gel_problem* p, int32_t B, const double* d_jvar, doub
   if (!p || !d_jvar || !d_jfull || B < 1) return fail(GEL_ERR_ARG, "bad argument");
   NEED_DEVICE(p);
   HIPCHK(gel::launch_expand(p->dims.total_nnz, p->dims.num_var_entries, B, p->d_cval.get(), p->d_src.get(), d_jvar, d_jfull,
-                            stream ? (hipStream_t)stream : p->stream.get()));
+                            stream_of(p, stream)));
   return GEL_OK;
 }
 
 int gel_sync(gel_problem* p, void* stream) {
   if (!p) return fail(GEL_ERR_ARG, "null argument");
   NEED_DEVICE(p);
-  hipStream_t s = stream ? (hipStream_t)stream : p->stream.get();
+  hipStream_t s = stream_of(p, stream);
   HIPCHK(hipMemcpyAsync(p->h_flag.get(), p->d_flag.get(), 4, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
+  int rc = GEL_OK;
   if (*p->h_flag.get()) {
-    HIPCHK(hipMemsetAsync(p->d_flag.get(), 0, 4, s));
-    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(clear_flag(p, s));
     *p->h_flag.get() = 0;
-    return GEL_NONFINITE;
+    rc = GEL_NONFINITE;
   }
-  return GEL_OK;
+  if (s == p->caller_stream) p->caller_stream = nullptr;   // drained: the caller may destroy it now
+  return rc;
 }
 
 // ---- generic forward difference, phase by phase (lib/jac_fd.py:29-62 on the four defect residuals) ----
@@ -1938,7 +1967,7 @@ static int jfd_host(gel_problem* p, int32_t group, const double* x, double* J, i
     HIPCHK(hipMemcpyAsync(p->h_flag.get(), p->d_flag.get(), 4, hipMemcpyDeviceToHost, p->stream.get()));
     HIPCHK(hipStreamSynchronize(p->stream.get()));
     p->jfd_status = GEL_OK;
-    if (*p->h_flag.get()) { *p->h_flag.get() = 0; HIPCHK(hipMemsetAsync(p->d_flag.get(), 0, 4, p->stream.get())); p->jfd_status = GEL_NONFINITE; }
+    if (*p->h_flag.get()) { *p->h_flag.get() = 0; HIPCHK(clear_flag(p, p->stream.get())); p->jfd_status = GEL_NONFINITE; }
     p->jfd_last_x.assign(x, x + nv);
   }
   size_t total = 0;
@@ -1997,7 +2026,7 @@ int gel_jac_fd_device(gel_problem* p, int32_t group, const double* d_x, double* 
   HIPCHK(hipSetDevice(p->device));
   int rc = jfd_allocate(p);
   if (rc) return rc;
-  hipStream_t s = stream ? (hipStream_t)stream : p->stream.get();
+  hipStream_t s = stream_of(p, stream);
   p->jfd_last_x.clear();   // the residuals kept for gel_jac_fd's host callers are overwritten
   if ((rc = jfd_evaluate(p, d_x, s))) return rc;
   size_t total = 0;
@@ -2190,7 +2219,7 @@ int gel_aero_configure(gel_problem* p, int32_t kind, int32_t nspec, const int32_
     HIPCHK(a.d_nodes.upload(a.nodes)); HIPCHK(a.d_ph.upload(a.ph));
     for (int part = 0; part < 2; part++)
       if (!a.part_nodes[part].empty()) HIPCHK(a.d_part_nodes[part].upload(a.part_nodes[part]));
-    HIPCHK(hipStreamSynchronize(p->stream.get()));   // launches in flight still read the old tables
+    HIPCHK(drain(p));   // launches in flight, on the handle's stream or on the caller's, still read the old tables
   }
   p->aero = std::move(a);
   return GEL_OK;
@@ -2246,7 +2275,7 @@ int gel_eval_batch_aero_device(gel_problem* p, int32_t B, const double* d_x, dou
     return fail(GEL_ERR_ARG, "gel_eval_batch_aero_device has no exact-Jacobian form (handle created with GEL_FLAG_EXACT_DEFECT_JAC)");
   NEED_DEVICE(p);
   if (p->aero.nodes.empty()) return fail(GEL_ERR_ARG, "no aero path constraints configured (gel_aero_configure)");
-  hipStream_t s = stream ? (hipStream_t)stream : p->stream.get();
+  hipStream_t s = stream_of(p, stream);
   gel::AeroLaunchOut out[2];
   for (int part = 0; part < 2; part++)
     for (int k = 0; k < 3; k++) {   // part A (spec-major): every pointer is the record itself
@@ -2314,7 +2343,7 @@ int gel_eval_aero_all_device(gel_problem* p, int32_t B, const double* d_x, doubl
     out.con[k] = out.nrows[k] ? d_con[k] : nullptr;
     out.jac[k] = (out.con[k] && d_jac) ? d_jac[k] : nullptr;
   }
-  HIPCHK(launch_aero_kinds(p, p->dev, (int)p->aero.nodes.size(), p->aero.d_nodes.get(), B, d_x, out, stream ? (hipStream_t)stream : p->stream.get()));
+  HIPCHK(launch_aero_kinds(p, p->dev, (int)p->aero.nodes.size(), p->aero.d_nodes.get(), B, d_x, out, stream_of(p, stream)));
   return GEL_OK;
 }
 
@@ -2371,7 +2400,7 @@ int gel_eval_aero_all(gel_problem* p, int32_t B, const double* x, double* const*
     }
   if (*p->h_flag.get()) {
     *p->h_flag.get() = 0;
-    if (!zero_copy) HIPCHK(hipMemsetAsync(p->d_flag.get(), 0, 4, p->stream.get()));
+    if (!zero_copy) HIPCHK(clear_flag(p, p->stream.get()));
     return GEL_NONFINITE;
   }
   return GEL_OK;
@@ -2409,7 +2438,7 @@ int gel_rows_configure(gel_problem* p, int32_t nlin, const gel_linear_row* lin, 
   if (p->device != GEL_DEVICE_NONE) {
     HIPCHK(hipSetDevice(p->device));
     HIPCHK(d_lin.upload(lin_rows)); HIPCHK(d_fn.upload(fn_rows));
-    HIPCHK(hipStreamSynchronize(p->stream.get()));   // launches in flight still read the old tables
+    HIPCHK(drain(p));   // launches in flight, on the handle's stream or on the caller's, still read the old tables
   }
   p->lin_rows = std::move(lin_rows); p->fn_rows = std::move(fn_rows);
   p->d_lin_rows = std::move(d_lin); p->d_fn_rows = std::move(d_fn);
@@ -2426,7 +2455,7 @@ int gel_rows_dims(const gel_problem* p, int32_t* nlin, int32_t* nfn) {
 int gel_rows_eval_device(gel_problem* p, int32_t B, const double* d_x, double* d_con, double* d_jfn, void* stream) {
   if (!p || B < 1 || !d_x || !d_con) return fail(GEL_ERR_ARG, "bad argument");
   NEED_DEVICE(p);
-  HIPCHK(launch_rows_kinds(p, p->dev, B, d_x, d_con, d_jfn, stream ? (hipStream_t)stream : p->stream.get()));
+  HIPCHK(launch_rows_kinds(p, p->dev, B, d_x, d_con, d_jfn, stream_of(p, stream)));
   return GEL_OK;
 }
 
@@ -2461,7 +2490,7 @@ int gel_rows_eval(gel_problem* p, int32_t B, const double* x, double* con, doubl
   if (jfn) HIPCHK(hipMemcpyAsync(jfn, p->d_rows_out.get() + nc, nj * 8, hipMemcpyDeviceToHost, p->stream.get()));
   HIPCHK(hipMemcpyAsync(p->h_flag.get(), p->d_flag.get(), 4, hipMemcpyDeviceToHost, p->stream.get()));
   HIPCHK(hipStreamSynchronize(p->stream.get()));
-  if (*p->h_flag.get()) { *p->h_flag.get() = 0; HIPCHK(hipMemsetAsync(p->d_flag.get(), 0, 4, p->stream.get())); return GEL_NONFINITE; }
+  if (*p->h_flag.get()) { *p->h_flag.get() = 0; HIPCHK(clear_flag(p, p->stream.get())); return GEL_NONFINITE; }
   return GEL_OK;
 }
 
@@ -2494,7 +2523,7 @@ int gel_mesh_error_device(gel_problem* p, int32_t B, const double* d_x, double* 
   if (!p || B < 1 || !d_x || !d_err) return fail(GEL_ERR_ARG, "bad argument");
   NEED_DEVICE(p);
   NEED_MESH(p);
-  HIPCHK(gel::launch_mesh(p->dev, p->mesh_dev, p->mesh_ph.data(), B, d_x, d_err, d_diff, stream ? (hipStream_t)stream : p->stream.get()));
+  HIPCHK(gel::launch_mesh(p->dev, p->mesh_dev, p->mesh_ph.data(), B, d_x, d_err, d_diff, stream_of(p, stream)));
   return GEL_OK;
 }
 
@@ -2528,7 +2557,7 @@ int gel_mesh_error(gel_problem* p, int32_t B, const double* x, double* err, doub
   if (diff) HIPCHK(hipMemcpyAsync(diff, p->d_mesh_out.get() + ne, nd * 8, hipMemcpyDeviceToHost, s));
   HIPCHK(hipMemcpyAsync(p->h_flag.get(), p->d_flag.get(), 4, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
-  if (*p->h_flag.get()) { *p->h_flag.get() = 0; HIPCHK(hipMemsetAsync(p->d_flag.get(), 0, 4, s)); return GEL_NONFINITE; }
+  if (*p->h_flag.get()) { *p->h_flag.get() = 0; HIPCHK(clear_flag(p, s)); return GEL_NONFINITE; }
   return GEL_OK;
 }
 
@@ -2593,7 +2622,10 @@ int gel_jac_products_host(const gel_problem* p, int32_t B, const double* jvar, c
 }
 
 static int jprod_device(gel_problem* p, int32_t B, const double* d_jvar, const double* d_in, double* d_out, int transpose, hipStream_t s) {
-  if (transpose) HIPCHK(p->d_jp_tpart.reserve((size_t)B * p->dims.S * 2));
+  if (transpose && p->d_jp_tpart.capacity() < (size_t)B * p->dims.S * 2) {
+    if (p->d_jp_tpart.get()) HIPCHK(drain(p));   // an earlier product in flight still sums through the old workspace
+    HIPCHK(p->d_jp_tpart.reserve((size_t)B * p->dims.S * 2));
+  }
   // GEL_JPROD_VB = 1 / 2 / 4 / 8: vectors per workgroup (measurement switch, read per call; a value whose staged inputs do not fit
   // is ignored).  The results do not depend on it.
   int vb = 0;
@@ -2612,7 +2644,7 @@ int gel_jac_matvec_device(gel_problem* p, int32_t B, const double* d_jvar, const
   NEED_JPROD_DEVICE(p);
   NEED_JPROD(p, 0);
   HIPCHK(hipSetDevice(p->device));
-  return jprod_device(p, B, d_jvar, d_v, d_y, 0, stream ? (hipStream_t)stream : p->stream.get());
+  return jprod_device(p, B, d_jvar, d_v, d_y, 0, stream_of(p, stream));
 }
 
 int gel_jac_rmatvec_device(gel_problem* p, int32_t B, const double* d_jvar, const double* d_lam, double* d_g, void* stream) {
@@ -2620,7 +2652,7 @@ int gel_jac_rmatvec_device(gel_problem* p, int32_t B, const double* d_jvar, cons
   NEED_JPROD_DEVICE(p);
   NEED_JPROD(p, 1);
   HIPCHK(hipSetDevice(p->device));
-  return jprod_device(p, B, d_jvar, d_lam, d_g, 1, stream ? (hipStream_t)stream : p->stream.get());
+  return jprod_device(p, B, d_jvar, d_lam, d_g, 1, stream_of(p, stream));
 }
 
 static int jprod_hostbuf(gel_problem* p, int32_t B, const double* jvar, const double* in, double* out, int transpose) {
@@ -2638,7 +2670,7 @@ static int jprod_hostbuf(gel_problem* p, int32_t B, const double* jvar, const do
   HIPCHK(hipMemcpyAsync(out, p->d_jp_out.get(), no * 8, hipMemcpyDeviceToHost, s));
   HIPCHK(hipMemcpyAsync(p->h_flag.get(), p->d_flag.get(), 4, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
-  if (*p->h_flag.get()) { *p->h_flag.get() = 0; HIPCHK(hipMemsetAsync(p->d_flag.get(), 0, 4, s)); return GEL_NONFINITE; }
+  if (*p->h_flag.get()) { *p->h_flag.get() = 0; HIPCHK(clear_flag(p, s)); return GEL_NONFINITE; }
   return GEL_OK;
 }
 

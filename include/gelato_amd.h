@@ -10,6 +10,17 @@
  * only; the caller owns every buffer it passes; the engine owns device memory.
  * One handle = one HIP device + one HIP stream; a handle is not thread-safe.
  *
+ * Streams.  The sixteen entry points with a `void* stream` parameter (the *_device forms and gel_sync) enqueue everything they
+ * do -- every launch, memset and use of a workspace of the handle -- on that stream, a hipStream_t of the caller (blocking or
+ * not) or NULL for the handle's own; every other call runs on the handle's own stream and returns synchronised.  The calls of
+ * ONE handle must not overlap on different streams (two handles on two streams may): order them on one stream, or gel_sync
+ * between them.  The non-finite status is per handle, not per stream: it is read and cleared by gel_sync on the stream the
+ * calls were given, and a host-form call made while device-form work is still pending may report and clear that work's status.
+ * The handle remembers the last caller stream it was given until gel_sync on it returns; whatever releases device memory that
+ * launches read -- gel_aero_configure, gel_rows_configure, gel_shard_plan, a workspace or staging buffer that has to grow --
+ * first waits for the handle's own stream AND for that stream, so a reconfiguration behind pending work is safe (and blocks the
+ * host until that work is done).  A caller's stream must stay valid until gel_sync on it has returned.
+ *
  * Packed decision vector x (all normalised by `units`, doubles) -- exactly the
  * concatenation of the reference's xdict arrays
  * (Trajectory_Optimization.py:318-352):
