@@ -129,6 +129,8 @@ SIGNATURES = {
     "gel_jac_rmatvec": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, _dp]),
     "gel_jac_products_host": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, _dp, C.c_int32]),
     "gel_jac_products_info": (C.c_int, [C.c_void_p, _lp]),
+    "gel_jac_products_launch_info": (C.c_int, [C.c_void_p, _ip]),
+    "gel_aero_launch_info": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _lp]),
     "gel_initial_guess": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, _dp, _dp]),
     "gel_output_table": (C.c_int, [C.c_void_p, _dp, _dp, C.c_double, C.c_double, _dp]),
     "gel_dynamics_velocity": (C.c_int, [C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int32, _dp, C.c_int32,

@@ -1357,6 +1357,7 @@ int gel_problem_create(const gel_problem_desc* d, gel_problem** out) {
     p->mesh_npts = npts;
   }
   if (const char* e = build_jprod_tables(*p)) return fail(GEL_ERR_ARG, e);
+  if (const char* e = getenv("GEL_JPROD_THREADS")) { if (atoi(e) == 256) p->jp_threads = 256; }   // host-only handles report it too
   for (int i = 0; i < S; i++)
     for (int j0 = 0; j0 < p->ph[i].n; j0 += 64) p->chunk_phase.push_back(i);
   if (p->device == GEL_DEVICE_NONE) {
@@ -1522,7 +1523,6 @@ int gel_problem_create(const gel_problem_desc* d, gel_problem** out) {
     md.S = S; md.npts = p->mesh_npts; md.ph = p->d_mesh_ph.get(); md.mat = p->d_mesh_mat.get(); md.vp = p->uv / p->up;
   }
   HIPCHK(p->d_jp_it.upload(p->jp_it)); HIPCHK(p->d_jp_dt.upload(p->jp_dt)); HIPCHK(p->d_jp_ph.upload(p->jp_ph));
-  if (const char* e = getenv("GEL_JPROD_THREADS")) { if (atoi(e) == 256) p->jp_threads = 256; }
   p->jp_dev.ph = p->d_jp_ph.get(); p->jp_dev.it = p->d_jp_it.get(); p->jp_dev.dt = p->d_jp_dt.get();
   *out = p.release();
   return GEL_OK;
@@ -2302,6 +2302,18 @@ int gel_eval_batch_aero_device(gel_problem* p, int32_t B, const double* d_x, dou
   return GEL_OK;
 }
 
+// which form aero_kernel's launcher takes for B vectors (gel::aero_form, the function launch_aero itself decides by); no stream, no
+// device: host-only handles answer too
+int gel_aero_launch_info(const gel_problem* p, int32_t B, int32_t records, int64_t* info) {
+  if (!p || !info || B < 1) return fail(GEL_ERR_ARG, "bad argument");
+  int32_t nrows[3];
+  for (int k = 0; k < 3; k++) nrows[k] = (int32_t)(records ? p->aero.part_rows[0][k].size() : p->aero.rows[k].size());
+  const int nnodes = (int)(records ? p->aero.part_nodes[0].size() : p->aero.nodes.size());
+  const gel::AeroForm f = gel::aero_form(nnodes, B, nrows, records ? p->aero.ld : 0);
+  info[0] = f.flat; info[1] = f.runs; info[2] = f.run_len; info[3] = f.max_bytes;
+  return GEL_OK;
+}
+
 int gel_aero_dims(const gel_problem* p, int32_t kind, int32_t* nrows, int64_t* nnz4) {
   if (!p || kind < 0 || kind > 2 || !nrows || !nnz4) return fail(GEL_ERR_ARG, "bad argument");
   const int64_t R = (int64_t)p->aero.rows[kind].size();
@@ -2621,21 +2633,31 @@ int gel_jac_products_host(const gel_problem* p, int32_t B, const double* jvar, c
   return rc;
 }
 
+// Vectors per workgroup of a product launch (what gel_jac_products_launch_info reports): the most whose staged inputs fit, or
+// GEL_JPROD_VB = 1 / 2 / 4 / 8 (measurement switch, read per call; a value whose staged inputs do not fit is ignored).  The results
+// do not depend on it.  0: not even one vector fits (NEED_JPROD).
+static int jprod_vb(const gel_problem* p, int transpose) {
+  const int nin = p->jp_nin_max[transpose ? 1 : 0];
+  if (const char* e = getenv("GEL_JPROD_VB")) {
+    const int w = atoi(e);
+    if ((w == 1 || w == 2 || w == 4 || w == 8) && gel::jprod_lds_bytes(nin, w, transpose != 0) <= gel::kJprodMaxLds) return w;
+  }
+  return gel::jprod_vectors_per_group(nin, transpose != 0);
+}
+
 static int jprod_device(gel_problem* p, int32_t B, const double* d_jvar, const double* d_in, double* d_out, int transpose, hipStream_t s) {
   if (transpose && p->d_jp_tpart.capacity() < (size_t)B * p->dims.S * 2) {
     if (p->d_jp_tpart.get()) HIPCHK(drain(p));   // an earlier product in flight still sums through the old workspace
     HIPCHK(p->d_jp_tpart.reserve((size_t)B * p->dims.S * 2));
   }
-  // GEL_JPROD_VB = 1 / 2 / 4 / 8: vectors per workgroup (measurement switch, read per call; a value whose staged inputs do not fit
-  // is ignored).  The results do not depend on it.
-  int vb = 0;
-  if (const char* e = getenv("GEL_JPROD_VB")) {
-    const int w = atoi(e);
-    if ((w == 1 || w == 2 || w == 4 || w == 8) &&
-        gel::jprod_lds_bytes(p->jp_nin_max[transpose ? 1 : 0], w, transpose != 0) <= gel::kJprodMaxLds) vb = w;
-  }
   HIPCHK(gel::launch_jprod(p->jp_dev, p->jp_nin_max[transpose ? 1 : 0], B, d_jvar, d_in, d_out, p->d_jp_tpart.get(), p->d_flag.get(),
-                           transpose, vb, p->jp_threads, s));
+                           transpose, jprod_vb(p, transpose), p->jp_threads, s));
+  return GEL_OK;
+}
+
+int gel_jac_products_launch_info(const gel_problem* p, int32_t* info) {
+  if (!p || !info) return fail(GEL_ERR_ARG, "null argument");
+  for (int t = 0; t < 2; t++) { info[2 * t] = jprod_vb(p, t); info[2 * t + 1] = p->jp_threads; }
   return GEL_OK;
 }
 

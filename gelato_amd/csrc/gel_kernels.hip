@@ -735,22 +735,37 @@ hipError_t launch_aero_wide(const ProblemDev& P, int nnodes, const AeroNodeDev* 
   return hipGetLastError();
 }
 
+// The decision at the top of launch_aero (host only; also reported through gel_aero_launch_info).  The flat (vector, node) mapping
+// needs every wavefront inside two vectors (nnodes >= 64, not a multiple of 64, more than one vector) and the gradient values of a
+// kind inside 32-bit byte offsets: dense arrays (ld = 0) beyond 2^32 - 2^24 bytes take one tile per vector instead; a batch of
+// records (ld != 0) whose span exceeds 2^32 - 2^25 bytes is launched in runs of vectors that stay below it.
+AeroForm aero_form(int nnodes, int B, const int32_t* nrows, long long ld) {
+  AeroForm f{false, 1, B, 0};
+  if (B <= 0 || nnodes <= 0) return f;
+  const bool flat_shape = B > 1 && nnodes >= 64 && (nnodes & 63) != 0;
+  if (ld > 0 && flat_shape) {
+    const long long run = ((1LL << 32) - (1LL << 25)) / (ld * 8);
+    if (run >= 1 && run < B) { f.runs = (B + run - 1) / run; f.run_len = run; }
+  }
+  for (int k = 0; k < 3; k++) f.max_bytes = std::max(f.max_bytes, f.run_len * (ld ? ld : (long long)nrows[k] * (8 + ((k == 1) ? 0 : 4))) * 8);
+  f.flat = f.run_len > 1 && nnodes >= 64 && (nnodes & 63) != 0 && f.max_bytes < (1LL << 32) - (1LL << 24);
+  return f;
+}
+
 // ld != 0: per-vector records (see AeroOut).  The flat mapping addresses a batch's gradient values with 32-bit byte offsets: a
 // batch whose records span more is launched in runs of vectors that do not.
 hipError_t launch_aero(const ProblemDev& P, int nnodes, const AeroNodeDev* nodes, int B, const double* d_x,
                        const AeroLaunchOut& out, hipStream_t s, long long ld, bool spec_major) {
   if (B <= 0 || nnodes <= 0) return hipSuccess;
-  if (ld > 0 && B > 1 && nnodes >= 64 && (nnodes & 63) != 0) {
-    const long long run = ((1LL << 32) - (1LL << 25)) / (ld * 8);
-    if (run >= 1 && run < B) {
-      for (long long b0 = 0; b0 < B; b0 += run) {
-        AeroLaunchOut o = out;
-        for (int k = 0; k < 3; k++) { if (o.con[k]) o.con[k] += b0 * ld; if (o.jac[k]) o.jac[k] += b0 * ld; }
-        const hipError_t e = launch_aero(P, nnodes, nodes, (int)std::min<long long>(run, B - b0), d_x + b0 * P.nvars, o, s, ld, spec_major);
-        if (e != hipSuccess) return e;
-      }
-      return hipSuccess;
+  const AeroForm form = aero_form(nnodes, B, out.nrows, ld);
+  if (form.runs > 1) {
+    for (long long b0 = 0; b0 < B; b0 += form.run_len) {   // every run decides its own form: a last run of one vector takes a tile
+      AeroLaunchOut o = out;
+      for (int k = 0; k < 3; k++) { if (o.con[k]) o.con[k] += b0 * ld; if (o.jac[k]) o.jac[k] += b0 * ld; }
+      const hipError_t e = launch_aero(P, nnodes, nodes, (int)std::min<long long>(form.run_len, B - b0), d_x + b0 * P.nvars, o, s, ld, spec_major);
+      if (e != hipSuccess) return e;
     }
+    return hipSuccess;
   }
   AeroOut O;
   for (int k = 0; k < 3; k++) { O.con[k] = out.con[k]; O.jac[k] = out.jac[k]; O.nrows[k] = out.nrows[k]; }
@@ -760,9 +775,7 @@ hipError_t launch_aero(const ProblemDev& P, int nnodes, const AeroNodeDev* nodes
   long long waves = (long long)B * tiles;
   // flat (vector, node) mapping (tiles = 0 tells the kernel): no mostly-empty last tile per vector; needs every wavefront inside two
   // vectors and the batch's gradient values of a kind inside 32-bit byte offsets
-  long long maxbytes = 0;
-  for (int k = 0; k < 3; k++) maxbytes = std::max(maxbytes, (long long)B * (ld ? ld : (long long)O.nrows[k] * (8 + ((k == 1) ? 0 : 4))) * 8);
-  if (B > 1 && nnodes >= 64 && (nnodes & 63) != 0 && maxbytes < (1LL << 32) - (1LL << 24)) {
+  if (form.flat) {
     waves = ((long long)B * nnodes + 63) / 64;
     tiles = 0;
   }

@@ -41,6 +41,11 @@ hipError_t launch_point(int kind, int n, const double* in, const double* aux, in
 
 // outputs of one aero launch: per kind (0 alpha, 1 q, 2 q-alpha) the constraint vector and the COO values, or null
 struct AeroLaunchOut { double* con[3]; double* jac[3]; int32_t nrows[3]; };
+// the form a launch_aero of B vectors takes: flat (vector, node) mapping or one tile per vector (of a full-length run), the runs
+// the batch is launched in and their length in vectors, and the bytes one launch's gradient values of the largest kind span
+// (what the flat mapping addresses with 32-bit byte offsets)
+struct AeroForm { bool flat; long long runs, run_len, max_bytes; };
+AeroForm aero_form(int nnodes, int B, const int32_t* nrows /* [3] */, long long ld);
 hipError_t launch_aero(const ProblemDev& P, int nnodes, const AeroNodeDev* nodes, int B, const double* d_x,
                        const AeroLaunchOut& out, hipStream_t s, long long ld = 0, bool spec_major = false);
 

@@ -533,6 +533,14 @@ class Engine:
         eval_batch_device, aero [B, width] one record per vector (aero_record_layout)"""
         check(lib().gel_eval_batch_aero_device(self._h, B, d_x, d_res, d_jvar, d_aero, stream or None))
 
+    def aero_launch_info(self, B, records=False):
+        """-> {"flat", "runs", "run_len", "max_bytes"}: the form aero_kernel's launcher takes for B vectors (gel_aero_launch_info) --
+        records=False: the dense arrays of eval_aero_all_device; True: part A of eval_batch_aero_device's records where aero_kernel
+        writes it.  A last, shorter run decides its own form: ask with its length."""
+        info = (C.c_int64 * 4)()
+        check(lib().gel_aero_launch_info(self._h, int(B), int(bool(records)), info))
+        return dict(zip(("flat", "runs", "run_len", "max_bytes"), (int(v) for v in info)))
+
     def eval_callback(self, x, want_jac, xptr=None):
         """ONE device round trip for one decision vector: the four defect groups, the row table (if configured) and the aero
         kinds (if configured), values only or values + derivatives.  -> dict of the engine's own output arrays (overwritten
@@ -724,10 +732,15 @@ class Engine:
                                  self.nres if t else self.nvars, self.nvars if t else self.nres)
 
     def jac_products_info(self):
-        """{"const_nnz", "var_entries", "max_row_nnz", "max_col_nnz"} of the operator tables"""
+        """{"const_nnz", "var_entries", "max_row_nnz", "max_col_nnz"} of the operator tables, and what a product launch will use
+        NOW (GEL_JPROD_VB is read per call): "vb" / "threads" of J v, "vb_t" / "threads_t" of J^T lambda"""
         info = (C.c_int64 * 4)()
         check(lib().gel_jac_products_info(self._h, info))
-        return dict(zip(("const_nnz", "var_entries", "max_row_nnz", "max_col_nnz"), (int(v) for v in info)))
+        out = dict(zip(("const_nnz", "var_entries", "max_row_nnz", "max_col_nnz"), (int(v) for v in info)))
+        li = (C.c_int32 * 4)()
+        check(lib().gel_jac_products_launch_info(self._h, li))
+        out.update(zip(("vb", "threads", "vb_t", "threads_t"), (int(v) for v in li)))
+        return out
 
     def jac_operator(self, jvar_row):
         """scipy.sparse.linalg.LinearOperator of shape (11N, nvars) for ONE vector's compact values; matvec / rmatvec run on the

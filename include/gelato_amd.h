@@ -355,6 +355,13 @@ int gel_aero_record_layout(const gel_problem* p, int64_t* width, int64_t* off_co
 int gel_aero_record_map(const gel_problem* p, int32_t kind, int32_t var, int64_t* idx);
 int gel_eval_batch_aero_device(gel_problem* p, int32_t B, const double* d_x, double* d_res, double* d_jvar, double* d_aero,
                                void* stream);
+/* which form aero_kernel's launcher takes for B vectors, from the function the launcher itself decides by (like gel_launch_info; works
+ * on GEL_DEVICE_NONE handles).  records = 0: the dense arrays of gel_eval_aero_all_device; 1: part A of the records of
+ * gel_eval_batch_aero_device where aero_kernel writes it (GEL_AERO_FUSED=0, GEL_FLAG_FD_RECOMPUTE, GEL_FLAG_EXACT_AERO_JAC, batches the
+ * fused form does not take).  info = {1 flat (vector, node) mapping with 32-bit byte offsets / 0 one tile per vector, number of runs
+ * the batch is launched in, vectors per full-length run, bytes that one run's gradient values of the largest kind span}.  A last,
+ * shorter run decides its own form: ask again with its length. */
+int gel_aero_launch_info(const gel_problem* p, int32_t B, int32_t records, int64_t* info /* [4] */);
 
 /* ---- knot / terminal / user rows.
  *  Linear rows: value = (coef0 * x[idx0] + coef1 * x[idx1]) + c0 (idx1 < 0: one term) over the packed decision vector --
@@ -439,6 +446,10 @@ int gel_jac_products_host(const gel_problem* p, int32_t B, const double* jvar, c
 /* info [4]: non-zero constant entries, variable entries, largest non-zero count of a row, of a column (variable entries count
  * as non-zero) */
 int gel_jac_products_info(const gel_problem* p, int64_t* info);
+/* what a product launch will use, as gel_jac_*_device decide it: info = {vectors per workgroup of J v, lanes per workgroup, the same
+ * two for J^T lambda}.  GEL_JPROD_VB (read per call) and GEL_JPROD_THREADS (read when the handle is created) are honoured; works on
+ * GEL_DEVICE_NONE handles.  (An entry point of its own: gel_jac_products_info's callers hold four values.) */
+int gel_jac_products_launch_info(const gel_problem* p, int32_t* info /* [4] */);
 
 /* ---- one optimiser callback = one device round trip: the four defect groups, the knot / terminal / user row table and the
  *      aero path constraints of ONE decision vector launched back to back on the handle's stream, one synchronise
