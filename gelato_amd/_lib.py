@@ -17,6 +17,7 @@ GEL_OK, GEL_NONFINITE = 0, 1
 GEL_FLAG_FD_RECOMPUTE = 8
 GEL_FLAG_EXACT_DEFECT_JAC = 32   # defect-group Jacobians exact to rounding (forward mode) instead of forward differences
 GEL_FLAG_EXACT_AERO_JAC = 64     # aero path constraints' gradients exact to rounding (forward mode) instead of forward differences
+GEL_INTERP_UNIT_QUAT = 1         # gel_interp_plan_create*: rows that are not copies get q / sqrt(q . q)
 GEL_FLAG_EXACT_ROWS_JAC = 128    # node-function rows' jfn (terminal, user, waypoint rows) exact to rounding instead of forward differences
 NUM_BLOCKS = 13
 
@@ -131,6 +132,14 @@ SIGNATURES = {
     "gel_jac_products_info": (C.c_int, [C.c_void_p, _lp]),
     "gel_jac_products_launch_info": (C.c_int, [C.c_void_p, _ip]),
     "gel_aero_launch_info": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _lp]),
+    "gel_interp_plan_create": (C.c_int, [C.c_void_p, _ip, _dp, C.c_int32, C.POINTER(C.c_void_p)]),
+    "gel_interp_plan_create_transfer": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]),
+    "gel_interp_plan_destroy": (C.c_int, [C.c_void_p]),
+    "gel_interp_plan_info": (C.c_int, [C.c_void_p, _lp]),
+    "gel_interp_matrices": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, _ip, _ip]),
+    "gel_interp": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp]),
+    "gel_interp_resident": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "gel_interp_host": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp]),
     "gel_initial_guess": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, _dp, _dp]),
     "gel_output_table": (C.c_int, [C.c_void_p, _dp, _dp, C.c_double, C.c_double, _dp]),
     "gel_dynamics_velocity": (C.c_int, [C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int32, _dp, C.c_int32,
@@ -148,7 +157,7 @@ def build(force=False):
     src_dir = os.path.join(_HERE, "csrc")
     if force and os.path.exists(SO_PATH):
         os.remove(SO_PATH)
-    subprocess.check_call(["make", "-s", "-j8", "-C", src_dir])   # eight translation units (kernels, the AERO instantiation, the three exact Jacobians, the mesh error estimate, the Jacobian products, host side)
+    subprocess.check_call(["make", "-s", "-j8", "-C", src_dir])   # nine translation units (kernels, the AERO instantiation, the three exact Jacobians, the mesh error estimate, the Jacobian products, the interpolation, host side)
     if not os.path.exists(SO_PATH):
         raise RuntimeError("building %s failed" % SO_PATH)
     _write_build_info()

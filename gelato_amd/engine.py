@@ -61,6 +61,75 @@ class _PinnedView(np.ndarray):
     """numpy view of the handle's pinned host memory that keeps the handle alive (attribute _owner on the base view)"""
 
 
+class InterpPlan:
+    """An interpolation plan of one engine (include/gelato_amd.h gel_interp_*): the matrices that evaluate every
+    section's polynomial at the plan's points -- a table of points (Engine.interp_plan) or another engine's mesh
+    (Engine.transfer_plan).  It holds the engine's handle owner, so the handle outlives it; close() destroys the plan."""
+
+    INFO = ("S", "mode", "state_rows", "out_doubles", "src_nvars", "vb")
+
+    def __init__(self, owner, ptr, src_nodes, P, Pu):
+        self._owner = owner       # the source engine's _Handle: not destroyed while a plan refers to it
+        self._p = ptr
+        self._n = [int(v) for v in src_nodes]
+        self._P, self._Pu = [int(v) for v in P], [int(v) for v in Pu]
+        i = self.info()
+        self.S, self.mode, self.nvars, self.out_doubles = i["S"], i["mode"], i["src_nvars"], i["out_doubles"]
+        self.out_shape = (i["state_rows"], 14) if self.mode == 0 else (self.out_doubles,)
+
+    def close(self):
+        if self._p:
+            ptr, self._p = self._p, None
+            if self._owner.ptr:     # (a handle closed first has taken the device down with it: the plan's host memory leaks)
+                lib().gel_interp_plan_destroy(ptr)
+        self._owner = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def info(self):
+        """{"S", "mode" (0 table, 1 transfer), "state_rows", "out_doubles" per vector, "src_nvars", "vb": vectors per workgroup a
+        launch will use NOW (GEL_INTERP_VB is read per call)}"""
+        info = (C.c_int64 * 6)()
+        check(lib().gel_interp_plan_info(self._p, info))
+        return dict(zip(self.INFO, (int(v) for v in info)))
+
+    def matrices(self, phase):
+        """{"Wx" [P, n+1], "Wu" [Pu, n], "copy_x" [P], "copy_u" [Pu]} of one phase"""
+        n, P, Pu = self._n[phase], self._P[phase], self._Pu[phase]
+        out = {"Wx": np.zeros((P, n + 1)), "Wu": np.zeros((Pu, n)), "copy_x": np.zeros(P, dtype=np.int32),
+               "copy_u": np.zeros(Pu, dtype=np.int32)}
+        check(lib().gel_interp_matrices(self._p, int(phase), _d(out["Wx"]), _d(out["Wu"]), out["copy_x"].ctypes.data_as(_ip),
+                                        out["copy_u"].ctypes.data_as(_ip)))
+        return out
+
+    def _apply(self, fn, X):
+        if not (self._p and self._owner.ptr):
+            raise _lib.GelatoAmdError("interpolation plan: closed, or its engine was closed first")
+        X = _f64(X).reshape(-1, self.nvars)
+        B = X.shape[0]
+        out = np.empty((B,) + self.out_shape)
+        rc = check(fn(self._p, B, _d(X), _d(out)))
+        return out, rc
+
+    def apply(self, X):
+        """X [B, nvars] (or [nvars]) -> (out [B, npts, 14] (table) or [B, dst nvars] (transfer), status): one device launch"""
+        return self._apply(lib().gel_interp, X)
+
+    def apply_host(self, X):
+        """the same in plain C++ on the host (works on host-only handles), the same bits -> (out, status)"""
+        return self._apply(lib().gel_interp_host, X)
+
+    def apply_resident(self, B, d_x, d_out):
+        """device buffers, asynchronous on the source engine's own stream; status through Engine.sync()"""
+        if not (self._p and self._owner.ptr):
+            raise _lib.GelatoAmdError("interpolation plan: closed, or its engine was closed first")
+        check(lib().gel_interp_resident(self._p, int(B), d_x, d_out))
+
+
 class Engine:
     """prob: dict with num_nodes, thrust, massflow, reference_area, nozzle_area, engine_on,
     attitude_hold, units (mass, position, velocity, u, t), dx, wind_table [K,3], ca_table [K,2];
@@ -696,6 +765,28 @@ class Engine:
     def mesh_error_device(self, B, d_x, d_err, d_diff=0, stream=0):
         """device buffers: d_err [B][S][4], d_diff [B][npts][11] or 0; status through sync()"""
         check(lib().gel_mesh_error_device(self._h, int(B), d_x, d_err, d_diff or None, stream or None))
+
+    # ------------------------------------------------------------------
+    # spectral interpolation: dense output and mesh transfer (include/gelato_amd.h gel_interp_*; DESIGN.md 3.13)
+    def interp_plan(self, points, unit_quat=False):
+        """points: a list of S arrays of points inside [-1, 1] (an empty one: no output for that phase) -> InterpPlan whose
+        apply(X) gives [B, npts, 14] = time | mass, position, velocity, quaternion | u at the points, in x's normalised units"""
+        if len(points) != self.S:
+            raise ValueError("points: one array per phase (%d)" % self.S)
+        pts = [_f64(np.asarray(p, dtype=np.float64).ravel()) for p in points]
+        npts = np.array([p.size for p in pts], dtype=np.int32)
+        allp = _f64(np.concatenate(pts)) if pts else np.zeros(0)
+        h = C.c_void_p()
+        check(lib().gel_interp_plan_create(self._h, npts.ctypes.data_as(_ip), _d(allp), int(bool(unit_quat)), C.byref(h)))
+        return InterpPlan(self._owner, h, self.num_nodes, npts, npts)
+
+    def transfer_plan(self, dst_engine, unit_quat=False):
+        """-> InterpPlan whose apply(X) gives [B, dst nvars]: the decision vectors carried to dst_engine's mesh (the same number
+        of phases; dst_engine may be host-only and may be closed afterwards)"""
+        h = C.c_void_p()
+        check(lib().gel_interp_plan_create_transfer(self._h, dst_engine._h, int(bool(unit_quat)), C.byref(h)))
+        nd = [int(v) for v in dst_engine.num_nodes]
+        return InterpPlan(self._owner, h, self.num_nodes, [n + 1 for n in nd], nd)
 
     # ------------------------------------------------------------------
     # Jacobian products from the compact values (include/gelato_amd.h gel_jac_*; DESIGN.md 3.10)

@@ -451,6 +451,56 @@ int gel_jac_products_info(const gel_problem* p, int64_t* info);
  * GEL_DEVICE_NONE handles.  (An entry point of its own: gel_jac_products_info's callers hold four values.) */
 int gel_jac_products_launch_info(const gel_problem* p, int32_t* info /* [4] */);
 
+/* ---- batched spectral interpolation: dense output and mesh transfer.  Per phase the collocation solution is a
+ *      polynomial: degree n in the 11 state components on the support [-1, tau_1 .. tau_n] (the n + 1 state nodes), degree n - 1
+ *      in the 2 controls on tau_1 .. tau_n.  A PLAN holds, for every phase of its source handle (on the handle's own tau, generated
+ *      or desc.tau), the matrices that evaluate this polynomial at the plan's points,
+ *        Wx[l][i] = the Lagrange basis on [-1, tau_1 .. tau_n] at point l,   Wu[l][j] = the basis on tau_1 .. tau_n at point l,
+ *      built at plan creation in extended precision with barycentric weights and rounded once (nothing is built at
+ *      gel_problem_create).  A point that equals a support node as an fp64 number is a COPY: copy_x[l] / copy_u[l] holds the
+ *      support index (else -1), its row is the unit row, and the value is copied, not multiplied -- bit-exact: a signed zero keeps
+ *      its sign and a NaN elsewhere in the phase does not reach it.  With generated nodes tau_n = +1 and the state support's -1
+ *      are exact, so every section's first and last state node is a copy between any two meshes (the knot states the linear
+ *      continuity rows read keep their bits), and a transfer between equal meshes is a bitwise copy.
+ *      Every other output is ONE fma chain over the support index in ascending order, starting from +0.0, on the device and in
+ *      gel_interp_host alike: both give the same bits, and a vector's result depends neither on B, nor on its position in the
+ *      batch, nor on the number of vectors a workgroup carries.
+ *      Table mode (mode 0): out [B][npts][14], rows in phase order, points in the order given; column 0 = the normalised time
+ *      sigma (tf - to)/2 + (tf + to)/2, columns 1..11 = the states (mass, position 3, velocity 3, quaternion 4), columns 12..13
+ *      = the controls, all in x's normalised units.  A control sampled below tau_1 is the control polynomial EXTRAPOLATED (the
+ *      controls have no node at -1).
+ *      Transfer mode (mode 1): the points are the destination handle's own nodes (states at [-1, tau^d], controls at tau^d);
+ *      out [B][dst num_vars] is the destination's packed decision vector, t copied bit for bit.  src and dst must have the same
+ *      number of phases.
+ *      Every element of out is written by every call.  GEL_INTERP_UNIT_QUAT: at rows that are not copies q is replaced by
+ *      q / sqrt(q . q) (the dot product one fma chain over components 0 .. 3); without the flag the map is purely linear.
+ *      A non-finite output raises the SOURCE handle's status: gel_interp and gel_interp_host return GEL_NONFINITE, the resident
+ *      form reports it through gel_sync(src, NULL); the other vectors' outputs stay valid.
+ *      Streams: gel_interp_resident takes no stream argument; it enqueues on the source handle's own stream, which is a blocking
+ *      stream and so orders itself against the null stream.  A caller working on a NON-BLOCKING stream must gel_sync(src, NULL)
+ *      before it consumes the output (and must have finished writing d_x before the call).
+ *      Lifetime: a plan is destroyed BEFORE its source handle; the destination handle of a transfer plan may be a host-only handle
+ *      and may be destroyed right after the plan is created.  A plan on a device handle refuses (GEL_ERR_ARG) a phase whose
+ *      staged slice, 13 n + 11 doubles, does not fit a workgroup's 64 KB of LDS (n > 629); gel_interp_host on a host-only
+ *      handle has no such limit.  B = 0 and npts[s] = 0 are valid. ---- */
+typedef struct gel_interp_plan gel_interp_plan; /* opaque */
+#define GEL_INTERP_UNIT_QUAT 1
+/* table mode: npts[s] points per phase (0 allowed), pts concatenated, each finite and in [-1, 1] */
+int gel_interp_plan_create(gel_problem* src, const int32_t* npts /* [S] */, const double* pts, int32_t flags, gel_interp_plan** out);
+/* transfer mode: the points are dst's own nodes; dst may be a host-only handle and may be destroyed afterwards */
+int gel_interp_plan_create_transfer(gel_problem* src, const gel_problem* dst, int32_t flags, gel_interp_plan** out);
+int gel_interp_plan_destroy(gel_interp_plan* plan);
+/* info [6]: S, mode (0 table, 1 transfer), state rows (table: the points; transfer: the destination's M), doubles per output
+ * vector, src num_vars, vectors per workgroup a launch will use NOW (the largest of 4, 2, 1 whose staged slice fits; GEL_INTERP_VB
+ * = 1 / 2 / 4 in the environment, read per call, overrides it where it fits) */
+int gel_interp_plan_info(const gel_interp_plan* plan, int64_t* info /* [6] */);
+/* row-major; P = Pu = npts[phase] (table), P = n_d + 1 and Pu = n_d (transfer); any pointer may be NULL */
+int gel_interp_matrices(const gel_interp_plan* plan, int32_t phase, double* Wx /* [P][n+1] */, double* Wu /* [Pu][n] */,
+                        int32_t* copy_x /* [P] */, int32_t* copy_u /* [Pu] */);
+int gel_interp(gel_interp_plan* plan, int32_t B, const double* x, double* out);              /* host buffers, one launch, synchronised */
+int gel_interp_resident(gel_interp_plan* plan, int32_t B, const double* d_x, double* d_out); /* device buffers, asynchronous */
+int gel_interp_host(const gel_interp_plan* plan, int32_t B, const double* x, double* out);   /* plain C++, works for GEL_DEVICE_NONE */
+
 /* ---- one optimiser callback = one device round trip: the four defect groups, the knot / terminal / user row table and the
  *      aero path constraints of ONE decision vector launched back to back on the handle's stream, one synchronise
  *      (what objfunc / sens of Trajectory_Optimization.py:194-312 need from the device).  Every output pointer may be
