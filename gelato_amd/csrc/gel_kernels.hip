@@ -1117,7 +1117,7 @@ __global__ void output_kernel(ProblemDev P, int M, const double* __restrict__ x,
     const double c1[3] = {c[0] / cn, c[1] / cn, c[2] / cn}, f1[3] = {f[0] / fn, f[1] / fn, f[2] / fn};
     const double inc = acos(c1[2]);
     double asc, argp;
-    if (inc > 1e-10) {
+    if (!(inc <= 1e-10)) {   // inc > 1e-10 for every number; a NaN state takes this side, so that it cannot leave a finite asc = 0
       asc = atan2(c1[0], -c1[1]);
       argp = acos(cos(asc) * f1[0] + sin(asc) * f1[1]);
       if (f[2] < 0) argp *= -1.0;
