@@ -10,6 +10,8 @@ error (it is the same finite step) but none of its rounding noise.  A correct fp
 reference's recomputation or the engine's exact-difference form -- lies within its own derivable rounding bound of these values;
 tests/test_exact_fd.py asserts both bounds.
 """
+import contextlib
+
 import numpy as np
 from mpmath import mp, mpf, sqrt, atan2, sin, cos, exp, power
 
@@ -35,6 +37,23 @@ MB = [mpf(v) for v in ("28.9644", "28.9644", "28.9644", "28.9644", "28.9644", "2
 def f64(v):
     """an fp64 number as an exact mpf"""
     return mpf(float(v))
+
+
+# the Earth rate as the reference's C++ holds it: the double nearest to the decimal above (9e-17 of it apart)
+OMEGA_F64 = f64(7.2921151467e-5)
+
+
+@contextlib.contextmanager
+def earth_rate(value):
+    """evaluate with OMEGA = value inside the block.  g15 / g18 / g21 were made with the decimal, which gives the same quotients to
+    1e-16 wherever |v - omega x r| is not tiny; g27 (at rest in the air, where that difference cancels to 1e-13 m/s and 9e-17 omega |r|
+    = 3e-14 m/s is all of it) takes OMEGA_F64: tests/golden/make_degenerate_fd.py and tests/test_degenerate_fd.py both go through here."""
+    global OMEGA
+    old, OMEGA = OMEGA, value
+    try:
+        yield
+    finally:
+        OMEGA = old
 
 
 def geodetic(x, y, z):

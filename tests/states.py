@@ -1,6 +1,8 @@
 """Synthetic extreme states shared by the parity tests and by tests/golden/make_exact_fd.py (which pins them with
 exact-arithmetic finite-difference values).  Every builder returns (prob, x): the static problem as the engine / oracle take
 it and a packed decision vector.  Deterministic (seeded)."""
+from fractions import Fraction
+
 import numpy as np
 
 
@@ -212,3 +214,169 @@ def noair_polar_state():
     x = np.concatenate([0.2 + rng.random(M), pos.ravel(), vel.ravel(), quat.ravel(), 2.0 * rng.standard_normal(2 * 2 * n),
                         [10.0 / ut, 200.0 / ut, 900.0 / ut]])
     return prob, x
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Degenerate states of the aerodynamic forms (tests/golden/make_degenerate_fd.py, tests/test_degenerate_fd.py): the polar axis,
+# where the exact-difference position sweeps (gel_rhs_parts.h pos_delta) hand over to the recomputing ones, and rest in the air.
+# ---------------------------------------------------------------------------------------------------------------------------
+POS_DELTA_U = 1.0e-4     # pos_delta's predicate: |u| < 1e-4 and |v| < 1e-4, u = dlt (2 x_k + dlt) / p^2, v ~ u / 2
+AXIS_NODES = (40, 40, 36)
+
+
+def pos_step(prob, xr):
+    """xr [.., 3] normalised -> (r [.., 3] in metres, dlt [.., 3]): the fp64 position the chain starts from and the exact step
+    fl((x + dx) unit) - fl(x unit) of each component's sweep"""
+    up, dx = float(prob["units"][1]), float(prob["dx"])
+    r = xr * up
+    return r, (xr + dx) * up - r
+
+
+def pos_delta_u(prob, xr):
+    """-> u [.., 2] of the x and the y sweep as pos_delta forms it (the z sweep leaves p alone: u = 0), p [..]"""
+    r, dlt = pos_step(prob, xr)
+    p2 = r[..., 0] ** 2 + r[..., 1] ** 2
+    with np.errstate(divide="ignore", invalid="ignore"):
+        u = dlt[..., :2] * (2.0 * r[..., :2] + dlt[..., :2]) / p2[..., None]
+    return u, np.sqrt(p2)
+
+
+def _polar_phase(prob, p, lon, alt, south):
+    """normalised positions [len(p), 3] at distance p (m) from the polar axis, longitude lon, altitude alt above the pole (the
+    ellipsoid falls 10 m below its polar radius at p = 11 km), south: which pole"""
+    b_e = 6356752.314245
+    up = prob["units"][1]
+    z = np.where(south, -1.0, 1.0) * (b_e + alt)
+    return np.column_stack([p * np.cos(lon), p * np.sin(lon), z]) / up
+
+
+def axis_state():
+    """Three aerodynamic phases in dense air (50 m .. 30 km, 300 .. 2500 m/s, the example's wind table) around BOTH poles, by
+    how pos_delta's predicate |u| < 1e-4 sorts their position sweeps (u = dlt (2 x + dlt) / p^2, dlt = dx unit_position =
+    6.4 cm: with x = p the switch lies at p = 2e4 dlt = 1276 m, its second condition |v| < 1e-4, v = u / 2, at 638 m):
+      phase 0  "covered"      p from just above the switch to 11 km; nodes within 2 % above it for the x sweep (y = 0), the y sweep
+                              (x = 0), both (x = y), with either sign;
+      phase 1  "fallback"     1 m <= p <= the switch; within 2 % below the switch and below 638 m, p = 1, 30, 300 m;
+      phase 2  "undecidable"  p = 0 exactly (both poles), 1e-6 .. 0.1 m; x or y negative and smaller than the step (the perturbed
+                              point crosses the axis), x = -dx exactly (it lands on it)
+    and no aerodynamics in the last one (the aero path constraints skip the last phase)."""
+    prob = _example_prob()
+    rng = np.random.default_rng(27)
+    nn = list(AXIS_NODES)
+    S = len(nn)
+    prob["num_nodes"] = np.array(nn, dtype=np.int32)
+    prob["thrust"] = np.full(S, 420000.0)
+    prob["massflow"] = np.full(S, 140.9)
+    prob["reference_area"] = np.full(S, 2.21)
+    prob["nozzle_area"] = np.full(S, 0.68)
+    prob["engine_on"] = np.ones(S, dtype=np.int32)
+    prob["attitude_hold"] = np.zeros(S, dtype=np.int32)
+    up, uv, ut, dx = prob["units"][1], prob["units"][2], prob["units"][4], float(prob["dx"])
+    step = dx * up
+    T = 2.0 * step / POS_DELTA_U          # x = p: |u| = 1e-4
+    T2 = T / np.sqrt(2.0)                 # x = y = p / sqrt 2: both sweeps at once
+    q = np.pi / 2
+    # (p, lon) per state node; node 0 of a phase has an aero row only
+    A = [(1.002 * T, 0.0), (1.010 * T, 0.0), (1.019 * T, 2 * q), (1.001 * T, q), (1.012 * T, -q), (1.018 * T, q),
+         (1.004 * T2, q / 2), (1.015 * T2, -3 * q / 2), (1.019 * T2, 3 * q / 2), (1.0005 * T, 1e-3), (1.003 * T, q - 1e-3)]
+    A += [(pp, ll) for pp, ll in zip(np.geomspace(1.03 * T, 11000.0, nn[0] + 1 - len(A)), np.arange(nn[0] + 1) * 0.61 - 3.0)]
+    B = [(1.0, 0.3), (1.0, q), (30.0, 0.0), (30.0, -2.0), (300.0, q), (300.0, 2.5), (0.999 * T, 0.0), (0.990 * T, 2 * q),
+         (0.981 * T, 0.0), (0.998 * T, q), (0.985 * T, -q), (0.996 * T2, q / 2), (0.982 * T2, -3 * q / 2), (0.999 * T / 2, 0.0),
+         (0.990 * T / 2, q), (0.981 * T / 2, 2 * q), (0.995 * T / 2, -q)]
+    B += [(pp, ll) for pp, ll in zip(np.geomspace(1.5, 0.97 * T, nn[1] + 1 - len(B)), np.arange(nn[1] + 1) * 0.47 - 3.0)]
+    Cp = np.array([0.0, 0.0, 1e-6, 1e-3, 0.03, 0.05, step, 0.1] * 5)[:nn[2] + 1]
+    Cl = np.array([0.0, q, 2 * q, -q, 2 * q, -q, 2 * q, 0.7] * 5)[:nn[2] + 1] + 0.0 * Cp
+    Cl[24:] = np.array([0.3, 2.0, -2.5, 1.0, -1.0, 2.9, 2 * q, -0.4] * 2)[:nn[2] + 1 - 24]
+    pos, k = [], 0
+    levels = np.array([50.0, 700.0, 1500.0, 2500.0, 4000.0, 6000.0, 8000.0, 9500.0, 12500.0, 14000.0, 17500.0, 21000.0, 25000.0,
+                       28000.0, 30000.0])
+    for nodes in (A, B, list(zip(Cp, Cl))):
+        p_, l_ = np.array([v[0] for v in nodes]), np.array([v[1] for v in nodes])
+        i = np.arange(len(nodes))
+        pos.append(_polar_phase(prob, p_, l_, levels[(3 * i + k) % len(levels)], (i + k) % 2 == 1))
+        k += 1
+    pos = np.vstack(pos)
+    # exact members of the undecidable class: ON the axis (the cos / sin of the builder leave 1e-17 there), and one step short of it
+    c0 = nn[0] + nn[1] + 2
+    for j in range(nn[2] + 1):
+        if Cp[j] == 0.0:
+            pos[c0 + j, :2] = 0.0
+        elif Cp[j] == step:
+            pos[c0 + j, :2] = (-dx, 0.0) if (j // 8) % 2 == 0 else (0.0, -dx)
+    M = sum(nn) + S
+    speed = rng.uniform(300.0, 2500.0, M) / uv
+    d = rng.standard_normal((M, 3))
+    vel = d / np.linalg.norm(d, axis=1, keepdims=True) * speed[:, None]
+    quat = rng.standard_normal((M, 4))
+    quat /= np.linalg.norm(quat, axis=1, keepdims=True)
+    x = np.concatenate([np.linspace(1.0, 0.5, M), pos.ravel(), vel.ravel(), quat.ravel(), 2.0 * rng.standard_normal(2 * sum(nn)),
+                        np.array([10.0, 60.0, 110.0, 160.0]) / ut])
+    return with_coast_tail(lambda: (prob, x))
+
+
+def rest_state():
+    """One aerodynamic phase of 36 nodes in calm, dense air (0.5 .. 30 km, |lat| <= 70 deg) at rest or nearly at rest in it: at
+    three nodes the air-relative velocity v unit - omega x r is EXACTLY zero in fp64, fused or not (x and y are powers of two
+    metres, so omega x and omega y are exact products; asserted), at the others |v_air| = 1e-13 .. 30 m/s in a random direction:
+    15 below the reference's clamp (|v_air| < 1e-6: alpha = 0), 9 from 3e-6 to 0.6 m/s -- where 1 / |v_air| multiplies a live angle
+    of attack and v_air is what is left of terms of |v| + omega |r| = 300 .. 930 m/s --, 10 from 1 to 30 m/s.  Mach <= 0.1: on the
+    CA table's first piece (its first knot is Mach 0), below every interior knot."""
+    prob = _example_prob()
+    rng = np.random.default_rng(72)
+    n = 36
+    omega = 7.2921151467e-5
+    prob["num_nodes"] = np.array([n], dtype=np.int32)
+    for k, v in [("thrust", 420000.0), ("massflow", 140.9), ("reference_area", 2.21), ("nozzle_area", 0.68)]:
+        prob[k] = np.array([v])
+    prob["engine_on"] = np.array([1], dtype=np.int32)
+    prob["attitude_hold"] = np.array([0], dtype=np.int32)
+    calm = np.array(prob["wind_table"], dtype=np.float64).copy()
+    calm[:, 1:] = 0.0
+    prob["wind_table"] = calm
+    up, uv, ut = prob["units"][1], prob["units"][2], prob["units"][4]
+    a_e, b_e = 6378137.0, 6356752.314245
+    lat = np.deg2rad(np.linspace(-70.0, 70.0, n + 1))
+    lon = rng.uniform(-np.pi, np.pi, n + 1)
+    alt = np.geomspace(500.0, 30000.0, n + 1)[rng.permutation(n + 1)]
+    R = a_e * b_e / np.sqrt((b_e * np.cos(lat)) ** 2 + (a_e * np.sin(lat)) ** 2) + alt
+    r = np.column_stack([R * np.cos(lat) * np.cos(lon), R * np.cos(lat) * np.sin(lon), R * np.sin(lat)])
+    exact = {5: (2.0 ** 22, 2.0 ** 21, 1.0), 17: (-2.0 ** 22, 2.0 ** 22, -1.0), 30: (2.0 ** 21, -2.0 ** 20, 1.0)}
+    for j, (x0, y0, sg) in exact.items():          # x, y powers of two; z puts the node at its altitude above the ellipsoid
+        pp = np.hypot(x0, y0)
+        z = b_e * np.sqrt(1.0 - (pp / a_e) ** 2)
+        r[j] = (x0, y0, sg * z * (1.0 + alt[j] / np.hypot(pp, z)))
+    xr = r / up
+
+    def reaching(target, unit, start):     # a double xs with fl(xs unit) == target, among the neighbours of start
+        xs = start
+        for _ in range(64):
+            got = xs * unit
+            if got == target:
+                return xs
+            xs = np.nextafter(xs, np.inf if (got < target) == (unit > 0) else -np.inf)
+        raise AssertionError("no fp64 number scales to %r" % target)
+
+    for j, (x0, y0, _) in exact.items():
+        xr[j, 0], xr[j, 1] = reaching(x0, up, x0 / up), reaching(y0, up, y0 / up)
+    rs = xr * up
+    slow = np.concatenate([np.geomspace(1e-13, 5e-7, 15), [3e-6, 1e-4, 1e-3, 3e-3, 1e-2, 3e-2, 0.1, 0.3, 0.6], np.geomspace(1.0, 30.0, 10)])
+    speed = np.zeros(n + 1)          # the three exact nodes get their velocity below
+    speed[[j for j in range(n + 1) if j not in exact]] = slow[rng.permutation(len(slow))]
+    d = rng.standard_normal((n + 1, 3))
+    v = np.column_stack([-omega * rs[:, 1], omega * rs[:, 0], np.zeros(n + 1)]) + d / np.linalg.norm(d, axis=1, keepdims=True) * speed[:, None]
+    xv = v / uv
+    for j in exact:
+        xv[j] = (reaching(-(omega * rs[j, 1]), uv, -(omega * rs[j, 1]) / uv), reaching(omega * rs[j, 0], uv, omega * rs[j, 0] / uv), 0.0)
+    vs = xv * uv
+    rel = np.column_stack([vs[:, 0] + omega * rs[:, 1], vs[:, 1] - omega * rs[:, 0], vs[:, 2]])
+    at_rest = ~rel.any(axis=1)
+    assert sorted(np.nonzero(at_rest)[0]) == sorted(exact), "three nodes exactly at rest in the air, in fp64"
+    for j in exact:      # ... and the products omega x, omega y are exact, so a fused multiply-add finds the same zero
+        assert all(Fraction(omega) * Fraction(rs[j, c]) == Fraction(omega * rs[j, c]) for c in (0, 1))
+    # the slowest sound of the standard atmosphere is 295 m/s (11 .. 20 km)
+    assert np.linalg.norm(rel, axis=1).max() / 295.0 < np.asarray(prob["ca_table"])[1, 0]
+    quat = rng.standard_normal((n + 1, 4))
+    quat /= np.linalg.norm(quat, axis=1, keepdims=True)
+    x = np.concatenate([np.linspace(1.0, 0.5, n + 1), xr.ravel(), xv.ravel(), quat.ravel(), 2.0 * rng.standard_normal(2 * n),
+                        [10.0 / ut, 160.0 / ut]])
+    return with_coast_tail(lambda: (prob, x))
