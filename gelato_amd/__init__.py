@@ -14,7 +14,8 @@ Host-side mirror of the reference interface for the hot path only:
 All numerics run in hand-written HIP kernels (gelato_amd/csrc) through the C-ABI in
 include/gelato_amd.h; there is no CPU fallback.
 """
-from .engine import Engine, InterpPlan, pack_x  # noqa: F401
+from .engine import Engine, InterpPlan, PropagationPlan, pack_x  # noqa: F401
 from .interp import refine, sample  # noqa: F401
+from .propagate import shooting_check  # noqa: F401
 
 __version__ = "0.1.0"

@@ -18,6 +18,7 @@ GEL_FLAG_FD_RECOMPUTE = 8
 GEL_FLAG_EXACT_DEFECT_JAC = 32   # defect-group Jacobians exact to rounding (forward mode) instead of forward differences
 GEL_FLAG_EXACT_AERO_JAC = 64     # aero path constraints' gradients exact to rounding (forward mode) instead of forward differences
 GEL_INTERP_UNIT_QUAT = 1         # gel_interp_plan_create*: rows that are not copies get q / sqrt(q . q)
+GEL_PROP_RESTART_NODE = 1        # gel_prop_plan_create: every node interval starts from the collocated state (the local defect)
 GEL_FLAG_EXACT_ROWS_JAC = 128    # node-function rows' jfn (terminal, user, waypoint rows) exact to rounding instead of forward differences
 NUM_BLOCKS = 13
 
@@ -140,6 +141,12 @@ SIGNATURES = {
     "gel_interp": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp]),
     "gel_interp_resident": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "gel_interp_host": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp]),
+    "gel_prop_plan_create": (C.c_int, [C.c_void_p, _ip, C.c_int32, C.POINTER(C.c_void_p)]),
+    "gel_prop_plan_destroy": (C.c_int, [C.c_void_p]),
+    "gel_prop_plan_info": (C.c_int, [C.c_void_p, _lp]),
+    "gel_prop_matrices": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, _ip]),
+    "gel_propagate": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, _dp]),
+    "gel_propagate_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gel_initial_guess": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, _dp, _dp]),
     "gel_output_table": (C.c_int, [C.c_void_p, _dp, _dp, C.c_double, C.c_double, _dp]),
     "gel_dynamics_velocity": (C.c_int, [C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int32, _dp, C.c_int32,
@@ -157,7 +164,7 @@ def build(force=False):
     src_dir = os.path.join(_HERE, "csrc")
     if force and os.path.exists(SO_PATH):
         os.remove(SO_PATH)
-    subprocess.check_call(["make", "-s", "-j8", "-C", src_dir])   # nine translation units (kernels, the AERO instantiation, the three exact Jacobians, the mesh error estimate, the Jacobian products, the interpolation, host side)
+    subprocess.check_call(["make", "-s", "-j8", "-C", src_dir])   # ten translation units (kernels, the AERO instantiation, the three exact Jacobians, the mesh error estimate, the Jacobian products, the interpolation, the propagation, host side)
     if not os.path.exists(SO_PATH):
         raise RuntimeError("building %s failed" % SO_PATH)
     _write_build_info()

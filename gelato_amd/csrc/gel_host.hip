@@ -22,6 +22,7 @@
 #include "gel_mesh.h"
 #include "gel_jprod.h"
 #include "gel_interp.h"
+#include "gel_prop.h"
 
 namespace {
 
@@ -2846,6 +2847,212 @@ int gel_interp(gel_interp_plan* plan, int32_t B, const double* x, double* out) {
   HIPCHK(gel::launch_interp(plan->dev, plan->ph.data(), plan->n_max, B, plan->d_x.get(), plan->d_out.get(), p->d_flag.get(),
                             interp_vb(plan), s));
   HIPCHK(hipMemcpyAsync(out, plan->d_out.get(), no * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(p->h_flag.get(), p->d_flag.get(), 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (*p->h_flag.get()) { *p->h_flag.get() = 0; HIPCHK(clear_flag(p, s)); return GEL_NONFINITE; }
+  return GEL_OK;
+}
+
+// ------------- batched explicit propagation of the sections with RK4: the shooting check -------------
+// A plan = per phase the stage points, the step of every node interval and the matrix that samples the control polynomial at the
+// stage points (the interpolation plan's builder: the same bits), row-major on the host (gel_prop_matrices), transposed on the
+// device (gel_prop.h).  It owns its device memory -- the tables, the control samples' workspace and the working set of the
+// host-buffer form -- and refers to the source handle for the device, the stream and the non-finite flag: it is destroyed before
+// that handle.
+struct gel_prop_plan {
+  gel_problem* src = nullptr;
+  int32_t flags = 0;
+  gel::PropDev dev{};
+  std::vector<gel::PropPhaseDev> ph;
+  std::vector<double> pts, Wu;    // per phase pts [Pp] at poff[s], Wu [Pp][n] row-major at woff[s]
+  std::vector<size_t> poff, woff;
+  std::vector<int32_t> cp;        // copy_u [Pp] per phase at ph[s].cu (the device's array as it is)
+  int64_t total_pts = 0;          // sum over all phases of Pp
+  int64_t sampled_pts = 0;        // sum over the free-attitude phases of Pp: the workspace's rows
+  int64_t lane_steps = 0;         // RK4 steps of the longest lane
+  int n_max_sampled = 0;
+  DeviceArray<double> d_mat, d_ws;
+  DeviceArray<int32_t> d_cp, d_seg;
+  DeviceArray<gel::PropPhaseDev> d_ph;
+  DeviceArray<double> d_x, d_y, d_err;   // working set of the host-buffer form
+};
+
+static constexpr int64_t kPropWsBytes = 1LL << 30;       // the control samples' workspace never exceeds this
+static constexpr int64_t kPropMaxSlab = 1 << 20;         // vectors per slab at the most
+static constexpr int64_t kPropMaxMatDoubles = 1LL << 27; // sum over phases of Pp n: the plan's matrices stay below 1 GB
+
+// Vectors per slab of a call (what gel_prop_plan_info reports): as many as the workspace cap holds, a multiple of 64; or
+// GEL_PROP_SLAB (measurement switch, read per call, rounded up to a multiple of 64; a value above the cap is ignored).  The
+// results do not depend on it.
+static int64_t prop_slab(const gel_prop_plan* pl) {
+  const int64_t per_vec = 16 * pl->sampled_pts;
+  int64_t vs = per_vec ? std::min<int64_t>(kPropMaxSlab, kPropWsBytes / per_vec / 64 * 64) : kPropMaxSlab;
+  if (vs < 64) vs = 64;   // (a host-only handle's plan may hold more stage points than a device handle's: creation refuses those there)
+  if (const char* e = getenv("GEL_PROP_SLAB")) {
+    const long long w = (atoll(e) + 63) / 64 * 64;
+    if (w >= 64 && w <= vs) vs = w;
+  }
+  return vs;
+}
+
+int gel_prop_plan_create(gel_problem* src, const int32_t* steps, int32_t flags, gel_prop_plan** out) {
+  if (!src || !steps || !out || (flags & ~GEL_PROP_RESTART_NODE)) return fail(GEL_ERR_ARG, "bad argument");
+  const int S = src->dims.S;
+  int64_t mat_doubles = 0;
+  for (int s = 0; s < S; s++) {
+    if (steps[s] < 1) return fail(GEL_ERR_ARG, "propagation plan: steps < 1");
+    if ((int64_t)steps[s] * src->ph[s].n > gel::kPropMaxLaneSteps)
+      return fail(GEL_ERR_ARG, "propagation plan: steps[s] n_s exceeds 2^20 RK4 steps in one section");
+    mat_doubles += (2 * (int64_t)steps[s] * src->ph[s].n + 1) * src->ph[s].n;
+  }
+  if (mat_doubles > kPropMaxMatDoubles) return fail(GEL_ERR_ARG, "propagation plan: the control matrices (sum of (2 k n + 1) n doubles) exceed 1 GB");
+  std::unique_ptr<gel_prop_plan> pl(new gel_prop_plan);
+  pl->src = src;
+  pl->flags = flags;
+  const bool restart = (flags & GEL_PROP_RESTART_NODE) != 0;
+  pl->ph.resize(S);
+  pl->poff.resize(S);
+  pl->woff.resize(S);
+  std::vector<double> matT;      // the device's table: per phase sig | hs | WuT (sampled phases only)
+  std::vector<int32_t> seg_phase;
+  for (int s = 0; s < S; s++) {
+    const HostPhase& h = src->ph[s];
+    const int n = h.n, k = steps[s];
+    const int64_t Pp = 2 * (int64_t)k * n + 1;
+    gel::PropPhaseDev& q = pl->ph[s];
+    q.n = n; q.k = k; q.sampled = h.hold ? 0 : 1; q.pad = 0;
+    q.ntile = q.sampled ? (int32_t)((Pp + gel::kPropSampleThreads - 1) / gel::kPropSampleThreads) : 0;
+    q.seg0 = (int32_t)seg_phase.size();
+    seg_phase.insert(seg_phase.end(), restart ? n : 1, s);
+    q.pt0 = pl->sampled_pts;
+    if (q.sampled) { pl->sampled_pts += Pp; pl->n_max_sampled = std::max(pl->n_max_sampled, n); }
+    pl->total_pts += Pp;
+    pl->lane_steps = std::max<int64_t>(pl->lane_steps, restart ? k : (int64_t)k * n);
+    std::vector<ld> tx(n + 1), tc(n);
+    tx[0] = -1.0L;
+    for (int j = 0; j < n; j++) tx[j + 1] = tc[j] = (ld)h.tau[j];
+    // stage points: a point on a node is the node's fp64 value itself
+    pl->poff[s] = pl->pts.size();
+    std::vector<double> hs(n);
+    for (int j = 0; j < n; j++) {
+      hs[j] = ((double)tx[j + 1] - (double)tx[j]) / (double)k;
+      for (int m = (j ? 1 : 0); m <= 2 * k; m++)
+        pl->pts.push_back(m == 0 ? (double)tx[j] : m == 2 * k ? (double)tx[j + 1]
+                                                             : (double)(tx[j] + (tx[j + 1] - tx[j]) * (ld)m / (ld)(2 * k)));
+    }
+    const double* z = pl->pts.data() + pl->poff[s];
+    const std::vector<ld> wc = bary_weights(tc);
+    pl->woff[s] = pl->Wu.size();
+    q.cu = (int64_t)pl->cp.size();
+    std::vector<ld> row(n);
+    for (int64_t l = 0; l < Pp; l++) {
+      lagrange_row(tc, wc, (ld)z[l], row.data());
+      int32_t c = -1;
+      for (int j = 0; j < n; j++) {
+        pl->Wu.push_back((double)row[j]);
+        if ((double)tc[j] == z[l]) c = j;
+      }
+      pl->cp.push_back(c);
+    }
+    q.sg = (int64_t)matT.size();
+    matT.insert(matT.end(), z, z + Pp);
+    q.hs = (int64_t)matT.size();
+    matT.insert(matT.end(), hs.begin(), hs.end());
+    q.wu = (int64_t)matT.size();
+    if (q.sampled) {
+      const double* W = pl->Wu.data() + pl->woff[s];
+      for (int j = 0; j < n; j++)
+        for (int64_t l = 0; l < Pp; l++) matT.push_back(W[(size_t)l * n + j]);
+    }
+  }
+  gel::PropDev& d = pl->dev;
+  d.S = S; d.restart = restart ? 1 : 0; d.nseg = (int32_t)seg_phase.size(); d.pad = 0;
+  d.vp = src->uv / src->up;
+  if (src->device != GEL_DEVICE_NONE) {
+    if (gel::prop_sample_lds_bytes(pl->n_max_sampled) > gel::kPropMaxLds)
+      return fail(GEL_ERR_ARG, "propagation plan: a free-attitude phase's controls (8 n doubles) do not fit a workgroup's LDS (n > 1024)");
+    if (64 * 16 * pl->sampled_pts > kPropWsBytes)
+      return fail(GEL_ERR_ARG, "propagation plan: the control samples of 64 vectors (16 bytes per stage point) exceed the 1 GB workspace");
+    HIPCHK(hipSetDevice(src->device));
+    HIPCHK(pl->d_mat.upload(matT));
+    HIPCHK(pl->d_cp.upload(pl->cp));
+    HIPCHK(pl->d_seg.upload(seg_phase));
+    HIPCHK(pl->d_ph.upload(pl->ph));
+    d.ph = pl->d_ph.get(); d.seg_phase = pl->d_seg.get(); d.mat = pl->d_mat.get(); d.cp = pl->d_cp.get();
+  }
+  *out = pl.release();
+  return GEL_OK;
+}
+
+int gel_prop_plan_destroy(gel_prop_plan* plan) {
+  if (!plan) return GEL_OK;
+  if (plan->src->device != GEL_DEVICE_NONE) {
+    hipSetDevice(plan->src->device);
+    (void)drain(plan->src);   // a device call in flight still reads the plan's tables and workspace
+  }
+  delete plan;
+  return GEL_OK;
+}
+
+int gel_prop_plan_info(const gel_prop_plan* plan, int64_t* info) {
+  if (!plan || !info) return fail(GEL_ERR_ARG, "null argument");
+  info[0] = plan->dev.S; info[1] = plan->flags; info[2] = plan->total_pts; info[3] = plan->lane_steps;
+  info[4] = 16 * plan->sampled_pts; info[5] = prop_slab(plan);
+  return GEL_OK;
+}
+
+int gel_prop_matrices(const gel_prop_plan* plan, int32_t phase, double* pts, double* Wu, int32_t* copy_u) {
+  if (!plan || phase < 0 || phase >= plan->dev.S) return fail(GEL_ERR_ARG, "bad argument");
+  const gel::PropPhaseDev& q = plan->ph[phase];
+  const size_t Pp = 2 * (size_t)q.k * q.n + 1;
+  if (pts) std::memcpy(pts, plan->pts.data() + plan->poff[phase], Pp * 8);
+  if (Wu) std::memcpy(Wu, plan->Wu.data() + plan->woff[phase], Pp * q.n * 8);
+  if (copy_u) std::memcpy(copy_u, plan->cp.data() + q.cu, Pp * 4);
+  return GEL_OK;
+}
+
+// the launches of one call on stream s: slab after slab the control samples and the integration, then err of all B vectors
+static int prop_enqueue(gel_prop_plan* plan, int32_t B, const double* d_x, double* d_y, double* d_err, hipStream_t s) {
+  gel_problem* p = plan->src;
+  const int64_t vs = prop_slab(plan), ldv = std::min<int64_t>(vs, ((int64_t)B + 63) / 64 * 64);
+  const size_t need = (size_t)ldv * 2 * (size_t)plan->sampled_pts;
+  if (plan->d_ws.capacity() < need) {
+    HIPCHK(drain(p));   // an earlier call in flight, on the handle's stream or on the caller's, still reads the old block
+    HIPCHK(plan->d_ws.reserve(need));
+  }
+  const size_t nv = (size_t)p->dims.num_vars, ny = (size_t)11 * p->dims.M;
+  for (int64_t v0 = 0; v0 < B; v0 += vs) {
+    const int nb = (int)std::min<int64_t>(vs, B - v0);
+    HIPCHK(gel::launch_prop_slab(p->dev, plan->dev, plan->ph.data(), plan->n_max_sampled, nb, d_x + (size_t)v0 * nv,
+                                 d_y + (size_t)v0 * ny, plan->d_ws.get(), ldv, s));
+  }
+  if (d_err) HIPCHK(gel::launch_prop_err(p->dev, plan->dev, B, d_x, d_y, d_err, s));
+  return GEL_OK;
+}
+
+int gel_propagate_device(gel_prop_plan* plan, int32_t B, const double* d_x, double* d_y, double* d_err) {
+  if (!plan || B < 0 || (B > 0 && (!d_x || !d_y))) return fail(GEL_ERR_ARG, "bad argument");
+  gel_problem* p = plan->src;
+  NEED_DEVICE(p);
+  if (B == 0) return GEL_OK;
+  HIPCHK(hipSetDevice(p->device));
+  return prop_enqueue(plan, B, d_x, d_y, d_err, p->stream.get());
+}
+
+int gel_propagate(gel_prop_plan* plan, int32_t B, const double* x, double* y, double* err) {
+  if (!plan || B < 0 || (B > 0 && (!x || !y))) return fail(GEL_ERR_ARG, "bad argument");
+  gel_problem* p = plan->src;
+  NEED_DEVICE(p);
+  if (B == 0) return GEL_OK;
+  HIPCHK(hipSetDevice(p->device));
+  const size_t nx = (size_t)B * p->dims.num_vars, ny = (size_t)B * 11 * p->dims.M, ne = err ? (size_t)B * p->dims.S * 4 : 0;
+  hipStream_t s = p->stream.get();
+  if (plan->d_x.capacity() < nx || plan->d_y.capacity() < ny || plan->d_err.capacity() < ne) HIPCHK(hipStreamSynchronize(s));
+  HIPCHK(plan->d_x.reserve(nx)); HIPCHK(plan->d_y.reserve(ny)); HIPCHK(plan->d_err.reserve(ne));
+  HIPCHK(hipMemcpyAsync(plan->d_x.get(), x, nx * 8, hipMemcpyHostToDevice, s));
+  if (const int rc = prop_enqueue(plan, B, plan->d_x.get(), plan->d_y.get(), err ? plan->d_err.get() : nullptr, s)) return rc;
+  HIPCHK(hipMemcpyAsync(y, plan->d_y.get(), ny * 8, hipMemcpyDeviceToHost, s));
+  if (err) HIPCHK(hipMemcpyAsync(err, plan->d_err.get(), ne * 8, hipMemcpyDeviceToHost, s));
   HIPCHK(hipMemcpyAsync(p->h_flag.get(), p->d_flag.get(), 4, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
   if (*p->h_flag.get()) { *p->h_flag.get() = 0; HIPCHK(clear_flag(p, s)); return GEL_NONFINITE; }

@@ -11,10 +11,12 @@
 // staged in LDS; the interpolation reads them as broadcasts and the matrices (transposed on the host: one coalesced load per
 // column) through the cache.  The same LDS region then holds |X~| for the per-component maxima, the right-hand sides F for the
 // product with I, and |X^ - X~| for the maxima over the points.  Nothing per point reaches HBM unless diff is asked for.
-// fp64 throughout; the right-hand side is built from the value functions of gel_rhs_parts.h / gel_physics.h.
+// fp64 throughout; the right-hand side is section_rhs (gel_section_rhs.h), built from the value functions of gel_rhs_parts.h /
+// gel_physics.h.
 #include <hip/hip_runtime.h>
 
 #include "gel_tables.h"
+#include "gel_section_rhs.h"
 #include "gel_mesh.h"
 
 namespace gel {
@@ -110,42 +112,8 @@ __global__ __launch_bounds__(kMeshMaxThreads) void mesh_kernel(ProblemDev P, Mes
   const double to = xb[11 * M + 2 * N + s], tf = xb[11 * M + 2 * N + s + 1];
   const double S = (tf - to) * P.ut / 2.0;
   double F[11];
-  F[0] = ph.engine_on ? ph.mf_um : 0.0;   // mass: the m[1:] - m[0] form when the engine is off
-#pragma unroll
-  for (int c = 0; c < 3; c++) F[1 + c] = xt[4 + c] * Md.vp;
   if (act) {   // (idle lanes stay out of the calm-air vote of wind_eci_or_calm)
-    const double m = xt[0] * P.um;
-    const double r[3] = {xt[1] * P.up, xt[2] * P.up, xt[3] * P.up};
-    const double q[4] = {xt[7], xt[8], xt[9], xt[10]};
-    double dir[3], f[3];
-    thrust_dir(q, dir);
-    if (ph.air) {
-      // dynamics_velocity at the normalised time of the point (PSparams.time_nodes, as the defect kernels take it)
-      const double v3[3] = {xt[4] * P.uv, xt[5] * P.uv, xt[6] * P.uv};
-      const PosPart pp = pos_part(r, tb, P.barC20);
-      const EarthAngle ea = earth_angle(sig * (tf - to) / 2 + (tf + to) / 2);
-      double w[3], Fa[3];
-      wind_eci_or_calm(r, ea, pp.shp, pp.chp, pp.inv_p, pp.wn, pp.we, w);
-      aero_force(r, v3, pp.rho, pp.inv_a, ea, w, ph.area, tb, Fa);
-      const double T = ph.thrust - ph.nozzle * pp.P;
-      const double Td[3] = {T * dir[0], T * dir[1], T * dir[2]};
-      accel(Td, Fa, 1.0 / m, pp.g, P.inv_uv, f);
-    } else {
-      double g[3];
-      gravity_eci(r, P.barC20, g);
-      const double Td[3] = {ph.thrust * dir[0], ph.thrust * dir[1], ph.thrust * dir[2]};
-      accel_noair(Td, 1.0 / m, g, P.inv_uv, f);
-    }
-#pragma unroll
-    for (int c = 0; c < 3; c++) F[4 + c] = f[c];
-    if (ph.hold) {
-      F[7] = F[8] = F[9] = F[10] = 0.0;
-    } else {
-      double dq[4];
-      quat_rate(q, u0, u1, P.uu, dq);
-#pragma unroll
-      for (int c = 0; c < 4; c++) F[7 + c] = dq[c];
-    }
+    section_rhs(P, ph, tb, Md.vp, sig, to, tf, xt, u0, u1, F);
 #pragma unroll
     for (int c = 0; c < 11; c++) Xs[c * np + l] = F[c];
   }

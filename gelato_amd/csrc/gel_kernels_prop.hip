@@ -1,0 +1,227 @@
+// gel_kernels_prop.hip -- batched explicit propagation of the sections with classical RK4 (gel_propagate*): take
+// the controls the optimiser found, integrate the equations of motion from a section's first state (or from every collocated
+// node: GEL_PROP_RESTART_NODE) and see whether the trajectory arrives where the collocated states say.  Independent of D and I.
+//
+// Three kernels per call, the first two once per slab of vectors:
+//   prop_sample_kernel   the control polynomial at every stage point of the free-attitude phases, in interp_kernel's register-
+//                        blocked style (a lane owns one stage point of kPropSampleVB vectors whose U lies in LDS; the matrix is
+//                        stored transposed: one coalesced load per column), into the plan's workspace [stage point][2][vector]
+//   prop_kernel          one lane = one (vector, segment); a wavefront = 64 consecutive vectors of ONE segment, so the phase and
+//                        the step count are wave-uniform and the two control samples of a stage are one coalesced load each.
+//                        The step is written down in gel_prop.h.  The loop lengths n and k come from the plan's tables, which
+//                        creation bounds (k n <= 2^20): a launch always ends.
+//   prop_err_kernel      err [B][S][4] from x and y: one lane = one (vector, phase), nodes in ascending order
+// fp64 throughout; the right-hand side is section_rhs (gel_section_rhs.h), the one mesh_kernel evaluates.
+#include <hip/hip_runtime.h>
+
+#include "gel_tables.h"
+#include "gel_section_rhs.h"
+#include "gel_prop.h"
+
+namespace gel {
+
+namespace {
+__device__ __forceinline__ bool nonfinite(double v) { return !(__builtin_fabs(v) <= 1.79769313486231570815e308); }
+// running maximum that keeps a NaN once it has seen one (fmax would drop it)
+__device__ __forceinline__ double nan_max(double acc, double v) { return (v > acc || v != v) ? v : acc; }
+// component c of state row xi of a packed vector (x, or y: the same layout)
+__device__ __forceinline__ size_t state_index(int M, int xi, int c) {
+  return (c == 0) ? (size_t)xi : (c < 4) ? (size_t)M + 3 * (size_t)xi + (c - 1) : (c < 7) ? 4 * (size_t)M + 3 * (size_t)xi + (c - 4)
+                                                                                      : 7 * (size_t)M + 4 * (size_t)xi + (c - 7);
+}
+}  // namespace
+
+__global__ __launch_bounds__(kPropSampleThreads) void prop_sample_kernel(ProblemDev P, PropDev Pd, int nb, const double* __restrict__ x,
+                                                                         double* __restrict__ ws, long long ld) {
+  extern __shared__ double lds[];
+  constexpr int VB = kPropSampleVB;
+  // workgroup -> (phase, group of vectors, point tile): the sampled phases' workgroups one after the other
+  const long long ng = ((long long)nb + VB - 1) / VB;
+  int s = 0;
+  long long wg = blockIdx.x;
+  for (; s < Pd.S; s++) {
+    const long long c = ng * Pd.ph[s].ntile;
+    if (wg < c) break;
+    wg -= c;
+  }
+  if (s >= Pd.S) return;   // (never: the grid is the sum over phases)
+  const PropPhaseDev q = Pd.ph[s];
+  const PhaseDev ph = load_phase(P.phases + s);
+  const long long grp = wg / q.ntile;
+  const int tile = (int)(wg - grp * q.ntile);
+  const int n = q.n, t = threadIdx.x;
+  const long long Pp = 2LL * q.k * n + 1;
+  const double* xv[VB];
+#pragma unroll
+  for (int v = 0; v < VB; v++) {
+    const long long b = grp * VB + v;
+    xv[v] = x + (size_t)(b < nb ? b : nb - 1) * P.nvars + 11 * (size_t)P.M + 2 * (size_t)ph.ua;   // (a tail group reads its last vector again)
+  }
+  for (int r = t; r < 2 * n; r += kPropSampleThreads) {
+#pragma unroll
+    for (int v = 0; v < VB; v++) lds[(size_t)r * VB + v] = xv[v][r];   // U [n][2][VB]
+  }
+  __syncthreads();
+  const long long l = (long long)tile * kPropSampleThreads + t;
+  if (l >= Pp) return;
+  double u[2][VB];
+#pragma unroll
+  for (int v = 0; v < VB; v++) u[0][v] = u[1][v] = 0.0;
+  const double* W = Pd.mat + q.wu + l;
+  for (int j = 0; j < n; j++) {
+    const double w = W[(size_t)j * Pp];
+    const double* Uj = lds + (size_t)j * 2 * VB;
+#pragma unroll
+    for (int c = 0; c < 2; c++)
+#pragma unroll
+      for (int v = 0; v < VB; v++) u[c][v] = __builtin_fma(w, Uj[c * VB + v], u[c][v]);
+  }
+  const int cu = Pd.cp[q.cu + l];
+  if (cu >= 0) {
+    const double* Uj = lds + (size_t)cu * 2 * VB;
+#pragma unroll
+    for (int c = 0; c < 2; c++)
+#pragma unroll
+      for (int v = 0; v < VB; v++) u[c][v] = Uj[c * VB + v];
+  }
+  double* o = ws + (size_t)(q.pt0 + l) * 2 * (size_t)ld + (size_t)grp * VB;
+#pragma unroll
+  for (int v = 0; v < VB; v++) {
+    if (grp * VB + v >= nb) continue;
+    o[v] = u[0][v];
+    o[(size_t)ld + v] = u[1][v];
+  }
+}
+
+__global__ __launch_bounds__(kPropThreads) void prop_kernel(ProblemDev P, PropDev Pd, int nb, const double* __restrict__ x,
+                                                            double* __restrict__ y, const double* __restrict__ ws, long long ld) {
+  extern __shared__ double lds[];
+  // workgroup -> (segment, group of kPropThreads vectors)
+  const int ngrp = (nb + kPropThreads - 1) / kPropThreads;
+  const int seg = blockIdx.x / ngrp, grp = blockIdx.x - seg * ngrp;
+  const Tables tb = stage_tables(P, lds);
+  const int v = grp * kPropThreads + (int)threadIdx.x;
+  if (seg >= Pd.nseg || v >= nb) return;   // (idle lanes leave: they stay out of the calm-air vote of wind_eci_or_calm; no barrier follows)
+  const int s = load_const(&Pd.seg_phase[seg]);
+  const PhaseDev ph = load_phase(P.phases + s);
+  const int n = load_const(&Pd.ph[s].n), k = load_const(&Pd.ph[s].k), sampled = load_const(&Pd.ph[s].sampled);
+  const int j0 = Pd.restart ? seg - load_const(&Pd.ph[s].seg0) : 0, j1 = Pd.restart ? j0 + 1 : n;
+  const double* const sig = Pd.mat + load_const(&Pd.ph[s].sg);
+  const double* const hs = Pd.mat + load_const(&Pd.ph[s].hs);
+  const double* const us = ws + (size_t)load_const(&Pd.ph[s].pt0) * 2 * (size_t)ld + v;
+  const int M = P.M, N = P.N;
+  const double* const xb = x + (size_t)v * P.nvars;
+  double* const yb = y + (size_t)v * 11 * (size_t)M;
+  const double to = xb[11 * M + 2 * N + s], tf = xb[11 * M + 2 * N + s + 1];
+  const double S = (tf - to) * P.ut / 2.0;
+  bool bad = false;
+
+  double yv[11];
+#pragma unroll
+  for (int c = 0; c < 11; c++) yv[c] = xb[state_index(M, ph.xa + j0, c)];
+  if (j0 == 0) {   // node xa: X_0 bit for bit
+#pragma unroll
+    for (int c = 0; c < 11; c++) { yb[state_index(M, ph.xa, c)] = yv[c]; bad |= nonfinite(yv[c]); }
+  }
+  for (int j = j0; j < j1; j++) {
+    const double Sh = S * hs[j], Sh2 = Sh * 0.5, Sh6 = Sh / 6.0;
+    for (int i = 0; i < k; i++) {
+      const int p = 2 * (k * j + i);
+      double acc[11], F[11];
+#pragma unroll
+      for (int c = 0; c < 11; c++) acc[c] = F[c] = 0.0;
+#pragma nounroll
+      for (int st = 0; st < 4; st++) {
+        const int pp = p + ((st + 1) >> 1);                 // stage points p, p + 1, p + 1, p + 2
+        const double a = (st == 3) ? Sh : Sh2;
+        const double w = (st == 3) ? 1.0 : 2.0;
+        double yt[11];
+#pragma unroll
+        for (int c = 0; c < 11; c++) yt[c] = st ? __builtin_fma(a, F[c], yv[c]) : yv[c];
+        double u0 = 0.0, u1 = 0.0;
+        if (sampled) {
+          u0 = us[(size_t)pp * 2 * (size_t)ld];
+          u1 = us[((size_t)pp * 2 + 1) * (size_t)ld];
+        }
+        section_rhs(P, ph, tb, Pd.vp, sig[pp], to, tf, yt, u0, u1, F);
+#pragma unroll
+        for (int c = 0; c < 11; c++) acc[c] = st ? __builtin_fma(w, F[c], acc[c]) : F[c];
+      }
+#pragma unroll
+      for (int c = 0; c < 11; c++) yv[c] = __builtin_fma(Sh6, acc[c], yv[c]);
+    }
+#pragma unroll
+    for (int c = 0; c < 11; c++) { yb[state_index(M, ph.xa + j + 1, c)] = yv[c]; bad |= nonfinite(yv[c]); }
+  }
+  if (bad) *(volatile int32_t*)P.flag = 1;
+}
+
+__global__ __launch_bounds__(256) void prop_err_kernel(ProblemDev P, PropDev Pd, int B, const double* __restrict__ x,
+                                                       const double* __restrict__ y, double* __restrict__ err) {
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (long long)B * Pd.S) return;
+  const long long b = t / Pd.S;
+  const int s = (int)(t - b * Pd.S);
+  const int n = P.phases[s].n, xa = P.phases[s].xa, M = P.M;
+  const double* xb = x + (size_t)b * P.nvars;
+  const double* yb = y + (size_t)b * 11 * (size_t)M;
+  double d[11], mx[11];
+#pragma unroll
+  for (int c = 0; c < 11; c++) { d[c] = 0.0; mx[c] = nan_max(0.0, fabs(xb[state_index(M, xa, c)])); }
+  for (int i = 1; i <= n; i++) {
+#pragma unroll
+    for (int c = 0; c < 11; c++) {
+      const size_t k = state_index(M, xa + i, c);
+      const double xv = xb[k];
+      d[c] = nan_max(d[c], fabs(yb[k] - xv));
+      mx[c] = nan_max(mx[c], fabs(xv));
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < 11; c++) d[c] = d[c] / (1.0 + mx[c]);   // max_i (|d_i| / den) = (max_i |d_i|) / den: the rounded quotient is monotone
+  bool bad = false;
+#pragma unroll
+  for (int g = 0; g < 4; g++) {
+    const int c0 = (g == 0) ? 0 : 3 * g - 2, c1 = (g == 0) ? 1 : (g == 3) ? 11 : 3 * g + 1;   // [0,1) [1,4) [4,7) [7,11)
+    double e = 0.0;
+#pragma unroll
+    for (int c = c0; c < c1; c++) e = nan_max(e, d[c]);
+    err[(size_t)t * 4 + g] = e;
+    bad |= nonfinite(e);
+  }
+  if (bad) *(volatile int32_t*)P.flag = 1;
+}
+
+hipError_t launch_prop_slab(const ProblemDev& P, const PropDev& Pd, const PropPhaseDev* host_ph, int n_max_sampled, int nb,
+                            const double* d_x, double* d_y, double* d_ws, int64_t ld, hipStream_t s) {
+  if (nb <= 0) return hipSuccess;
+  if (ld < nb) return hipErrorInvalidValue;
+  const long long ng = ((long long)nb + kPropSampleVB - 1) / kPropSampleVB;
+  long long grid = 0;
+  for (int i = 0; i < Pd.S; i++) grid += ng * host_ph[i].ntile;
+  if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
+  if (grid > 0) {
+    const size_t lds = prop_sample_lds_bytes(n_max_sampled);
+    if (lds > kPropMaxLds) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(prop_sample_kernel, dim3((unsigned)grid), dim3(kPropSampleThreads), lds, s, P, Pd, nb, d_x, d_ws, (long long)ld);
+    if (const hipError_t e = hipGetLastError()) return e;
+  }
+  const long long ngrp = ((long long)nb + kPropThreads - 1) / kPropThreads;
+  grid = ngrp * Pd.nseg;
+  if (grid <= 0) return hipSuccess;
+  if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
+  const size_t lds = sizeof(double) * staged_table_doubles(P.Kw, P.Kc);
+  hipLaunchKernelGGL(prop_kernel, dim3((unsigned)grid), dim3(kPropThreads), lds, s, P, Pd, nb, d_x, d_y, d_ws, (long long)ld);
+  return hipGetLastError();
+}
+
+hipError_t launch_prop_err(const ProblemDev& P, const PropDev& Pd, int B, const double* d_x, const double* d_y, double* d_err,
+                           hipStream_t s) {
+  if (B <= 0) return hipSuccess;
+  const long long grid = ((long long)B * Pd.S + 255) / 256;
+  if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(prop_err_kernel, dim3((unsigned)grid), dim3(256), 0, s, P, Pd, B, d_x, d_y, d_err);
+  return hipGetLastError();
+}
+
+}  // namespace gel

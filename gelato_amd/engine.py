@@ -130,6 +130,72 @@ class InterpPlan:
         check(lib().gel_interp_resident(self._p, int(B), d_x, d_out))
 
 
+class PropagationPlan:
+    """An RK4 propagation plan of one engine (include/gelato_amd.h gel_prop_*): per section the stage points and
+    the matrix that samples the control polynomial there.  apply() integrates the equations of motion explicitly through every
+    section -- the shooting check.  It holds the engine's handle owner, so the handle outlives it; close() destroys the plan."""
+
+    INFO = ("S", "flags", "stage_points", "lane_steps", "workspace_bytes_per_vector", "slab")
+
+    def __init__(self, owner, ptr, nodes, steps, dims):
+        self._owner = owner       # the engine's _Handle: not destroyed while a plan refers to it
+        self._p = ptr
+        self._n = [int(v) for v in nodes]
+        self.steps = [int(v) for v in steps]
+        self.S, self.M, self.nvars = dims
+
+    def close(self):
+        if self._p:
+            ptr, self._p = self._p, None
+            if self._owner.ptr:     # (a handle closed first has taken the device down with it: the plan's host memory leaks)
+                lib().gel_prop_plan_destroy(ptr)
+        self._owner = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _live(self):
+        if not (self._p and self._owner.ptr):
+            raise _lib.GelatoAmdError("propagation plan: closed, or its engine was closed first")
+
+    def info(self):
+        """{"S", "flags", "stage_points" in total, "lane_steps": RK4 steps of the longest lane, "workspace_bytes_per_vector",
+        "slab": vectors per slab a call will use NOW (GEL_PROP_SLAB is read per call)}"""
+        self._live()
+        info = (C.c_int64 * 6)()
+        check(lib().gel_prop_plan_info(self._p, info))
+        return dict(zip(self.INFO, (int(v) for v in info)))
+
+    def matrices(self, phase):
+        """{"pts" [Pp], "Wu" [Pp, n], "copy_u" [Pp]} of one phase, Pp = 2 steps n + 1 (works on host-only handles)"""
+        self._live()
+        n = self._n[phase]
+        Pp = 2 * self.steps[phase] * n + 1
+        out = {"pts": np.zeros(Pp), "Wu": np.zeros((Pp, n)), "copy_u": np.zeros(Pp, dtype=np.int32)}
+        check(lib().gel_prop_matrices(self._p, int(phase), _d(out["pts"]), _d(out["Wu"]), out["copy_u"].ctypes.data_as(_ip)))
+        return out
+
+    def apply(self, X, want_err=True):
+        """X [B, nvars] (or [nvars]) -> (Y [B, 11 M]: the propagated state at every state node, laid out like the state part of
+        x; err [B, S, 4] (mass, position, velocity, quaternion) | None; status)"""
+        self._live()
+        X = _f64(X).reshape(-1, self.nvars)
+        B = X.shape[0]
+        Y = np.empty((B, 11 * self.M))
+        err = np.empty((B, self.S, 4)) if want_err else None
+        rc = check(lib().gel_propagate(self._p, B, _d(X), _d(Y), _d(err) if want_err else None))
+        return Y, err, rc
+
+    def apply_device(self, B, d_x, d_y, d_err=0):
+        """device buffers: d_y [B][11 M], d_err [B][S][4] or 0; asynchronous on the engine's own stream; status through
+        Engine.sync()"""
+        self._live()
+        check(lib().gel_propagate_device(self._p, int(B), d_x, d_y, d_err or None))
+
+
 class Engine:
     """prob: dict with num_nodes, thrust, massflow, reference_area, nozzle_area, engine_on,
     attitude_hold, units (mass, position, velocity, u, t), dx, wind_table [K,3], ca_table [K,2];
@@ -787,6 +853,24 @@ class Engine:
         check(lib().gel_interp_plan_create_transfer(self._h, dst_engine._h, int(bool(unit_quat)), C.byref(h)))
         nd = [int(v) for v in dst_engine.num_nodes]
         return InterpPlan(self._owner, h, self.num_nodes, [n + 1 for n in nd], nd)
+
+    # ------------------------------------------------------------------
+    # explicit RK4 propagation of the sections: the shooting check (include/gelato_amd.h gel_prop_*)
+    def propagation_plan(self, steps=4, restart="section"):
+        """steps: RK4 steps per node interval, one number or one per phase; restart: "section" (integrate from the section's
+        first state to its last node) or "node" (every node interval starts from the collocated state) -> PropagationPlan"""
+        if restart not in ("section", "node"):
+            raise ValueError("restart: 'section' or 'node'")
+        st = np.asarray(steps)
+        if st.ndim > 1 or (st.ndim == 1 and st.size != self.S):
+            raise ValueError("steps: one number, or one per phase (%d)" % self.S)
+        if not np.issubdtype(st.dtype, np.integer):
+            raise TypeError("steps: integers")
+        st = np.ascontiguousarray(np.broadcast_to(st, (self.S,)), dtype=np.int32)
+        h = C.c_void_p()
+        check(lib().gel_prop_plan_create(self._h, st.ctypes.data_as(_ip), _lib.GEL_PROP_RESTART_NODE if restart == "node" else 0,
+                                         C.byref(h)))
+        return PropagationPlan(self._owner, h, self.num_nodes, st, (self.S, self.M, self.nvars))
 
     # ------------------------------------------------------------------
     # Jacobian products from the compact values (include/gelato_amd.h gel_jac_*; DESIGN.md 3.10)

@@ -501,6 +501,59 @@ int gel_interp(gel_interp_plan* plan, int32_t B, const double* x, double* out); 
 int gel_interp_resident(gel_interp_plan* plan, int32_t B, const double* d_x, double* d_out); /* device buffers, asynchronous */
 int gel_interp_host(const gel_interp_plan* plan, int32_t B, const double* x, double* out);   /* plain C++, works for GEL_DEVICE_NONE */
 
+/* ---- batched explicit propagation of the sections with classical RK4: the shooting check.  Take the controls
+ *      of a decision vector, integrate the equations of motion explicitly from a section's first state and see whether the
+ *      trajectory arrives where the collocated states say -- a check that uses neither D nor I.
+ *      Phase s of n nodes, support tau_x = [-1, tau_1 .. tau_n], S = (tf - to) unit_t / 2, k = steps[s] >= 1:
+ *      Steps: every node interval [tau_x_j, tau_x_{j+1}] is cut into k equal RK4 steps h_j = (tau_x_{j+1} - tau_x_j) / k (fp64).
+ *      The phase has Pp = 2 k n + 1 STAGE POINTS; point 2 (k j + i) + m, m = 0, 1, 2, is tau_x_j + (tau_x_{j+1} - tau_x_j)
+ *      (2 i + m) / (2 k), formed in extended precision and rounded once; a point that falls on a node is the node's fp64 value.
+ *      Right-hand side F(sigma, X, U): exactly the one gel_mesh_error evaluates (mass -massflow/unit_mass with the engine on, else
+ *      0; position X_vel unit_v/unit_p; velocity dynamics_velocity or _NoAir by reference_area, at the normalised time sigma
+ *      (tf - to)/2 + (tf + to)/2; quaternion dynamics_quaternion, or 0 for a held attitude).  Quaternions are never renormalised.
+ *      Controls: U(sigma) = the control polynomial on tau_1 .. tau_n sampled at the stage points with Wu [Pp][n], built as
+ *      gel_interp_plan_create builds its Wu (the same bits), each sample ONE fma chain over the node index in ascending order from
+ *      +0.0; a stage point that is a collocation node is a copy (copy_u); below tau_1 the polynomial is extrapolated.
+ *      Step (y at the step's first stage point p; every operation rounds once, fma where written):
+ *        Sh = S h_j;  k1 = F(p, y);  k2 = F(p + 1, fma(Sh/2, k1, y));  k3 = F(p + 1, fma(Sh/2, k2, y));  k4 = F(p + 2, fma(Sh, k3, y))
+ *        a = fma(2, k2, k1);  a = fma(2, k3, a);  a = fma(1, k4, a);  y <- fma(Sh / 6, a, y)
+ *      Restart: by default (section mode) y starts at X_0 of the section and runs to its last node; with GEL_PROP_RESTART_NODE every
+ *      node interval starts from the collocated X_j (the local defect: WHERE a section is bad).  The first interval is the same
+ *      computation in both modes: the same bits.
+ *      Outputs: y [B][11 M], laid out like the state part of x (mass M | position 3M | velocity 3M | quaternion 4M): the propagated
+ *      state at every state node; node xa of each phase is X_0 copied bit for bit.  err (optional) [B][S][4] in gel_mesh_error's
+ *      normalisation: max_{i=1..n} |y_c(i) - x_c(i)| / (1 + max_{i=0..n} |x_c(i)|), then the maximum over each group's components
+ *      (mass, position, velocity, quaternion); a NaN is kept.  Every element is written by every call.  A non-finite output raises
+ *      the source handle's status (GEL_NONFINITE from gel_propagate, through gel_sync for the device form); the other vectors'
+ *      outputs stay valid.  A vector's result depends neither on B, nor on its position in the batch, nor on anything another
+ *      vector holds, nor on the slab size.
+ *      Refusals (GEL_ERR_ARG): steps[s] < 1; steps[s] n_s > 2^20 (no lane runs longer than that many steps: a launch always ends);
+ *      control matrices of more than 2^27 doubles in all (sum of Pp n); on a device handle a free-attitude phase of more than 1024
+ *      nodes (its controls are staged in a workgroup's LDS) and more than 2^20 stage points of free-attitude phases in all (the
+ *      control samples of 64 vectors, 16 bytes per stage point, must fit the 1 GB workspace).
+ *      The plan owns every buffer it needs: its tables, the control samples' workspace [stage point][2][vector] (16 bytes per
+ *      stage point of a free-attitude phase and vector, capped at 1 GB: a larger batch is walked in slabs of vectors on the stream)
+ *      and the working set of gel_propagate.  A plan is destroyed BEFORE
+ *      its source handle.  B = 0 is valid.  There is no host form: the evaluation calls refuse a GEL_DEVICE_NONE handle. ---- */
+typedef struct gel_prop_plan gel_prop_plan; /* opaque */
+#define GEL_PROP_RESTART_NODE 1
+int gel_prop_plan_create(gel_problem* src, const int32_t* steps /* [S] */, int32_t flags, gel_prop_plan** out);
+int gel_prop_plan_destroy(gel_prop_plan* plan);
+/* info [6]: S, flags, stage points in total (sum of Pp), RK4 steps of the longest lane (max k n, or max k with
+ * GEL_PROP_RESTART_NODE), workspace bytes per vector, vectors per slab a call will use NOW (the most the workspace cap holds, a
+ * multiple of 64; GEL_PROP_SLAB in the environment, read per call and rounded up to a multiple of 64, overrides it where it fits) */
+int gel_prop_plan_info(const gel_prop_plan* plan, int64_t* info /* [6] */);
+/* row-major, Pp = 2 steps[phase] n + 1; any pointer may be NULL; works on GEL_DEVICE_NONE handles */
+int gel_prop_matrices(const gel_prop_plan* plan, int32_t phase, double* pts /* [Pp] */, double* Wu /* [Pp][n] */,
+                      int32_t* copy_u /* [Pp] */);
+/* host buffers, synchronised; returns GEL_OK or GEL_NONFINITE; err may be NULL */
+int gel_propagate(gel_prop_plan* plan, int32_t B, const double* x, double* y, double* err);
+/* device buffers, asynchronous; like gel_interp_resident it takes no stream argument: everything is enqueued on the source
+ * handle's own stream, which is a blocking stream and so orders itself against the null stream; status through
+ * gel_sync(src, NULL).  A caller working on a NON-BLOCKING stream must have finished writing d_x before the call and must
+ * gel_sync(src, NULL) before it consumes the outputs. */
+int gel_propagate_device(gel_prop_plan* plan, int32_t B, const double* d_x, double* d_y, double* d_err /* or NULL */);
+
 /* ---- one optimiser callback = one device round trip: the four defect groups, the knot / terminal / user row table and the
  *      aero path constraints of ONE decision vector launched back to back on the handle's stream, one synchronise
  *      (what objfunc / sens of Trajectory_Optimization.py:194-312 need from the device).  Every output pointer may be
