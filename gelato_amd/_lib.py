@@ -133,6 +133,13 @@ SIGNATURES = {
     "gel_jac_products_info": (C.c_int, [C.c_void_p, _lp]),
     "gel_jac_products_launch_info": (C.c_int, [C.c_void_p, _ip]),
     "gel_aero_launch_info": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _lp]),
+    "gel_con_products_dims": (C.c_int, [C.c_void_p, _lp]),
+    "gel_con_matvec_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gel_con_rmatvec_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p,
+                                          C.c_int32]),
+    "gel_con_matvec": (C.c_int, [C.c_void_p, C.c_int32, _dp, C.POINTER(_dp), _dp, _dp, _dp]),
+    "gel_con_rmatvec": (C.c_int, [C.c_void_p, C.c_int32, _dp, C.POINTER(_dp), _dp, _dp, _dp, C.c_int32]),
+    "gel_con_products_host": (C.c_int, [C.c_void_p, C.c_int32, _dp, C.POINTER(_dp), _dp, _dp, _dp, C.c_int32, C.c_int32]),
     "gel_interp_plan_create": (C.c_int, [C.c_void_p, _ip, _dp, C.c_int32, C.POINTER(C.c_void_p)]),
     "gel_interp_plan_create_transfer": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(C.c_void_p)]),
     "gel_interp_plan_destroy": (C.c_int, [C.c_void_p]),
@@ -164,7 +171,7 @@ def build(force=False):
     src_dir = os.path.join(_HERE, "csrc")
     if force and os.path.exists(SO_PATH):
         os.remove(SO_PATH)
-    subprocess.check_call(["make", "-s", "-j8", "-C", src_dir])   # ten translation units (kernels, the AERO instantiation, the three exact Jacobians, the mesh error estimate, the Jacobian products, the interpolation, the propagation, host side)
+    subprocess.check_call(["make", "-s", "-j8", "-C", src_dir])   # eleven translation units (kernels, the AERO instantiation, the three exact Jacobians, the mesh error estimate, the two Jacobian products, the interpolation, the propagation, host side)
     if not os.path.exists(SO_PATH):
         raise RuntimeError("building %s failed" % SO_PATH)
     _write_build_info()

@@ -21,6 +21,7 @@
 #include "gel_launch.h"
 #include "gel_mesh.h"
 #include "gel_jprod.h"
+#include "gel_conprod.h"
 #include "gel_interp.h"
 #include "gel_prop.h"
 
@@ -400,6 +401,23 @@ struct gel_problem {
   DeviceArray<gel::JprodPhaseDev> d_jp_ph;
   DeviceArray<double> d_jp_tpart;                             // [B][S][2] partial sums of the time columns of J^T lambda
   DeviceArray<double> d_jp_jv, d_jp_in, d_jp_out;             // working set of the host-buffer calls
+  // Products with K, the Jacobian of every row that is not a defect row (gel_con_*): the operator tables of
+  // gel_conprod.h in both directions (0: by row, K v; 1: by column, K^T lambda), rebuilt as a whole by gel_rows_configure and
+  // gel_aero_configure and swapped in with the tables they come from (host-only handles included; the host product reads the
+  // same arrays), and their device copies
+  struct Conprod {
+    int32_t nlin = 0, nfn = 0, nrows[3] = {0, 0, 0};
+    int64_t R = 0, nnz = 0, max_row = 0, max_col = 0, jac_len[3] = {0, 0, 0};
+    struct Dir {
+      std::vector<int32_t> ptr, idx, src;
+      std::vector<int64_t> offd, offr;                        // dense form, record form
+      std::vector<double> cval;
+      DeviceArray<int32_t> d_ptr, d_idx, d_src;
+      DeviceArray<int64_t> d_offd, d_offr;
+      DeviceArray<double> d_cval;
+    } dir[2];
+  } conprod;
+  DeviceArray<double> d_cp_jfn, d_cp_aero[3], d_cp_in, d_cp_out;   // working set of the host-buffer calls
   // large host batches (gel_eval_batch): two staging slots of kPipeEvals decision vectors each, every
   // slot with its own stream, so that PCIe in, kernel, PCIe out and the host copies of neighbouring
   // sub-batches overlap
@@ -2092,6 +2110,129 @@ int gel_dynamics_quaternion(int32_t n, const double* quat, const double* u_e, do
   return GEL_OK;
 }
 
+namespace {
+// The two walks that describe the aero gradients of a configuration `a` of handle p (gel_aero_pattern, gel_aero_record_map and
+// the tables of the K products all go through them: there is no second description of the layout).
+// emission order of inequality_jac_max_*: con_aero.py:437-463
+void aero_pattern_of(const gel_problem* p, const gel_problem::Aero& a, int kind, int var, int32_t* rows, int32_t* cols) {
+  const auto& A = a.rows[kind];
+  int64_t o = 0;
+  for (size_t r0 = 0; r0 < A.size(); r0 += A[r0].nk) {
+    const int nk = A[r0].nk, i = A[r0].phase, xa = p->ph[i].xa, iRow = (int)r0;
+    if (var == 3) {
+      for (int k = 0; k < nk; k++) { rows[o] = iRow + k; cols[o++] = i; }
+      for (int k = 0; k < nk; k++) { rows[o] = iRow + k; cols[o++] = i + 1; }
+    } else if (!(var == 2 && kind == 1)) {
+      const int w = (var == 2) ? 4 : 3;
+      for (int j = 0; j < w; j++)
+        for (int k = 0; k < nk; k++) { rows[o] = iRow + k; cols[o++] = (xa + k) * w + j; }
+    }
+  }
+}
+// record index of every entry of gel_eval_aero_all's arrays: var = -1 the constraint vector [nrows], var 0..3 the position /
+// velocity / quaternion / t block of the gradient values (in the order of aero_pattern_of)
+void aero_record_map_of(const gel_problem* p, const gel_problem::Aero& a, int kind, int var, int64_t* idx) {
+  const auto& A = a.rows[kind];
+  const int nq = (kind == 1) ? 0 : 4;
+  int64_t o = 0;
+  if (var == -1) {
+    for (size_t r = 0; r < A.size(); r++) {
+      const int32_t po = a.part_of[kind][r];
+      if (po & 1) idx[o++] = a.off_con[1][kind] + (po >> 1);
+      else idx[o++] = a.partA_base[kind][po >> 1] + ((po >> 1) - a.part_rows[0][kind][po >> 1].row0);
+    }
+    return;
+  }
+  if (var == 2 && kind == 1) return;   // dynamic pressure has no quaternion block
+  const int64_t w = (var == 2) ? 4 : ((var == 3) ? 2 : 3);
+  const int64_t bo = (var == 0) ? 0 : ((var == 1) ? 3 : ((var == 2) ? 6 : 6 + nq));
+  for (size_t r0 = 0; r0 < A.size(); r0 += A[r0].nk)
+    for (int64_t j = 0; j < w; j++)
+      for (int k = 0; k < A[r0].nk; k++) {     // the reference's emission order: spec, column, node (aero_pattern_of)
+        const int32_t po = a.part_of[kind][r0 + k];
+        const int part = po & 1;
+        const auto& q = a.part_rows[part][kind][po >> 1];
+        const int64_t R = (int64_t)a.part_rows[part][kind].size();
+        const int64_t ko = (po >> 1) - q.row0;
+        if (part == 1) idx[o++] = a.off_jac[1][kind] + bo * R + w * q.row0 + j * q.nk + ko;
+        else if (var == 3 && !p->fd_recompute) idx[o++] = -1;      // an exact zero, not stored (AeroPhaseDev)
+        else idx[o++] = a.partA_base[kind][po >> 1] + (((var == 0) ? 1 : ((var == 1) ? 4 : ((var == 2) ? 7 : 11))) + j) * q.nk + ko;
+      }
+}
+
+// The tables of the K products (gel_conprod.h) for the row table (lin, fn) and the aero configuration a, host arrays and device
+// copies, into `out` (a local of the configure call that swaps it in).  Rows [linear | node-function | alpha | q | q-alpha];
+// a row's entries in the order of its definition (linear: idx0, idx1; node-function: jfn column 0 .. 6; aero: var 0 .. 3, inside
+// a var the pattern's order); a column's entries by ascending row, equal rows in the row's own order.
+int conprod_build(const gel_problem* p, const std::vector<gel::LinRowDev>& lin, const std::vector<gel::FnRowDev>& fn,
+                  const gel_problem::Aero& a, gel_problem::Conprod& out) {
+  struct Entry { int32_t row, col, src; int64_t offd, offr; double cval; };
+  const int M = p->dims.M, N = p->dims.N, nvars = p->dims.num_vars;
+  const int32_t var_off[4] = {M, 4 * M, 7 * M, 11 * M + 2 * N};   // position, velocity, quaternion, t inside the packed vector
+  std::vector<std::vector<Entry>> by_row;
+  out.nlin = (int32_t)lin.size(); out.nfn = (int32_t)fn.size();
+  for (size_t r = 0; r < lin.size(); r++) {
+    by_row.emplace_back();
+    by_row.back().push_back(Entry{(int32_t)r, lin[r].idx0, gel::kConSrcConst, 0, 0, lin[r].coef0});
+    if (lin[r].idx1 >= 0) by_row.back().push_back(Entry{(int32_t)r, lin[r].idx1, gel::kConSrcConst, 0, 0, lin[r].coef1});
+  }
+  for (size_t r = 0; r < fn.size(); r++) {
+    by_row.emplace_back();
+    const int32_t row = out.nlin + (int32_t)r;
+    for (int c = 0; c < 6; c++)
+      by_row.back().push_back(Entry{row, var_off[c / 3] + 3 * fn[r].node + c % 3, gel::kConSrcJfn, (int64_t)r * 7 + c, (int64_t)r * 7 + c, 0.0});
+    if (fn[r].tcol >= 0)   // jfn[r][6] of a row without a time column is never read
+      by_row.back().push_back(Entry{row, var_off[3] + fn[r].tcol, gel::kConSrcJfn, (int64_t)r * 7 + 6, (int64_t)r * 7 + 6, 0.0});
+  }
+  int32_t row0 = out.nlin + out.nfn;
+  for (int kd = 0; kd < 3; kd++) {
+    const int64_t Rk = (int64_t)a.rows[kd].size();
+    out.nrows[kd] = (int32_t)Rk;
+    out.jac_len[kd] = Rk * ((kd == 1) ? 8 : 12);
+    by_row.resize((size_t)row0 + Rk);
+    int64_t dense0 = 0;
+    for (int var = 0; var < 4; var++) {
+      const int64_t nnz = (var == 3) ? 2 * Rk : ((var == 2) ? ((kd == 1) ? 0 : 4 * Rk) : 3 * Rk);
+      std::vector<int32_t> rows(nnz), cols(nnz);
+      std::vector<int64_t> rec(nnz);
+      if (nnz) { aero_pattern_of(p, a, kd, var, rows.data(), cols.data()); aero_record_map_of(p, a, kd, var, rec.data()); }
+      for (int64_t e = 0; e < nnz; e++)
+        if (rec[e] >= 0)   // a structural zero is not an entry of K, in either source form
+          by_row[(size_t)row0 + rows[e]].push_back(Entry{row0 + rows[e], var_off[var] + cols[e], gel::kConSrcAero0 + kd, dense0 + e, rec[e], 0.0});
+      dense0 += nnz;
+    }
+    row0 += (int32_t)Rk;
+  }
+  out.R = row0;
+  std::vector<Entry> all;
+  for (const auto& r : by_row) all.insert(all.end(), r.begin(), r.end());
+  if (all.size() > (size_t)0x7fffffff) return fail(GEL_ERR_ARG, "K products: too many entries");
+  out.nnz = (int64_t)all.size();
+  out.max_row = out.max_col = 0;
+  for (int d = 0; d < 2; d++) {
+    gel_problem::Conprod::Dir& D = out.dir[d];
+    const int nout = d ? nvars : (int)out.R;
+    if (d) std::stable_sort(all.begin(), all.end(), [](const Entry& x, const Entry& y) { return x.col < y.col; });
+    D.ptr.assign((size_t)nout + 1, 0);
+    for (const Entry& e : all) D.ptr[(size_t)(d ? e.col : e.row) + 1]++;
+    for (int o = 0; o < nout; o++) {
+      (d ? out.max_col : out.max_row) = std::max<int64_t>(d ? out.max_col : out.max_row, D.ptr[(size_t)o + 1]);
+      D.ptr[(size_t)o + 1] += D.ptr[o];
+    }
+    D.idx.clear(); D.src.clear(); D.offd.clear(); D.offr.clear(); D.cval.clear();
+    for (const Entry& e : all) {
+      D.idx.push_back(d ? e.row : e.col); D.src.push_back(e.src); D.offd.push_back(e.offd); D.offr.push_back(e.offr);
+      D.cval.push_back(e.cval);
+    }
+    if (p->device != GEL_DEVICE_NONE) {
+      HIPCHK(D.d_ptr.upload(D.ptr)); HIPCHK(D.d_idx.upload(D.idx)); HIPCHK(D.d_src.upload(D.src));
+      HIPCHK(D.d_offd.upload(D.offd)); HIPCHK(D.d_offr.upload(D.offr)); HIPCHK(D.d_cval.upload(D.cval));
+    }
+  }
+  return GEL_OK;
+}
+}  // namespace
+
 // ------------------ aero path constraints (lib/con_aero.py) ------------------
 int gel_aero_configure(gel_problem* p, int32_t kind, int32_t nspec, const int32_t* phase, const int32_t* range_all,
                        const double* limit) {
@@ -2221,9 +2362,12 @@ int gel_aero_configure(gel_problem* p, int32_t kind, int32_t nspec, const int32_
     HIPCHK(a.d_nodes.upload(a.nodes)); HIPCHK(a.d_ph.upload(a.ph));
     for (int part = 0; part < 2; part++)
       if (!a.part_nodes[part].empty()) HIPCHK(a.d_part_nodes[part].upload(a.part_nodes[part]));
-    HIPCHK(drain(p));   // launches in flight, on the handle's stream or on the caller's, still read the old tables
   }
+  gel_problem::Conprod cp;   // the K products' tables follow the new configuration (and stay the old ones if this fails)
+  if (const int rc = conprod_build(p, p->lin_rows, p->fn_rows, a, cp)) return rc;
+  if (p->device != GEL_DEVICE_NONE) HIPCHK(drain(p));   // launches in flight, on the handle's stream or on the caller's, still read the old tables
   p->aero = std::move(a);
+  p->conprod = std::move(cp);
   return GEL_OK;
 }
 
@@ -2239,32 +2383,7 @@ int gel_aero_record_layout(const gel_problem* p, int64_t* width, int64_t* off_co
 // velocity / quaternion / t block of the gradient values (in the order of gel_aero_pattern)
 int gel_aero_record_map(const gel_problem* p, int32_t kind, int32_t var, int64_t* idx) {
   if (!p || kind < 0 || kind > 2 || var < -1 || var > 3 || !idx) return fail(GEL_ERR_ARG, "bad argument");
-  const auto& A = p->aero.rows[kind];
-  const int nq = (kind == 1) ? 0 : 4;
-  int64_t o = 0;
-  if (var == -1) {
-    for (size_t r = 0; r < A.size(); r++) {
-      const int32_t po = p->aero.part_of[kind][r];
-      if (po & 1) idx[o++] = p->aero.off_con[1][kind] + (po >> 1);
-      else idx[o++] = p->aero.partA_base[kind][po >> 1] + ((po >> 1) - p->aero.part_rows[0][kind][po >> 1].row0);
-    }
-    return GEL_OK;
-  }
-  if (var == 2 && kind == 1) return GEL_OK;   // dynamic pressure has no quaternion block
-  const int64_t w = (var == 2) ? 4 : ((var == 3) ? 2 : 3);
-  const int64_t bo = (var == 0) ? 0 : ((var == 1) ? 3 : ((var == 2) ? 6 : 6 + nq));
-  for (size_t r0 = 0; r0 < A.size(); r0 += A[r0].nk)
-    for (int64_t j = 0; j < w; j++)
-      for (int k = 0; k < A[r0].nk; k++) {     // the reference's emission order: spec, column, node (gel_aero_pattern)
-        const int32_t po = p->aero.part_of[kind][r0 + k];
-        const int part = po & 1;
-        const auto& q = p->aero.part_rows[part][kind][po >> 1];
-        const int64_t R = (int64_t)p->aero.part_rows[part][kind].size();
-        const int64_t ko = (po >> 1) - q.row0;
-        if (part == 1) idx[o++] = p->aero.off_jac[1][kind] + bo * R + w * q.row0 + j * q.nk + ko;
-        else if (var == 3 && !p->fd_recompute) idx[o++] = -1;      // an exact zero, not stored (AeroPhaseDev)
-        else idx[o++] = p->aero.partA_base[kind][po >> 1] + (((var == 0) ? 1 : ((var == 1) ? 4 : ((var == 2) ? 7 : 11))) + j) * q.nk + ko;
-      }
+  aero_record_map_of(p, p->aero, kind, var, idx);
   return GEL_OK;
 }
 
@@ -2325,21 +2444,8 @@ int gel_aero_dims(const gel_problem* p, int32_t kind, int32_t* nrows, int64_t* n
 }
 
 int gel_aero_pattern(const gel_problem* p, int32_t kind, int32_t var, int32_t* rows, int32_t* cols) {
-  // emission order of inequality_jac_max_*: con_aero.py:437-463
   if (!p || kind < 0 || kind > 2 || var < 0 || var > 3 || !rows || !cols) return fail(GEL_ERR_ARG, "bad argument");
-  const auto& A = p->aero.rows[kind];
-  int64_t o = 0;
-  for (size_t r0 = 0; r0 < A.size(); r0 += A[r0].nk) {
-    const int nk = A[r0].nk, i = A[r0].phase, xa = p->ph[i].xa, iRow = (int)r0;
-    if (var == 3) {
-      for (int k = 0; k < nk; k++) { rows[o] = iRow + k; cols[o++] = i; }
-      for (int k = 0; k < nk; k++) { rows[o] = iRow + k; cols[o++] = i + 1; }
-    } else if (!(var == 2 && kind == 1)) {
-      const int w = (var == 2) ? 4 : 3;
-      for (int j = 0; j < w; j++)
-        for (int k = 0; k < nk; k++) { rows[o] = iRow + k; cols[o++] = (xa + k) * w + j; }
-    }
-  }
+  aero_pattern_of(p, p->aero, kind, var, rows, cols);
   return GEL_OK;
 }
 
@@ -2452,10 +2558,13 @@ int gel_rows_configure(gel_problem* p, int32_t nlin, const gel_linear_row* lin, 
   if (p->device != GEL_DEVICE_NONE) {
     HIPCHK(hipSetDevice(p->device));
     HIPCHK(d_lin.upload(lin_rows)); HIPCHK(d_fn.upload(fn_rows));
-    HIPCHK(drain(p));   // launches in flight, on the handle's stream or on the caller's, still read the old tables
   }
+  gel_problem::Conprod cp;   // the K products' tables follow the new rows (and stay the old ones if this fails)
+  if (const int rc = conprod_build(p, lin_rows, fn_rows, p->aero, cp)) return rc;
+  if (p->device != GEL_DEVICE_NONE) HIPCHK(drain(p));   // launches in flight, on the handle's stream or on the caller's, still read the old tables
   p->lin_rows = std::move(lin_rows); p->fn_rows = std::move(fn_rows);
   p->d_lin_rows = std::move(d_lin); p->d_fn_rows = std::move(d_fn);
+  p->conprod = std::move(cp);
   return GEL_OK;
 }
 
@@ -3184,6 +3293,166 @@ static int jprod_hostbuf(gel_problem* p, int32_t B, const double* jvar, const do
 
 int gel_jac_matvec(gel_problem* p, int32_t B, const double* jvar, const double* v, double* y) { return jprod_hostbuf(p, B, jvar, v, y, 0); }
 int gel_jac_rmatvec(gel_problem* p, int32_t B, const double* jvar, const double* lam, double* g) { return jprod_hostbuf(p, B, jvar, lam, g, 1); }
+
+// ------------- products with K, the Jacobian of every row that is not a defect row -------------
+int gel_con_products_dims(const gel_problem* p, int64_t* info) {
+  if (!p || !info) return fail(GEL_ERR_ARG, "null argument");
+  const gel_problem::Conprod& c = p->conprod;
+  info[0] = c.R; info[1] = c.nlin; info[2] = c.nfn;
+  for (int k = 0; k < 3; k++) info[3 + k] = c.nrows[k];
+  info[6] = c.nnz; info[7] = c.max_row; info[8] = c.max_col;
+  return GEL_OK;
+}
+
+// the argument rules every form shares
+static int conprod_check(const gel_problem* p, int32_t B, const double* jfn, const double* const* aero_jac, const double* aero_record,
+                         const void* in, const void* out) {
+  if (!p || B < 1 || !in || !out) return fail(GEL_ERR_ARG, "bad argument");
+  const gel_problem::Conprod& c = p->conprod;
+  if (c.R == 0) return fail(GEL_ERR_ARG, "K products: no rows configured (gel_rows_configure, gel_aero_configure)");
+  if (c.nfn && !jfn) return fail(GEL_ERR_ARG, "K products: jfn is required when the row table has node-function rows");
+  const bool any_aero = c.nrows[0] || c.nrows[1] || c.nrows[2];
+  if (!any_aero) {
+    if (aero_jac || aero_record) return fail(GEL_ERR_ARG, "K products: no aero kind has rows, aero_jac and aero_record must be NULL");
+    return GEL_OK;
+  }
+  if ((aero_jac != nullptr) == (aero_record != nullptr))
+    return fail(GEL_ERR_ARG, "K products: exactly one of aero_jac and aero_record must be given");
+  if (aero_jac)
+    for (int k = 0; k < 3; k++)
+      if (c.nrows[k] && !aero_jac[k]) return fail(GEL_ERR_ARG, "K products: aero_jac of a kind with rows is NULL");
+  return GEL_OK;
+}
+
+static gel::ConprodVals conprod_vals(const gel_problem* p, const double* jfn, const double* const* aero_jac, const double* aero_record) {
+  const gel_problem::Conprod& c = p->conprod;
+  gel::ConprodVals v{};
+  v.jfn = c.nfn ? jfn : nullptr;
+  v.jfn_stride = c.nfn ? (int64_t)c.nfn * 7 : 0;
+  for (int k = 0; k < 3; k++) {
+    const bool has = c.nrows[k] != 0;
+    v.aero[k] = !has ? nullptr : (aero_record ? aero_record : aero_jac[k]);
+    v.aero_stride[k] = !has ? 0 : (aero_record ? p->aero.ld : c.jac_len[k]);
+  }
+  return v;
+}
+
+int gel_con_products_host(const gel_problem* p, int32_t B, const double* jfn, const double* const* aero_jac, const double* aero_record,
+                          const double* in, double* out, int32_t transpose, int32_t accumulate) {
+  if (const int rc = conprod_check(p, B, jfn, aero_jac, aero_record, in, out)) return rc;
+  const gel_problem::Conprod& c = p->conprod;
+  const gel_problem::Conprod::Dir& D = c.dir[transpose ? 1 : 0];
+  const gel::ConprodVals v = conprod_vals(p, jfn, aero_jac, aero_record);
+  const std::vector<int64_t>& off = aero_record ? D.offr : D.offd;
+  const size_t nin = transpose ? (size_t)c.R : (size_t)p->dims.num_vars, nout = transpose ? (size_t)p->dims.num_vars : (size_t)c.R;
+  int rc = GEL_OK;
+  for (int32_t b = 0; b < B; b++) {
+    const double* ib = in + (size_t)b * nin;
+    double* ob = out + (size_t)b * nout;
+    for (size_t o = 0; o < nout; o++) {   // the same chain as a lane of conprod_kernel
+      double acc = 0.0;
+      for (int32_t e = D.ptr[o]; e < D.ptr[o + 1]; e++) {
+        const int sc = D.src[e];
+        const double a = (sc == gel::kConSrcConst) ? D.cval[e]
+                       : (sc == gel::kConSrcJfn)   ? v.jfn[(size_t)b * v.jfn_stride + off[e]]
+                                                   : v.aero[sc - gel::kConSrcAero0][(size_t)b * v.aero_stride[sc - gel::kConSrcAero0] + off[e]];
+        acc = std::fma(a, ib[D.idx[e]], acc);
+      }
+      if (accumulate) acc = ob[o] + acc;
+      ob[o] = acc;
+      if (!std::isfinite(acc)) rc = GEL_NONFINITE;
+    }
+  }
+  return rc;
+}
+
+static int conprod_device(gel_problem* p, int32_t B, const double* d_jfn, const double* const* d_aero_jac, const double* d_aero_record,
+                          const double* d_in, double* d_out, int transpose, int accumulate, hipStream_t s) {
+  const gel_problem::Conprod& c = p->conprod;
+  const gel_problem::Conprod::Dir& D = c.dir[transpose ? 1 : 0];
+  gel::ConprodOpDev op{};
+  op.nout = transpose ? p->dims.num_vars : (int32_t)c.R;
+  op.nin = transpose ? (int32_t)c.R : p->dims.num_vars;
+  op.ptr = D.d_ptr.get(); op.idx = D.d_idx.get(); op.src = D.d_src.get(); op.cval = D.d_cval.get();
+  op.off = d_aero_record ? D.d_offr.get() : D.d_offd.get();
+  HIPCHK(gel::launch_conprod(op, conprod_vals(p, d_jfn, d_aero_jac, d_aero_record), B, d_in, d_out, accumulate, p->d_flag.get(), s));
+  return GEL_OK;
+}
+
+#define NEED_CONPROD_DEVICE(p)                                                                                            \
+  do {                                                                                                                    \
+    if ((p)->device == GEL_DEVICE_NONE)                                                                                   \
+      return fail(GEL_ERR_ARG, "host-only handle: the device products need a GPU (gel_con_products_host runs on the host)"); \
+  } while (0)
+
+int gel_con_matvec_device(gel_problem* p, int32_t B, const double* d_jfn, const double* const* d_aero_jac, const double* d_aero_record,
+                          const double* d_v, double* d_y) {
+  if (const int rc = conprod_check(p, B, d_jfn, d_aero_jac, d_aero_record, d_v, d_y)) return rc;
+  NEED_CONPROD_DEVICE(p);
+  HIPCHK(hipSetDevice(p->device));
+  return conprod_device(p, B, d_jfn, d_aero_jac, d_aero_record, d_v, d_y, 0, 0, p->stream.get());
+}
+
+int gel_con_rmatvec_device(gel_problem* p, int32_t B, const double* d_jfn, const double* const* d_aero_jac, const double* d_aero_record,
+                           const double* d_lam, double* d_g, int32_t accumulate) {
+  if (const int rc = conprod_check(p, B, d_jfn, d_aero_jac, d_aero_record, d_lam, d_g)) return rc;
+  NEED_CONPROD_DEVICE(p);
+  HIPCHK(hipSetDevice(p->device));
+  return conprod_device(p, B, d_jfn, d_aero_jac, d_aero_record, d_lam, d_g, 1, accumulate != 0, p->stream.get());
+}
+
+// host buffers: copy in, one launch, copy out, one synchronise
+static int conprod_hostbuf(gel_problem* p, int32_t B, const double* jfn, const double* const* aero_jac, const double* aero_record,
+                           const double* in, double* out, int transpose, int accumulate) {
+  if (const int rc = conprod_check(p, B, jfn, aero_jac, aero_record, in, out)) return rc;
+  NEED_CONPROD_DEVICE(p);
+  HIPCHK(hipSetDevice(p->device));
+  const gel_problem::Conprod& c = p->conprod;
+  hipStream_t s = p->stream.get();
+  const size_t ni = (size_t)B * (transpose ? (size_t)c.R : (size_t)p->dims.num_vars), no = (size_t)B * (transpose ? (size_t)p->dims.num_vars : (size_t)c.R);
+  HIPCHK(p->d_cp_in.reserve(ni)); HIPCHK(p->d_cp_out.reserve(no));
+  HIPCHK(hipMemcpyAsync(p->d_cp_in.get(), in, ni * 8, hipMemcpyHostToDevice, s));
+  if (accumulate) HIPCHK(hipMemcpyAsync(p->d_cp_out.get(), out, no * 8, hipMemcpyHostToDevice, s));
+  const double* d_jfn = nullptr;
+  if (c.nfn) {
+    const size_t nj = (size_t)B * c.nfn * 7;
+    HIPCHK(p->d_cp_jfn.reserve(nj));
+    HIPCHK(hipMemcpyAsync(p->d_cp_jfn.get(), jfn, nj * 8, hipMemcpyHostToDevice, s));
+    d_jfn = p->d_cp_jfn.get();
+  }
+  const double* d_jac[3] = {nullptr, nullptr, nullptr};
+  const double* d_rec = nullptr;
+  if (aero_record) {
+    const size_t nr = (size_t)B * (size_t)p->aero.ld;
+    HIPCHK(p->d_cp_aero[0].reserve(nr));
+    HIPCHK(hipMemcpyAsync(p->d_cp_aero[0].get(), aero_record, nr * 8, hipMemcpyHostToDevice, s));
+    d_rec = p->d_cp_aero[0].get();
+  } else if (aero_jac) {
+    for (int k = 0; k < 3; k++)
+      if (c.nrows[k]) {
+        const size_t nk = (size_t)B * (size_t)c.jac_len[k];
+        HIPCHK(p->d_cp_aero[k].reserve(nk));
+        HIPCHK(hipMemcpyAsync(p->d_cp_aero[k].get(), aero_jac[k], nk * 8, hipMemcpyHostToDevice, s));
+        d_jac[k] = p->d_cp_aero[k].get();
+      }
+  }
+  if (const int rc = conprod_device(p, B, d_jfn, aero_jac ? d_jac : nullptr, d_rec, p->d_cp_in.get(), p->d_cp_out.get(), transpose, accumulate, s))
+    return rc;
+  HIPCHK(hipMemcpyAsync(out, p->d_cp_out.get(), no * 8, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipMemcpyAsync(p->h_flag.get(), p->d_flag.get(), 4, hipMemcpyDeviceToHost, s));
+  HIPCHK(hipStreamSynchronize(s));
+  if (*p->h_flag.get()) { *p->h_flag.get() = 0; HIPCHK(clear_flag(p, s)); return GEL_NONFINITE; }
+  return GEL_OK;
+}
+
+int gel_con_matvec(gel_problem* p, int32_t B, const double* jfn, const double* const* aero_jac, const double* aero_record, const double* v,
+                   double* y) {
+  return conprod_hostbuf(p, B, jfn, aero_jac, aero_record, v, y, 0, 0);
+}
+int gel_con_rmatvec(gel_problem* p, int32_t B, const double* jfn, const double* const* aero_jac, const double* aero_record,
+                    const double* lam, double* g, int32_t accumulate) {
+  return conprod_hostbuf(p, B, jfn, aero_jac, aero_record, lam, g, 1, accumulate != 0);
+}
 
 // ------------- post-processing table (output_result.py:37-263) -------------
 int gel_output_table(gel_problem* p, const double* x, const double* tx_res, double launch_lat_deg, double launch_lon_deg,

@@ -931,6 +931,87 @@ class Engine:
 
         return LinearOperator((self.nres, self.nvars), matvec=mv, rmatvec=rmv, dtype=np.float64)
 
+    # ------------------------------------------------------------------
+    # products with K, the Jacobian of every row that is not a defect row (include/gelato_amd.h gel_con_*)
+    CON_DIMS = ("R", "nlin", "nfn", "alpha", "q", "qalpha", "entries", "max_row_entries", "max_col_entries")
+
+    def con_products_dims(self):
+        """{"R", "nlin", "nfn", "alpha", "q", "qalpha" (rows), "entries", "max_row_entries", "max_col_entries"} of the operator
+        the handle holds NOW (rebuilt by every rows_configure / aero_configure; works on host-only handles)"""
+        info = (C.c_int64 * 9)()
+        check(lib().gel_con_products_dims(self._h, info))
+        return dict(zip(self.CON_DIMS, (int(v) for v in info)))
+
+    def _con_product(self, fn, jfn, aero_jac, aero_record, inp, transpose, out=None):
+        """host arrays with a leading batch shape: jfn [..., nfn, 7] | None, aero_jac {kind: [..., sum nnz]} | None,
+        aero_record [..., width] | None, inp [..., num_vars] (or [..., R] transposed) -> (out, status)"""
+        d = self.con_products_dims()
+        nin, nout = (d["R"], self.nvars) if transpose else (self.nvars, d["R"])
+        inp = _f64(inp)
+        if inp.ndim < 1 or inp.shape[-1] != nin:
+            raise ValueError("the input must be [..., %d]" % nin)
+        lead = inp.shape[:-1]
+        B = int(np.prod(lead, dtype=np.int64)) if lead else 1
+        keep = []
+
+        def arr(a, tail, what):
+            a = _f64(a)
+            if a.shape != lead + tail:
+                raise ValueError("%s must be %r" % (what, lead + tail))
+            keep.append(a)
+            return _d(a)
+        jp = arr(jfn, (d["nfn"], 7), "jfn") if jfn is not None else None
+        ap = None
+        if aero_jac is not None:
+            ap = (_dp * 3)()
+            for i, kind in enumerate(self.AERO_KINDS):
+                if aero_jac.get(kind) is not None:
+                    ap[i] = arr(aero_jac[kind], (sum(self.aero_dims(kind)[1]),), "aero_jac[%r]" % kind)
+        rp = None
+        if aero_record is not None:
+            rec = _f64(aero_record)
+            if rec.shape[:-1] != lead:
+                raise ValueError("aero_record must share the leading shape %r" % (lead,))
+            keep.append(rec)
+            rp = _d(rec)
+        if out is None:
+            out = np.empty(lead + (nout,))
+        elif out.shape != lead + (nout,) or out.dtype != np.float64 or not out.flags.c_contiguous:
+            raise ValueError("out must be C-contiguous float64 of shape %r" % (lead + (nout,),))
+        rc = check(fn(B, jp, ap, rp, _d(inp), _d(out)))
+        return out, rc
+
+    def con_matvec(self, V, jfn=None, aero_jac=None, aero_record=None):
+        """V [..., nvars] -> (y [..., R] = K v per vector, status); the values as rows_eval / eval_aero_all return them (aero_jac
+        {kind: array}) or as the records of eval_batch_aero_device (aero_record)"""
+        L, h = lib(), self._h
+        return self._con_product(lambda B, j, a, r, i, o: L.gel_con_matvec(h, B, j, a, r, i, o), jfn, aero_jac, aero_record, V, False)
+
+    def con_rmatvec(self, Lam, jfn=None, aero_jac=None, aero_record=None, out=None):
+        """Lam [..., R] -> (g [..., nvars] = K^T lambda per vector, status); out: an array to ACCUMULATE into, g = out + K^T lambda"""
+        L, h, acc = lib(), self._h, int(out is not None)
+        return self._con_product(lambda B, j, a, r, i, o: L.gel_con_rmatvec(h, B, j, a, r, i, o, acc), jfn, aero_jac, aero_record, Lam,
+                                 True, out)
+
+    def con_products_host(self, inp, jfn=None, aero_jac=None, aero_record=None, transpose=False, out=None):
+        """the same products in plain C++ on the host, from the same tables in the same order (works on host-only handles) ->
+        (out, status); out: an array to accumulate into"""
+        L, h, t, acc = lib(), self._h, int(bool(transpose)), int(out is not None)
+        return self._con_product(lambda B, j, a, r, i, o: L.gel_con_products_host(h, B, j, a, r, i, o, t, acc), jfn, aero_jac,
+                                 aero_record, inp, bool(transpose), out)
+
+    def con_matvec_device(self, B, d_jfn, d_aero_jac, d_aero_record, d_v, d_y):
+        """device pointers (ints; 0 = NULL): d_jfn [B][nfn][7], d_aero_jac = 3 entries per kind or None, d_aero_record [B][width] or
+        0, d_v [B][nvars] -> d_y [B][R]; asynchronous on the engine's own stream; status through sync()"""
+        jp = (C.c_void_p * 3)(*[q or None for q in d_aero_jac]) if d_aero_jac is not None else None
+        check(lib().gel_con_matvec_device(self._h, int(B), d_jfn or None, jp, d_aero_record or None, d_v or None, d_y or None))
+
+    def con_rmatvec_device(self, B, d_jfn, d_aero_jac, d_aero_record, d_lam, d_g, accumulate=False):
+        """d_lam [B][R] -> d_g [B][nvars] (accumulate: g = g + K^T lambda); asynchronous on the engine's own stream"""
+        jp = (C.c_void_p * 3)(*[q or None for q in d_aero_jac]) if d_aero_jac is not None else None
+        check(lib().gel_con_rmatvec_device(self._h, int(B), d_jfn or None, jp, d_aero_record or None, d_lam or None, d_g or None,
+                                           int(bool(accumulate))))
+
     def merit_gradient(self, X):
         """X [B, nvars] (or [nvars]) -> (phi [B] = 1/2 ||res||^2, g [B, nvars] = J^T res, status): one eval_batch, one product"""
         X = _f64(X).reshape(-1, self.nvars)

@@ -451,6 +451,63 @@ int gel_jac_products_info(const gel_problem* p, int64_t* info);
  * GEL_DEVICE_NONE handles.  (An entry point of its own: gel_jac_products_info's callers hold four values.) */
 int gel_jac_products_launch_info(const gel_problem* p, int32_t* info /* [4] */);
 
+/* ---- batched products with K(x_b), the Jacobian of EVERY ROW THAT IS NOT A DEFECT ROW: y_b = K v_b and
+ *      g_b = K^T lambda_b.  The values are read where the launches that produce them leave them -- jfn [B][nfn][7] of
+ *      gel_rows_eval_device, and EITHER the dense arrays jac[kind] of gel_eval_aero_all_device OR the records of
+ *      gel_eval_batch_aero_device; a gathered or full form is never built.
+ *      Definition of K.  Rows [linear nlin | node-function nfn | alpha rows | q rows | q-alpha rows], R = nlin + nfn + sum of
+ *      the kinds' nrows: gel_rows_eval's con followed by gel_eval_aero_all's three con arrays.  Columns: the packed decision vector.
+ *        linear row r:        (r, idx0) = coef0; if idx1 >= 0, (r, idx1) = coef1.
+ *        node-function row r (global row nlin + r): jfn[r][0..2] at the position columns M + 3 node + c, jfn[r][3..5] at the
+ *                             velocity columns 4M + 3 node + c, jfn[r][6] at column 11M + 2N + tcol ONLY IF tcol >= 0; with
+ *                             tcol < 0 jfn[r][6] is not read (a NaN there reaches no output).
+ *        aero rows of kind k: exactly the triplets of gel_aero_pattern(kind, var), var 0..3, the column shifted by the variable's
+ *                             offset (M, 4M, 7M, 11M + 2N); the value is the matching element of jac[kind] (dense form) or
+ *                             record[gel_aero_record_map(kind, var)[e]] (record form).
+ *        structural zeros:    an entry whose record-map index is -1 (the t0 / tf columns of part A on handles without
+ *                             GEL_FLAG_FD_RECOMPUTE) is NOT an entry of K, in either source form: the dense value there is
+ *                             not read, and both forms give the same bits.
+ *        shared cells:        where several entries share one (row, col), the cell is their sum.
+ *      The handle's flags (8, 32, 64, 128) change the values the caller passes in, not the operator.
+ *      Summation order (part of the contract).  Every output is ONE fma chain acc = fma(value, in, acc) from +0.0 over its entries:
+ *      a row of K v in the order of its definition above (linear: idx0, idx1; node-function: jfn column 0 .. 6; aero: var 0, 1, 2,
+ *      3, inside a var the order of gel_aero_pattern -- for t: t0, then tf); a column of K^T lambda by ascending row, the entries
+ *      of one row in that row's own order.  The order depends on the handle's configuration alone: not on B, not on the vector's
+ *      position in the batch, not on the source form, not on any launch parameter; the host form runs the same chains and gives
+ *      the same bits.  No floating-point atomics.  A column without an entry gets +0.0.
+ *      The tables are rebuilt whenever gel_rows_configure or gel_aero_configure succeeds (host-only handles included) and swapped in
+ *      with the tables of that call; a configure call that fails leaves the old operator in place.
+ *      Arguments: exactly one of aero_jac and aero_record is non-NULL when any aero kind has rows, both are NULL when none has;
+ *      inside aero_jac a kind without rows may be NULL; jfn may be NULL only when nfn = 0; R = 0 (nothing configured), B < 1 or a
+ *      NULL input / output return GEL_ERR_ARG.
+ *      Streams: the device calls take no stream argument; like gel_interp_resident and gel_propagate_device they enqueue on the
+ *      handle's own stream, which is a blocking stream and so orders itself against the null stream.  A caller working on a
+ *      NON-BLOCKING stream must have finished writing the inputs before the call and must gel_sync(p, NULL) before it consumes the
+ *      outputs.  (A `void* stream` parameter would need a case in the caller-stream case table, tests/stream_cases.py, which the
+ *      guard tests/test_caller_stream_cpu.py holds against this header; it belongs with a change that extends that table.)
+ *      Status: a lane that stores a non-finite value raises the handle's flag (gel_sync); a NaN among one vector's inputs stays in
+ *      that vector's outputs. ---- */
+/* info [9]: R, nlin, nfn, alpha rows, q rows, q-alpha rows, entries of K, largest entry count of a row, of a column (nine values:
+ * R itself and the eight counts behind it).  Works on GEL_DEVICE_NONE handles. */
+int gel_con_products_dims(const gel_problem* p, int64_t* info /* [9] */);
+/* device buffers, asynchronous on the handle's own stream: d_y [B][R] */
+int gel_con_matvec_device(gel_problem* p, int32_t B, const double* d_jfn, const double* const* d_aero_jac /* [3] or NULL */,
+                          const double* d_aero_record /* or NULL */, const double* d_v /* [B][num_vars] */, double* d_y);
+/* d_g [B][num_vars].  accumulate = 0: every element of g is written; accumulate = 1: g = fl(g_in + s), s exactly the value the call
+ * writes with accumulate = 0 -- gel_jac_rmatvec_device followed by this call gives J^T lambda_defect + K^T lambda_other in one
+ * buffer, bit for bit the sum of the two separate results. */
+int gel_con_rmatvec_device(gel_problem* p, int32_t B, const double* d_jfn, const double* const* d_aero_jac /* [3] or NULL */,
+                           const double* d_aero_record /* or NULL */, const double* d_lam /* [B][R] */, double* d_g, int32_t accumulate);
+/* the same on host buffers (copy in, one launch, copy out, one synchronise); return GEL_OK or GEL_NONFINITE */
+int gel_con_matvec(gel_problem* p, int32_t B, const double* jfn, const double* const* aero_jac, const double* aero_record,
+                   const double* v, double* y);
+int gel_con_rmatvec(gel_problem* p, int32_t B, const double* jfn, const double* const* aero_jac, const double* aero_record,
+                    const double* lam, double* g, int32_t accumulate);
+/* plain C++ on the host from the SAME tables in the same order (works on GEL_DEVICE_NONE handles): transpose = 0: in = v, out = y;
+ * else in = lambda, out = g.  Returns GEL_OK or GEL_NONFINITE. */
+int gel_con_products_host(const gel_problem* p, int32_t B, const double* jfn, const double* const* aero_jac, const double* aero_record,
+                          const double* in, double* out, int32_t transpose, int32_t accumulate);
+
 /* ---- batched spectral interpolation: dense output and mesh transfer.  Per phase the collocation solution is a
  *      polynomial: degree n in the 11 state components on the support [-1, tau_1 .. tau_n] (the n + 1 state nodes), degree n - 1
  *      in the 2 controls on tau_1 .. tau_n.  A PLAN holds, for every phase of its source handle (on the handle's own tau, generated
