@@ -324,7 +324,6 @@ struct gel_problem {
     DeviceArray<gel::AeroNodeDev> d_nodes, d_part_nodes[2];
     DeviceArray<gel::AeroPhaseDev> d_ph;
   } aero;
-  DeviceArray<double> d_aero_x, d_aero_out;                 // working set of large host-buffer calls
   // device buffers (static)
   DeviceArray<gel::PhaseDev> d_phases;
   DeviceArray<int32_t> d_node_phase;
@@ -353,6 +352,11 @@ struct gel_problem {
   DeviceArray<double> d_x, d_res, d_jv;
   PinnedArray<double> h_x, h_res, h_jv;
   PinnedArray<int32_t> h_flag;
+  // The working set of every synchronous host-buffer call of the handle and of the plans that refer to it (staged_call): those calls
+  // run on the handle's stream and return synchronised, so no two of them are in flight together and one pair serves them all.
+  // Both only grow and are kept until the handle is closed.
+  DeviceArray<double> d_arena;
+  PinnedArray<double> h_arena;
   // gel_jac_fd working set: kept between calls; the residuals of all num_vars + 1 perturbed vectors are
   // re-used while x stays the same (the four groups are asked for one after the other)
   DeviceArray<double> jfd_x, jfd_Xp, jfd_res, jfd_J;
@@ -373,9 +377,6 @@ struct gel_problem {
   std::vector<gel::FnRowDev> fn_rows;
   DeviceArray<gel::LinRowDev> d_lin_rows;
   DeviceArray<gel::FnRowDev> d_fn_rows;
-  PinnedArray<double> h_rows;                                 // pinned outputs of small gel_rows_eval calls: con | jfn
-  DeviceArray<double> d_rows_x, d_rows_out;                   // working set of large host-buffer calls
-  PinnedArray<double> h_aero;                                 // pinned outputs of small gel_eval_aero calls
   // collocation error estimate (gel_mesh_*): per phase the host block sigma | Lx | Lu | I (row-major) at mesh_hoff[i], the device
   // copy transposed (gel_mesh.h); none when a phase has more nodes than mesh_kernel's workgroup has lanes
   std::vector<double> mesh_host;
@@ -385,8 +386,6 @@ struct gel_problem {
   gel::MeshDev mesh_dev{};
   DeviceArray<double> d_mesh_mat;
   DeviceArray<gel::MeshPhaseDev> d_mesh_ph;
-  DeviceArray<double> d_mesh_x, d_mesh_out;                   // working set of large host-buffer calls
-  PinnedArray<double> h_mesh;                                 // pinned outputs of small gel_mesh_error calls: err | diff
   // Jacobian products from the compact values (gel_jac_*): the operator tables of gel_jprod.h, built from the
   // pattern walk (host-only handles included; the host product reads the same arrays), and their device copies
   std::vector<int32_t> jp_it;
@@ -400,7 +399,6 @@ struct gel_problem {
   DeviceArray<double> d_jp_dt;
   DeviceArray<gel::JprodPhaseDev> d_jp_ph;
   DeviceArray<double> d_jp_tpart;                             // [B][S][2] partial sums of the time columns of J^T lambda
-  DeviceArray<double> d_jp_jv, d_jp_in, d_jp_out;             // working set of the host-buffer calls
   // Products with K, the Jacobian of every row that is not a defect row (gel_con_*): the operator tables of
   // gel_conprod.h in both directions (0: by row, K v; 1: by column, K^T lambda), rebuilt as a whole by gel_rows_configure and
   // gel_aero_configure and swapped in with the tables they come from (host-only handles included; the host product reads the
@@ -417,7 +415,6 @@ struct gel_problem {
       DeviceArray<double> d_cval;
     } dir[2];
   } conprod;
-  DeviceArray<double> d_cp_jfn, d_cp_aero[3], d_cp_in, d_cp_out;   // working set of the host-buffer calls
   // large host batches (gel_eval_batch): two staging slots of kPipeEvals decision vectors each, every
   // slot with its own stream, so that PCIe in, kernel, PCIe out and the host copies of neighbouring
   // sub-batches overlap
@@ -775,11 +772,15 @@ hipError_t clear_flag(gel_problem* p, hipStream_t s) {
   return hipStreamSynchronize(s);
 }
 
-#define NEED_DEVICE(p)                                                                              \
-  do {                                                                                              \
-    if ((p)->device == GEL_DEVICE_NONE)                                                             \
-      return fail(GEL_ERR_HIP, "host-only handle: nothing can be evaluated without a GPU (no CPU fallback)"); \
+// A host-only handle is refused with the code and the text of the entry point's family.
+#define NEED_DEVICE(p, code, text)                                  \
+  do {                                                              \
+    if ((p)->device == GEL_DEVICE_NONE) return fail(code, text);    \
   } while (0)
+constexpr const char* kNoGpu = "host-only handle: nothing can be evaluated without a GPU (no CPU fallback)";
+constexpr const char* kNoGpuInterp = "host-only handle: the device interpolation needs a GPU (gel_interp_host runs on the host)";
+constexpr const char* kNoGpuJprod = "host-only handle: the device products need a GPU (gel_jac_products_host runs on the host)";
+constexpr const char* kNoGpuConprod = "host-only handle: the device products need a GPU (gel_con_products_host runs on the host)";
 
 // The defect groups of B vectors: one launch of the fused kernel; on a handle created with GEL_FLAG_EXACT_DEFECT_JAC, a call with
 // derivatives is the residual-only launch of the fused kernel (when residuals are asked for) followed by the exact-Jacobian kernel.
@@ -826,8 +827,85 @@ hipError_t launch_rows_kinds(const gel_problem* p, const gel::ProblemDev& dv, in
 // calls moving less than this are served zero-copy out of the pinned staging buffers (run_host)
 constexpr size_t kZeroCopyBytes = (size_t)1 << 20;
 
+// ---- One synchronous host-buffer call on the handle's own stream (staged_call): every gel_* entry point that takes host arrays,
+// runs a launch on them and returns synchronised, apart from the one-vector and pipelined evaluation paths (run_host*).
+// A buffer of the call in the caller's memory: read before the launch (src), written after it (dst), or both.  One that the caller
+// did not pass (NULL) takes no space and the launch sees nullptr; one of length 0 still has an address.
+struct StagedBuf { const void* src; void* dst; size_t bytes; };
+template <class T> StagedBuf staged_in(const T* h, size_t n) { return {h, nullptr, n * sizeof(T)}; }
+template <class T> StagedBuf staged_out(T* h, size_t n) { return {nullptr, h, n * sizeof(T)}; }
+template <class T> StagedBuf staged_inout(T* h, size_t n) { return {h, h, n * sizeof(T)}; }
+enum { kStagedZeroCopy = 1,    // a call moving at most kZeroCopyBytes is served out of pinned host memory: no copy engine, one wait
+       kStagedNoFlag = 2 };    // the non-finite flag is not read back
+constexpr int kStagedMaxBufs = 8;
+
+// Lays the buffers out in the handle's arena (each at a multiple of 256 bytes, hipMalloc's own alignment), brings the inputs in,
+// runs launch(dv, a) -- a[i] the address of buffer i, dv the handle's ProblemDev with the flag word of the branch; returns a gel
+// status -- on the handle's stream, brings the outputs out and waits.  Zero-copy branch: memcpy into the pinned arena, the kernel
+// reads and writes it in place and raises h_flag, memcpy out.  Copied branch: hipMemcpyAsync into the device arena, outputs and
+// d_flag back behind the launch.  GEL_NONFINITE resets the host word and, on the copied branch, the device's (clear_flag waits).
+// Once something is enqueued every return is behind a hipStreamSynchronize: after an error no copy that names a caller's array
+// is still pending.
+template <class Launch>
+int staged_call(gel_problem* p, int opts, std::initializer_list<StagedBuf> bufs, const Launch& launch) {
+  if (bufs.size() > (size_t)kStagedMaxBufs) return fail(GEL_ERR_ARG, "staged_call: too many buffers");
+  const StagedBuf* b = bufs.begin();
+  const int n = (int)bufs.size();
+  size_t off[kStagedMaxBufs], total = 0, moved = 0;
+  for (int i = 0; i < n; i++) {
+    off[i] = total;
+    if (!b[i].src && !b[i].dst) continue;
+    total += (std::max<size_t>(b[i].bytes, 1) + 255) / 256 * 256;
+    moved += b[i].bytes;
+  }
+  const bool zero_copy = (opts & kStagedZeroCopy) && moved <= kZeroCopyBytes, flag = !(opts & kStagedNoFlag);
+  hipStream_t s = p->stream.get();
+  char* base;
+  if (zero_copy) {
+    HIPCHK(p->h_arena.reserve(total / 8));
+    base = reinterpret_cast<char*>(p->h_arena.get());
+  } else {
+    if (p->d_arena.capacity() < total / 8) {
+      HIPCHK(hipStreamSynchronize(s));   // a resident call of a plan, enqueued on this stream, may still be running: the old block goes
+      HIPCHK(p->d_arena.reserve(total / 8));
+    }
+    base = reinterpret_cast<char*>(p->d_arena.get());
+  }
+  double* a[kStagedMaxBufs];
+  for (int i = 0; i < n; i++) a[i] = (b[i].src || b[i].dst) ? reinterpret_cast<double*>(base + off[i]) : nullptr;
+  gel::ProblemDev dv = p->dev;
+  if (zero_copy) dv.flag = p->h_flag.get();
+  const auto enqueue = [&]() -> int {
+    for (int i = 0; i < n; i++) {
+      if (!b[i].src || !b[i].bytes) continue;
+      if (zero_copy) std::memcpy(a[i], b[i].src, b[i].bytes);
+      else HIPCHK(hipMemcpyAsync(a[i], b[i].src, b[i].bytes, hipMemcpyHostToDevice, s));
+    }
+    if (const int rc = launch(dv, a)) return rc;
+    if (zero_copy) return GEL_OK;
+    for (int i = 0; i < n; i++)
+      if (b[i].dst && b[i].bytes) HIPCHK(hipMemcpyAsync(b[i].dst, a[i], b[i].bytes, hipMemcpyDeviceToHost, s));
+    if (flag) HIPCHK(hipMemcpyAsync(p->h_flag.get(), p->d_flag.get(), 4, hipMemcpyDeviceToHost, s));
+    return GEL_OK;
+  };
+  if (const int rc = enqueue()) {
+    (void)hipStreamSynchronize(s);   // the error of the step that failed is the one reported
+    return rc;
+  }
+  HIPCHK(hipStreamSynchronize(s));
+  if (zero_copy)
+    for (int i = 0; i < n; i++)
+      if (b[i].dst && b[i].bytes) std::memcpy(b[i].dst, a[i], b[i].bytes);
+  if (flag && *p->h_flag.get()) {
+    *p->h_flag.get() = 0;
+    if (!zero_copy) HIPCHK(clear_flag(p, s));
+    return GEL_NONFINITE;
+  }
+  return GEL_OK;
+}
+
 int ensure_capacity(gel_problem* p, int B) {
-  NEED_DEVICE(p);
+  NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
   if (B <= p->capB) return GEL_OK;
   HIPCHK(hipSetDevice(p->device));
   HIPCHK(drain(p));   // the old staging blocks go: nothing in flight may still use them
@@ -1001,7 +1079,7 @@ void par_copy(void* dst, const void* src, size_t bytes) {
 }
 
 int ensure_slots(gel_problem* p) {
-  NEED_DEVICE(p);
+  NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
   if (p->pipe_evals) return GEL_OK;
   HIPCHK(hipSetDevice(p->device));
   const size_t per_eval = 8 * (size_t)std::max<int64_t>(p->dims.num_var_entries, 1);
@@ -1608,7 +1686,7 @@ int gel_full_source(const gel_problem* p, int32_t* src) {
 
 int gel_pinned_buffers(gel_problem* p, double** res, double** vals_full, double** x0, double** x1) {
   if (!p) return fail(GEL_ERR_ARG, "null argument");
-  NEED_DEVICE(p);
+  NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
   if (int rc = ensure_full(p)) return rc;
   if (res) *res = p->cb_res.get();
   if (vals_full) *vals_full = p->h_full.get();
@@ -1632,7 +1710,7 @@ int gel_eval_jacobian(gel_problem* p, const double* x, double* vals_full, int32_
 
 int gel_eval(gel_problem* p, const double* x, double* res, double* vals_full, int32_t fill_constants) {
   if (!p || !x || !vals_full) return fail(GEL_ERR_ARG, "null argument");
-  NEED_DEVICE(p);
+  NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
   bool coo = coo_direct(p);
   if (coo) { if (int rc0 = ensure_full(p)) return rc0; }
   const bool own = res && p->cb_res.get() && res == p->cb_res.get();
@@ -1646,7 +1724,7 @@ int gel_eval(gel_problem* p, const double* x, double* res, double* vals_full, in
 
 int gel_eval_batch(gel_problem* p, int32_t B, const double* x, double* res, double* jvar) {
   if (!p || !x || B < 1 || (!res && !jvar)) return fail(GEL_ERR_ARG, "bad argument");
-  NEED_DEVICE(p);
+  NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
   // more than one staging slot's worth: sub-batches through the two-slot pipeline
   if ((size_t)B * 8 * (size_t)std::max<int64_t>(p->dims.num_var_entries, 1) > kPipeBytes) return run_host_pipelined(p, B, x, res, jvar);
   const int rc = run_host(p, B, x, res != nullptr, jvar != nullptr);
@@ -1658,7 +1736,7 @@ int gel_eval_batch(gel_problem* p, int32_t B, const double* x, double* res, doub
 
 int gel_eval_batch_device(gel_problem* p, int32_t B, const double* d_x, double* d_res, double* d_jvar, void* stream) {
   if (!p || !d_x || B < 1 || (!d_res && !d_jvar)) return fail(GEL_ERR_ARG, "bad argument");
-  NEED_DEVICE(p);
+  NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
   HIPCHK(launch_defects(p, p->dev, B, d_x, d_res, d_jvar, stream_of(p, stream)));
   return GEL_OK;
 }
@@ -1667,7 +1745,7 @@ int gel_eval_shard_units_device(gel_problem* p, int32_t B, const double* d_x, do
                                 int32_t unit_begin, int32_t unit_count, void* stream) {
   if (!p || !d_x || B < 1 || !d_jvar) return fail(GEL_ERR_ARG, "bad argument (the unit form always writes Jacobian values)");
   NO_EXACT(p, "gel_eval_shard_units_device");
-  NEED_DEVICE(p);
+  NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
   const int32_t total = 4 * (int32_t)p->chunk_phase.size();
   if (unit_begin < 0 || unit_count < 0 || unit_begin + unit_count > total)
     return fail(GEL_ERR_ARG, "unit range out of bounds");
@@ -1695,7 +1773,7 @@ int gel_chunk_phase(const gel_problem* p, int32_t* phase) {
 
 int gel_launch_info(const gel_problem* p, int32_t B, int32_t want_res, int32_t want_jac, int32_t* info) {
   if (!p || !info || B < 1) return fail(GEL_ERR_ARG, "bad argument");
-  NEED_DEVICE(p);
+  NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
   const gel::EvalForm f = gel::eval_form(p->dev, B, want_res != 0, want_jac != 0);
   info[0] = f.jac; info[1] = f.mfma; info[2] = f.split; info[3] = (int32_t)std::min<long long>(f.waves, INT32_MAX);
   info[4] = f.pack;
@@ -1822,7 +1900,7 @@ int gel_eval_shard_packed_device(gel_problem* p, int32_t B, const double* d_x, d
                                  int64_t width_expected, void* stream) {
   if (!p || !d_x || !d_out || B < 1) return fail(GEL_ERR_ARG, "bad argument");
   NO_EXACT(p, "gel_eval_shard_packed_device");
-  NEED_DEVICE(p);
+  NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
   if (int rc = check_plan(p, nranks_expected, width_expected)) return rc;
   if (!p->d_unit_base.get()) return fail(GEL_ERR_ARG, "gel_shard_plan has not been called on this handle");
   const int nranks = (int)p->shard_begin.size() - 1;
@@ -1844,7 +1922,7 @@ int gel_eval_shard_packed_device(gel_problem* p, int32_t B, const double* d_x, d
 int gel_shard_unpack_device(gel_problem* p, int32_t B, const double* d_out, double* d_res, double* d_jvar, int32_t nranks_expected,
                             int64_t width_expected, void* stream) {
   if (!p || !d_out || B < 1 || (!d_res && !d_jvar)) return fail(GEL_ERR_ARG, "bad argument");
-  NEED_DEVICE(p);
+  NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
   if (int rc = check_plan(p, nranks_expected, width_expected)) return rc;
   if (!p->d_shard_pos.get()) return fail(GEL_ERR_ARG, "gel_shard_plan has not been called on this handle");
   HIPCHK(gel::launch_shard_unpack(11 * p->dims.N, p->dims.num_var_entries, p->shard_width, B, p->d_shard_pos.get(), d_out, d_res, d_jvar,
@@ -1854,14 +1932,14 @@ int gel_shard_unpack_device(gel_problem* p, int32_t B, const double* d_out, doub
 
 int gel_fill_full_device(gel_problem* p, int32_t B, double* d_jfull, void* stream) {
   if (!p || !d_jfull || B < 1) return fail(GEL_ERR_ARG, "bad argument");
-  NEED_DEVICE(p);
+  NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
   HIPCHK(gel::launch_fill_full(p->dims.total_nnz, B, p->d_cval.get(), d_jfull, stream_of(p, stream)));
   return GEL_OK;
 }
 
 int gel_update_full_device(gel_problem* p, int32_t B, const double* d_jvar, double* d_jfull, void* stream) {
   if (!p || !d_jvar || !d_jfull || B < 1) return fail(GEL_ERR_ARG, "bad argument");
-  NEED_DEVICE(p);
+  NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
   HIPCHK(gel::launch_update_full(p->dims.total_nnz, p->dims.num_var_entries, p->nvar_entries, B, p->d_vdst.get(), p->d_vsrc.get(),
                                  p->nvar_lines, p->d_vline.get(), p->d_src.get(), p->d_cval.get(), d_jvar, d_jfull,
                                  stream_of(p, stream)));
@@ -1870,7 +1948,7 @@ int gel_update_full_device(gel_problem* p, int32_t B, const double* d_jvar, doub
 
 int gel_eval_full_device(gel_problem* p, int32_t B, const double* d_x, double* d_res, double* d_jvar, double* d_jfull, void* stream) {
   if (!p || !d_x || !d_jvar || !d_jfull || B < 1) return fail(GEL_ERR_ARG, "bad argument");
-  NEED_DEVICE(p);
+  NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
   hipStream_t s = stream_of(p, stream);
   gel::ProblemDev dv = p->dev;
   dv.cached_out = 1;   // the compact values are read again by the update below: kept in the caches when the launch fits them
@@ -1882,7 +1960,7 @@ int gel_eval_full_device(gel_problem* p, int32_t B, const double* d_x, double* d
 
 int gel_expand_full_device(gel_problem* p, int32_t B, const double* d_jvar, double* d_jfull, void* stream) {
   if (!p || !d_jvar || !d_jfull || B < 1) return fail(GEL_ERR_ARG, "bad argument");
-  NEED_DEVICE(p);
+  NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
   HIPCHK(gel::launch_expand(p->dims.total_nnz, p->dims.num_var_entries, B, p->d_cval.get(), p->d_src.get(), d_jvar, d_jfull,
                             stream_of(p, stream)));
   return GEL_OK;
@@ -1890,7 +1968,7 @@ int gel_expand_full_device(gel_problem* p, int32_t B, const double* d_jvar, doub
 
 int gel_sync(gel_problem* p, void* stream) {
   if (!p) return fail(GEL_ERR_ARG, "null argument");
-  NEED_DEVICE(p);
+  NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
   hipStream_t s = stream_of(p, stream);
   HIPCHK(hipMemcpyAsync(p->h_flag.get(), p->d_flag.get(), 4, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
@@ -1971,7 +2049,7 @@ static size_t jfd_block_doubles(const gel_problem* p, int group) {
 
 static int jfd_host(gel_problem* p, int32_t group, const double* x, double* J, int blocks) {
   if (!p || !x || !J || group < 0 || group >= GEL_NUM_GROUPS) return fail(GEL_ERR_ARG, "bad argument");
-  NEED_DEVICE(p);
+  NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
   HIPCHK(hipSetDevice(p->device));
   int rc = ensure_slots(p);  // the two pinned staging slots also carry J back to the caller
   if (rc) return rc;
@@ -2042,7 +2120,7 @@ int gel_jac_fd_block_cols(const gel_problem* p, int32_t phase, int32_t* cols) {
 
 int gel_jac_fd_device(gel_problem* p, int32_t group, const double* d_x, double* d_J, int32_t blocks, void* stream) {
   if (!p || !d_x || !d_J || group < 0 || group >= GEL_NUM_GROUPS) return fail(GEL_ERR_ARG, "bad argument");
-  NEED_DEVICE(p);
+  NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
   HIPCHK(hipSetDevice(p->device));
   int rc = jfd_allocate(p);
   if (rc) return rc;
@@ -2394,7 +2472,7 @@ int gel_eval_batch_aero_device(gel_problem* p, int32_t B, const double* d_x, dou
   if (!p || !d_x || B < 1 || !d_res || !d_jvar || !d_aero) return fail(GEL_ERR_ARG, "bad argument");
   if (p->exact && !p->exact_aero)   // the exact defect Jacobian has no fused form with the FORWARD-DIFFERENCE aero rows
     return fail(GEL_ERR_ARG, "gel_eval_batch_aero_device has no exact-Jacobian form (handle created with GEL_FLAG_EXACT_DEFECT_JAC)");
-  NEED_DEVICE(p);
+  NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
   if (p->aero.nodes.empty()) return fail(GEL_ERR_ARG, "no aero path constraints configured (gel_aero_configure)");
   hipStream_t s = stream_of(p, stream);
   gel::AeroLaunchOut out[2];
@@ -2456,7 +2534,7 @@ size_t aero_jac_len(const gel_problem* p, int kind) { return p->aero.rows[kind].
 int gel_eval_aero_all_device(gel_problem* p, int32_t B, const double* d_x, double* const* d_con, double* const* d_jac,
                              void* stream) {
   if (!p || B < 1 || !d_x || !d_con) return fail(GEL_ERR_ARG, "bad argument");
-  NEED_DEVICE(p);
+  NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
   gel::AeroLaunchOut out;
   for (int k = 0; k < 3; k++) {
     out.nrows[k] = (int32_t)p->aero.rows[k].size();
@@ -2469,61 +2547,26 @@ int gel_eval_aero_all_device(gel_problem* p, int32_t B, const double* d_x, doubl
 
 int gel_eval_aero_all(gel_problem* p, int32_t B, const double* x, double* const* con, double* const* jac) {
   if (!p || B < 1 || !x || !con) return fail(GEL_ERR_ARG, "bad argument");
-  NEED_DEVICE(p);
+  NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
   if (p->aero.nodes.empty()) return GEL_OK;
   HIPCHK(hipSetDevice(p->device));
-  // one contiguous output area: con[0] | jac[0] | con[1] | jac[1] | con[2] | jac[2] (only what was asked for)
-  size_t off_c[3], off_j[3], total = 0;
-  for (int k = 0; k < 3; k++) {
-    const size_t R = p->aero.rows[k].size();
-    off_c[k] = total; total += (con[k] && R) ? (size_t)B * R : 0;
-    off_j[k] = total; total += (con[k] && R && jac && jac[k]) ? (size_t)B * aero_jac_len(p, k) : 0;
-  }
-  if (total == 0) return GEL_OK;
-  const size_t nx = (size_t)B * p->dims.num_vars;
-  const bool zero_copy = (nx + total) * 8 <= kZeroCopyBytes;
-  int rc;
-  double* base;
-  if (zero_copy) {
-    // the optimiser's callback: x and every output in pinned host memory, one launch + one synchronise
-    if ((rc = ensure_capacity(p, B))) return rc;
-    HIPCHK(p->h_aero.reserve(total));
-    std::memcpy(p->h_x.get(), x, nx * 8);
-    base = p->h_aero.get();
-  } else {
-    HIPCHK(p->d_aero_x.reserve(nx)); HIPCHK(p->d_aero_out.reserve(total));
-    HIPCHK(hipMemcpyAsync(p->d_aero_x.get(), x, nx * 8, hipMemcpyHostToDevice, p->stream.get()));
-    base = p->d_aero_out.get();
-  }
+  // x and one output area: con[0] | jac[0] | con[1] | jac[1] | con[2] | jac[2] (only what was asked for; small calls are the
+  // optimiser's callback)
   gel::AeroLaunchOut out;
+  StagedBuf oc[3], oj[3];
   for (int k = 0; k < 3; k++) {
     const size_t R = p->aero.rows[k].size();
     out.nrows[k] = (int32_t)R;
-    out.con[k] = (con[k] && R) ? base + off_c[k] : nullptr;
-    out.jac[k] = (out.con[k] && jac && jac[k]) ? base + off_j[k] : nullptr;
+    oc[k] = staged_out(R ? con[k] : nullptr, (size_t)B * R);
+    oj[k] = staged_out((oc[k].dst && jac) ? jac[k] : nullptr, (size_t)B * aero_jac_len(p, k));
   }
-  gel::ProblemDev dv = p->dev;
-  if (zero_copy) dv.flag = p->h_flag.get();
-  HIPCHK(launch_aero_kinds(p, dv, (int)p->aero.nodes.size(), p->aero.d_nodes.get(), B, zero_copy ? p->h_x.get() : p->d_aero_x.get(), out, p->stream.get()));
-  if (!zero_copy) {
-    for (int k = 0; k < 3; k++) {
-      if (out.con[k]) HIPCHK(hipMemcpyAsync(con[k], out.con[k], (size_t)B * p->aero.rows[k].size() * 8, hipMemcpyDeviceToHost, p->stream.get()));
-      if (out.jac[k]) HIPCHK(hipMemcpyAsync(jac[k], out.jac[k], (size_t)B * aero_jac_len(p, k) * 8, hipMemcpyDeviceToHost, p->stream.get()));
-    }
-    HIPCHK(hipMemcpyAsync(p->h_flag.get(), p->d_flag.get(), 4, hipMemcpyDeviceToHost, p->stream.get()));
-  }
-  HIPCHK(hipStreamSynchronize(p->stream.get()));
-  if (zero_copy)
-    for (int k = 0; k < 3; k++) {
-      if (out.con[k]) std::memcpy(con[k], out.con[k], (size_t)B * p->aero.rows[k].size() * 8);
-      if (out.jac[k]) std::memcpy(jac[k], out.jac[k], (size_t)B * aero_jac_len(p, k) * 8);
-    }
-  if (*p->h_flag.get()) {
-    *p->h_flag.get() = 0;
-    if (!zero_copy) HIPCHK(clear_flag(p, p->stream.get()));
-    return GEL_NONFINITE;
-  }
-  return GEL_OK;
+  if (!oc[0].dst && !oc[1].dst && !oc[2].dst) return GEL_OK;
+  return staged_call(p, kStagedZeroCopy, {staged_in(x, (size_t)B * p->dims.num_vars), oc[0], oj[0], oc[1], oj[1], oc[2], oj[2]},
+                     [&](const gel::ProblemDev& dv, double* const* a) -> int {
+                       for (int k = 0; k < 3; k++) { out.con[k] = a[1 + 2 * k]; out.jac[k] = a[2 + 2 * k]; }
+                       HIPCHK(launch_aero_kinds(p, dv, (int)p->aero.nodes.size(), p->aero.d_nodes.get(), B, a[0], out, p->stream.get()));
+                       return GEL_OK;
+                     });
 }
 
 int gel_eval_aero(gel_problem* p, int32_t kind, int32_t B, const double* x, double* con, double* jac_vals) {
@@ -2577,7 +2620,7 @@ int gel_rows_dims(const gel_problem* p, int32_t* nlin, int32_t* nfn) {
 
 int gel_rows_eval_device(gel_problem* p, int32_t B, const double* d_x, double* d_con, double* d_jfn, void* stream) {
   if (!p || B < 1 || !d_x || !d_con) return fail(GEL_ERR_ARG, "bad argument");
-  NEED_DEVICE(p);
+  NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
   HIPCHK(launch_rows_kinds(p, p->dev, B, d_x, d_con, d_jfn, stream_of(p, stream)));
   return GEL_OK;
 }
@@ -2585,36 +2628,16 @@ int gel_rows_eval_device(gel_problem* p, int32_t B, const double* d_x, double* d
 
 int gel_rows_eval(gel_problem* p, int32_t B, const double* x, double* con, double* jfn) {
   if (!p || B < 1 || !x || !con) return fail(GEL_ERR_ARG, "bad argument");
-  NEED_DEVICE(p);
+  NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
   const size_t R = p->lin_rows.size() + p->fn_rows.size(), nf = p->fn_rows.size();
   if (R == 0) return GEL_OK;
   HIPCHK(hipSetDevice(p->device));
-  const size_t nx = (size_t)B * p->dims.num_vars, nc = (size_t)B * R, nj = jfn ? (size_t)B * nf * 7 : 0;
-  int rc;
-  if ((nx + nc + nj) * 8 <= kZeroCopyBytes) {
-    // the optimiser's callback: the kernel reads x from and writes to pinned host memory, one launch + one synchronise
-    if ((rc = ensure_capacity(p, B))) return rc;
-    HIPCHK(p->h_rows.reserve(nc + nj + 1));
-    std::memcpy(p->h_x.get(), x, nx * 8);
-    gel::ProblemDev dv = p->dev;
-    dv.flag = p->h_flag.get();
-    HIPCHK(launch_rows_kinds(p, dv, B, p->h_x.get(), p->h_rows.get(), jfn ? p->h_rows.get() + nc : nullptr, p->stream.get()));
-    HIPCHK(hipStreamSynchronize(p->stream.get()));
-    std::memcpy(con, p->h_rows.get(), nc * 8);
-    if (jfn) std::memcpy(jfn, p->h_rows.get() + nc, nj * 8);
-    if (*p->h_flag.get()) { *p->h_flag.get() = 0; return GEL_NONFINITE; }
-    return GEL_OK;
-  }
-  HIPCHK(p->d_rows_x.reserve(nx)); HIPCHK(p->d_rows_out.reserve(nc + nj + 1));
-  HIPCHK(hipMemcpyAsync(p->d_rows_x.get(), x, nx * 8, hipMemcpyHostToDevice, p->stream.get()));
-  HIPCHK(launch_rows_kinds(p, p->dev, B, p->d_rows_x.get(), p->d_rows_out.get(), jfn ? p->d_rows_out.get() + nc : nullptr,
-                           p->stream.get()));
-  HIPCHK(hipMemcpyAsync(con, p->d_rows_out.get(), nc * 8, hipMemcpyDeviceToHost, p->stream.get()));
-  if (jfn) HIPCHK(hipMemcpyAsync(jfn, p->d_rows_out.get() + nc, nj * 8, hipMemcpyDeviceToHost, p->stream.get()));
-  HIPCHK(hipMemcpyAsync(p->h_flag.get(), p->d_flag.get(), 4, hipMemcpyDeviceToHost, p->stream.get()));
-  HIPCHK(hipStreamSynchronize(p->stream.get()));
-  if (*p->h_flag.get()) { *p->h_flag.get() = 0; HIPCHK(clear_flag(p, p->stream.get())); return GEL_NONFINITE; }
-  return GEL_OK;
+  // small calls are the optimiser's callback
+  return staged_call(p, kStagedZeroCopy, {staged_in(x, (size_t)B * p->dims.num_vars), staged_out(con, (size_t)B * R), staged_out(jfn, (size_t)B * nf * 7)},
+                     [&](const gel::ProblemDev& dv, double* const* a) -> int {
+                       HIPCHK(launch_rows_kinds(p, dv, B, a[0], a[1], a[2], p->stream.get()));
+                       return GEL_OK;
+                     });
 }
 
 // ------------- collocation error estimate per section -------------
@@ -2644,7 +2667,7 @@ int gel_mesh_matrices(const gel_problem* p, int32_t phase, double* sigma, double
 
 int gel_mesh_error_device(gel_problem* p, int32_t B, const double* d_x, double* d_err, double* d_diff, void* stream) {
   if (!p || B < 1 || !d_x || !d_err) return fail(GEL_ERR_ARG, "bad argument");
-  NEED_DEVICE(p);
+  NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
   NEED_MESH(p);
   HIPCHK(gel::launch_mesh(p->dev, p->mesh_dev, p->mesh_ph.data(), B, d_x, d_err, d_diff, stream_of(p, stream)));
   return GEL_OK;
@@ -2652,43 +2675,22 @@ int gel_mesh_error_device(gel_problem* p, int32_t B, const double* d_x, double* 
 
 int gel_mesh_error(gel_problem* p, int32_t B, const double* x, double* err, double* diff) {
   if (!p || B < 1 || !x || !err) return fail(GEL_ERR_ARG, "bad argument");
-  NEED_DEVICE(p);
+  NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
   NEED_MESH(p);
   HIPCHK(hipSetDevice(p->device));
-  const size_t nx = (size_t)B * p->dims.num_vars, ne = (size_t)B * p->dims.S * 4, nd = diff ? (size_t)B * p->mesh_npts * 11 : 0;
-  hipStream_t s = p->stream.get();
-  int rc;
-  if ((nx + ne + nd) * 8 <= kZeroCopyBytes) {
-    // a few vectors (after a solve): the kernel reads x from and writes to pinned host memory, one launch + one synchronise
-    if ((rc = ensure_capacity(p, B))) return rc;
-    HIPCHK(p->h_mesh.reserve(ne + nd));
-    std::memcpy(p->h_x.get(), x, nx * 8);
-    gel::ProblemDev dv = p->dev;
-    dv.flag = p->h_flag.get();
-    HIPCHK(gel::launch_mesh(dv, p->mesh_dev, p->mesh_ph.data(), B, p->h_x.get(), p->h_mesh.get(), diff ? p->h_mesh.get() + ne : nullptr, s));
-    HIPCHK(hipStreamSynchronize(s));
-    std::memcpy(err, p->h_mesh.get(), ne * 8);
-    if (diff) std::memcpy(diff, p->h_mesh.get() + ne, nd * 8);
-    if (*p->h_flag.get()) { *p->h_flag.get() = 0; return GEL_NONFINITE; }
-    return GEL_OK;
-  }
-  HIPCHK(p->d_mesh_x.reserve(nx)); HIPCHK(p->d_mesh_out.reserve(ne + nd));
-  HIPCHK(hipMemcpyAsync(p->d_mesh_x.get(), x, nx * 8, hipMemcpyHostToDevice, s));
-  HIPCHK(gel::launch_mesh(p->dev, p->mesh_dev, p->mesh_ph.data(), B, p->d_mesh_x.get(), p->d_mesh_out.get(),
-                          diff ? p->d_mesh_out.get() + ne : nullptr, s));
-  HIPCHK(hipMemcpyAsync(err, p->d_mesh_out.get(), ne * 8, hipMemcpyDeviceToHost, s));
-  if (diff) HIPCHK(hipMemcpyAsync(diff, p->d_mesh_out.get() + ne, nd * 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(p->h_flag.get(), p->d_flag.get(), 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  if (*p->h_flag.get()) { *p->h_flag.get() = 0; HIPCHK(clear_flag(p, s)); return GEL_NONFINITE; }
-  return GEL_OK;
+  return staged_call(p, kStagedZeroCopy,
+                     {staged_in(x, (size_t)B * p->dims.num_vars), staged_out(err, (size_t)B * p->dims.S * 4), staged_out(diff, (size_t)B * p->mesh_npts * 11)},
+                     [&](const gel::ProblemDev& dv, double* const* a) -> int {
+                       HIPCHK(gel::launch_mesh(dv, p->mesh_dev, p->mesh_ph.data(), B, a[0], a[1], a[2], p->stream.get()));
+                       return GEL_OK;
+                     });
 }
 
 // ------------- batched spectral interpolation: dense output and mesh transfer -------------
 // A plan = the matrices of every phase of the source handle at the plan's points, built here in extended precision from the
 // handle's own tau with the barycentric machinery of the mesh estimate, rounded once; row-major on the host (gel_interp_matrices,
-// gel_interp_host), transposed on the device (gel_interp.h).  It owns its device memory and refers to the source handle for the
-// device, the stream and the non-finite flag: it is destroyed before that handle.
+// gel_interp_host), transposed on the device (gel_interp.h).  It owns its tables and refers to the source handle for the device,
+// the stream, the non-finite flag and the arena of the host-buffer form (staged_call): it is destroyed before that handle.
 struct gel_interp_plan {
   gel_problem* src = nullptr;
   gel::InterpDev dev{};
@@ -2702,7 +2704,6 @@ struct gel_interp_plan {
   DeviceArray<double> d_mat;
   DeviceArray<int32_t> d_cp;
   DeviceArray<gel::InterpPhaseDev> d_ph;
-  DeviceArray<double> d_x, d_out; // working set of the host-buffer form
 };
 
 // Vectors per workgroup of an interpolation launch (what gel_interp_plan_info reports): the most whose staged slice fits, or
@@ -2934,8 +2935,7 @@ int gel_interp_host(const gel_interp_plan* plan, int32_t B, const double* x, dou
 int gel_interp_resident(gel_interp_plan* plan, int32_t B, const double* d_x, double* d_out) {
   if (!plan || B < 0 || (B > 0 && (!d_x || !d_out))) return fail(GEL_ERR_ARG, "bad argument");
   gel_problem* p = plan->src;
-  if (p->device == GEL_DEVICE_NONE)
-    return fail(GEL_ERR_ARG, "host-only handle: the device interpolation needs a GPU (gel_interp_host runs on the host)");
+  NEED_DEVICE(p, GEL_ERR_ARG, kNoGpuInterp);
   HIPCHK(hipSetDevice(p->device));
   HIPCHK(gel::launch_interp(plan->dev, plan->ph.data(), plan->n_max, B, d_x, d_out, p->d_flag.get(), interp_vb(plan), p->stream.get()));
   return GEL_OK;
@@ -2944,30 +2944,22 @@ int gel_interp_resident(gel_interp_plan* plan, int32_t B, const double* d_x, dou
 int gel_interp(gel_interp_plan* plan, int32_t B, const double* x, double* out) {
   if (!plan || B < 0 || (B > 0 && (!x || !out))) return fail(GEL_ERR_ARG, "bad argument");
   gel_problem* p = plan->src;
-  if (p->device == GEL_DEVICE_NONE)
-    return fail(GEL_ERR_ARG, "host-only handle: the device interpolation needs a GPU (gel_interp_host runs on the host)");
+  NEED_DEVICE(p, GEL_ERR_ARG, kNoGpuInterp);
   if (B == 0 || plan->dev.ostride == 0) return GEL_OK;
   HIPCHK(hipSetDevice(p->device));
-  const size_t nx = (size_t)B * plan->dev.nvars, no = (size_t)B * plan->dev.ostride;
-  hipStream_t s = p->stream.get();
-  if (plan->d_x.capacity() < nx || plan->d_out.capacity() < no) HIPCHK(hipStreamSynchronize(s));
-  HIPCHK(plan->d_x.reserve(nx)); HIPCHK(plan->d_out.reserve(no));
-  HIPCHK(hipMemcpyAsync(plan->d_x.get(), x, nx * 8, hipMemcpyHostToDevice, s));
-  HIPCHK(gel::launch_interp(plan->dev, plan->ph.data(), plan->n_max, B, plan->d_x.get(), plan->d_out.get(), p->d_flag.get(),
-                            interp_vb(plan), s));
-  HIPCHK(hipMemcpyAsync(out, plan->d_out.get(), no * 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(p->h_flag.get(), p->d_flag.get(), 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  if (*p->h_flag.get()) { *p->h_flag.get() = 0; HIPCHK(clear_flag(p, s)); return GEL_NONFINITE; }
-  return GEL_OK;
+  return staged_call(p, 0, {staged_in(x, (size_t)B * plan->dev.nvars), staged_out(out, (size_t)B * plan->dev.ostride)},
+                     [&](const gel::ProblemDev&, double* const* a) -> int {
+                       HIPCHK(gel::launch_interp(plan->dev, plan->ph.data(), plan->n_max, B, a[0], a[1], p->d_flag.get(), interp_vb(plan),
+                                                 p->stream.get()));
+                       return GEL_OK;
+                     });
 }
 
 // ------------- batched explicit propagation of the sections with RK4: the shooting check -------------
 // A plan = per phase the stage points, the step of every node interval and the matrix that samples the control polynomial at the
 // stage points (the interpolation plan's builder: the same bits), row-major on the host (gel_prop_matrices), transposed on the
-// device (gel_prop.h).  It owns its device memory -- the tables, the control samples' workspace and the working set of the
-// host-buffer form -- and refers to the source handle for the device, the stream and the non-finite flag: it is destroyed before
-// that handle.
+// device (gel_prop.h).  It owns its tables and the control samples' workspace and refers to the source handle for the device,
+// the stream, the non-finite flag and the arena of the host-buffer form (staged_call): it is destroyed before that handle.
 struct gel_prop_plan {
   gel_problem* src = nullptr;
   int32_t flags = 0;
@@ -2983,7 +2975,6 @@ struct gel_prop_plan {
   DeviceArray<double> d_mat, d_ws;
   DeviceArray<int32_t> d_cp, d_seg;
   DeviceArray<gel::PropPhaseDev> d_ph;
-  DeviceArray<double> d_x, d_y, d_err;   // working set of the host-buffer form
 };
 
 static constexpr int64_t kPropWsBytes = 1LL << 30;       // the control samples' workspace never exceeds this
@@ -3142,7 +3133,7 @@ static int prop_enqueue(gel_prop_plan* plan, int32_t B, const double* d_x, doubl
 int gel_propagate_device(gel_prop_plan* plan, int32_t B, const double* d_x, double* d_y, double* d_err) {
   if (!plan || B < 0 || (B > 0 && (!d_x || !d_y))) return fail(GEL_ERR_ARG, "bad argument");
   gel_problem* p = plan->src;
-  NEED_DEVICE(p);
+  NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
   if (B == 0) return GEL_OK;
   HIPCHK(hipSetDevice(p->device));
   return prop_enqueue(plan, B, d_x, d_y, d_err, p->stream.get());
@@ -3151,21 +3142,11 @@ int gel_propagate_device(gel_prop_plan* plan, int32_t B, const double* d_x, doub
 int gel_propagate(gel_prop_plan* plan, int32_t B, const double* x, double* y, double* err) {
   if (!plan || B < 0 || (B > 0 && (!x || !y))) return fail(GEL_ERR_ARG, "bad argument");
   gel_problem* p = plan->src;
-  NEED_DEVICE(p);
+  NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
   if (B == 0) return GEL_OK;
   HIPCHK(hipSetDevice(p->device));
-  const size_t nx = (size_t)B * p->dims.num_vars, ny = (size_t)B * 11 * p->dims.M, ne = err ? (size_t)B * p->dims.S * 4 : 0;
-  hipStream_t s = p->stream.get();
-  if (plan->d_x.capacity() < nx || plan->d_y.capacity() < ny || plan->d_err.capacity() < ne) HIPCHK(hipStreamSynchronize(s));
-  HIPCHK(plan->d_x.reserve(nx)); HIPCHK(plan->d_y.reserve(ny)); HIPCHK(plan->d_err.reserve(ne));
-  HIPCHK(hipMemcpyAsync(plan->d_x.get(), x, nx * 8, hipMemcpyHostToDevice, s));
-  if (const int rc = prop_enqueue(plan, B, plan->d_x.get(), plan->d_y.get(), err ? plan->d_err.get() : nullptr, s)) return rc;
-  HIPCHK(hipMemcpyAsync(y, plan->d_y.get(), ny * 8, hipMemcpyDeviceToHost, s));
-  if (err) HIPCHK(hipMemcpyAsync(err, plan->d_err.get(), ne * 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(p->h_flag.get(), p->d_flag.get(), 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  if (*p->h_flag.get()) { *p->h_flag.get() = 0; HIPCHK(clear_flag(p, s)); return GEL_NONFINITE; }
-  return GEL_OK;
+  return staged_call(p, 0, {staged_in(x, (size_t)B * p->dims.num_vars), staged_out(y, (size_t)B * 11 * p->dims.M), staged_out(err, (size_t)B * p->dims.S * 4)},
+                     [&](const gel::ProblemDev&, double* const* a) { return prop_enqueue(plan, B, a[0], a[1], a[2], p->stream.get()); });
 }
 
 // ------------- Jacobian products from the compact values -------------
@@ -3173,12 +3154,6 @@ int gel_propagate(gel_prop_plan* plan, int32_t B, const double* x, double* y, do
   do {                                                                                                                    \
     if (!gel::jprod_vectors_per_group((p)->jp_nin_max[(t) ? 1 : 0], (t) != 0))                                             \
       return fail(GEL_ERR_ARG, "Jacobian products: a phase's slice of the input does not fit a workgroup's LDS");          \
-  } while (0)
-
-#define NEED_JPROD_DEVICE(p)                                                                                             \
-  do {                                                                                                                   \
-    if ((p)->device == GEL_DEVICE_NONE)                                                                                  \
-      return fail(GEL_ERR_ARG, "host-only handle: the device products need a GPU (gel_jac_products_host runs on the host)"); \
   } while (0)
 
 int gel_jac_products_info(const gel_problem* p, int64_t* info) {
@@ -3258,7 +3233,7 @@ int gel_jac_products_launch_info(const gel_problem* p, int32_t* info) {
 
 int gel_jac_matvec_device(gel_problem* p, int32_t B, const double* d_jvar, const double* d_v, double* d_y, void* stream) {
   if (!p || B < 1 || !d_jvar || !d_v || !d_y) return fail(GEL_ERR_ARG, "bad argument");
-  NEED_JPROD_DEVICE(p);
+  NEED_DEVICE(p, GEL_ERR_ARG, kNoGpuJprod);
   NEED_JPROD(p, 0);
   HIPCHK(hipSetDevice(p->device));
   return jprod_device(p, B, d_jvar, d_v, d_y, 0, stream_of(p, stream));
@@ -3266,7 +3241,7 @@ int gel_jac_matvec_device(gel_problem* p, int32_t B, const double* d_jvar, const
 
 int gel_jac_rmatvec_device(gel_problem* p, int32_t B, const double* d_jvar, const double* d_lam, double* d_g, void* stream) {
   if (!p || B < 1 || !d_jvar || !d_lam || !d_g) return fail(GEL_ERR_ARG, "bad argument");
-  NEED_JPROD_DEVICE(p);
+  NEED_DEVICE(p, GEL_ERR_ARG, kNoGpuJprod);
   NEED_JPROD(p, 1);
   HIPCHK(hipSetDevice(p->device));
   return jprod_device(p, B, d_jvar, d_lam, d_g, 1, stream_of(p, stream));
@@ -3274,21 +3249,12 @@ int gel_jac_rmatvec_device(gel_problem* p, int32_t B, const double* d_jvar, cons
 
 static int jprod_hostbuf(gel_problem* p, int32_t B, const double* jvar, const double* in, double* out, int transpose) {
   if (!p || B < 1 || !jvar || !in || !out) return fail(GEL_ERR_ARG, "bad argument");
-  NEED_JPROD_DEVICE(p);
+  NEED_DEVICE(p, GEL_ERR_ARG, kNoGpuJprod);
   NEED_JPROD(p, transpose);
   HIPCHK(hipSetDevice(p->device));
-  const size_t nj = (size_t)B * std::max<int64_t>(1, p->dims.num_var_entries), nv = (size_t)B * p->dims.num_vars, nr = (size_t)B * 11 * p->dims.N;
-  const size_t ni = transpose ? nr : nv, no = transpose ? nv : nr;
-  hipStream_t s = p->stream.get();
-  HIPCHK(p->d_jp_jv.reserve(nj)); HIPCHK(p->d_jp_in.reserve(ni)); HIPCHK(p->d_jp_out.reserve(no));
-  HIPCHK(hipMemcpyAsync(p->d_jp_jv.get(), jvar, (size_t)B * p->dims.num_var_entries * 8, hipMemcpyHostToDevice, s));
-  HIPCHK(hipMemcpyAsync(p->d_jp_in.get(), in, ni * 8, hipMemcpyHostToDevice, s));
-  if (const int rc = jprod_device(p, B, p->d_jp_jv.get(), p->d_jp_in.get(), p->d_jp_out.get(), transpose, s)) return rc;
-  HIPCHK(hipMemcpyAsync(out, p->d_jp_out.get(), no * 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(p->h_flag.get(), p->d_flag.get(), 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  if (*p->h_flag.get()) { *p->h_flag.get() = 0; HIPCHK(clear_flag(p, s)); return GEL_NONFINITE; }
-  return GEL_OK;
+  const size_t nv = (size_t)B * p->dims.num_vars, nr = (size_t)B * 11 * p->dims.N;
+  return staged_call(p, 0, {staged_in(jvar, (size_t)B * p->dims.num_var_entries), staged_in(in, transpose ? nr : nv), staged_out(out, transpose ? nv : nr)},
+                     [&](const gel::ProblemDev&, double* const* a) { return jprod_device(p, B, a[0], a[1], a[2], transpose, p->stream.get()); });
 }
 
 int gel_jac_matvec(gel_problem* p, int32_t B, const double* jvar, const double* v, double* y) { return jprod_hostbuf(p, B, jvar, v, y, 0); }
@@ -3379,16 +3345,10 @@ static int conprod_device(gel_problem* p, int32_t B, const double* d_jfn, const 
   return GEL_OK;
 }
 
-#define NEED_CONPROD_DEVICE(p)                                                                                            \
-  do {                                                                                                                    \
-    if ((p)->device == GEL_DEVICE_NONE)                                                                                   \
-      return fail(GEL_ERR_ARG, "host-only handle: the device products need a GPU (gel_con_products_host runs on the host)"); \
-  } while (0)
-
 int gel_con_matvec_device(gel_problem* p, int32_t B, const double* d_jfn, const double* const* d_aero_jac, const double* d_aero_record,
                           const double* d_v, double* d_y) {
   if (const int rc = conprod_check(p, B, d_jfn, d_aero_jac, d_aero_record, d_v, d_y)) return rc;
-  NEED_CONPROD_DEVICE(p);
+  NEED_DEVICE(p, GEL_ERR_ARG, kNoGpuConprod);
   HIPCHK(hipSetDevice(p->device));
   return conprod_device(p, B, d_jfn, d_aero_jac, d_aero_record, d_v, d_y, 0, 0, p->stream.get());
 }
@@ -3396,7 +3356,7 @@ int gel_con_matvec_device(gel_problem* p, int32_t B, const double* d_jfn, const 
 int gel_con_rmatvec_device(gel_problem* p, int32_t B, const double* d_jfn, const double* const* d_aero_jac, const double* d_aero_record,
                            const double* d_lam, double* d_g, int32_t accumulate) {
   if (const int rc = conprod_check(p, B, d_jfn, d_aero_jac, d_aero_record, d_lam, d_g)) return rc;
-  NEED_CONPROD_DEVICE(p);
+  NEED_DEVICE(p, GEL_ERR_ARG, kNoGpuConprod);
   HIPCHK(hipSetDevice(p->device));
   return conprod_device(p, B, d_jfn, d_aero_jac, d_aero_record, d_lam, d_g, 1, accumulate != 0, p->stream.get());
 }
@@ -3405,44 +3365,21 @@ int gel_con_rmatvec_device(gel_problem* p, int32_t B, const double* d_jfn, const
 static int conprod_hostbuf(gel_problem* p, int32_t B, const double* jfn, const double* const* aero_jac, const double* aero_record,
                            const double* in, double* out, int transpose, int accumulate) {
   if (const int rc = conprod_check(p, B, jfn, aero_jac, aero_record, in, out)) return rc;
-  NEED_CONPROD_DEVICE(p);
+  NEED_DEVICE(p, GEL_ERR_ARG, kNoGpuConprod);
   HIPCHK(hipSetDevice(p->device));
   const gel_problem::Conprod& c = p->conprod;
-  hipStream_t s = p->stream.get();
   const size_t ni = (size_t)B * (transpose ? (size_t)c.R : (size_t)p->dims.num_vars), no = (size_t)B * (transpose ? (size_t)p->dims.num_vars : (size_t)c.R);
-  HIPCHK(p->d_cp_in.reserve(ni)); HIPCHK(p->d_cp_out.reserve(no));
-  HIPCHK(hipMemcpyAsync(p->d_cp_in.get(), in, ni * 8, hipMemcpyHostToDevice, s));
-  if (accumulate) HIPCHK(hipMemcpyAsync(p->d_cp_out.get(), out, no * 8, hipMemcpyHostToDevice, s));
-  const double* d_jfn = nullptr;
-  if (c.nfn) {
-    const size_t nj = (size_t)B * c.nfn * 7;
-    HIPCHK(p->d_cp_jfn.reserve(nj));
-    HIPCHK(hipMemcpyAsync(p->d_cp_jfn.get(), jfn, nj * 8, hipMemcpyHostToDevice, s));
-    d_jfn = p->d_cp_jfn.get();
-  }
-  const double* d_jac[3] = {nullptr, nullptr, nullptr};
-  const double* d_rec = nullptr;
-  if (aero_record) {
-    const size_t nr = (size_t)B * (size_t)p->aero.ld;
-    HIPCHK(p->d_cp_aero[0].reserve(nr));
-    HIPCHK(hipMemcpyAsync(p->d_cp_aero[0].get(), aero_record, nr * 8, hipMemcpyHostToDevice, s));
-    d_rec = p->d_cp_aero[0].get();
-  } else if (aero_jac) {
-    for (int k = 0; k < 3; k++)
-      if (c.nrows[k]) {
-        const size_t nk = (size_t)B * (size_t)c.jac_len[k];
-        HIPCHK(p->d_cp_aero[k].reserve(nk));
-        HIPCHK(hipMemcpyAsync(p->d_cp_aero[k].get(), aero_jac[k], nk * 8, hipMemcpyHostToDevice, s));
-        d_jac[k] = p->d_cp_aero[k].get();
-      }
-  }
-  if (const int rc = conprod_device(p, B, d_jfn, aero_jac ? d_jac : nullptr, d_rec, p->d_cp_in.get(), p->d_cp_out.get(), transpose, accumulate, s))
-    return rc;
-  HIPCHK(hipMemcpyAsync(out, p->d_cp_out.get(), no * 8, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipMemcpyAsync(p->h_flag.get(), p->d_flag.get(), 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  if (*p->h_flag.get()) { *p->h_flag.get() = 0; HIPCHK(clear_flag(p, s)); return GEL_NONFINITE; }
-  return GEL_OK;
+  // the values: jfn when there are node-function rows; the record, or the dense array of every kind that has rows
+  StagedBuf aero[3];
+  for (int k = 0; k < 3; k++)
+    aero[k] = (aero_record && k == 0) ? staged_in(aero_record, (size_t)B * (size_t)p->aero.ld)
+                                      : staged_in((aero_jac && c.nrows[k]) ? aero_jac[k] : nullptr, (size_t)B * (size_t)c.jac_len[k]);
+  return staged_call(p, 0, {staged_in(in, ni), accumulate ? staged_inout(out, no) : staged_out(out, no),
+                            staged_in(c.nfn ? jfn : nullptr, (size_t)B * c.nfn * 7), aero[0], aero[1], aero[2]},
+                     [&](const gel::ProblemDev&, double* const* a) {
+                       return conprod_device(p, B, a[2], aero_jac ? a + 3 : nullptr, aero_record ? a[3] : nullptr, a[0], a[1], transpose,
+                                             accumulate, p->stream.get());
+                     });
 }
 
 int gel_con_matvec(gel_problem* p, int32_t B, const double* jfn, const double* const* aero_jac, const double* aero_record, const double* v,
@@ -3458,7 +3395,7 @@ int gel_con_rmatvec(gel_problem* p, int32_t B, const double* jfn, const double* 
 int gel_output_table(gel_problem* p, const double* x, const double* tx_res, double launch_lat_deg, double launch_lon_deg,
                      double* out) {
   if (!p || !x || !tx_res || !out) return fail(GEL_ERR_ARG, "null argument");
-  NEED_DEVICE(p);
+  NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
   HIPCHK(hipSetDevice(p->device));
   const int M = p->dims.M;
   // the section of every state node (output_result.py:121-143: section s owns its n + 1 state nodes)
@@ -3466,20 +3403,12 @@ int gel_output_table(gel_problem* p, const double* x, const double* tx_res, doub
   for (size_t i = 0; i < p->ph.size(); i++)
     for (int k = 0; k <= p->ph[i].n; k++) sec[(size_t)p->ph[i].xa + k] = (int32_t)i;
   const size_t nx = (size_t)p->dims.num_vars, no = (size_t)M * gel::kOutputColumns;
-  // one scratch buffer: x | tx | out | node sections (as doubles' worth of bytes)
-  const size_t words = nx + (size_t)M + no + ((size_t)M + 1) / 2;
-  HIPCHK(p->d_rows_x.reserve(words));
-  double* d_x = p->d_rows_x.get();
-  double* d_tx = d_x + nx;
-  double* d_out = d_tx + M;
-  int32_t* d_sec = reinterpret_cast<int32_t*>(d_out + no);
-  HIPCHK(hipMemcpyAsync(d_x, x, nx * 8, hipMemcpyHostToDevice, p->stream.get()));
-  HIPCHK(hipMemcpyAsync(d_tx, tx_res, (size_t)M * 8, hipMemcpyHostToDevice, p->stream.get()));
-  HIPCHK(hipMemcpyAsync(d_sec, sec.data(), (size_t)M * 4, hipMemcpyHostToDevice, p->stream.get()));
-  HIPCHK(gel::launch_output(p->dev, M, d_x, d_tx, d_sec, launch_lat_deg, launch_lon_deg, d_out, p->stream.get()));
-  HIPCHK(hipMemcpyAsync(out, d_out, no * 8, hipMemcpyDeviceToHost, p->stream.get()));
-  HIPCHK(hipStreamSynchronize(p->stream.get()));
-  return GEL_OK;
+  return staged_call(p, kStagedNoFlag, {staged_in(x, nx), staged_in(tx_res, (size_t)M), staged_in(sec.data(), (size_t)M), staged_out(out, no)},
+                     [&](const gel::ProblemDev&, double* const* a) -> int {
+                       HIPCHK(gel::launch_output(p->dev, M, a[0], a[1], reinterpret_cast<const int32_t*>(a[2]), launch_lat_deg, launch_lon_deg,
+                                                 a[3], p->stream.get()));
+                       return GEL_OK;
+                     });
 }
 
 // ------------- from-file initial guess on the host (initialize.py:322-409) -------------
@@ -3534,7 +3463,7 @@ int gel_initial_guess(const gel_problem* p, int32_t nref, const double* t_ref, c
 // ------------- one callback = one device round trip -------------
 int gel_eval_callback(gel_problem* p, const double* x, const gel_callback_io* io) {
   if (!p || !x || !io) return fail(GEL_ERR_ARG, "null argument");
-  NEED_DEVICE(p);
+  NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
   HIPCHK(hipSetDevice(p->device));
   int rc = ensure_capacity(p, 1);
   if (rc) return rc;
@@ -3548,8 +3477,12 @@ int gel_eval_callback(gel_problem* p, const double* x, const gel_callback_io* io
     off_j[k] = atotal; atotal += (io->aero_con[k] && n && io->aero_jac[k]) ? aero_jac_len(p, k) : 0;
     aero = aero || (io->aero_con[k] && n);
   }
-  if (rows) HIPCHK(p->h_rows.reserve(R + 7 * nfn + 1));
-  if (aero) HIPCHK(p->h_aero.reserve(atotal));
+  // the pinned outputs of the row table (con | jfn) and of the aero kinds behind them: the handle's pinned arena, as in the
+  // host-buffer forms -- this call, too, runs on the handle's stream and returns synchronised
+  const size_t nrows_out = rows ? R + 7 * nfn : 0;
+  if (rows || aero) HIPCHK(p->h_arena.reserve(nrows_out + atotal));
+  double* const h_rows = p->h_arena.get();
+  double* const h_aero = h_rows + nrows_out;
   const bool x_pinned = p->cb_x[0].get() && (x == p->cb_x[0].get() || x == p->cb_x[1].get());
   if (!x_pinned) std::memcpy(p->h_x.get(), x, (size_t)p->dims.num_vars * 8);
   const double* const xin = x_pinned ? x : p->h_x.get();
@@ -3585,20 +3518,20 @@ int gel_eval_callback(gel_problem* p, const double* x, const gel_callback_io* io
     for (int k = 0; k < 3; k++) {
       const size_t n = p->aero.rows[k].size();
       out.nrows[k] = (int32_t)n;
-      out.con[k] = (io->aero_con[k] && n) ? p->h_aero.get() + off_c[k] : nullptr;
-      out.jac[k] = (out.con[k] && io->aero_jac[k]) ? p->h_aero.get() + off_j[k] : nullptr;
+      out.con[k] = (io->aero_con[k] && n) ? h_aero + off_c[k] : nullptr;
+      out.jac[k] = (out.con[k] && io->aero_jac[k]) ? h_aero + off_j[k] : nullptr;
     }
   if (cb_mode == 3 || !fused || split_exact || split_aero || split_rows) {
     if (fused) HIPCHK(launch_defects(p, dv, 1, xin, res_to, want_jac ? p->h_jv.get() : nullptr, p->stream.get()));
-    if (rows) HIPCHK(launch_rows_kinds(p, dv, 1, xin, p->h_rows.get(), io->rows_jfn ? p->h_rows.get() + R : nullptr, p->stream.get()));
+    if (rows) HIPCHK(launch_rows_kinds(p, dv, 1, xin, h_rows, io->rows_jfn ? h_rows + R : nullptr, p->stream.get()));
     if (aero) HIPCHK(launch_aero_kinds(p, dv, (int)p->aero.nodes.size(), p->aero.d_nodes.get(), 1, xin, out, p->stream.get()));
   } else {
     // ONE launch: defect groups, aero kinds and row table as workgroup ranges of one grid (gel_kernels.hip callback_kernel)
     arm_done(p, dv);
     HIPCHK(gel::launch_callback(dv, want_jac, xin, res_to, want_jac ? p->h_jv.get() : nullptr,
                                 aero ? (int)p->aero.nodes.size() : 0, p->aero.d_nodes.get(), aero ? &out : nullptr,
-                                (int)nlin, p->d_lin_rows.get(), (int)nfn, p->d_fn_rows.get(), rows ? p->h_rows.get() : nullptr,
-                                (rows && io->rows_jfn) ? p->h_rows.get() + R : nullptr, p->stream.get()));
+                                (int)nlin, p->d_lin_rows.get(), (int)nfn, p->d_fn_rows.get(), rows ? h_rows : nullptr,
+                                (rows && io->rows_jfn) ? h_rows + R : nullptr, p->stream.get()));
   }
   HIPCHK(wait_done(p, dv));   // the ONE wait of the callback: the kernel's own word where it signals, else the runtime's synchronise
   if (io->res && !own_res) std::memcpy(io->res, p->h_res.get(), (size_t)11 * p->dims.N * 8);
@@ -3607,8 +3540,8 @@ int gel_eval_callback(gel_problem* p, const double* x, const gel_callback_io* io
     else scatter_full(p, p->h_jv.get(), io->vals_full, io->fill_constants);
   }
   if (rows) {
-    std::memcpy(io->rows_con, p->h_rows.get(), R * 8);
-    if (io->rows_jfn) std::memcpy(io->rows_jfn, p->h_rows.get() + R, 7 * nfn * 8);
+    std::memcpy(io->rows_con, h_rows, R * 8);
+    if (io->rows_jfn) std::memcpy(io->rows_jfn, h_rows + R, 7 * nfn * 8);
   }
   if (aero)
     for (int k = 0; k < 3; k++) {
