@@ -161,6 +161,7 @@ SIGNATURES = {
     "gel_dynamics_velocity_NoAir": (C.c_int, [C.c_int32, _dp, _dp, _dp, _dp, _dp, C.c_double, _dp]),
     "gel_dynamics_quaternion": (C.c_int, [C.c_int32, _dp, _dp, C.c_double, _dp]),
     "gel_point_eval": (C.c_int, [C.c_int32, C.c_int32, _dp, _dp, C.c_int32, _dp]),
+    "gel_table_limits": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, _lp]),
     "gel_last_error": (C.c_char_p, []),
     "gel_version": (C.c_char_p, []),
 }
@@ -283,6 +284,15 @@ def lib():
             fn.argtypes = args
         _LIB = L
     return _LIB
+
+
+def table_limits(wind_rows, ca_rows, n=0):
+    """-> {"table", "fused", "aero", "mesh", "plain", "cap_bytes", "mesh_vectors"}: the doubles the staged tables take, the table
+    doubles that fit each family of launches (gel_table_limits; "mesh" for a phase of n nodes, -1 without one) and the vectors a
+    workgroup of the estimate takes of such a phase.  Needs no GPU."""
+    info = (C.c_int64 * 7)()
+    check(lib().gel_table_limits(int(wind_rows), int(ca_rows), int(n), info))
+    return dict(zip(("table", "fused", "aero", "mesh", "plain", "cap_bytes", "mesh_vectors"), (int(v) for v in info)))
 
 
 class GelatoAmdError(RuntimeError):

@@ -383,6 +383,7 @@ struct gel_problem {
   std::vector<size_t> mesh_hoff;
   std::vector<gel::MeshPhaseDev> mesh_ph;
   int32_t mesh_npts = 0;
+  size_t mesh_lds_max = 0;     // LDS of the widest phase's workgroup (gel::mesh_lds_bytes), host-only handles included
   gel::MeshDev mesh_dev{};
   DeviceArray<double> d_mesh_mat;
   DeviceArray<gel::MeshPhaseDev> d_mesh_ph;
@@ -780,6 +781,26 @@ hipError_t clear_flag(gel_problem* p, hipStream_t s) {
 constexpr const char* kNoGpu = "host-only handle: nothing can be evaluated without a GPU (no CPU fallback)";
 constexpr const char* kNoGpuInterp = "host-only handle: the device interpolation needs a GPU (gel_interp_host runs on the host)";
 constexpr const char* kNoGpuJprod = "host-only handle: the device products need a GPU (gel_jac_products_host runs on the host)";
+// Launches that stage the tables pass no launch attribute: a workgroup of theirs may take gel::kLaunchMaxLds bytes.  The host decides
+// with the launchers' own sizes (gel_launch.h, gel_mesh.h), before anything is enqueued; the device is never asked.
+// lds_room: the table doubles that fit beside `rest` doubles of other LDS (padded: the rest starts at an even double)
+size_t lds_room(size_t rest, bool padded) {
+  const size_t cap = gel::kLaunchMaxLds / sizeof(double);
+  const size_t r = rest < cap ? cap - rest : 0;
+  return padded ? (r & ~(size_t)1) : r;
+}
+// GEL_OK, or GEL_ERR_ARG with the table doubles asked for and those that fit; `staged` = the doubles the tables take in the launch
+int check_launch_lds(const char* what, size_t lds_bytes, size_t asked, size_t staged, bool padded) {
+  if (lds_bytes <= gel::kLaunchMaxLds) return GEL_OK;
+  const size_t room = lds_room(lds_bytes / sizeof(double) - staged, padded);
+  return fail(GEL_ERR_ARG, std::string(what) + ": the tables take " + std::to_string(asked) + " doubles of LDS, " + std::to_string(room) +
+                               " fit beside the launch's own (64 KB per workgroup): fewer wind or CA rows");
+}
+int check_table_launches(int Kw, int Kc) {
+  const size_t T = gel::staged_table_doubles(Kw, Kc), Tp = gel::padded_table_doubles(Kw, Kc);
+  if (int rc = check_launch_lds("fused kernel", gel::eval_lds_bytes_max(Kw, Kc), T, Tp, true)) return rc;
+  return check_launch_lds("aero kernels", gel::aero_lds_bytes(Kw, Kc), T, Tp, true);
+}
 constexpr const char* kNoGpuConprod = "host-only handle: the device products need a GPU (gel_con_products_host runs on the host)";
 
 // The defect groups of B vectors: one launch of the fused kernel; on a handle created with GEL_FLAG_EXACT_DEFECT_JAC, a call with
@@ -1266,6 +1287,9 @@ int gel_problem_create(const gel_problem_desc* d, gel_problem** out) {
       ((d->flags & GEL_FLAG_FD_RECOMPUTE) || !(std::fabs(d->dx * d->unit_position) <= 1.0)))
     return fail(GEL_ERR_ARG, "GEL_FLAG_EXACT_AERO_JAC cannot be combined with GEL_FLAG_FD_RECOMPUTE (nor with |dx * unit_position| > 1)");
   if (const char* why = gel::check_tables(d->wind_table, d->wind_rows, d->ca_table, d->ca_rows)) return fail(GEL_ERR_ARG, why);
+  // every evaluation goes through the fused and the aero launches; their limit (1792 table doubles) is below that of the launches
+  // that keep nothing behind the tables (exact forms, propagation, output table: 8192), which therefore need no check of their own
+  if (int rc = check_table_launches(d->wind_rows, d->ca_rows)) return rc;
   for (int i = 0; i < d->num_sections; i++)
     if (d->num_nodes[i] < 2) return fail(GEL_ERR_ARG, "every phase needs >= 2 LGR nodes (nodes_LGR requires n >= 2)");
   // device == GEL_DEVICE_NONE: a host-only handle (dims, LGR data, sparsity pattern, constant values,
@@ -1453,7 +1477,9 @@ int gel_problem_create(const gel_problem_desc* d, gel_problem** out) {
     p->mesh_host = std::move(mh);
     p->mesh_hoff = std::move(hoff);
     p->mesh_npts = npts;
+    for (int i = 0; fits && i < S; i++) p->mesh_lds_max = std::max(p->mesh_lds_max, gel::mesh_lds_bytes(d->wind_rows, d->ca_rows, p->ph[i].n));
   }
+  p->dev.Kw = d->wind_rows; p->dev.Kc = d->ca_rows;
   if (const char* e = build_jprod_tables(*p)) return fail(GEL_ERR_ARG, e);
   if (const char* e = getenv("GEL_JPROD_THREADS")) { if (atoi(e) == 256) p->jp_threads = 256; }   // host-only handles report it too
   for (int i = 0; i < S; i++)
@@ -1566,7 +1592,7 @@ int gel_problem_create(const gel_problem_desc* d, gel_problem** out) {
   dv.phases = p->d_phases.get(); dv.node_phase = p->d_node_phase.get(); dv.Dt = p->d_Dt.get(); dv.tau = p->d_tau.get();
   dv.tables = p->d_tables.get(); dv.flag = p->d_flag.get();
   dv.nchunks = (int32_t)chunks.size(); dv.chunks = p->d_chunks_sorted.get(); dv.Dsw = p->d_Dsw.get(); dv.Dst = p->d_Dst.get();
-  dv.park_off = (int32_t)((tables.size() + 1) / 2 * 2);
+  dv.park_off = (int32_t)gel::padded_table_doubles(d->wind_rows, d->ca_rows);
   {
     // D.X path.  fp64 MFMA and fp64 VALU instructions share the SIMD's fp64 datapath on this part (measured: their busy
     // times add up), so the matrix pipe is not free throughput; what it buys is fewer issue slots and the
@@ -1596,14 +1622,15 @@ int gel_problem_create(const gel_problem_desc* d, gel_problem** out) {
     // the estimate's device tables: each phase's matrices transposed (point index fastest), LDS per workgroup of vpb vectors
     std::vector<double> mat;
     std::vector<gel::MeshPhaseDev> mph(S);
-    const size_t tab_lds = ((gel::staged_table_doubles(d->wind_rows, d->ca_rows) + 1) & ~(size_t)1);
     int32_t pt0 = 0;
     for (int i = 0; i < S; i++) {
       const int n = p->ph[i].n, P = n + 1;
       const double* hb = p->mesh_host.data() + p->mesh_hoff[i];
       const double *sg = hb, *Lx = sg + P, *Lu = Lx + (size_t)P * P, *I = Lu + (size_t)P * n;
       gel::MeshPhaseDev& q = mph[i];
-      q.n = n; q.vpb = gel::kMeshMaxThreads / P; q.pt0 = pt0; q.pad = 0;
+      q.n = n; q.pt0 = pt0; q.pad = 0;
+      q.vpb = gel::kMeshMaxThreads / P;                                                   // the vectors the workgroup has lanes for ...
+      q.vpb = std::min(q.vpb, gel::mesh_vectors_that_fit(d->wind_rows, d->ca_rows, n));   // ... and LDS (gel::mesh_vectors_per_group)
       pt0 += P;
       q.lx = (int64_t)mat.size();
       for (int k = 0; k < P; k++) for (int l = 0; l < P; l++) mat.push_back(Lx[(size_t)l * P + k]);
@@ -1613,7 +1640,7 @@ int gel_problem_create(const gel_problem_desc* d, gel_problem** out) {
       for (int k = 0; k < P; k++) for (int l = 0; l < P; l++) mat.push_back(I[(size_t)l * P + k]);
       q.sg = (int64_t)mat.size();
       for (int l = 0; l < P; l++) mat.push_back(sg[l]);
-      q.lds = (int64_t)(8 * (tab_lds + (size_t)q.vpb * (11 * P + 2 * n + 11)));
+      q.lds = (int64_t)gel::mesh_lds_bytes(d->wind_rows, d->ca_rows, n);
     }
     HIPCHK(p->d_mesh_mat.upload(mat)); HIPCHK(p->d_mesh_ph.upload(mph));
     p->mesh_ph = std::move(mph);
@@ -2147,7 +2174,10 @@ int gel_dynamics_velocity(int32_t n, const double* mass_e, const double* pos_e, 
   if (n < 0 || !mass_e || !pos_e || !vel_e || !quat || !t || !param || !wind || !ca || !units || !out)
     return fail(GEL_ERR_ARG, "null argument");
   if (n == 0) return GEL_OK;
-  int rc = need_device();
+  if (Kw < 2 || Kc < 2) return fail(GEL_ERR_ARG, "the wind and CA tables need at least two rows");
+  int rc = check_launch_lds("gel_dynamics_velocity", gel::table_lds_bytes(Kw, Kc), gel::staged_table_doubles(Kw, Kc), gel::staged_table_doubles(Kw, Kc), false);
+  if (rc) return rc;
+  rc = need_device();
   if (rc) return rc;
   if (const char* why = gel::check_tables(wind, Kw, ca, Kc)) return fail(GEL_ERR_ARG, why);
   const std::vector<double> tables = gel::build_tables(wind, Kw, ca, Kc);
@@ -2641,6 +2671,13 @@ int gel_rows_eval(gel_problem* p, int32_t B, const double* x, double* con, doubl
 }
 
 // ------------- collocation error estimate per section -------------
+#define MESH_FITS(p)                                                                                                   \
+  do {                                                                                                                 \
+    if (int rc_ = check_launch_lds("collocation error estimate", (p)->mesh_lds_max,                                    \
+                                   gel::staged_table_doubles((p)->dev.Kw, (p)->dev.Kc),                                \
+                                   gel::padded_table_doubles((p)->dev.Kw, (p)->dev.Kc), true))                         \
+      return rc_;                                                                                                      \
+  } while (0)
 #define NEED_MESH(p)                                                                                                   \
   do {                                                                                                                 \
     if ((p)->mesh_hoff.empty())                                                                                        \
@@ -2667,6 +2704,7 @@ int gel_mesh_matrices(const gel_problem* p, int32_t phase, double* sigma, double
 
 int gel_mesh_error_device(gel_problem* p, int32_t B, const double* d_x, double* d_err, double* d_diff, void* stream) {
   if (!p || B < 1 || !d_x || !d_err) return fail(GEL_ERR_ARG, "bad argument");
+  MESH_FITS(p);
   NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
   NEED_MESH(p);
   HIPCHK(gel::launch_mesh(p->dev, p->mesh_dev, p->mesh_ph.data(), B, d_x, d_err, d_diff, stream_of(p, stream)));
@@ -2675,6 +2713,7 @@ int gel_mesh_error_device(gel_problem* p, int32_t B, const double* d_x, double* 
 
 int gel_mesh_error(gel_problem* p, int32_t B, const double* x, double* err, double* diff) {
   if (!p || B < 1 || !x || !err) return fail(GEL_ERR_ARG, "bad argument");
+  MESH_FITS(p);
   NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
   NEED_MESH(p);
   HIPCHK(hipSetDevice(p->device));
@@ -3552,11 +3591,27 @@ int gel_eval_callback(gel_problem* p, const double* x, const gel_callback_io* io
   return GEL_OK;
 }
 
+int gel_table_limits(int32_t wind_rows, int32_t ca_rows, int32_t n, int64_t* info) {
+  if (wind_rows < 2 || ca_rows < 2 || !info) return fail(GEL_ERR_ARG, "bad argument");
+  const size_t T = gel::staged_table_doubles(wind_rows, ca_rows), Tp = gel::padded_table_doubles(wind_rows, ca_rows);
+  info[0] = (int64_t)T;
+  info[1] = (int64_t)lds_room(gel::eval_lds_bytes_max(wind_rows, ca_rows) / 8 - Tp, true);
+  info[2] = (int64_t)lds_room(gel::aero_lds_bytes(wind_rows, ca_rows) / 8 - Tp, true);
+  info[3] = (n >= 2 && n < gel::kMeshMaxThreads) ? (int64_t)lds_room(gel::mesh_vector_doubles(n), true) : -1;
+  info[4] = (int64_t)lds_room(gel::table_lds_bytes(wind_rows, ca_rows) / 8 - T, false);
+  info[5] = (int64_t)gel::kLaunchMaxLds;
+  info[6] = info[3] < 0 ? -1 : (int64_t)gel::mesh_vectors_per_group(wind_rows, ca_rows, n);
+  return GEL_OK;
+}
+
 int gel_point_eval(int32_t kind, int32_t n, const double* in, const double* aux, int32_t aux_rows, double* out) {
   static const int nin[15] = {1, 3, 3, 6, 7, 1, 1, 2, 2, 8, 8, 8, 7, 4, 1}, nout[15] = {5, 3, 3, 3, 3, 3, 1, 4, 6, 8, 16, 4, 3, 7, 2};
   if (kind < 0 || kind > 14 || n < 0 || !in || !out) return fail(GEL_ERR_ARG, "bad argument");
   if (n == 0) return GEL_OK;
-  int rc = need_device();
+  const bool tabulated = kind == 5 || kind == 6 || kind == 9 || kind == 10;
+  int rc = tabulated ? check_launch_lds("gel_point_eval", gel::point_lds_bytes(aux_rows), 5 * (size_t)std::max(aux_rows, 0), 5 * (size_t)std::max(aux_rows, 0), false) : GEL_OK;
+  if (rc) return rc;
+  rc = need_device();
   if (rc) return rc;
   double atm[gel::kAtmTableDoubles];
   size_t naux = 0;

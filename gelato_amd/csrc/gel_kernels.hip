@@ -391,6 +391,13 @@ constexpr int kAeroWaves = 4;
 // park slots of one wavefront (doubles; the last six hold up to 12 ints per lane)
 enum { AP_ILIM = 0, AP_AC = 3, AP_QC, AP_CC, AP_IS, AP_IND, AP_W = 8, AP_A0 = 11, AP_DIR = 14, AP_RHO = 17, AP_NV2 = 18, AP_INTS = 19,
        kAeroParkSlots = 25 };
+// every form's region per wavefront fits the Jacobian forms' park, so eval_lds_bytes_max() bounds every launch of the fused kernel
+static_assert(wave_lds_doubles(false, false, false) <= kWaveLds && wave_lds_doubles(false, true, false, true) <= kWaveLds &&
+              wave_lds_doubles(false, true, true) <= kWaveLds && wave_lds_doubles(false, true, false, false, true) <= kWaveLds &&
+              wave_lds_doubles(false, true, false, false, false) <= kWaveLds, "kWaveLds is the largest region");
+static size_t eval_lds_bytes(size_t park_off, int wave_doubles) { return sizeof(double) * (park_off + (size_t)wave_doubles * (kBlock / 64)); }
+size_t eval_lds_bytes_max(int Kw, int Kc) { return eval_lds_bytes(padded_table_doubles(Kw, Kc), kWaveLds); }
+size_t aero_lds_bytes(int Kw, int Kc) { return sizeof(double) * (padded_table_doubles(Kw, Kc) + (size_t)kAeroWaves * kAeroParkSlots * 64); }
 typedef __attribute__((address_space(3))) int lds_int;
 typedef __attribute__((address_space(3))) double lds_f64;
 // ROLES (the B = 1 callback launch, where the length of one wavefront's chain is what counts): the four wavefronts of a
@@ -729,7 +736,7 @@ hipError_t launch_aero_wide(const ProblemDev& P, int nnodes, const AeroNodeDev* 
   AeroOut O;
   for (int k = 0; k < 3; k++) { O.con[k] = out.con[k]; O.jac[k] = out.jac[k]; O.nrows[k] = out.nrows[k]; }
   O.ld = ld; O.sm = 0;
-  const size_t lds = sizeof(double) * (((staged_table_doubles(P.Kw, P.Kc) + 1) & ~(size_t)1) + (size_t)kAeroWaves * kAeroParkSlots * 64);
+  const size_t lds = aero_lds_bytes(P.Kw, P.Kc);
   const long long waves = ((long long)B * nnodes + 63) / 64;
   hipLaunchKernelGGL(aero_wide_kernel, dim3((unsigned)((waves + kAeroWaves - 1) / kAeroWaves)), dim3(64 * kAeroWaves), lds, s, P, nnodes, nodes, B, d_x, O);
   return hipGetLastError();
@@ -771,7 +778,7 @@ hipError_t launch_aero(const ProblemDev& P, int nnodes, const AeroNodeDev* nodes
   for (int k = 0; k < 3; k++) { O.con[k] = out.con[k]; O.jac[k] = out.jac[k]; O.nrows[k] = out.nrows[k]; }
   O.ld = ld; O.sm = (ld > 0 && spec_major) ? 1 : 0;
   int tiles = (nnodes + 63) / 64;
-  const size_t lds = sizeof(double) * (((staged_table_doubles(P.Kw, P.Kc) + 1) & ~(size_t)1) + (size_t)kAeroWaves * kAeroParkSlots * 64);
+  const size_t lds = aero_lds_bytes(P.Kw, P.Kc);
   long long waves = (long long)B * tiles;
   // flat (vector, node) mapping (tiles = 0 tells the kernel): no mostly-empty last tile per vector; needs every wavefront inside two
   // vectors and the batch's gradient values of a kind inside 32-bit byte offsets
@@ -1035,8 +1042,8 @@ hipError_t launch_callback(const ProblemDev& P0, bool want_jac, const double* d_
     A.lin_blocks = (nlin + 255) / 256;
     rows_blocks = A.lin_blocks + (nfn * 8 + 255) / 256;
   }
-  const size_t lds_eval = sizeof(double) * ((size_t)P.park_off + (size_t)wave_lds_doubles(want_jac, P.use_mfma != 0, false, true) * 4);
-  const size_t lds_aero = sizeof(double) * (((staged_table_doubles(P.Kw, P.Kc) + 1) & ~(size_t)1) + (size_t)kAeroWaves * kAeroParkSlots * 64);
+  const size_t lds_eval = eval_lds_bytes((size_t)P.park_off, wave_lds_doubles(want_jac, P.use_mfma != 0, false, true));
+  const size_t lds_aero = aero_lds_bytes(P.Kw, P.Kc);
   const size_t lds = lds_eval > lds_aero ? lds_eval : lds_aero;
   const dim3 grid((unsigned)(A.nb_eval + A.nb_aero + rows_blocks));
   if (P.done_flag) P.done_total = (int32_t)grid.x;
@@ -1215,7 +1222,7 @@ __global__ void output_kernel(ProblemDev P, int M, const double* __restrict__ x,
 
 hipError_t launch_output(const ProblemDev& P, int M, const double* d_x, const double* d_tx, const int32_t* d_node_sec,
                          double lat0, double lon0, double* d_out, hipStream_t s) {
-  hipLaunchKernelGGL(output_kernel, dim3((M + 63) / 64), dim3(64), sizeof(double) * staged_table_doubles(P.Kw, P.Kc), s, P, M, d_x, d_tx, d_node_sec,
+  hipLaunchKernelGGL(output_kernel, dim3((M + 63) / 64), dim3(64), table_lds_bytes(P.Kw, P.Kc), s, P, M, d_x, d_tx, d_node_sec,
                      lat0, lon0, d_out);
   return hipGetLastError();
 }
@@ -1234,7 +1241,6 @@ hipError_t launch_rows(const ProblemDev& P, int nlin, const LinRowDev* lin, int 
 // launches with at most this many wavefronts (after the x4) use the split latency form: one per SIMD
 constexpr long long kSplitMaxWaves = 1024;
 
-static size_t table_lds_bytes(int Kw, int Kc) { return sizeof(double) * staged_table_doubles(Kw, Kc); }
 
 // which instantiation a launch takes (also reported through gel_launch_info)
 EvalForm eval_form(const ProblemDev& P, int B, bool want_res, bool want_jac) {
@@ -1259,7 +1265,7 @@ static void launch_coop(const ProblemDev& P, int B, const double* d_x, double* d
   const unsigned nb = (unsigned)((B + (PACK ? 7 : 3)) / (PACK ? 8 : 4));
   // vector-group major order deals the groups to the eight XCDs in blocks of eight (short last block: idle workgroups leave at once)
   const unsigned grid = P.vmajor ? (unsigned)P.nchunks * 8u * ((nb + 7u) / 8u) : (unsigned)P.nchunks * nb;
-  const size_t lds = sizeof(double) * ((size_t)P.park_off + (size_t)wave_lds_doubles(JAC, true, PACK, false, LONGP) * (kBlock / 64));
+  const size_t lds = eval_lds_bytes((size_t)P.park_off, wave_lds_doubles(JAC, true, PACK, false, LONGP));
   hipLaunchKernelGGL((eval_kernel<JAC, true, false, PACK, LONGP, NTS>), dim3(grid), dim3(kBlock), lds, s, P, B, d_x, d_res, d_jvar);
 }
 
@@ -1284,7 +1290,7 @@ hipError_t launch_eval(const ProblemDev& P, int B, const double* d_x, double* d_
   }
   const unsigned grid = (unsigned)((f.waves * 64 + kBlock - 1) / kBlock);
   // tables | one region per wavefront (the park, or only what a residual-only launch parks)
-  const size_t lds = sizeof(double) * ((size_t)P.park_off + (size_t)wave_lds_doubles(f.jac, f.mfma, false) * (kBlock / 64));
+  const size_t lds = eval_lds_bytes((size_t)P.park_off, wave_lds_doubles(f.jac, f.mfma, false));
   if (f.split) {
     ProblemDev Q = P;
     if (Q.nunits <= 0) { Q.unit0 = 4 * P.chunk0; Q.nunits = 4 * P.nchunks; }  // the whole list, split
@@ -1398,7 +1404,7 @@ hipError_t launch_rhs_quat(int n, const double* quat, const double* u_e, double 
 
 hipError_t launch_point(int kind, int n, const double* in, const double* aux, int aux_rows, double* out,
                         hipStream_t s) {
-  const size_t lds = sizeof(double) * (size_t)(kAtmDoubles + 5 * (aux_rows > 0 ? aux_rows : 0));
+  const size_t lds = point_lds_bytes(aux_rows);
   hipLaunchKernelGGL(point_kernel, dim3((n + 63) / 64), dim3(64), lds, s, kind, n, in, aux, aux_rows, out);
   return hipGetLastError();
 }

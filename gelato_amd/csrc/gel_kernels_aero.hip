@@ -22,7 +22,7 @@ hipError_t launch_eval_aero(const ProblemDev& P, int B, const double* d_x, doubl
   // grid and LDS as launch_coop() of gel_kernels.hip (one vector per wavefront, four per workgroup)
   const unsigned nb = (unsigned)((B + 3) / 4);
   const unsigned grid = P.vmajor ? (unsigned)P.nchunks * 8u * ((nb + 7u) / 8u) : (unsigned)P.nchunks * nb;
-  const size_t lds = sizeof(double) * ((size_t)P.park_off + (size_t)wave_lds_doubles(true, true, false, false, true) * (kBlock / 64));
+  const size_t lds = eval_lds_bytes_max(P.Kw, P.Kc);
   hipLaunchKernelGGL((eval_kernel<true, true, false, false, true, true, true>), dim3(grid), dim3(kBlock), lds, s, P, B, d_x, d_res, d_jvar);
   return hipGetLastError();
 }

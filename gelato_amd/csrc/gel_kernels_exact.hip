@@ -194,7 +194,7 @@ hipError_t launch_eval_exact(const ProblemDev& P, int B, const double* d_x, doub
   if (P.fd_recompute || !d_jvar) return hipErrorInvalidValue;   // the default compact layout only (t0 / tf, quaternion slots)
   const long long threads = (long long)B * P.N;
   const unsigned grid = (unsigned)((threads + kExactBlock - 1) / kExactBlock);
-  const size_t lds = sizeof(double) * staged_table_doubles(P.Kw, P.Kc);
+  const size_t lds = table_lds_bytes(P.Kw, P.Kc);
   hipLaunchKernelGGL(exact_jac_kernel, dim3(grid), dim3(kExactBlock), lds, s, P, B, d_x, d_jvar);
   return hipGetLastError();
 }

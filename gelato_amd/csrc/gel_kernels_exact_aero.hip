@@ -148,7 +148,7 @@ hipError_t launch_aero_exact(const ProblemDev& P, int nnodes, const AeroNodeDev*
   if (P.fd_recompute) return hipErrorInvalidValue;   // the default layout only (t columns as exact zeros, blocks of 11 n in part A)
   const long long threads = (long long)B * nnodes;
   const unsigned grid = (unsigned)((threads + kExactAeroBlock - 1) / kExactAeroBlock);
-  const size_t lds = sizeof(double) * staged_table_doubles(P.Kw, P.Kc);
+  const size_t lds = table_lds_bytes(P.Kw, P.Kc);
   hipLaunchKernelGGL(exact_aero_kernel, dim3(grid), dim3(kExactAeroBlock), lds, s, P, nnodes, nodes, B, d_x, out, ld,
                      (ld > 0 && spec_major) ? 1 : 0);
   return hipGetLastError();

@@ -7,7 +7,8 @@
 // Output: max_j e over the components of each group (mass, position, velocity, quaternion), and on request X^ - X~ per point.
 //
 // One lane = one (decision vector, test point) pair of one phase; a workgroup of kMeshMaxThreads lanes carries vpb = 512 / (n + 1)
-// vectors of the same phase (3 at n = 128, 7 at n = 64, 170 at n = 2).  Each vector's state (11 (n+1)) and control (2 n) are
+// vectors of the same phase (3 at n = 128, 7 at n = 64) -- fewer where that many do not fit 64 KB of LDS beside the tables
+// (gel_mesh.h mesh_vectors_per_group: 167 instead of 170 at n = 2 with the example's tables); lanes with v >= vpb stay idle.  Each vector's state (11 (n+1)) and control (2 n) are
 // staged in LDS; the interpolation reads them as broadcasts and the matrices (transposed on the host: one coalesced load per
 // column) through the cache.  The same LDS region then holds |X~| for the per-component maxima, the right-hand sides F for the
 // product with I, and |X^ - X~| for the maxima over the points.  Nothing per point reaches HBM unless diff is asked for.

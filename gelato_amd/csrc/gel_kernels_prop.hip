@@ -210,7 +210,7 @@ hipError_t launch_prop_slab(const ProblemDev& P, const PropDev& Pd, const PropPh
   grid = ngrp * Pd.nseg;
   if (grid <= 0) return hipSuccess;
   if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
-  const size_t lds = sizeof(double) * staged_table_doubles(P.Kw, P.Kc);
+  const size_t lds = table_lds_bytes(P.Kw, P.Kc);
   hipLaunchKernelGGL(prop_kernel, dim3((unsigned)grid), dim3(kPropThreads), lds, s, P, Pd, nb, d_x, d_y, d_ws, (long long)ld);
   return hipGetLastError();
 }

@@ -82,4 +82,15 @@ void append_rows_and_slopes(std::vector<double>& rows_out, std::vector<double>& 
 // doubles of the staged tables (atmosphere | wind rows | CA rows | wind slopes | CA slopes), as gel_physics.h table_doubles()
 inline size_t staged_table_doubles(int Kw, int Kc) { return (size_t)kAtmTableDoubles + 3 * (size_t)Kw + 2 * (size_t)Kc + 2 * (size_t)(Kw - 1) + (size_t)(Kc - 1); }
 
+// LDS of the launches that stage the tables.  They pass no launch attribute, so a workgroup may take kLaunchMaxLds bytes at most;
+// the launchers size their launches with these functions and the host refuses with them (gel_host.hip: gel_problem_create,
+// gel_mesh_error, gel_dynamics_velocity, gel_point_eval; gel_table_limits reports them) before anything is enqueued.
+constexpr size_t kLaunchMaxLds = 64 * 1024;
+// first double behind the staged tables (ProblemDev::park_off; the park base of aero_body, `base` of mesh_kernel): kept even
+inline size_t padded_table_doubles(int Kw, int Kc) { return (staged_table_doubles(Kw, Kc) + 1) & ~(size_t)1; }
+inline size_t table_lds_bytes(int Kw, int Kc) { return sizeof(double) * staged_table_doubles(Kw, Kc); }   // the kernels that keep nothing behind the tables
+size_t eval_lds_bytes_max(int Kw, int Kc);   // the fused kernel's largest form (gel_kernels.hip)
+size_t aero_lds_bytes(int Kw, int Kc);       // aero_kernel, aero_sm_kernel, aero_wide_kernel; callback_kernel takes the larger of the two
+inline size_t point_lds_bytes(int aux_rows) { return sizeof(double) * (size_t)(kAtmTableDoubles + 5 * (aux_rows > 0 ? aux_rows : 0)); }
+
 }  // namespace gel

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "gel_device.h"
+#include "gel_launch.h"
 
 namespace gel {
 
@@ -16,7 +17,7 @@ namespace gel {
 //   IT  [P][P]                     IT[k P + l]  = I[l][k]    Radau integration matrix of the fine grid, (D^[:, 1:])^-1
 //   sig [P]                        sigma_1 .. sigma_P
 struct MeshPhaseDev {
-  int32_t n, vpb;        // collocation nodes; decision vectors per workgroup (kMeshMaxThreads / P)
+  int32_t n, vpb;        // collocation nodes; decision vectors per workgroup (mesh_vectors_per_group: kMeshMaxThreads / P, or what fits the LDS)
   int32_t pt0;           // first test point of the phase in the [npts] rows of the optional differences
   int32_t pad;
   int64_t lx, lu, it, sg;  // offsets (doubles) of LxT, LuT, IT and sigma in MeshDev::mat
@@ -31,6 +32,23 @@ struct MeshDev {
 };
 
 constexpr int kMeshMaxThreads = 512;   // workgroup size of mesh_kernel: phases of up to 511 nodes
+// LDS of a phase of n nodes: the padded tables, then per vector X [11][n+1] | U [2][n] and the 11 per-component maxima.  A workgroup
+// takes as many decision vectors as it has lanes for (kMeshMaxThreads / (n + 1)) and as fit kLaunchMaxLds beside the tables
+// (MeshPhaseDev::vpb, ::lds; a short phase is bound by the LDS: 170 vectors of n = 2 alone take 65 280 bytes), at least one: a
+// phase whose single vector does not fit is refused by the host (gel_mesh_error*)
+inline size_t mesh_vector_doubles(int n) { return 11 * (size_t)(n + 1) + 2 * (size_t)n + 11; }
+inline int mesh_vectors_that_fit(int Kw, int Kc, int n) {   // beside the tables, under kLaunchMaxLds; 1 if not even one does
+  const size_t cap = kLaunchMaxLds / sizeof(double), tab = padded_table_doubles(Kw, Kc);
+  const size_t fit = tab < cap ? (cap - tab) / mesh_vector_doubles(n) : 0;
+  return (int)(fit > 0 ? (fit < (size_t)kMeshMaxThreads ? fit : (size_t)kMeshMaxThreads) : 1);
+}
+inline int mesh_vectors_per_group(int Kw, int Kc, int n) {
+  const int lanes = kMeshMaxThreads / (n + 1), fit = mesh_vectors_that_fit(Kw, Kc, n);
+  return fit < lanes ? fit : lanes;
+}
+inline size_t mesh_lds_bytes(int Kw, int Kc, int n) {
+  return sizeof(double) * (padded_table_doubles(Kw, Kc) + (size_t)mesh_vectors_per_group(Kw, Kc, n) * mesh_vector_doubles(n));
+}
 
 // err [B][S][4] (mass, position, velocity, quaternion); diff [B][npts][11] or null.  The non-finite flag is P.flag.
 hipError_t launch_mesh(const ProblemDev& P, const MeshDev& Md, const MeshPhaseDev* host_ph, int B, const double* d_x, double* d_err,

@@ -690,6 +690,21 @@ int gel_dynamics_quaternion(int32_t n, const double* quat_eci2body, const double
  */
 int gel_point_eval(int32_t kind, int32_t n, const double* in, const double* aux, int32_t aux_rows, double* out);
 
+/* ---- limits of the wind and CA tables.  Every kernel that evaluates aerodynamics keeps the tables in a workgroup's LDS:
+ *  T = 85 + 5 wind_rows + 3 ca_rows doubles (atmosphere 88 | wind rows | CA rows | their slopes), beside the launch's own LDS.
+ *  No launch asks for more than the 64 KB a workgroup gets without launch attributes; a call whose launch would need more
+ *  returns GEL_ERR_ARG before anything is enqueued, and gel_last_error() states the table doubles asked for and those that fit:
+ *  gel_problem_create for the fused kernel (T <= 3328) and the aero / callback kernels (T <= 1792, e.g. 320 wind and 32 CA
+ *  rows), which also covers the launches that keep nothing behind the tables (exact Jacobians, propagation, output table:
+ *  T <= 8192); gel_mesh_error[_device] for the estimate, whose workgroup takes as many vectors of a phase as fit beside the
+ *  tables and needs room for one (T <= 8170 - 13 n, below the aero limit only from n = 491 on; the handle stays usable for
+ *  everything else); gel_dynamics_velocity (T <= 8192) and gel_point_eval kinds 5, 6, 9, 10 (88 + 5 aux_rows <= 8192) for theirs.
+ *  gel_table_limits (needs no GPU): info[0] = T, info[1] = the T that fits the fused kernel, [2] the aero and callback kernels,
+ *  [3] one vector of the collocation error estimate of a phase of n nodes (-1 if n is outside 2 .. 511), [4] the launches with nothing
+ *  behind the tables, [5] = the cap in bytes, [6] the vectors a workgroup of the estimate takes of such a phase beside these tables
+ *  (512 / (n + 1), or fewer where the LDS binds; -1 like [3]). */
+int gel_table_limits(int32_t wind_rows, int32_t ca_rows, int32_t n, int64_t* info /* [7] */);
+
 const char* gel_last_error(void);
 const char* gel_version(void);
 

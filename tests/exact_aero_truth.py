@@ -11,6 +11,7 @@ KINDS = ["alpha", "q", "qalpha"]
 VARS = ["position", "velocity", "quaternion", "t"]
 LIMITS = {"alpha": 0.2, "q": 4.0e4, "qalpha": 5.0e3}     # units[3] of con_aero.py for the synthetic cases
 CASES = ["g9_example", "g9_synthetic", "ragged", "polar", "layers", "breaks", "mixed-6x64", "corners"]
+LONG_CASES = ["climb", "knots"]     # g28_long_tables.npz: tests/states.py table_state("LONG", (40, 65, 2), .)
 COLS = {"position": slice(0, 3), "velocity": slice(3, 6), "quaternion": slice(6, 10)}
 
 
@@ -43,6 +44,10 @@ def case(name):
         from gelato_amd import con_dynamics, pack_x, problem
         pdict, unitdict, _, xdict = problem.make_problem(name)
         prob, D, x = _with_tau(dict(con_dynamics.problem_arrays(pdict, unitdict)), pack_x(xdict))
+        return prob, D, x, _all_aero(prob)
+    if name in LONG_CASES:
+        import table_cases as TC
+        prob, D, x = _with_tau(*states.table_state("LONG", TC.MESHES["coop"], name))
         return prob, D, x, _all_aero(prob)
     if name == "corners":
         import exact_jac_truth

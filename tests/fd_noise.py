@@ -115,9 +115,12 @@ C_RHO = 64.0
 OMEGA_E = 7.2921151467e-5
 
 
-def aero_noise_terms(orc, prob, x, spec):
+def aero_noise_terms(orc, prob, x, spec, secants=(10.0,)):
     """spec: rows of (phase, range_all, ...) -> per constrained node (rows in the constraint's order): alpha, q, sin(alpha), the
-    cancellation factor A, d_alt, |d alpha / d alt|, |d q / d alt|, and the node's normalised values (for the drift term)"""
+    cancellation factor A, d_alt, |d alpha / d alt|, |d q / d alt|, and the node's normalised values (for the drift term).
+    secants [m]: the radial steps the two altitude sensitivities are measured over on the oracle, the largest quotient counts -- 10 m
+    for the example's tables (intervals of kilometres); tables with intervals of metres need steps inside an interval as well
+    (tests/test_table_sizes.py)"""
     import ctypes as C
     L = orc.lib()
     dp = C.POINTER(C.c_double)
@@ -150,14 +153,17 @@ def aero_noise_terms(orc, prob, x, spec):
             pos, vel, quat = xr[xa + k] * up, xv[xa + k] * uv, np.ascontiguousarray(xq[xa + k])
             a, q = point(pos, vel, quat, t)
             rn = np.linalg.norm(pos)
-            a2, q2 = point(pos * (1.0 + 10.0 / rn), vel, quat, t)
+            da_dalt = dq_dalt = 0.0
+            for sc in secants:
+                a2, q2 = point(pos * (1.0 + sc / rn), vel, quat, t)
+                da_dalt, dq_dalt = max(da_dalt, abs(a2 - a) / abs(sc)), max(dq_dalt, abs(q2 - q) / abs(sc))
             lat_deg, _, alt = orc.ecef2geodetic(*pos)
             lat = np.deg2rad(lat_deg)
             nv = np.linalg.norm(vel - np.cross([0.0, 0.0, OMEGA_E], pos)) - wmax      # a lower bound of |v_air|
             A = (np.linalg.norm(vel) + OMEGA_E * rn + wmax) / nv if nv > 0.0 else np.inf
             qq = np.hypot(pos[0], pos[1]) / max(abs(np.cos(lat)), 1e-300)
             dalt = EPS * (qq * (1.0 + C_LAT * abs(lat * np.tan(lat))) + 6.4e6)
-            rows.append((a, q, np.sin(a), A, dalt, abs(a2 - a) / 10.0, abs(q2 - q) / 10.0,
+            rows.append((a, q, np.sin(a), A, dalt, da_dalt, dq_dalt,
                          np.concatenate([np.abs(xr[xa + k]), np.abs(xv[xa + k]), np.abs(xq[xa + k])]), lat_deg))
     keys = ("alpha", "q", "sin", "A", "dalt", "dalpha_dalt", "dq_dalt", "xabs", "lat_deg")
     return {k: np.array([r[i] for r in rows]) for i, k in enumerate(keys)}
@@ -187,11 +193,11 @@ def aero_drift(terms, grad_abs, dx):
     return (grad_abs * EPS * (terms["xabs"] + dx)).sum(axis=1) / dx
 
 
-def aero_coo_bounds(orc, prob, x, kind, spec, drift_of=None):
+def aero_coo_bounds(orc, prob, x, kind, spec, drift_of=None, secants=(10.0,)):
     """{var: bound of every gradient entry, in the reference's emission order (per spec row, component-major: con_aero.py:437-463)}
     for ONE implementation against the exact quotient.  drift_of: {var: values in the same order} of a reference-style
     implementation -- adds the drift of its in-place perturbations, estimated from its own entries."""
-    terms = aero_noise_terms(orc, prob, x, spec)
+    terms = aero_noise_terms(orc, prob, x, spec, secants)
     nn = [int(v) for v in prob["num_nodes"]]
     blocks, lim, r0 = [], [], 0
     for sp in spec:

@@ -380,3 +380,144 @@ def rest_state():
     x = np.concatenate([np.linspace(1.0, 0.5, n + 1), xr.ravel(), xv.ravel(), quat.ravel(), 2.0 * rng.standard_normal(2 * n),
                         [10.0 / ut, 160.0 / ut]])
     return with_coast_tail(lambda: (prob, x))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# Small problems over the long wind / CA tables of tests/table_cases.py (tests/test_table_sizes.py, tests/golden/make_long_tables.py)
+# ---------------------------------------------------------------------------------------------------------------------------
+GEOPOT_R0 = 6356766.0
+TABLE_KNOT_OFFSETS = (-0.04, -0.004, 0.004, 0.04)
+
+
+def _geometric(h):
+    """geometric altitude whose geopotential altitude (src/Air.cpp:47-54) is h: the inverse of r0 z / (r0 + z) below 86 km
+    geometric, h itself from there on.  Geopotential 84 852 .. 86 000 m is the image of no altitude."""
+    h = np.asarray(h, dtype=np.float64)
+    assert not np.any((h > 84850.0) & (h < 86000.0))
+    return np.where(h < 84851.0, GEOPOT_R0 * h / (GEOPOT_R0 - h), h)
+
+
+def table_knots(case):
+    """the (up to) six wind knots the `knots` vector sits around: the first and the last row among them"""
+    import table_cases as TC
+    alt = TC.CASES[case][0][:, 0]
+    K = len(alt)
+    idx = sorted({0, 1, K // 3, K // 2, K - 2, K - 1})
+    return [float(alt[k]) for k in idx if not 84850.0 < alt[k] < 86000.0]
+
+
+def table_state(case, nn, vector="climb"):
+    """Aerodynamic phases of nn[:-1] nodes and a coasting tail of nn[-1] without aerodynamics, over the wind and CA tables of
+    tests/table_cases.py CASES[case].
+      "climb"  the state nodes climb from 50 m to 130 km: two below the wind table's first row, three above its last, the others
+               inside as many different intervals of it as there are nodes (none within 1 m of a knot); air-relative speeds aim
+               at Mach 0.05 .. 20 -- inside as many different CA intervals as possible, some above the last Mach row;
+      "knots"  the same, but for nodes 4 mm and 4 cm below and above table_knots(case) (the geodetic construction of
+               layer_break_state): a position sweep (dx * unit = 6.4 cm) carries some of them across the knot."""
+    import oracle
+    import table_cases as TC
+    assert vector in ("climb", "knots") and len(nn) >= 2
+    prob = TC.with_tables(_example_prob(), case)
+    wind, ca = TC.CASES[case]
+    rng = np.random.default_rng(1000 + sum(nn) + len(wind))
+    S = len(nn)
+    prob["num_nodes"] = np.array(nn, dtype=np.int32)
+    prob["thrust"] = np.array([420000.0, 30700.0, 9000.0][:S - 1] + [0.0])
+    prob["massflow"] = np.array([140.9, 9.8, 2.5][:S - 1] + [0.0])
+    prob["reference_area"] = np.array([2.21, 1.3, 0.7][:S - 1] + [0.0])
+    prob["nozzle_area"] = np.array([0.68, 0.1, 0.0][:S - 1] + [0.0])
+    prob["engine_on"] = np.array([1] * (S - 1) + [0], dtype=np.int32)
+    prob["attitude_hold"] = np.zeros(S, dtype=np.int32)
+    up, uv, ut = prob["units"][1], prob["units"][2], prob["units"][4]
+    N, M = sum(nn), sum(nn) + S
+    Ma = M - (nn[-1] + 1)                                            # state nodes of the aerodynamic phases
+    # geopotential altitudes: below, inside (one interval each while there are enough), above
+    gaps = np.diff(wind[:, 0])
+    usable = [k for k in range(len(gaps)) if gaps[k] >= 2.5 and not (wind[k, 0] < 86000.0 and wind[k + 1, 0] > 84850.0)]
+    n_in = Ma - 5
+    pick = [usable[i] for i in np.unique(np.round(np.linspace(0, len(usable) - 1, min(n_in, len(usable)))).astype(int))]
+    pick = (pick * (n_in // len(pick) + 1))[:n_in]
+    f = rng.uniform(0.3, 0.7, n_in)
+    inside = np.array([wind[k, 0] + min(max(1.05, fi * gaps[k]), gaps[k] - 1.05) for k, fi in zip(pick, f)])
+    h = np.sort(np.concatenate([[50.0, min(150.0, 0.5 * (50.0 + wind[0, 0]))] if wind[0, 0] > 60.0 else [50.0, 1500.0], inside,
+                                [100e3, 115e3, 130e3]]))
+    alt = _geometric(h)
+    if vector == "knots":
+        at = np.round(np.linspace(1, Ma - 2, 4 * len(table_knots(case)))).astype(int)
+        assert len(set(at)) == len(at)
+        alt[at] = [float(_geometric(hk)) + off for hk in table_knots(case) for off in TABLE_KNOT_OFFSETS]
+    alt = np.concatenate([alt, np.full(M - Ma, alt[-1])])
+    lat = np.concatenate([rng.uniform(-1.0, 1.0, Ma), np.zeros(M - Ma)])
+    lon = np.concatenate([rng.uniform(-np.pi, np.pi, Ma), np.zeros(M - Ma)])
+    lat[Ma:], lon[Ma:] = lat[Ma - 1], lon[Ma - 1]
+    a_e, b_e = 6378137.0, 6356752.314245
+    e2 = 1.0 - (b_e / a_e) ** 2
+    Np = a_e / np.sqrt(1.0 - e2 * np.sin(lat) ** 2)
+    r = np.column_stack([(Np + alt) * np.cos(lat) * np.cos(lon), (Np + alt) * np.cos(lat) * np.sin(lon), (Np * (1.0 - e2) + alt) * np.sin(lat)])
+    # Mach targets: the middle of a CA interval each, in shuffled order; the ends and beyond the last row
+    mids = 0.5 * (ca[:-1, 0] + ca[1:, 0])
+    mach = np.concatenate([[0.05, 0.5 * (ca[-1, 0] + 20.0), 12.0, 20.0], np.tile(mids, Ma // len(mids) + 1)])[:Ma]
+    mach = np.concatenate([mach[rng.permutation(Ma)], np.full(M - Ma, 5.0)])
+    hh = np.array([oracle.geopotential_altitude(z) for z in alt])
+    sound = np.array([oracle.speed_of_sound(z) for z in hh])
+    d = rng.standard_normal((M, 3))
+    omega = 7.2921151467e-5
+    v = np.column_stack([-omega * r[:, 1], omega * r[:, 0], np.zeros(M)]) + d / np.linalg.norm(d, axis=1, keepdims=True) * (mach * sound)[:, None]
+    quat = rng.standard_normal((M, 4))
+    quat /= np.linalg.norm(quat, axis=1, keepdims=True)
+    t = np.array([10.0, 160.0, 400.0, 640.0][:S - 1] + [0.0]) / ut
+    t[-1] = t[-2] + 10.0 / ut
+    x = np.concatenate([np.linspace(1.0, 0.4, M), (r / up).ravel(), (v / uv).ravel(), quat.ravel(), 2.0 * rng.standard_normal(2 * N),
+                        [5.0 / ut], t])
+    return prob, x
+
+
+def table_node_times(prob, x):
+    """tx [M]: the time of every state node in seconds (output_result.py:121-143 with the oracle's LGR nodes)"""
+    import oracle
+    nn = [int(v) for v in prob["num_nodes"]]
+    S, N = len(nn), sum(nn)
+    M = N + S
+    tn = x[11 * M + 2 * N:] * float(prob["units"][4])
+    return np.concatenate([np.concatenate([[-1.0], oracle.lgr_nodes(n)]) * (tn[s + 1] - tn[s]) / 2.0 + (tn[s + 1] + tn[s]) / 2.0
+                           for s, n in enumerate(nn)])
+
+
+def table_oracle_rows(prob, x, launch=(28.5, 0.0)):
+    """{column: [M]} of the oracle's post-processing table (oracle/output_table.py) of (prob, x) on prob's own tables: "altitude"
+    (geodetic, m) and "M" (Mach number) per state node among them"""
+    from oracle import output_table as ot
+    nn = [int(v) for v in prob["num_nodes"]]
+    S, N = len(nn), sum(nn)
+    params = [(prob["thrust"][s], prob["reference_area"][s], prob["nozzle_area"][s]) for s in range(S)]
+    return ot.table(x, N + S, N, nn, tuple(prob["units"][:3]), table_node_times(prob, x), params, np.asarray(prob["wind_table"]),
+                    np.asarray(prob["ca_table"]), launch[0], launch[1])
+
+
+def check_table_state(case, nn, vector):
+    """what table_state promises, from the oracle's altitude and Mach number per node -> (wind intervals hit, CA intervals hit)"""
+    import oracle
+    import table_cases as TC
+    prob, x = table_state(case, nn, vector)
+    wind, ca = TC.CASES[case]
+    T = table_oracle_rows(prob, x)
+    Ma = sum(nn) + len(nn) - (nn[-1] + 1)
+    alt, mach = T["altitude"][:Ma], T["M"][:Ma]
+    h = np.array([oracle.geopotential_altitude(z) for z in alt])
+    assert alt.min() < 60.0 and alt.max() > 129e3 and mach.min() < 0.2 and mach.max() > 15.0
+    assert (h < wind[0, 0]).sum() >= (2 if wind[0, 0] > 60.0 else 0) and (h > wind[-1, 0]).sum() >= 3 and (mach > ca[-1, 0]).sum() >= 3
+    dk = np.abs(h[:, None] - wind[None, :, 0]).min(axis=1)
+    assert np.abs(mach[:, None] - ca[None, :, 0]).min() > 1e-6
+    if vector == "climb":
+        assert dk.min() > 1.0
+    else:
+        near = np.sort(dk)[:4 * len(table_knots(case))]
+        assert np.all(near < 0.05) and (near < 0.01).sum() == 2 * len(table_knots(case)) and np.sort(dk)[4 * len(table_knots(case))] > 1.0
+        for hk in table_knots(case):                               # two nodes on either side of every knot
+            side = h[np.abs(h - hk) < 0.05] - hk
+            assert (side < 0).sum() == 2 and (side > 0).sum() == 2, (hk, side)
+    inw = h[(h > wind[0, 0]) & (h <= wind[-1, 0])]
+    inc = mach[(mach > ca[0, 0]) & (mach <= ca[-1, 0])]
+    hit_w = len(set(np.searchsorted(wind[:, 0], inw, side="left") - 1))
+    hit_c = len(set(np.searchsorted(ca[:, 0], inc, side="left") - 1))
+    return hit_w, hit_c

@@ -55,9 +55,9 @@ def aero():
     return _lib.GEL_FLAG_EXACT_AERO_JAC
 
 
-def check_against_truth(name, flags, report):
+def check_against_truth(name, flags, report, fixture="g20_exact_aero_jac.npz"):
     """-> number of entries outside the bound (asserted 0 by the caller for the exact handle)"""
-    G = load_golden("g20_exact_aero_jac.npz")
+    G = load_golden(fixture)
     E, prob, x, specs = engine(name, flags)
     from gelato_amd import Engine
     A = Engine(prob, D=T.case(name)[1], tau=prob["tau"], flags=aero())   # the same rows with limit 1: alpha, dalpha, dq as they are
@@ -136,6 +136,18 @@ def test_exact_against_the_ground_truth_and_the_fd_handle_fails_it():
     print("exact: (case, kind, small-alpha rows, clamped rows, fails)", report)
     print("forward differences: entries outside the bound", fd, fd_report)
     assert fd >= FD_FAILS_AT_LEAST, fd
+
+
+@pytest.mark.parametrize("name", T.LONG_CASES)
+def test_exact_against_the_ground_truth_over_long_tables(name):
+    """the same bound and rules, nothing excluded, over 160 wind rows and 48 CA rows (tests/table_cases.py LONG; g28,
+    tests/golden/make_long_tables.py) on the (40, 65, 2) mesh, all three kinds on both aerodynamic phases: exact_aero_kernel's
+    wind slopes come from slope[idx] of the bisection branch; the forward-difference handle fails the bound"""
+    report, fd_report = [], []
+    assert check_against_truth(name, aero(), report, "g28_long_tables.npz") == 0
+    fd = check_against_truth(name, 0, fd_report, "g28_long_tables.npz")
+    print("exact:", report, "forward differences: entries outside the bound", fd)
+    assert fd >= 300, fd        # the q rows' position entries alone (105 rows x 3): truncation dx unit_p / (2 H) = 6e-6 of the entry
 
 
 @pytest.mark.parametrize("name", ["mixed-6x64", "g9_synthetic"])

@@ -32,53 +32,77 @@ def bits(a):
 TRUTH_STATES = ["example", "ragged", "layers", "breaks", "polar", "corners"]
 
 
+def check_state_against_truth(G, name, prob, x):
+    """one state of a fixture written by make_exact_jac.state_truth against the exact handle (asserted) and the default handle
+    -> (velocity-group entries of aerodynamic phases the forward differences have outside the bound, their number)"""
+    import exact_jac_truth
+    from gelato_amd import Engine
+    from gelato_amd.engine import BLOCKS
+    fd_bad = fd_all = 0
+    assert np.array_equal(x, G[name + "_x"]), "the state builder no longer reproduces the fixture's decision vector"
+    E0, E1 = Engine(prob, device=0), Engine(prob, device=0, flags=EXACT)
+    _, v1, rc = E1.eval(x)
+    assert rc == 0
+    want = [exact_jac_truth.expected_full(E1, prob, x, G, name, w) for w in ("c", "f", "b")]
+    var = E1.var_mask()
+    assert np.all(np.isfinite(want[0][var])) and np.all(np.isnan(want[0][~var]))
+    # where the value jumps (the polar-axis nodes, x / y position columns) no derivative exists: the engine follows the stated
+    # convention (the partials of p and of the longitude are 0: the air of the axis point held), to the same bound
+    jump = exact_jac_truth.jump_entries(E1, prob, G, name)
+    assert name == "corners" or not jump.any()
+    assert jump.sum() <= 18
+    conv = exact_jac_truth.expected_full(E1, prob, x, G, name, "conv")
+    cex = np.abs(v1 - conv) - (1e-12 + 1e-9 * np.abs(conv))
+    assert cex[jump].max(initial=-1.0) <= 0.0, "convention at the polar axis: excess %g" % cex[jump].max()
+    ex = np.min([np.abs(v1 - w) - (1e-12 + 1e-9 * np.abs(w)) for w in want], axis=0)[var & ~jump]
+    assert ex.max() <= 0.0, "%s: %d entries outside 1e-12 + 1e-9 |true|, worst excess %g" % (
+        name, int((ex > 0).sum()), ex.max())
+    if name == "corners":
+        return fd_bad, fd_all
+    _, v0, _ = E0.eval(x)
+    ex0 = np.min([np.abs(v0 - w) - (1e-12 + 1e-9 * np.abs(w)) for w in want], axis=0)
+    nn = [int(v) for v in prob["num_nodes"]]
+    aero_node = np.repeat(np.asarray(prob["reference_area"]) > 0, nn)
+    pat = E1.pattern()
+    for b, (grp, vn) in enumerate(BLOCKS):
+        if grp != "vel" or vn == "t":
+            continue
+        sl = slice(E1.block_off[b], E1.block_off[b + 1])
+        m = var[sl] & aero_node[pat[b][0] // 3]
+        fd_all += int(m.sum())
+        fd_bad += int((ex0[sl][m] > 0).sum())
+    return fd_bad, fd_all
+
+
 def test_exact_against_the_ground_truth():
     """every x-dependent entry of the exact handle within 1e-12 + 1e-9 |true| of the 60-digit derivative (at a node with a knot
     within the truth's step -- the polar-axis nodes, whose longitude jumps, and the nodes at rest in the air -- of the central
     or of either one-sided quotient); teeth: the default handle's forward differences (truncation dx / 2 |f''| ~ 1e-8 of an
     entry, plus rounding amplified by 1 / dx) fail the bound on most velocity-group entries of the aerodynamic phases"""
     import exact_jac_truth
-    from gelato_amd import Engine
-    from gelato_amd.engine import BLOCKS
     G = load_golden("g19_exact_jac.npz")
     builders = exact_jac_truth.states()
     fd_bad = fd_all = 0
     for name in TRUTH_STATES:
         prob, x = builders[name]()
-        assert np.array_equal(x, G[name + "_x"]), "the state builder no longer reproduces the fixture's decision vector"
-        E0, E1 = Engine(prob, device=0), Engine(prob, device=0, flags=EXACT)
-        _, v1, rc = E1.eval(x)
-        assert rc == 0
-        want = [exact_jac_truth.expected_full(E1, prob, x, G, name, w) for w in ("c", "f", "b")]
-        var = E1.var_mask()
-        assert np.all(np.isfinite(want[0][var])) and np.all(np.isnan(want[0][~var]))
-        # where the value jumps (the polar-axis nodes, x / y position columns) no derivative exists: the engine follows the stated
-        # convention (the partials of p and of the longitude are 0: the air of the axis point held), to the same bound
-        jump = exact_jac_truth.jump_entries(E1, prob, G, name)
-        assert name == "corners" or not jump.any()
-        assert jump.sum() <= 18
-        conv = exact_jac_truth.expected_full(E1, prob, x, G, name, "conv")
-        cex = np.abs(v1 - conv) - (1e-12 + 1e-9 * np.abs(conv))
-        assert cex[jump].max(initial=-1.0) <= 0.0, "convention at the polar axis: excess %g" % cex[jump].max()
-        ex = np.min([np.abs(v1 - w) - (1e-12 + 1e-9 * np.abs(w)) for w in want], axis=0)[var & ~jump]
-        assert ex.max() <= 0.0, "%s: %d entries outside 1e-12 + 1e-9 |true|, worst excess %g" % (
-            name, int((ex > 0).sum()), ex.max())
-        if name == "corners":
-            continue
-        _, v0, _ = E0.eval(x)
-        ex0 = np.min([np.abs(v0 - w) - (1e-12 + 1e-9 * np.abs(w)) for w in want], axis=0)
-        nn = [int(v) for v in prob["num_nodes"]]
-        aero_node = np.repeat(np.asarray(prob["reference_area"]) > 0, nn)
-        pat = E1.pattern()
-        for b, (grp, vn) in enumerate(BLOCKS):
-            if grp != "vel" or vn == "t":
-                continue
-            sl = slice(E1.block_off[b], E1.block_off[b + 1])
-            m = var[sl] & aero_node[pat[b][0] // 3]
-            fd_all += int(m.sum())
-            fd_bad += int((ex0[sl][m] > 0).sum())
+        bad, n = check_state_against_truth(G, name, prob, x)
+        fd_bad, fd_all = fd_bad + bad, fd_all + n
     assert fd_bad > 0.5 * fd_all, "the forward-difference handle meets the exact bound on %d of %d entries" % (fd_all - fd_bad, fd_all)
     print("forward differences outside the exact bound: %d of %d velocity-group entries" % (fd_bad, fd_all))
+
+
+@pytest.mark.parametrize("vector", ["climb", "knots"])
+def test_exact_against_the_ground_truth_over_long_tables(vector):
+    """the same bound, nothing excluded, over 160 wind rows and 48 CA rows (tests/table_cases.py LONG: the bisection branch of the
+    lookups and of interp_tab_slope's slope[idx]; g28, tests/golden/make_long_tables.py) on the (40, 65, 2) mesh: `climb` visits
+    102 wind and 45 CA intervals, `knots` has nodes 4 mm and 4 cm either side of six wind knots (none ON a knot: the fixture has no `kink` entry) -- a slope taken from the
+    neighbouring interval is off by the table's noise, far outside 1e-9 of the entry"""
+    import states
+    import table_cases as TC
+    G = load_golden("g28_long_tables.npz")
+    prob, x = states.table_state("LONG", TC.MESHES["coop"], vector)
+    fd_bad, fd_all = check_state_against_truth(G, vector, prob, x)
+    assert fd_bad > 0.5 * fd_all, (fd_bad, fd_all)
 
 
 @pytest.mark.parametrize("name", ["example", "3x32", "mixed6x64", "dense6x64", "negarea"])

@@ -286,17 +286,20 @@ def reference_noise_per_row(P, prob, x, barC20=None):
 BENIGN_LAT_DEG = 55.0   # the latitude rounds 1-2 kept dense air below; the margins table reports the flat tolerance's excess below it separately
 
 
-def defect_margins(E, P, x, prob=None, barC20=None):
+def defect_margins(E, P, x, prob=None, barC20=None, res=None, vals=None):
     """Engine against oracle, every x-dependent Jacobian entry: per block the largest difference, how far it is inside the
     FLAT tolerance 1e-5 + 1e-6 |ref| of SURVEY 8(c), how many entries need the DERIVED allowance (the reference's own
     finite-difference noise at that node, velocity group of aerodynamic phases; only when `prob` is given), the largest
     allowance in use, and the worst flat excess among the rows below BENIGN_LAT_DEG.  -> (rows of the table, res, vals).
-    tests/parity_margin.py writes the table to profiles/; check_against_oracle asserts on it."""
+    tests/parity_margin.py writes the table to profiles/; check_against_oracle asserts on it.  res / vals: the residuals and the
+    full COO values of x as another entry point returned them, instead of gel_eval_residual's and gel_eval_jacobian's."""
     oracle = _setup()
-    res, rc = E.eval_residual(x)
-    assert rc == 0
-    vals, rc = E.eval_jacobian(x)
-    assert rc == 0
+    if res is None:
+        res, rc = E.eval_residual(x)
+        assert rc == 0
+    if vals is None:
+        vals, rc = E.eval_jacobian(x)
+        assert rc == 0
     J = E.jac_dicts(vals)
     var_mask = E.var_mask()
     noise = reference_noise_per_row(P, prob, x, barC20) if prob is not None else None
@@ -328,7 +331,7 @@ def defect_margins(E, P, x, prob=None, barC20=None):
     return table, res, vals
 
 
-def check_against_oracle(E, P, x, what, prob=None, barC20=None):
+def check_against_oracle(E, P, x, what, prob=None, barC20=None, res=None, vals=None):
     """Engine against oracle: residuals 1e-12 + 1e-10 |ref| (+ the D.X summation bound), constants and pattern bit-exact,
     x-dependent Jacobian entries 1e-5 + 1e-6 |ref| -- plus, for the velocity group of aerodynamic phases when `prob` is given,
     the derived rounding noise of the reference's OWN finite differences at that node (high latitude, dense air: the
@@ -336,7 +339,7 @@ def check_against_oracle(E, P, x, what, prob=None, barC20=None):
     entries lean on the allowance is on the record (tests/parity_margin.py -> profiles/r04/parity_margins.json: a handful per
     extreme state); that the DEFAULT engine needs none of it against the exact quotients is asserted in tests/test_exact_fd.py."""
     oracle = _setup()
-    table, res, vals = defect_margins(E, P, x, prob, barC20)
+    table, res, vals = defect_margins(E, P, x, prob, barC20, res, vals)
     R = E.split_res(res)
     bound = dx_roundoff_bound(E, x)
     for grp in oracle.GROUPS:
@@ -526,7 +529,7 @@ def test_lookups_through_a_kept_interval_equal_fresh_lookups():
     """The fused kernel keeps the table interval of a node's previous CA / wind lookup and takes a short way when every
     lane of the wavefront falls into its own kept interval.  Sequences that sit on breakpoints, cross them by an ulp or by
     1e-8, leave the table at both ends, and carry NaN / inf -- different in every lane -- give the bits of fresh lookups."""
-    from gelato_amd.dynamics import point_eval
+    import table_cases as TC          # the sequence builder and the comparison, shared with tests/test_table_lookups.py
     rng = np.random.default_rng(99)
     xp = np.array([0.0, 0.7, 1.0, 1.5, 2.0, 5.0, 100.0])
     tab = np.column_stack([xp, [0.3, 0.3, 0.65, 0.65, 0.6, 0.3, 0.3]])
@@ -534,31 +537,8 @@ def test_lookups_through_a_kept_interval_equal_fresh_lookups():
     wind = np.column_stack([alt, 3.0 * np.sin(np.arange(9.0)), 10.0 * np.cos(np.arange(9.0))])
     wind[[0, 1, -1], 1:] = 0.0
     n = 64 * 40 + 17
-    for kind_c, kind_f, t, cols in ((9, 6, tab, 1), (10, 5, wind, 3)):
-        bp = t[:, 0]
-        base = bp[rng.integers(0, len(bp), n)]
-        seq = np.empty((n, 8))
-        seq[:, 0] = base * (1.0 - 1e-9) - 1e-12                       # just below a breakpoint
-        seq[:, 1] = base                                              # on it
-        seq[:, 2] = np.nextafter(base, np.inf)                        # an ulp above
-        seq[:, 3] = base * (1.0 + 1e-8) + 1e-8                        # a forward-difference step above
-        seq[:, 4] = seq[:, 3] + 1e-8 * np.abs(seq[:, 3])              # and another (same interval: the short way)
-        seq[:, 5] = rng.uniform(bp[0] - 1.0, min(bp[-1], 3e4) * 1.1, n)   # anywhere, also beyond both ends
-        seq[:, 6] = seq[:, 5] * (1.0 + 1e-8)
-        seq[:, 7] = seq[:, 6]
-        calm = rng.random(n) < 0.5                                    # half of the lanes stay put: wavefronts with hits AND misses
-        seq[calm, :] = seq[calm, 5:6] * (1.0 + 1e-9 * np.arange(8)[None, :])
-        seq[rng.integers(0, n, 25), rng.integers(0, 8, 25)] = np.nan
-        seq[rng.integers(0, n, 25), rng.integers(0, 8, 25)] = np.inf
-        seq[rng.integers(0, n, 25), rng.integers(0, 8, 25)] = -np.inf
-        got = point_eval(kind_c, seq, aux=t)
-        fresh = point_eval(kind_f, seq.ravel(), aux=t)
-        if kind_f == 5:
-            fresh = fresh[:, :2].reshape(n, 16)
-        else:
-            fresh = fresh.reshape(n, 8)
-        assert np.array_equal(got, fresh, equal_nan=True), (kind_c, np.argwhere(~((got == fresh) | (np.isnan(got) & np.isnan(fresh))))[:5])
-        assert np.isnan(got).any() and np.isfinite(got).any()
+    for kind_c, kind_f, t in ((9, 6, tab), (10, 5, wind)):
+        TC.check_kept_equal_fresh(t, kind_c, kind_f, TC.kept_interval_sequences(rng, t, n))
 
 
 @pytest.mark.parametrize("name,B,jac", [("mixed-6x64", 65536, True), ("dense-6x64", 65536, True), ("stress-12x128", 16384, True),

@@ -276,3 +276,70 @@ def test_jac_fd_blocks_cover_the_reference_pattern(name):
             r, c = pat[b]
             assert all((int(ci) + voff[var]) in inside[phase_of_row[int(ri)]] for ri, ci in zip(r[::7], c[::7]))
     assert int(off[-1]) * 2 < E.nrows[3] * E.nvars                   # equal phases: 1/S of the dense matrix (0.167 at 6 x 64)
+
+
+# ---- the wind / CA tables' limits: every launch that stages them stays inside 64 KB of LDS, decided on the host ----
+def _tables_of(Kw, Kc):
+    h = np.linspace(0.0, 90e3, Kw)
+    m = np.linspace(0.0, 8.0, Kc)
+    return np.column_stack([h, np.sin(h / 7e3), np.cos(h / 9e3)]), np.column_stack([m, 0.3 + 0.1 * np.cos(m)])
+
+
+def _host_only(nn, Kw, Kc):
+    from gelato_amd import Engine
+    pdict, unitdict, _c, _x = problem.make_problem("example")
+    prob = dict(con_dynamics.problem_arrays(pdict, unitdict))
+    S = len(nn)
+    prob["num_nodes"] = np.array(nn, dtype=np.int32)
+    for k, v in (("thrust", 4.2e5), ("massflow", 140.0), ("reference_area", 2.21), ("nozzle_area", 0.68)):
+        prob[k] = np.full(S, v)
+    prob["engine_on"] = np.ones(S, dtype=np.int32)
+    prob["attitude_hold"] = np.zeros(S, dtype=np.int32)
+    prob["wind_table"], prob["ca_table"] = _tables_of(Kw, Kc)
+    return Engine(prob, device=-1)
+
+
+def test_table_limits_are_the_launchers_budgets():
+    """gel_table_limits: T = 85 + 5 Kw + 3 Kc doubles beside 4 x 19 x 64 (fused kernel), 4 x 25 x 64 (aero and callback kernels),
+    one vector of the estimate (13 n + 22), or nothing, under 8192 doubles"""
+    lim = _lib.table_limits(7, 9, 64)
+    assert lim == {"table": 85 + 35 + 27, "fused": 8192 - 4864, "aero": 8192 - 6400, "mesh": (8192 - (13 * 64 + 22)) & ~1, "plain": 8192,
+                   "cap_bytes": 65536, "mesh_vectors": 7}
+    assert _lib.table_limits(320, 32)["table"] == 1781 <= lim["aero"] < _lib.table_limits(340, 32)["table"] == 1881
+    assert _lib.table_limits(2, 2, 511)["mesh"] == 1526 and _lib.table_limits(2, 2, 512)["mesh"] == -1 and _lib.table_limits(2, 2)["mesh"] == -1
+    with pytest.raises(_lib.GelatoAmdError):
+        _lib.table_limits(1, 2)
+
+
+def test_tables_beyond_a_launchs_lds_are_refused_by_the_host():
+    """Kw = 340 does not fit the aero kernels: gel_problem_create says so, with the doubles asked for and those that fit, on a
+    handle that never sees a device; Kw = 320 is taken.  The stand-alone entry points refuse theirs before they look for a GPU."""
+    from gelato_amd import dynamics
+    with pytest.raises(_lib.GelatoAmdError, match=r"error -1: aero kernels: the tables take 1881 doubles of LDS, 1792 fit"):
+        _host_only([8, 5], 340, 32)
+    with pytest.raises(_lib.GelatoAmdError, match=r"error -1: fused kernel: the tables take 3481 doubles of LDS, 3328 fit"):
+        _host_only([8, 5], 660, 32)
+    E = _host_only([8, 5], 320, 32)
+    assert E.N == 13
+    with pytest.raises(_lib.GelatoAmdError, match=r"error -2: host-only handle"):       # nothing to refuse: only the GPU is missing
+        E.mesh_error(np.zeros(E.nvars))
+    wind, ca = _tables_of(1700, 32)
+    one = np.ones(1)
+    with pytest.raises(_lib.GelatoAmdError, match=r"error -1: gel_dynamics_velocity: the tables take 8681 doubles of LDS, 8192 fit"):
+        dynamics.dynamics_velocity(one, np.ones((1, 3)), np.ones((1, 3)), np.ones((1, 4)), one, np.ones(5), wind, ca, np.ones(3))
+    tab = np.column_stack([np.arange(1621.0), np.arange(1621.0)])
+    for kind, t in ((6, tab), (9, tab), (5, np.column_stack([tab, tab[:, 0]])), (10, np.column_stack([tab, tab[:, 0]]))):
+        with pytest.raises(_lib.GelatoAmdError, match=r"error -1: gel_point_eval: the tables take 8105 doubles of LDS, 8104 fit"):
+            dynamics.point_eval(kind, np.zeros(8), aux=t)
+
+
+def test_estimate_of_a_phase_too_long_for_the_tables_is_refused_by_the_host():
+    """the estimate's workgroup keeps one vector of a phase (13 n + 22 doubles) beside the tables: at n = 500 with 320 wind rows it
+    does not fit.  gel_mesh_error[_device] say so before they ask for a device; the handle serves everything else"""
+    E = _host_only([500, 4], 320, 32)
+    msg = r"error -1: collocation error estimate: the tables take 1781 doubles of LDS, 1670 fit"
+    with pytest.raises(_lib.GelatoAmdError, match=msg):
+        E.mesh_error(np.zeros(E.nvars))
+    with pytest.raises(_lib.GelatoAmdError, match=msg):
+        E.mesh_error_device(1, 8, 8)
+    assert E.mesh_npts() == 506 and E.mesh_matrices(1)["Lx"].shape == (5, 5)

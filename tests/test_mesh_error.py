@@ -28,12 +28,8 @@ def _engine(prob, **kw):
 USAGE = {}
 
 
-@pytest.mark.parametrize("name", ["example", "mixed-6x64", "stress-12x128", "ragged"])
-def test_parity_with_restatement(name):
-    from gelato_amd import problem
-    prob, x0 = _named(name)
-    E = _engine(prob)
-    X = problem.synthetic_batch(x0, E.M, 3)
+def check_parity(E, prob, X, name):
+    """gel_mesh_error of X [B, nvars] against the restatement, within its bound -> the bound's usage [2, 4]"""
     err, diff, rc = E.mesh_error(X, want_diff=True)
     assert rc == 0
     use = np.zeros((2, 4))
@@ -46,7 +42,16 @@ def test_parity_with_restatement(name):
         for g, (a, c) in enumerate(mt.GROUP_COLS):
             use[0, g] = max(use[0, g], float((ge / be)[:, g].max()))
             use[1, g] = max(use[1, g], float((gd / bd)[:, a:c].max()))
-    USAGE[name] = use
+    return use
+
+
+@pytest.mark.parametrize("name", ["example", "mixed-6x64", "stress-12x128", "ragged"])
+def test_parity_with_restatement(name):
+    from gelato_amd import problem
+    prob, x0 = _named(name)
+    E = _engine(prob)
+    X = problem.synthetic_batch(x0, E.M, 3)
+    use = USAGE[name] = check_parity(E, prob, X, name)
     print("bound usage %s: err %s diff %s" % (name, np.array2string(use[0], precision=3), np.array2string(use[1], precision=3)))
 
 

@@ -67,11 +67,21 @@ def test_parity_with_restatement(name, k, restart):
     """y and err of the device against numpy RK4 with the oracle's right-hand sides, within 2 E (propagate_truth)"""
     prob, E, X = _case(name)
     plan = E.propagation_plan(steps=k, restart="node" if restart else "section")
+    use, worst = check_parity(E, plan, X, _reference(name, k, restart))
+    USAGE[(name, k, restart)] = use
+    print("bound usage %s k=%d %s: y %s err %s" % (name, k, "node" if restart else "section", np.array2string(use[0], precision=3),
+                                                  np.array2string(use[1], precision=3)))
+    assert all(wy <= 1.0 and we <= 1.0 for wy, we in worst), (name, k, restart, worst)
+
+
+def check_parity(E, plan, X, reference):
+    """the plan applied to X [B, nvars] against the restatement's (y, bound_y, err, bound_err) per vector -> (usage [2, 4] of the
+    bounds per group, [(worst y usage, worst err usage)] per vector: the caller asserts them <= 1)"""
     Y, err, rc = plan.apply(X)
     assert rc == 0
     use = np.zeros((2, 4))
     worst = []
-    for b, (ry, by, re, be) in enumerate(_reference(name, k, restart)):
+    for b, (ry, by, re, be) in enumerate(reference):
         gy = np.abs(pt.unpack_y(Y[b], E.M) - ry)
         ge = np.abs(err[b] - re)
         with np.errstate(divide="ignore", invalid="ignore"):
@@ -81,10 +91,7 @@ def test_parity_with_restatement(name, k, restart):
             use[0, g] = max(use[0, g], float(sy[:, a:c].max()))
             use[1, g] = max(use[1, g], float(se[:, g].max()))
         worst.append((float(sy.max()), float(se.max())))
-    USAGE[(name, k, restart)] = use
-    print("bound usage %s k=%d %s: y %s err %s" % (name, k, "node" if restart else "section", np.array2string(use[0], precision=3),
-                                                  np.array2string(use[1], precision=3)))
-    assert all(wy <= 1.0 and we <= 1.0 for wy, we in worst), (name, k, restart, worst)
+    return use, worst
 
 
 @pytest.mark.parametrize("mutate", ["no_unit_t", "hold_control", "equal_steps"])

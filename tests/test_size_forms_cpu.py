@@ -114,6 +114,19 @@ def test_mesh_vectors_per_workgroup_constant():
     assert re.search(r"q\.vpb\s*=\s*gel::kMeshMaxThreads\s*/\s*P\s*;", text)
 
 
+def test_mesh_vectors_per_workgroup_where_the_lds_binds():
+    """... unless 64 KB of LDS hold fewer beside the tables (gel_mesh.h mesh_vectors_per_group, reported by gel_table_limits): not at
+    the phases test_size_forms.py uses, 167 instead of 170 at n = 2 with the example's tables, 149 with 160 wind and 48 CA rows"""
+    from gelato_amd import _lib
+    for name, n in (("mixed-6x64", 64), ("stress-12x128", 128)):
+        E, prob, _x = SF.engine(name, device=-1)
+        assert n in [int(v) for v in E.num_nodes]
+        assert _lib.table_limits(len(prob["wind_table"]), len(prob["ca_table"]), n)["mesh_vectors"] == 512 // (n + 1), name
+    assert _lib.table_limits(7, 9, 2)["mesh_vectors"] == (8192 - 148) // 48 == 167 < 512 // 3
+    assert _lib.table_limits(160, 48, 2)["mesh_vectors"] == (8192 - 1030) // 48 == 149
+    assert _lib.table_limits(320, 32, 500)["mesh_vectors"] == 1 and _lib.table_limits(7, 9, 512)["mesh_vectors"] == -1
+
+
 def test_batch_size_helpers():
     assert SF.round_up(1) == 256 and SF.round_up(256) == 256 and SF.round_up(257) == 512
     assert SF.first_multiple_past(2 ** 31, 607424) == 3584 and 3584 * 607424 > 2 ** 31 >= 3328 * 607424
