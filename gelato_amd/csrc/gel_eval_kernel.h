@@ -1179,16 +1179,17 @@ __device__ __forceinline__ void eval_body(const ProblemDev P, int B, const doubl
     EMIT_GROUP(3, kSlotVM, vm_, CG_VM, 0, false, true);                                                                \
   } while (0)
     if (ph.air) {
-      // The Earth angle omega t enters the RHS only through the rotation of the wind into ECI (the air-relative velocity's two
-      // rotations cancel, aero_force()): a wavefront in calm air -- both wind components exactly zero in every lane, e.g. above
-      // and below the measured part of the wind table -- never needs it.  It is formed on first need (wave-uniform), its
-      // half-angle pair kept (full_angle()); position sweeps do not change it.
+      // The Earth angle omega t enters the RHS only through the wind in ECI (the air-relative velocity's two rotations cancel,
+      // aero_force()), and there only in a lane exactly ON the polar axis, whose ECI longitude it is (wind_eci(): everywhere else
+      // the wind goes by the local north and east axes of the inertial position).  It is formed on first need -- a windy lane on
+      // the axis (wind_needs_angle(), wave-uniform vote) -- its half-angle pair kept (full_angle()); position sweeps do not change
+      // it, and a wavefront that never formed it passes the identity, which no lane reads.
       EarthHalf eh{1.0, 0.0};
       bool have_eh = false;
       // the node's time once more, for the rare late first need (a load behind the stores: it waits for them)
-#define GEL_NEED_EARTH_ANGLE(wn_, we_)                                                                                 \
+#define GEL_NEED_EARTH_ANGLE(ip_, wn_, we_)                                                                            \
   do {                                                                                                                 \
-    if (!have_eh && __builtin_amdgcn_ballot_w64(!((wn_) == 0.0 && (we_) == 0.0)) != 0) {                                \
+    if (!have_eh && __builtin_amdgcn_ballot_w64(wind_needs_angle(ip_, wn_, we_)) != 0) {                                \
       int jl_ = jc;                                                                                                    \
       if (AERO) asm volatile("" : "+v"(jl_));   /* AERO: the address is formed here, not carried from the top of the kernel */ \
       const double tau_ = P.tau[ph.toff + jl_];                                                                        \
@@ -1234,9 +1235,9 @@ __device__ __forceinline__ void eval_body(const ProblemDev P, int B, const doubl
 #endif
       const bool aero_on = AERO && akinds != 0;                 // wave-uniform
       const bool a_need_alpha = AERO && (akinds & 5) != 0;      // an alpha or q-alpha row
-#define GEL_AERO_NEED_EA(wn_, we_)                                                                                     \
+#define GEL_AERO_NEED_EA(ip_, wn_, we_)                                                                                \
   do {                                                                                                                 \
-    if (!have_aeh && __builtin_amdgcn_ballot_w64(!((wn_) == 0.0 && (we_) == 0.0)) != 0) {                               \
+    if (!have_aeh && __builtin_amdgcn_ballot_w64(wind_needs_angle(ip_, wn_, we_)) != 0) {                               \
       int jl_ = jc;                                                                                                    \
       asm volatile("" : "+v"(jl_));   /* the address is formed here, not carried (and spilled) from the top of the kernel */ \
       const double tau_ = P.tau[ph.toff + jl_];                                                                        \
@@ -1298,18 +1299,21 @@ __device__ __forceinline__ void eval_body(const ProblemDev P, int B, const doubl
         const double r[3] = {fresh_product(re[0], P.up), fresh_product(re[1], P.up), fresh_product(re[2], P.up)};
         if (JAC) pp = pos_part<true, ParkSink>(r, tb, P.barC20, nullptr, ParkSink{park}, &pt);
         else pp = pos_part(r, tb, P.barC20);
-        if (__builtin_amdgcn_ballot_w64(!(pp.wn == 0.0 && pp.we == 0.0)) != 0) {   // tn is still in registers here
+        // the centre's wind is not calm in some lane (wave-uniform): what the aero rows' centre asks below
+        const bool cen_windy = AERO && __builtin_amdgcn_ballot_w64(!(pp.wn == 0.0 && pp.we == 0.0)) != 0;
+        if (__builtin_amdgcn_ballot_w64(wind_needs_angle(pp.inv_p, pp.wn, pp.we)) != 0) {   // tn is still in registers here
           const EarthAngle e0 = earth_angle(tn);
           eh.ch = e0.ch; eh.sh = e0.sh; have_eh = true;
           // AERO: con_aero's Earth angle is formed where the aero rows begin (below), from the node's time waiting in the slot that
           // cos(alpha_c) takes over there -- not here, where its pair would occupy four registers across the centre evaluation
           if (aero_on) PARK_SET(PK_ACC, tn);
         }
-        const EarthAngle ea = full_angle(eh);
+        EarthAngle ea{1.0, 0.0, 1.0, 0.0};
+        if (have_eh) ea = full_angle(eh);
         wind_eci_or_calm(r, ea, pp.shp, pp.chp, pp.inv_p, pp.wn, pp.we, w);
 #pragma unroll
         for (int c = 0; c < 3; c++) v[c] = PARK_GET(PK_V0 + c) * P.uv;
-        aero_force(r, v, pp.rho, pp.inv_a, ea, w, ph.area, tb, F, GEL_CA_BRACKET);
+        aero_force(r, v, pp.rho, pp.inv_a, w, ph.area, tb, F, GEL_CA_BRACKET);
         // thrust = T * direction is formed where it is used (T from the parked pressure): three registers instead of eight
 #define GEL_T (ph.thrust - ph.nozzle * pp.P)
 #define GEL_TDC(name) const double name[3] = {GEL_T * dir[0], GEL_T * dir[1], GEL_T * dir[2]}
@@ -1364,7 +1368,7 @@ __device__ __forceinline__ void eval_body(const ProblemDev P, int B, const doubl
 #pragma unroll
               for (int c = 0; c < 3; c++) vp[c] = ((k == c) ? (PARK_GET(PK_V0 + c) + dx) : PARK_GET(PK_V0 + c)) * P.uv;
               const double r[3] = {fresh_product(re[0], P.up), fresh_product(re[1], P.up), fresh_product(re[2], P.up)};
-              aero_force(r, vp, pp.rho, pp.inv_a, ea, w, ph.area, tb, Fp, GEL_CA_BRACKET);
+              aero_force(r, vp, pp.rho, pp.inv_a, w, ph.area, tb, Fp, GEL_CA_BRACKET);
               GEL_TDC(Tdc);
               accel(Tdc, Fp, inv_m, pp.g, inv_uv, f);
               // submat_vel[3j+c, 3(j+1)+k] = D[j][j+1]*(c==k) + rh_vel   (con_dynamics.py:341-343,415-416)
@@ -1421,16 +1425,18 @@ __device__ __forceinline__ void eval_body(const ProblemDev P, int B, const doubl
           // centre's position part is taken from where it lies by now -- the half-latitude pair from the park, 1/p and the wind
           // components formed again (geodetic_p_ih, pos_centre_tail: bit-identical) -- instead of five values kept in registers
           // across the centre evaluation
-          if (have_eh) {   // the centre's wind is not calm in some lane (wave-uniform): the node's time in seconds (lib/con_aero.py:45)
+          if (have_eh) {   // a windy lane of the centre is on the polar axis (wave-uniform): the node's time in seconds (lib/con_aero.py:45)
             const EarthAngle e1 = earth_angle(PARK_GET(PK_ACC) * P.ut);
             aeh.ch = e1.ch; aeh.sh = e1.sh; have_aeh = true;
           }
-          if (have_aeh) {
+          if (cen_windy) {
             PosCentre pcx;
             double wn_, we_, p_, ip_, ih_;
             pos_centre_tail(pt, pp.rho, pp.P, tb, pcx, wn_, we_);
             geodetic_p_ih(ra[0], ra[1], ra[2], p_, ip_, ih_);
-            wind_eci(ra, full_angle(GEL_AEH), PARK_GET(PK_LV0), PARK_GET(PK_LV1), ip_, wn_, we_, wa);
+            EarthAngle e2{1.0, 0.0, 1.0, 0.0};
+            if (have_aeh) e2 = full_angle(GEL_AEH);
+            wind_eci(ra, e2, PARK_GET(PK_LV0), PARK_GET(PK_LV1), ip_, wn_, we_, wa);
           } else {
             wa[0] = 0.0; wa[1] = 0.0; wa[2] = 0.0;
           }
@@ -1493,11 +1499,12 @@ __device__ __forceinline__ void eval_body(const ProblemDev P, int B, const doubl
 #define GEL_POS_SWEEP_F(rp, pq, f_)                                                                           \
   do {                                                                                                        \
     double wq_[3], Fp_[3];                                                                                    \
-    GEL_NEED_EARTH_ANGLE((pq).wn, (pq).we);                                                                   \
-    const EarthAngle ea = full_angle(eh);                                                                     \
+    GEL_NEED_EARTH_ANGLE((pq).inv_p, (pq).wn, (pq).we);                                                       \
+    EarthAngle ea{1.0, 0.0, 1.0, 0.0};                                                                        \
+    if (have_eh) ea = full_angle(eh);                                                                         \
     wind_eci_or_calm(rp, ea, (pq).shp, (pq).chp, (pq).inv_p, (pq).wn, (pq).we, wq_);                          \
     const double vq_[3] = {PARK_GET(PK_V0) * P.uv, PARK_GET(PK_V1) * P.uv, PARK_GET(PK_V2) * P.uv};           \
-    aero_force(rp, vq_, (pq).rho, (pq).inv_a, ea, wq_, ph.area, tb, Fp_, GEL_CA_BRACKET);                     \
+    aero_force(rp, vq_, (pq).rho, (pq).inv_a, wq_, ph.area, tb, Fp_, GEL_CA_BRACKET);                         \
     const double Tp_ = ph.thrust - ph.nozzle * (pq).P;                                                        \
     const double Td_[3] = {Tp_ * PARK_GET(PK_Q3), Tp_ * PARK_GET(PK_DJJ), Tp_ * dir2};                        \
     accel(Td_, Fp_, inv_m, (pq).g, inv_uv, f_);                                                               \
@@ -1512,8 +1519,10 @@ __device__ __forceinline__ void eval_body(const ProblemDev P, int B, const doubl
 #define GEL_AERO_POS(kk, rp, pq, okl_)                                                                        \
   do {                                                                                                        \
     double wq_[3], a_[3];                                                                                     \
-    GEL_AERO_NEED_EA((pq).wn, (pq).we);                                                                       \
-    wind_eci_or_calm(rp, full_angle(GEL_AEH), (pq).shp, (pq).chp, (pq).inv_p, (pq).wn, (pq).we, wq_);             \
+    GEL_AERO_NEED_EA((pq).inv_p, (pq).wn, (pq).we);                                                           \
+    EarthAngle ea_{1.0, 0.0, 1.0, 0.0};                                                                       \
+    if (have_aeh) ea_ = full_angle(GEL_AEH);                                                                  \
+    wind_eci_or_calm(rp, ea_, (pq).shp, (pq).chp, (pq).inv_p, (pq).wn, (pq).we, wq_);                         \
     const double vq_[3] = {PARK_GET(PK_V0) * P.uv, PARK_GET(PK_V1) * P.uv, PARK_GET(PK_V2) * P.uv};           \
     const double nv2_ = aero_vair2(rp, vq_, wq_, a_);                                                         \
     const double dd_[3] = {PARK_GET(PK_Q3), PARK_GET(PK_DJJ), dir2};                                          \
@@ -1638,9 +1647,9 @@ __device__ __forceinline__ void eval_body(const ProblemDev P, int B, const doubl
           const EarthAngle eq = earth_angle(tnp);
           double wq[3], Fp[3], f[3];
           const double rq[3] = {re[0] * P.up, re[1] * P.up, re[2] * P.up};
-          wind_eci_or_calm(rq, eq, PARK_GET(PK_FP0), PARK_GET(PK_FP1), PARK_GET(PK_FP2), PARK_GET(PK_FP3), PARK_GET(PK_FP4), wq);
+          wind_eci_chain_or_calm(rq, eq, PARK_GET(PK_FP0), PARK_GET(PK_FP1), PARK_GET(PK_FP2), PARK_GET(PK_FP3), PARK_GET(PK_FP4), wq);
           const double vq[3] = {PARK_GET(PK_V0) * P.uv, PARK_GET(PK_V1) * P.uv, PARK_GET(PK_V2) * P.uv};
-          aero_force(rq, vq, PARK_GET(PK_FP5), PARK_GET(PK_FP6), eq, wq, ph.area, tb, Fp, GEL_CA_BRACKET);
+          aero_force(rq, vq, PARK_GET(PK_FP5), PARK_GET(PK_FP6), wq, ph.area, tb, Fp, GEL_CA_BRACKET);
           const double Tq[3] = {PARK_GET(PK_Q0), PARK_GET(PK_Q1), PARK_GET(PK_Q2)};
           const double gq[3] = {PARK_GET(PK_LV0), PARK_GET(PK_LV1), PARK_GET(PK_LV2)};
           accel(Tq, Fp, inv_m, gq, inv_uv, f);

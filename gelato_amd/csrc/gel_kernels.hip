@@ -169,7 +169,7 @@ __global__ void rhs_vel_air_kernel(RhsArgs A) {
   const EarthAngle ea = earth_angle(A.t[i]);
   double w[3], F[3], dir[3], f[3];
   wind_eci(r, ea, pp.shp, pp.chp, pp.inv_p, pp.wn, pp.we, w);
-  aero_force(r, v, pp.rho, pp.inv_a, ea, w, A.area, tb, F);
+  aero_force(r, v, pp.rho, pp.inv_a, w, A.area, tb, F);
   thrust_dir(q, dir);
   const double T = A.thrust - A.nozzle * pp.P;
   const double Td[3] = {T * dir[0], T * dir[1], T * dir[2]};
@@ -477,12 +477,13 @@ __device__ __forceinline__ void aero_body(const ProblemDev P, int nnodes, const 
   // Calm air [r5]: where both wind components of every lane are exactly zero (below and above the measured part of the wind table: in
   // the shipped example below 1 km and from 23 km up) the rotation of the zero vector into ECI is the zero vector -- wind_eci_or_calm()
   // skips its ~70 instructions, four times per tile -- and the Earth angle, which enters the air-relative velocity only through that
-  // rotation (aero_vair2), is not formed at all (as in the fused kernel).  A sweep whose perturbed point leaves the calm (a step across
-  // the table's end: the recomputing fallback) forms it on first need, from the node's time read again.
+  // rotation (aero_vair2), is not formed at all (as in the fused kernel).  Nor is it where the air moves: wind_eci() reads the angle
+  // only in a lane exactly on the polar axis, so the vote is wind_needs_angle() -- windy AND on the axis -- at the centre and, from
+  // the node's time read again, in any sweep whose perturbed point is the first to need it.
   bool have_ea = false;
-#define GEL_AERO_NEED_EA(wn_, we_)                                                                                     \
+#define GEL_AERO_NEED_EA(ip_, wn_, we_)                                                                                \
   do {                                                                                                                 \
-    if (!have_ea && __builtin_amdgcn_ballot_w64(!((wn_) == 0.0 && (we_) == 0.0)) != 0) {                                \
+    if (!have_ea && __builtin_amdgcn_ballot_w64(wind_needs_angle(ip_, wn_, we_)) != 0) {                                \
       const int kn_ = nodes[ni].k, phn_ = nodes[ni].phase;                                                             \
       const double to_ = xb[11 * M + 2 * N + phn_], tf_ = xb[11 * M + 2 * N + phn_ + 1];                               \
       const double tau_ = (kn_ == 0) ? 0.0 : P.tau[P.phases[phn_].toff + kn_ - 1];                                     \
@@ -501,7 +502,7 @@ __device__ __forceinline__ void aero_body(const ProblemDev P, int nnodes, const 
     PosCentreTail pt;
     pp = pos_part<true, PosCentreSink, false>(r, tb, 0.0, nullptr, PosCentreSink{&pc}, &pt);
     pos_centre_tail(pt, pp.rho, pp.P, tb, pc, pp.wn, pp.we);
-    GEL_AERO_NEED_EA(pp.wn, pp.we);
+    GEL_AERO_NEED_EA(pp.inv_p, pp.wn, pp.we);
     wind_eci_or_calm(r, ea, pp.shp, pp.chp, pp.inv_p, pp.wn, pp.we, w);
     const double nv2 = aero_vair2(r, v, w, a0);
     thrust_dir(q, dir);
@@ -603,7 +604,7 @@ __device__ __forceinline__ void aero_body(const ProblemDev P, int nnodes, const 
         const double r[3] = {fresh_product(re[0], P.up), fresh_product(re[1], P.up), fresh_product(re[2], P.up)};
         const double vq[3] = {xb[4 * M + 3 * xi] * P.uv, xb[4 * M + 3 * xi + 1] * P.uv, xb[4 * M + 3 * xi + 2] * P.uv};
         double wq[3], aq[3];
-        wind_eci(r, eq, pp.shp, pp.chp, pp.inv_p, pp.wn, pp.we, wq);
+        wind_eci_chain(r, eq, pp.shp, pp.chp, pp.inv_p, pp.wn, pp.we, wq);   // the reference's chain: see wind_eci_chain_or_calm()
         const double nvq = aero_vair2(r, vq, wq, aq);
         const double dq[3] = {AP_GET(AP_DIR), AP_GET(AP_DIR + 1), AP_GET(AP_DIR + 2)};
         GEL_AERO_EMIT(-1, 2, c, aq, nvq, dq, AP_GET(AP_IND), pp.rho, false, false, false);
@@ -616,7 +617,7 @@ __device__ __forceinline__ void aero_body(const ProblemDev P, int nnodes, const 
 #define GEL_AERO_POS_TAIL(c, rp, pq, skip_)                                                          \
   do {                                                                                               \
     double wq_[3], a_[3];                                                                            \
-    GEL_AERO_NEED_EA((pq).wn, (pq).we);                                                              \
+    GEL_AERO_NEED_EA((pq).inv_p, (pq).wn, (pq).we);                                                  \
     wind_eci_or_calm(rp, ea, (pq).shp, (pq).chp, (pq).inv_p, (pq).wn, (pq).we, wq_);                 \
     const double vq_[3] = {xb[4 * M + 3 * xi] * P.uv, xb[4 * M + 3 * xi + 1] * P.uv, xb[4 * M + 3 * xi + 2] * P.uv}; \
     const double nv2_ = aero_vair2(rp, vq_, wq_, a_);                                                \

@@ -97,7 +97,7 @@ __global__ __launch_bounds__(kExactBlock) void exact_jac_kernel(ProblemDev P, in
     double wv[3], F[3];
     wind_eci_or_calm(r, ea, pp.shp, pp.chp, pp.inv_p, pp.wn, pp.we, wv);
     const double v[3] = {ve[0] * P.uv, ve[1] * P.uv, ve[2] * P.uv};
-    aero_force(r, v, pp.rho, pp.inv_a, ea, wv, ph.area, tb, F);
+    aero_force(r, v, pp.rho, pp.inv_a, wv, ph.area, tb, F);
     T = ph.thrust - ph.nozzle * pp.P;
     {
       const double Td[3] = {T * dir[0], T * dir[1], T * dir[2]};

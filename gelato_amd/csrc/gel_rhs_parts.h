@@ -3,7 +3,7 @@
 //
 //   pos_part(r)            atmosphere, wind (NED), gravity, geodetic latitude   <- position only
 //   earth_angle(t)         cos/sin(omega t), cos/sin(omega t / 2)               <- time only
-//   wind_eci(r, ea, ...)   wind rotated NED -> ECI                              <- position, time
+//   wind_eci(r, ea, ...)   wind NED -> ECI by the local north / east axes       <- position (time on the polar axis only)
 //   aero_force(...)        axial aerodynamic force                               <- velocity + the above
 //   accel(...)             (thrust + aero)/m + g, normalised                     <- mass, thrust direction
 //
@@ -233,14 +233,36 @@ GEL_DEV EarthAngle earth_angle(double t) {
 
 // Wind vector in ECI = quatrot(quat_nedg2eci(pos, t), wind_ned)  (src/pybind_dynamics.cpp:51-52).
 // quat_nedg2eci = conj( q_eci2ecef(t) * q_ecef2ned( Rz(-omega t) pos ) )  (src/Coordinate.cpp:75-110).
-// The reference re-runs the Bowring latitude on the rotated position (Coordinate.cpp:86); a rotation
-// about z leaves (sqrt(x^2+y^2), z) and therefore the latitude unchanged, so pos_part's latitude is
-// reused (equal to a recomputation up to rounding).  The longitude IS taken from the rotated position;
-// the reference forms lon = atan2(py, px) and uses only cos/sin(lon/2) (Coordinate.cpp:87-88): they are
-// obtained from (cos lon, sin lon) = (px, py)/p by the half-angle identities, on the branch that has no
-// cancellation (lon/2 in (-pi/2, pi/2], so cos(lon/2) >= 0).
-GEL_DEV void wind_eci(const double r[3], const EarthAngle& e, double s_hp, double c_hp, double inv_p, double wn,
-                      double we, double w[3]) {
+// Off the polar axis the two rotations by omega t cancel and the chain composes to the wind along the local north and east
+// axes at the ECI longitude lon, (cos lon, sin lon) = (x, y)/p:
+//   w = wn N + we E,   N = (-sin lat cos lon, -sin lat sin lon, cos lat),   E = (-sin lon, cos lon, 0)
+// -- no Earth angle, no half-angle chain, no transcendental (the identity wind_eci_tangent(), gel_exact.h, differentiates).
+// Exactly on the axis (inv_p == 0) the reference's atan2(0, 0) makes the ECEF longitude 0, the rotation back to ECI makes the
+// ECI longitude omega t, and the Earth angle is the longitude: (cos lon, sin lon) = (e.c, e.s).  Those lanes alone read e; a
+// caller whose lanes are all off the axis need not form it.
+// The reference re-runs the Bowring latitude on the rotated position (Coordinate.cpp:86); a rotation about z leaves
+// (sqrt(x^2+y^2), z) and therefore the latitude unchanged, so pos_part's half-latitude pair is reused, and sin / cos lat formed
+// from it by the double-angle identities.  The roundings are pinned (fresh_mul, explicit fma): every kernel that calls this
+// gets the same bits whatever surrounds the call.
+// GEL_WIND_CHAIN=1 (ablation; needs the Earth angle in every windy lane, so it also turns the fused kernels' on-axis vote
+// back into the any-lane-windy one): the reference's quaternion chain operation by operation (wind_eci_chain()) -- the longitude taken from
+// the rotated position as (cos lon, sin lon) = (px, py)/p, its half-angle pair by the half-angle identities on the branch
+// that has no cancellation (lon/2 in (-pi/2, pi/2], so cos(lon/2) >= 0), ~90 instructions.
+#ifndef GEL_WIND_CHAIN
+#define GEL_WIND_CHAIN 0
+#endif
+// does this lane's wind_eci() read the Earth angle?  (the vote the fused kernels take before they form it)
+GEL_DEV bool wind_needs_angle(double inv_p, double wn, double we) {
+  const bool windy = !(wn == 0.0 && we == 0.0);
+#if GEL_WIND_CHAIN
+  return windy;
+#else
+  return windy && !(inv_p > 0.0);
+#endif
+}
+// the reference's chain, operation by operation: GEL_WIND_CHAIN, and the t0 / tf sweeps of GEL_FLAG_FD_RECOMPUTE (below)
+GEL_DEV void wind_eci_chain(const double r[3], const EarthAngle& e, double s_hp, double c_hp, double inv_p, double wn,
+                            double we, double w[3]) {
   // eci2ecef(pos, t): src/Coordinate.cpp:51-59
   const double px = r[0] * e.c + r[1] * e.s;
   const double py = -r[0] * e.s + r[1] * e.c;
@@ -268,11 +290,27 @@ GEL_DEV void wind_eci(const double r[3], const EarthAngle& e, double s_hp, doubl
   w[1] = q0 * t2 + q1 * t3 - q2 * t0 - q3 * t1;
   w[2] = q0 * t3 - q1 * t2 + q2 * t1 - q3 * t0;
 }
+GEL_DEV void wind_eci(const double r[3], const EarthAngle& e, double s_hp, double c_hp, double inv_p, double wn,
+                      double we, double w[3]) {
+#if GEL_WIND_CHAIN
+  wind_eci_chain(r, e, s_hp, c_hp, inv_p, wn, we, w);
+#else
+  const bool off_axis = inv_p > 0.0;
+  const double clon = off_axis ? r[0] * inv_p : e.c;
+  const double slon = off_axis ? r[1] * inv_p : e.s;
+  const double sl = fresh_mul(2.0 * s_hp, c_hp);
+  const double cl = fresh_mul(c_hp - s_hp, c_hp + s_hp);
+  const double nh = -fresh_mul(wn, sl);   // the north component's horizontal part, along (cos lon, sin lon)
+  w[0] = __builtin_fma(nh, clon, -fresh_mul(we, slon));
+  w[1] = __builtin_fma(nh, slon, fresh_mul(we, clon));
+  w[2] = fresh_mul(wn, cl);
+#endif
+}
 
 // wind_eci unless the whole wavefront is in calm air: where both wind components are exactly zero (below / above the
 // measured part of a wind table, as in the shipped example from 23 km up) the rotation of the zero vector is the zero
-// vector, so its ~110 instructions are skipped -- six times per node in the fused kernel.  Non-finite components are not
-// zero and take the full path.
+// vector, so the call is skipped -- six times per node in the fused kernel (~110 instructions each with the quaternion
+// chain, GEL_WIND_CHAIN; some 20 with the local axes).  Non-finite components are not zero and take the full path.
 GEL_DEV void wind_eci_or_calm(const double r[3], const EarthAngle& e, double s_hp, double c_hp, double inv_p, double wn,
                               double we, double w[3]) {
 #if GEL_CALM_SHORTCUT
@@ -283,29 +321,34 @@ GEL_DEV void wind_eci_or_calm(const double r[3], const EarthAngle& e, double s_h
 #endif
   wind_eci(r, e, s_hp, c_hp, inv_p, wn, we, w);
 }
+// The t0 / tf sweeps of GEL_FLAG_FD_RECOMPUTE (the audit form: what the reference's own sweeps give) move nothing but the Earth
+// angle, which the local-axes form does not read off the polar axis -- it would return the centre's bits and the columns would be
+// exact zeros, which the reference's are not: its two runs of the chain differ by their rounding.  These sweeps therefore
+// evaluate the perturbed point with the reference's chain and the perturbed angle, like the reference does.
+GEL_DEV void wind_eci_chain_or_calm(const double r[3], const EarthAngle& e, double s_hp, double c_hp, double inv_p, double wn,
+                                    double we, double w[3]) {
+#if GEL_CALM_SHORTCUT
+  if (__builtin_amdgcn_ballot_w64(!(wn == 0.0 && we == 0.0)) == 0) {   // wave-uniform branch
+    w[0] = 0.0; w[1] = 0.0; w[2] = 0.0;
+    return;
+  }
+#endif
+  wind_eci_chain(r, e, s_hp, c_hp, inv_p, wn, we, w);
+}
 
 // aerodynamic force (ECI): src/pybind_dynamics.cpp:48-59 given the shared parts.
 // Air-relative velocity: the reference forms vel_eci2ecef(v, r, t) = Rz(-omega t) (v - omega x r) and then rotates it straight
 // back, ecef2eci(., t) = Rz(+omega t) (src/Coordinate.cpp:69-73, 41-49, src/pybind_dynamics.cpp:48,53).  The two rotations
-// cancel; they are not performed here (GEL_AERO_ROTATE=1 restores them): v - omega x r - w_eci differs from the round trip by
-// its rounding (<= 4 ulp of |v|, i.e. 1e-15 of the force), identically in the centre and in every perturbed evaluation.
-#ifndef GEL_AERO_ROTATE
-#define GEL_AERO_ROTATE 0
-#endif
-GEL_DEV void aero_force(const double r[3], const double v[3], double rho, double inv_a_sound, const EarthAngle& e,
-                        const double w[3], double area, const Tables& tb, double F[3], Bracket* br = nullptr) {
+// cancel and are not performed: v - omega x r - w_eci differs from the round trip by its rounding (<= 4 ulp of |v|, i.e. 1e-15
+// of the force), identically in the centre and in every perturbed evaluation.  With the wind by the local axes (wind_eci())
+// nothing on this path reads the Earth angle off the polar axis.
+GEL_DEV void aero_force(const double r[3], const double v[3], double rho, double inv_a_sound, const double w[3], double area,
+                        const Tables& tb, double F[3], Bracket* br = nullptr) {
   // omega x r = (-w y, w x, 0)
   const double d0 = v[0] + kOmega * r[1];
   const double d1 = v[1] - kOmega * r[0];
-#if GEL_AERO_ROTATE
-  const double e0 = d0 * e.c + d1 * e.s;
-  const double e1 = -d0 * e.s + d1 * e.c;
-  const double a0 = (e0 * e.c - e1 * e.s) - w[0];
-  const double a1 = (e0 * e.s + e1 * e.c) - w[1];
-#else
   const double a0 = d0 - w[0];
   const double a1 = d1 - w[1];
-#endif
   const double a2 = v[2] - w[2];
   // a vehicle at rest in the air (vn = 0) is a legitimate input: clamp below anything physical so that
   // fsqrt stays defined; the force is k * (-a) = 0 either way

@@ -31,7 +31,7 @@ GEL_DEV void section_rhs(const ProblemDev& P, const PhaseDev& ph, const Tables& 
     const EarthAngle ea = earth_angle(sig * (tf - to) / 2 + (tf + to) / 2);
     double w[3], Fa[3];
     wind_eci_or_calm(r, ea, pp.shp, pp.chp, pp.inv_p, pp.wn, pp.we, w);
-    aero_force(r, v3, pp.rho, pp.inv_a, ea, w, ph.area, tb, Fa);
+    aero_force(r, v3, pp.rho, pp.inv_a, w, ph.area, tb, Fa);
     const double T = ph.thrust - ph.nozzle * pp.P;
     const double Td[3] = {T * dir[0], T * dir[1], T * dir[2]};
     accel(Td, Fa, 1.0 / m, pp.g, P.inv_uv, f);
