@@ -19,6 +19,8 @@ GEL_FLAG_EXACT_DEFECT_JAC = 32   # defect-group Jacobians exact to rounding (for
 GEL_FLAG_EXACT_AERO_JAC = 64     # aero path constraints' gradients exact to rounding (forward mode) instead of forward differences
 GEL_INTERP_UNIT_QUAT = 1         # gel_interp_plan_create*: rows that are not copies get q / sqrt(q . q)
 GEL_PROP_RESTART_NODE = 1        # gel_prop_plan_create: every node interval starts from the collocated state (the local defect)
+GEL_PROP_CHAIN = 2               # gel_prop_plan_create: one integration per vector through all phases, the state carried across the knots (the flight)
+GEL_PROP_NDISP = 4               # gel_propagate_dispersed*: factors per (vector, phase): thrust, mass flow, reference area, wind
 GEL_FLAG_EXACT_ROWS_JAC = 128    # node-function rows' jfn (terminal, user, waypoint rows) exact to rounding instead of forward differences
 NUM_BLOCKS = 13
 
@@ -154,6 +156,8 @@ SIGNATURES = {
     "gel_prop_matrices": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, _ip]),
     "gel_propagate": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, _dp]),
     "gel_propagate_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gel_propagate_dispersed": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, _dp, _dp]),
+    "gel_propagate_dispersed_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gel_initial_guess": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, _dp, _dp]),
     "gel_output_table": (C.c_int, [C.c_void_p, _dp, _dp, C.c_double, C.c_double, _dp]),
     "gel_dynamics_velocity": (C.c_int, [C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int32, _dp, C.c_int32,

@@ -3035,15 +3035,21 @@ static int64_t prop_slab(const gel_prop_plan* pl) {
 }
 
 int gel_prop_plan_create(gel_problem* src, const int32_t* steps, int32_t flags, gel_prop_plan** out) {
-  if (!src || !steps || !out || (flags & ~GEL_PROP_RESTART_NODE)) return fail(GEL_ERR_ARG, "bad argument");
+  if (!src || !steps || !out || (flags & ~(GEL_PROP_RESTART_NODE | GEL_PROP_CHAIN))) return fail(GEL_ERR_ARG, "bad argument");
+  if ((flags & GEL_PROP_RESTART_NODE) && (flags & GEL_PROP_CHAIN))
+    return fail(GEL_ERR_ARG, "propagation plan: GEL_PROP_CHAIN and GEL_PROP_RESTART_NODE exclude each other");
   const int S = src->dims.S;
-  int64_t mat_doubles = 0;
+  const bool chain = (flags & GEL_PROP_CHAIN) != 0;
+  int64_t mat_doubles = 0, chain_steps = 0;
   for (int s = 0; s < S; s++) {
     if (steps[s] < 1) return fail(GEL_ERR_ARG, "propagation plan: steps < 1");
     if ((int64_t)steps[s] * src->ph[s].n > gel::kPropMaxLaneSteps)
       return fail(GEL_ERR_ARG, "propagation plan: steps[s] n_s exceeds 2^20 RK4 steps in one section");
     mat_doubles += (2 * (int64_t)steps[s] * src->ph[s].n + 1) * src->ph[s].n;
+    chain_steps += (int64_t)steps[s] * src->ph[s].n;   // (at most S 2^20: no overflow)
   }
+  if (chain && chain_steps > gel::kPropMaxLaneSteps)
+    return fail(GEL_ERR_ARG, "propagation plan: the sum of steps[s] n_s exceeds 2^20 RK4 steps in one chained flight");
   if (mat_doubles > kPropMaxMatDoubles) return fail(GEL_ERR_ARG, "propagation plan: the control matrices (sum of (2 k n + 1) n doubles) exceed 1 GB");
   std::unique_ptr<gel_prop_plan> pl(new gel_prop_plan);
   pl->src = src;
@@ -3066,7 +3072,7 @@ int gel_prop_plan_create(gel_problem* src, const int32_t* steps, int32_t flags, 
     q.pt0 = pl->sampled_pts;
     if (q.sampled) { pl->sampled_pts += Pp; pl->n_max_sampled = std::max(pl->n_max_sampled, n); }
     pl->total_pts += Pp;
-    pl->lane_steps = std::max<int64_t>(pl->lane_steps, restart ? k : (int64_t)k * n);
+    pl->lane_steps = chain ? chain_steps : std::max<int64_t>(pl->lane_steps, restart ? k : (int64_t)k * n);
     std::vector<ld> tx(n + 1), tc(n);
     tx[0] = -1.0L;
     for (int j = 0; j < n; j++) tx[j + 1] = tc[j] = (ld)h.tau[j];
@@ -3105,7 +3111,7 @@ int gel_prop_plan_create(gel_problem* src, const int32_t* steps, int32_t flags, 
     }
   }
   gel::PropDev& d = pl->dev;
-  d.S = S; d.restart = restart ? 1 : 0; d.nseg = (int32_t)seg_phase.size(); d.pad = 0;
+  d.S = S; d.restart = restart ? 1 : 0; d.nseg = (int32_t)seg_phase.size(); d.chain = chain ? 1 : 0;
   d.vp = src->uv / src->up;
   if (src->device != GEL_DEVICE_NONE) {
     if (gel::prop_sample_lds_bytes(pl->n_max_sampled) > gel::kPropMaxLds)
@@ -3151,7 +3157,8 @@ int gel_prop_matrices(const gel_prop_plan* plan, int32_t phase, double* pts, dou
 }
 
 // the launches of one call on stream s: slab after slab the control samples and the integration, then err of all B vectors
-static int prop_enqueue(gel_prop_plan* plan, int32_t B, const double* d_x, double* d_y, double* d_err, hipStream_t s) {
+static int prop_enqueue(gel_prop_plan* plan, int32_t B, const double* d_x, double* d_y, double* d_err, const double* d_disp,
+                        hipStream_t s) {
   gel_problem* p = plan->src;
   const int64_t vs = prop_slab(plan), ldv = std::min<int64_t>(vs, ((int64_t)B + 63) / 64 * 64);
   const size_t need = (size_t)ldv * 2 * (size_t)plan->sampled_pts;
@@ -3159,33 +3166,43 @@ static int prop_enqueue(gel_prop_plan* plan, int32_t B, const double* d_x, doubl
     HIPCHK(drain(p));   // an earlier call in flight, on the handle's stream or on the caller's, still reads the old block
     HIPCHK(plan->d_ws.reserve(need));
   }
-  const size_t nv = (size_t)p->dims.num_vars, ny = (size_t)11 * p->dims.M;
+  const size_t nv = (size_t)p->dims.num_vars, ny = (size_t)11 * p->dims.M, nd = (size_t)p->dims.S * GEL_PROP_NDISP;
   for (int64_t v0 = 0; v0 < B; v0 += vs) {
     const int nb = (int)std::min<int64_t>(vs, B - v0);
     HIPCHK(gel::launch_prop_slab(p->dev, plan->dev, plan->ph.data(), plan->n_max_sampled, nb, d_x + (size_t)v0 * nv,
-                                 d_y + (size_t)v0 * ny, plan->d_ws.get(), ldv, s));
+                                 d_y + (size_t)v0 * ny, plan->d_ws.get(), ldv, d_disp ? d_disp + (size_t)v0 * nd : nullptr, s));
   }
   if (d_err) HIPCHK(gel::launch_prop_err(p->dev, plan->dev, B, d_x, d_y, d_err, s));
   return GEL_OK;
 }
 
-int gel_propagate_device(gel_prop_plan* plan, int32_t B, const double* d_x, double* d_y, double* d_err) {
+int gel_propagate_dispersed_device(gel_prop_plan* plan, int32_t B, const double* d_x, const double* d_disp, double* d_y,
+                                   double* d_err) {
   if (!plan || B < 0 || (B > 0 && (!d_x || !d_y))) return fail(GEL_ERR_ARG, "bad argument");
   gel_problem* p = plan->src;
   NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
   if (B == 0) return GEL_OK;
   HIPCHK(hipSetDevice(p->device));
-  return prop_enqueue(plan, B, d_x, d_y, d_err, p->stream.get());
+  return prop_enqueue(plan, B, d_x, d_y, d_err, d_disp, p->stream.get());
 }
 
-int gel_propagate(gel_prop_plan* plan, int32_t B, const double* x, double* y, double* err) {
+int gel_propagate_device(gel_prop_plan* plan, int32_t B, const double* d_x, double* d_y, double* d_err) {
+  return gel_propagate_dispersed_device(plan, B, d_x, nullptr, d_y, d_err);
+}
+
+int gel_propagate_dispersed(gel_prop_plan* plan, int32_t B, const double* x, const double* disp, double* y, double* err) {
   if (!plan || B < 0 || (B > 0 && (!x || !y))) return fail(GEL_ERR_ARG, "bad argument");
   gel_problem* p = plan->src;
   NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
   if (B == 0) return GEL_OK;
   HIPCHK(hipSetDevice(p->device));
-  return staged_call(p, 0, {staged_in(x, (size_t)B * p->dims.num_vars), staged_out(y, (size_t)B * 11 * p->dims.M), staged_out(err, (size_t)B * p->dims.S * 4)},
-                     [&](const gel::ProblemDev&, double* const* a) { return prop_enqueue(plan, B, a[0], a[1], a[2], p->stream.get()); });
+  return staged_call(p, 0, {staged_in(x, (size_t)B * p->dims.num_vars), staged_out(y, (size_t)B * 11 * p->dims.M), staged_out(err, (size_t)B * p->dims.S * 4),
+                            staged_in(disp, (size_t)B * p->dims.S * GEL_PROP_NDISP)},
+                     [&](const gel::ProblemDev&, double* const* a) { return prop_enqueue(plan, B, a[0], a[1], a[2], a[3], p->stream.get()); });
+}
+
+int gel_propagate(gel_prop_plan* plan, int32_t B, const double* x, double* y, double* err) {
+  return gel_propagate_dispersed(plan, B, x, nullptr, y, err);
 }
 
 // ------------- Jacobian products from the compact values -------------

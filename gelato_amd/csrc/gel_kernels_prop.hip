@@ -10,6 +10,9 @@
 //                        the step count are wave-uniform and the two control samples of a stage are one coalesced load each.
 //                        The step is written down in gel_prop.h.  The loop lengths n and k come from the plan's tables, which
 //                        creation bounds (k n <= 2^20): a launch always ends.
+//                        Template parameters: kChain (GEL_PROP_CHAIN) one lane = one vector through ALL phases, the state carried
+//                        across the knots; kDisp (gel_propagate_dispersed*) per (vector, phase) factors of thrust, mass flow,
+//                        reference area and wind.  <false, false> is the kernel as it was before the template.
 //   prop_err_kernel      err [B][S][4] from x and y: one lane = one (vector, phase), nodes in ascending order
 // fp64 throughout; the right-hand side is section_rhs (gel_section_rhs.h), the one mesh_kernel evaluates.
 #include <hip/hip_runtime.h>
@@ -93,66 +96,94 @@ __global__ __launch_bounds__(kPropSampleThreads) void prop_sample_kernel(Problem
   }
 }
 
+// kDisp (gel_propagate_dispersed*): disp [nb][S][kPropNDisp]; the lane's four factors of a phase scale the phase record once (thrust,
+// mass flow, reference area: one product each) and the interpolated wind inside section_rhs.
+// kChain (GEL_PROP_CHAIN): one lane = one vector, which walks the phases in order and carries its state across the knots; a
+// workgroup = kPropThreads consecutive vectors, so the phase stays wave-uniform.  Without either the code is the one-segment body.
+template <bool kDisp, bool kChain>
 __global__ __launch_bounds__(kPropThreads) void prop_kernel(ProblemDev P, PropDev Pd, int nb, const double* __restrict__ x,
-                                                            double* __restrict__ y, const double* __restrict__ ws, long long ld) {
+                                                            double* __restrict__ y, const double* __restrict__ ws, long long ld,
+                                                            const double* __restrict__ disp) {
   extern __shared__ double lds[];
-  // workgroup -> (segment, group of kPropThreads vectors)
+  // workgroup -> (segment, group of kPropThreads vectors); chain mode: the group alone
   const int ngrp = (nb + kPropThreads - 1) / kPropThreads;
-  const int seg = blockIdx.x / ngrp, grp = blockIdx.x - seg * ngrp;
+  const int seg = kChain ? 0 : blockIdx.x / ngrp, grp = blockIdx.x - seg * ngrp;
   const Tables tb = stage_tables(P, lds);
   const int v = grp * kPropThreads + (int)threadIdx.x;
   if (seg >= Pd.nseg || v >= nb) return;   // (idle lanes leave: they stay out of the calm-air vote of wind_eci_or_calm; no barrier follows)
-  const int s = load_const(&Pd.seg_phase[seg]);
-  const PhaseDev ph = load_phase(P.phases + s);
-  const int n = load_const(&Pd.ph[s].n), k = load_const(&Pd.ph[s].k), sampled = load_const(&Pd.ph[s].sampled);
-  const int j0 = Pd.restart ? seg - load_const(&Pd.ph[s].seg0) : 0, j1 = Pd.restart ? j0 + 1 : n;
-  const double* const sig = Pd.mat + load_const(&Pd.ph[s].sg);
-  const double* const hs = Pd.mat + load_const(&Pd.ph[s].hs);
-  const double* const us = ws + (size_t)load_const(&Pd.ph[s].pt0) * 2 * (size_t)ld + v;
-  const int M = P.M, N = P.N;
-  const double* const xb = x + (size_t)v * P.nvars;
-  double* const yb = y + (size_t)v * 11 * (size_t)M;
-  const double to = xb[11 * M + 2 * N + s], tf = xb[11 * M + 2 * N + s + 1];
-  const double S = (tf - to) * P.ut / 2.0;
   bool bad = false;
-
   double yv[11];
+  int s = kChain ? 0 : load_const(&Pd.seg_phase[seg]);
+  do {
+    PhaseDev ph = load_phase(P.phases + s);
+    const int n = load_const(&Pd.ph[s].n), k = load_const(&Pd.ph[s].k), sampled = load_const(&Pd.ph[s].sampled);
+    const int j0 = (!kChain && Pd.restart) ? seg - load_const(&Pd.ph[s].seg0) : 0, j1 = (!kChain && Pd.restart) ? j0 + 1 : n;
+    const double* const sig = Pd.mat + load_const(&Pd.ph[s].sg);
+    const double* const hs = Pd.mat + load_const(&Pd.ph[s].hs);
+    const double* const us = ws + (size_t)load_const(&Pd.ph[s].pt0) * 2 * (size_t)ld + v;
+    const int M = P.M, N = P.N;
+    const double* const xb = x + (size_t)v * P.nvars;
+    double* const yb = y + (size_t)v * 11 * (size_t)M;
+    const double to = xb[11 * M + 2 * N + s], tf = xb[11 * M + 2 * N + s + 1];
+    const double S = (tf - to) * P.ut / 2.0;
+    double fw = 1.0;
+    if constexpr (kDisp) {
+      const double* const fac = disp + ((size_t)v * Pd.S + s) * kPropNDisp;
+      const double f_thrust = fac[0], f_mf = fac[1], f_area = fac[2];
+      fw = fac[3];
+      ph.thrust = ph.thrust * f_thrust;
+      ph.mf_um = ph.mf_um * f_mf;
+      ph.area = ph.area * f_area;
+    }
+
+    if (kChain && s > 0) {
+      // across the knot the collocated jump x(first node of s) - x(last node of s - 1) is added to the carried state; a zero jump
+      // carries the bits (y + 0 would turn a -0 into +0)
 #pragma unroll
-  for (int c = 0; c < 11; c++) yv[c] = xb[state_index(M, ph.xa + j0, c)];
-  if (j0 == 0) {   // node xa: X_0 bit for bit
+      for (int c = 0; c < 11; c++) {
+        const double jump = xb[state_index(M, ph.xa, c)] - xb[state_index(M, ph.xa - 1, c)];
+        yv[c] = (jump == 0.0) ? yv[c] : yv[c] + jump;
+      }
+    } else {
 #pragma unroll
-    for (int c = 0; c < 11; c++) { yb[state_index(M, ph.xa, c)] = yv[c]; bad |= nonfinite(yv[c]); }
-  }
-  for (int j = j0; j < j1; j++) {
-    const double Sh = S * hs[j], Sh2 = Sh * 0.5, Sh6 = Sh / 6.0;
-    for (int i = 0; i < k; i++) {
-      const int p = 2 * (k * j + i);
-      double acc[11], F[11];
+      for (int c = 0; c < 11; c++) yv[c] = xb[state_index(M, ph.xa + j0, c)];
+    }
+    if (j0 == 0) {   // node xa: X_0 bit for bit (chain mode beyond phase 0: the carried state)
 #pragma unroll
-      for (int c = 0; c < 11; c++) acc[c] = F[c] = 0.0;
+      for (int c = 0; c < 11; c++) { yb[state_index(M, ph.xa, c)] = yv[c]; bad |= nonfinite(yv[c]); }
+    }
+    for (int j = j0; j < j1; j++) {
+      const double Sh = S * hs[j], Sh2 = Sh * 0.5, Sh6 = Sh / 6.0;
+      for (int i = 0; i < k; i++) {
+        const int p = 2 * (k * j + i);
+        double acc[11], F[11];
+#pragma unroll
+        for (int c = 0; c < 11; c++) acc[c] = F[c] = 0.0;
 #pragma nounroll
-      for (int st = 0; st < 4; st++) {
-        const int pp = p + ((st + 1) >> 1);                 // stage points p, p + 1, p + 1, p + 2
-        const double a = (st == 3) ? Sh : Sh2;
-        const double w = (st == 3) ? 1.0 : 2.0;
-        double yt[11];
+        for (int st = 0; st < 4; st++) {
+          const int pp = p + ((st + 1) >> 1);                 // stage points p, p + 1, p + 1, p + 2
+          const double a = (st == 3) ? Sh : Sh2;
+          const double w = (st == 3) ? 1.0 : 2.0;
+          double yt[11];
 #pragma unroll
-        for (int c = 0; c < 11; c++) yt[c] = st ? __builtin_fma(a, F[c], yv[c]) : yv[c];
-        double u0 = 0.0, u1 = 0.0;
-        if (sampled) {
-          u0 = us[(size_t)pp * 2 * (size_t)ld];
-          u1 = us[((size_t)pp * 2 + 1) * (size_t)ld];
+          for (int c = 0; c < 11; c++) yt[c] = st ? __builtin_fma(a, F[c], yv[c]) : yv[c];
+          double u0 = 0.0, u1 = 0.0;
+          if (sampled) {
+            u0 = us[(size_t)pp * 2 * (size_t)ld];
+            u1 = us[((size_t)pp * 2 + 1) * (size_t)ld];
+          }
+          if constexpr (kDisp) section_rhs<true>(P, ph, tb, Pd.vp, sig[pp], to, tf, yt, u0, u1, F, fw);
+          else section_rhs(P, ph, tb, Pd.vp, sig[pp], to, tf, yt, u0, u1, F);
+#pragma unroll
+          for (int c = 0; c < 11; c++) acc[c] = st ? __builtin_fma(w, F[c], acc[c]) : F[c];
         }
-        section_rhs(P, ph, tb, Pd.vp, sig[pp], to, tf, yt, u0, u1, F);
 #pragma unroll
-        for (int c = 0; c < 11; c++) acc[c] = st ? __builtin_fma(w, F[c], acc[c]) : F[c];
+        for (int c = 0; c < 11; c++) yv[c] = __builtin_fma(Sh6, acc[c], yv[c]);
       }
 #pragma unroll
-      for (int c = 0; c < 11; c++) yv[c] = __builtin_fma(Sh6, acc[c], yv[c]);
+      for (int c = 0; c < 11; c++) { yb[state_index(M, ph.xa + j + 1, c)] = yv[c]; bad |= nonfinite(yv[c]); }
     }
-#pragma unroll
-    for (int c = 0; c < 11; c++) { yb[state_index(M, ph.xa + j + 1, c)] = yv[c]; bad |= nonfinite(yv[c]); }
-  }
+  } while (kChain && ++s < Pd.S);
   if (bad) *(volatile int32_t*)P.flag = 1;
 }
 
@@ -193,7 +224,7 @@ __global__ __launch_bounds__(256) void prop_err_kernel(ProblemDev P, PropDev Pd,
 }
 
 hipError_t launch_prop_slab(const ProblemDev& P, const PropDev& Pd, const PropPhaseDev* host_ph, int n_max_sampled, int nb,
-                            const double* d_x, double* d_y, double* d_ws, int64_t ld, hipStream_t s) {
+                            const double* d_x, double* d_y, double* d_ws, int64_t ld, const double* d_disp, hipStream_t s) {
   if (nb <= 0) return hipSuccess;
   if (ld < nb) return hipErrorInvalidValue;
   const long long ng = ((long long)nb + kPropSampleVB - 1) / kPropSampleVB;
@@ -207,11 +238,13 @@ hipError_t launch_prop_slab(const ProblemDev& P, const PropDev& Pd, const PropPh
     if (const hipError_t e = hipGetLastError()) return e;
   }
   const long long ngrp = ((long long)nb + kPropThreads - 1) / kPropThreads;
-  grid = ngrp * Pd.nseg;
+  grid = Pd.chain ? ngrp : ngrp * Pd.nseg;
   if (grid <= 0) return hipSuccess;
   if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
   const size_t lds = table_lds_bytes(P.Kw, P.Kc);
-  hipLaunchKernelGGL(prop_kernel, dim3((unsigned)grid), dim3(kPropThreads), lds, s, P, Pd, nb, d_x, d_y, d_ws, (long long)ld);
+  auto* const kern = Pd.chain ? (d_disp ? prop_kernel<true, true> : prop_kernel<false, true>)
+                              : (d_disp ? prop_kernel<true, false> : prop_kernel<false, false>);
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kPropThreads), lds, s, P, Pd, nb, d_x, d_y, d_ws, (long long)ld, d_disp);
   return hipGetLastError();
 }
 

@@ -18,6 +18,11 @@
 //   y  = fma(Sh6, a, y)
 // F = section_rhs (gel_section_rhs.h) at the stage point's sigma; U(p) = the control samples of the plan's workspace.  Quaternions
 // are never renormalised.
+//
+// THE CHAIN (GEL_PROP_CHAIN): phase 0 starts at its X_0; into phase s + 1, per component, jump = x(first node of s + 1) - x(last node
+// of s) (one subtraction) and the start value is y itself where jump == 0, else y + jump (one addition).  The step is the one above.
+// THE FACTORS (gel_propagate_dispersed*): thrust f0, mf_um f1, area f2 -- one product each, once per (vector, phase) -- and wn f3,
+// we f3 on the interpolated wind inside F; a factor of 1.0 changes no bit.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -42,7 +47,7 @@ struct PropPhaseDev {
 struct PropDev {
   int32_t S, restart;    // phases; 0: one segment = one phase, 1 (GEL_PROP_RESTART_NODE): one segment = one node interval
   int32_t nseg;          // S, or N in restart mode
-  int32_t pad;
+  int32_t chain;         // 1 (GEL_PROP_CHAIN): one lane = one vector through all phases; nseg = S, every phase its own segment
   const PropPhaseDev* ph;
   const int32_t* seg_phase;   // [nseg] phase of every segment
   const double* mat;
@@ -54,15 +59,17 @@ constexpr int kPropThreads = 256;         // prop_kernel: 4 wavefronts, each 64 
 constexpr int kPropSampleThreads = 256;   // prop_sample_kernel: one lane per stage point of a tile
 constexpr int kPropSampleVB = 4;          // prop_sample_kernel: decision vectors per workgroup
 constexpr size_t kPropMaxLds = 64 * 1024;
-constexpr int64_t kPropMaxLaneSteps = 1 << 20;   // steps[s] n_s may not exceed this: no lane runs longer
+constexpr int64_t kPropMaxLaneSteps = 1 << 20;   // steps[s] n_s (chain mode: their sum over the phases) may not exceed this: no lane runs longer
+constexpr int kPropNDisp = 4;             // dispersion factors per (vector, phase): thrust, mass flow, reference area, wind (GEL_PROP_NDISP)
 
 // bytes of LDS the sample kernel takes for a phase of n nodes: U [n][2][kPropSampleVB]
 inline size_t prop_sample_lds_bytes(int n) { return (size_t)16 * n * kPropSampleVB; }
 
 // One slab of nb vectors (x, y: the slab's first vector; ws: [stage point][2][ld] with ld >= nb):
-// control samples into ws, then y [nb][11 M] from x [nb][nvars].  n_max_sampled sizes the sample kernel's LDS.
+// control samples into ws, then y [nb][11 M] from x [nb][nvars].  n_max_sampled sizes the sample kernel's LDS.  d_disp: the slab's
+// factors [nb][S][kPropNDisp], or null (the undispersed instantiation).
 hipError_t launch_prop_slab(const ProblemDev& P, const PropDev& Pd, const PropPhaseDev* host_ph, int n_max_sampled, int nb,
-                            const double* d_x, double* d_y, double* d_ws, int64_t ld, hipStream_t s);
+                            const double* d_x, double* d_y, double* d_ws, int64_t ld, const double* d_disp, hipStream_t s);
 // err [B][S][4] from x and y (all B vectors in one launch)
 hipError_t launch_prop_err(const ProblemDev& P, const PropDev& Pd, int B, const double* d_x, const double* d_y, double* d_err,
                            hipStream_t s);

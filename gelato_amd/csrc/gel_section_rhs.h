@@ -14,8 +14,12 @@ namespace gel {
 //   quaternion  quat_rate, or 0 for a held attitude
 // The caller keeps idle lanes out: wind_eci_or_calm takes a vote of the lanes that are here.  (All of F, the mass and position
 // rows included, is therefore formed for active lanes only; the callers store and read F only there.)
+// kDisp (gel_propagate_dispersed): the caller has already scaled ph.thrust, ph.mf_um and ph.area by its lane's factors (one product
+// each, once per phase); fw scales the two wind components AFTER the interpolation -- the tables in LDS are the workgroup's --
+// and before wind_eci_or_calm.  ph.air stays the handle's.  Without kDisp fw is not read: the code is what it was.
+template <bool kDisp = false>
 GEL_DEV void section_rhs(const ProblemDev& P, const PhaseDev& ph, const Tables& tb, double vp, double sig, double to, double tf,
-                         const double xt[11], double u0, double u1, double F[11]) {
+                         const double xt[11], double u0, double u1, double F[11], double fw = 1.0) {
   F[0] = ph.engine_on ? ph.mf_um : 0.0;   // mass: the m[1:] - m[0] form when the engine is off
 #pragma unroll
   for (int c = 0; c < 3; c++) F[1 + c] = xt[4 + c] * vp;
@@ -30,7 +34,12 @@ GEL_DEV void section_rhs(const ProblemDev& P, const PhaseDev& ph, const Tables& 
     const PosPart pp = pos_part(r, tb, P.barC20);
     const EarthAngle ea = earth_angle(sig * (tf - to) / 2 + (tf + to) / 2);
     double w[3], Fa[3];
-    wind_eci_or_calm(r, ea, pp.shp, pp.chp, pp.inv_p, pp.wn, pp.we, w);
+    if constexpr (kDisp) {
+      const double wn = pp.wn * fw, we = pp.we * fw;
+      wind_eci_or_calm(r, ea, pp.shp, pp.chp, pp.inv_p, wn, we, w);
+    } else {
+      wind_eci_or_calm(r, ea, pp.shp, pp.chp, pp.inv_p, pp.wn, pp.we, w);
+    }
     aero_force(r, v3, pp.rho, pp.inv_a, w, ph.area, tb, Fa);
     const double T = ph.thrust - ph.nozzle * pp.P;
     const double Td[3] = {T * dir[0], T * dir[1], T * dir[2]};

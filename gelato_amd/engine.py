@@ -178,22 +178,34 @@ class PropagationPlan:
         check(lib().gel_prop_matrices(self._p, int(phase), _d(out["pts"]), _d(out["Wu"]), out["copy_u"].ctypes.data_as(_ip)))
         return out
 
-    def apply(self, X, want_err=True):
+    def apply(self, X, want_err=True, dispersion=None):
         """X [B, nvars] (or [nvars]) -> (Y [B, 11 M]: the propagated state at every state node, laid out like the state part of
-        x; err [B, S, 4] (mass, position, velocity, quaternion) | None; status)"""
+        x; err [B, S, 4] (mass, position, velocity, quaternion) | None; status).  dispersion: None, or float64 [B, S, 4] ([S, 4]
+        for one vector): per vector and phase the factors of thrust, mass flow, reference area and wind (gel_propagate_dispersed)"""
         self._live()
         X = _f64(X).reshape(-1, self.nvars)
         B = X.shape[0]
+        disp = None
+        if dispersion is not None:
+            disp = np.asarray(dispersion)
+            if disp.dtype != np.float64:
+                raise TypeError("dispersion: float64")
+            if disp.shape == (self.S, _lib.GEL_PROP_NDISP) and B == 1:
+                disp = disp[None]
+            if disp.shape != (B, self.S, _lib.GEL_PROP_NDISP):
+                raise ValueError("dispersion: [B, S, %d] = %s, not %s" % (_lib.GEL_PROP_NDISP, (B, self.S, _lib.GEL_PROP_NDISP), disp.shape))
+            disp = np.ascontiguousarray(disp)
         Y = np.empty((B, 11 * self.M))
         err = np.empty((B, self.S, 4)) if want_err else None
-        rc = check(lib().gel_propagate(self._p, B, _d(X), _d(Y), _d(err) if want_err else None))
+        rc = check(lib().gel_propagate_dispersed(self._p, B, _d(X), _d(disp) if disp is not None else None, _d(Y),
+                                                 _d(err) if want_err else None))
         return Y, err, rc
 
-    def apply_device(self, B, d_x, d_y, d_err=0):
-        """device buffers: d_y [B][11 M], d_err [B][S][4] or 0; asynchronous on the engine's own stream; status through
-        Engine.sync()"""
+    def apply_device(self, B, d_x, d_y, d_err=0, d_dispersion=0):
+        """device buffers: d_y [B][11 M], d_err [B][S][4] or 0, d_dispersion [B][S][4] or 0; asynchronous on the engine's own
+        stream; status through Engine.sync()"""
         self._live()
-        check(lib().gel_propagate_device(self._p, int(B), d_x, d_y, d_err or None))
+        check(lib().gel_propagate_dispersed_device(self._p, int(B), d_x, d_dispersion or None, d_y, d_err or None))
 
 
 class Engine:
@@ -221,6 +233,7 @@ class Engine:
 
         wind, ca = _f64(prob["wind_table"]), _f64(prob["ca_table"])
         units = _f64(prob["units"])
+        self.units = units.copy()   # (mass, position, velocity, u, t)
         self.prob = {k: np.array(prob[k]) for k in ("num_nodes", "thrust", "massflow", "reference_area", "nozzle_area",
                                                     "engine_on", "attitude_hold")}
         d = GelProblemDesc()
@@ -858,9 +871,10 @@ class Engine:
     # explicit RK4 propagation of the sections: the shooting check (include/gelato_amd.h gel_prop_*)
     def propagation_plan(self, steps=4, restart="section"):
         """steps: RK4 steps per node interval, one number or one per phase; restart: "section" (integrate from the section's
-        first state to its last node) or "node" (every node interval starts from the collocated state) -> PropagationPlan"""
-        if restart not in ("section", "node"):
-            raise ValueError("restart: 'section' or 'node'")
+        first state to its last node), "node" (every node interval starts from the collocated state) or "chain" (one flight per
+        vector: the state is carried across the knots, with the collocated jump added) -> PropagationPlan"""
+        if restart not in ("section", "node", "chain"):
+            raise ValueError("restart: 'section', 'node' or 'chain'")
         st = np.asarray(steps)
         if st.ndim > 1 or (st.ndim == 1 and st.size != self.S):
             raise ValueError("steps: one number, or one per phase (%d)" % self.S)
@@ -868,8 +882,7 @@ class Engine:
             raise TypeError("steps: integers")
         st = np.ascontiguousarray(np.broadcast_to(st, (self.S,)), dtype=np.int32)
         h = C.c_void_p()
-        check(lib().gel_prop_plan_create(self._h, st.ctypes.data_as(_ip), _lib.GEL_PROP_RESTART_NODE if restart == "node" else 0,
-                                         C.byref(h)))
+        check(lib().gel_prop_plan_create(self._h, st.ctypes.data_as(_ip), {"section": 0, "node": _lib.GEL_PROP_RESTART_NODE, "chain": _lib.GEL_PROP_CHAIN}[restart], C.byref(h)))
         return PropagationPlan(self._owner, h, self.num_nodes, st, (self.S, self.M, self.nvars))
 
     # ------------------------------------------------------------------

@@ -5,6 +5,10 @@ The shooting check takes the controls the optimiser found, integrates the equati
 section's first state (include/gelato_amd.h gel_propagate) and compares the trajectory with the collocated
 states at the nodes.  It exposes a control polynomial that oscillates between its nodes, which the node values hide.  The
 integration runs on the device (Engine.propagation_plan); this module turns it into one record per section.
+
+fly() is the flight itself: ONE integration per decision vector from lift-off to the last node (the plan's chain mode), the state
+carried across the knots with the collocated jump (a stage drop) added, optionally under per-vector dispersions of thrust, mass
+flow, reference area and wind (sample_dispersion) -- the terminal miss of a solution and its Monte-Carlo spread.
 """
 import numpy as np
 
@@ -66,3 +70,82 @@ def shooting_check(xdict, pdict, unitdict, steps=4, engine=None):
         rec["integrator"] = max(rec["integrator_groups"].values())
         report.append(rec)
     return report
+
+
+def sample_dispersion(B, S, sigma, seed, per="vector"):
+    """Factors [B, S, 4] (thrust, mass flow, reference area, wind) for PropagationPlan.apply / fly: 1 + sigma N(0, 1) per factor.
+    sigma: one number or one per factor [4]; per="vector": one draw per vector and factor, the same in all its phases;
+    per="phase": one per (vector, phase, factor).  numpy only, deterministic in seed; sigma = 0 gives exact ones."""
+    if per not in ("vector", "phase"):
+        raise ValueError("per: 'vector' or 'phase'")
+    B, S = int(B), int(S)
+    if B < 0 or S < 1:
+        raise ValueError("B >= 0 and S >= 1")
+    sg = np.asarray(sigma, dtype=np.float64)
+    if sg.shape not in ((), (4,)) or not np.all(sg >= 0):
+        raise ValueError("sigma: one non-negative number, or one per factor (4)")
+    z = np.random.default_rng(seed).standard_normal((B, S if per == "phase" else 1, 4))
+    return np.array(np.broadcast_to(1.0 + sg * z, (B, S, 4)), order="C")   # (an array of its own: writable, contiguous)
+
+
+def fly(xdict_or_X, pdict, unitdict, steps=4, dispersion=None, engine=None):
+    """The flight of every decision vector: the controls integrated from lift-off to the last node in ONE chain
+    (Engine.propagation_plan(restart="chain")), RK4 with 2 * steps steps per node interval.  xdict_or_X: a solution xdict, or
+    packed vectors [B, nvars] / [nvars]; dispersion: None or [B, S, 4] (sample_dispersion); engine: an Engine of the same
+    problem (one is created on device 0 from pdict / unitdict otherwise, which may be None when it is given).
+    -> {"steps": 2 * steps, "status": 0 or GEL_NONFINITE (a non-finite vector does not stop the others),
+        "y" [B, 11 M]: the flown state at every state node, laid out like the state part of x,
+        "err" [B, S, 4]: the accumulated flight error per section (mass, position, velocity, quaternion), |y - x| / (1 + max |x|);
+                         its last row is the terminal miss in that normalisation,
+        "integrator" [B, S, 4]: the step-doubling estimate of RK4's own share of err, max |y_steps - y_2steps| / 15 / (1 + max |x|),
+        "x_flown" [B, nvars] = [y | u | t]: a decision vector that holds the flown states -- what Engine.rows_eval,
+                         Engine.output_table and the aero constraints take,
+        "terminal": {group: [B, 1 | 3 | 3 | 4]}: y - x at the last state node in physical units (kg, m, m/s, 1),
+        "rows" [B, rows]: the engine's row table (orbit insertion errors, ...) at x_flown -- only where one is configured}"""
+    steps = int(steps)
+    if steps < 1:
+        raise ValueError("steps: at least 1")
+    if engine is None:
+        S = pdict["num_sections"]
+        ps = pdict["ps_params"]
+        engine = Engine(con_dynamics.problem_arrays(pdict, unitdict), D=[ps.D(i) for i in range(S)],
+                        tau=[ps.tau(i) for i in range(S)])
+    X = pack_x(xdict_or_X) if isinstance(xdict_or_X, dict) else np.asarray(xdict_or_X, dtype=np.float64)
+    X = np.ascontiguousarray(X).reshape(-1, engine.nvars)
+    B, M, S = X.shape[0], engine.M, engine.S
+    runs, status = [], 0
+    for k in (steps, 2 * steps):
+        plan = engine.propagation_plan(steps=k, restart="chain")
+        try:
+            Y, err, rc = plan.apply(X, dispersion=dispersion)
+        finally:
+            plan.close()
+        status = max(status, rc)
+        runs.append((Y, err))
+    (Y1, _e1), (Y, err) = runs
+    nn = [int(v) for v in engine.num_nodes]
+    with np.errstate(invalid="ignore"):
+        Xn = np.stack([_node_states(X[b], M) for b in range(B)]) if B else np.zeros((0, M, 11))
+        d12 = np.abs(np.stack([_node_states(Y1[b], M) - _node_states(Y[b], M) for b in range(B)])) if B else np.zeros((0, M, 11))
+        integ = np.zeros((B, S, 4))
+        xa = 0
+        for i in range(S):
+            rows = slice(xa, xa + nn[i] + 1)
+            den = 1.0 + np.abs(Xn[:, rows]).max(axis=1)
+            est = d12[:, rows].max(axis=1) / den / 15.0
+            for g, (a, b) in enumerate(GROUP_COLS):
+                integ[:, i, g] = est[:, a:b].max(axis=1)
+            xa += nn[i] + 1
+    x_flown = X.copy()
+    x_flown[:, :11 * M] = Y
+    u = engine.units
+    scale = (u[0], u[1], u[2], 1.0)
+    last = M - 1
+    idx = ([last], [M + 3 * last + c for c in range(3)], [4 * M + 3 * last + c for c in range(3)], [7 * M + 4 * last + c for c in range(4)])
+    out = {"steps": 2 * steps, "status": int(status), "y": Y, "err": err, "integrator": integ, "x_flown": x_flown,
+           "terminal": {k: (Y[:, ix] - X[:, ix]) * sc for k, ix, sc in zip(GROUPS, idx, scale)}}
+    if engine._nlin + engine._nfn:
+        con, _jfn, rc = engine.rows_eval(x_flown, want_jac=False)
+        out["rows"] = con
+        out["status"] = max(out["status"], int(rc))
+    return out

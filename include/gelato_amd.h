@@ -577,6 +577,22 @@ int gel_interp_host(const gel_interp_plan* plan, int32_t B, const double* x, dou
  *      Restart: by default (section mode) y starts at X_0 of the section and runs to its last node; with GEL_PROP_RESTART_NODE every
  *      node interval starts from the collocated X_j (the local defect: WHERE a section is bad).  The first interval is the same
  *      computation in both modes: the same bits.
+ *      Chain (GEL_PROP_CHAIN, excludes GEL_PROP_RESTART_NODE): the flight.  One integration per vector from lift-off to the last
+ *      node, the phases in order; to and tf of every phase come from the vector's own x, as in the other modes.  Phase 0 starts at
+ *      its X_0, bit for bit.  Across the knot into phase s + 1, per component c: jump = x_c(first node of s + 1) - x_c(last node of
+ *      s) (one subtraction); the start value is y_c itself where jump == 0, else y_c + jump (one addition) -- a continuous knot
+ *      carries the bits, a stage drop carries the collocated mass jump without reading the row table.  The carried state is what y
+ *      holds at node xa of phase s + 1.  err is then the ACCUMULATED flight error per section; its last row is the terminal miss.
+ *      Dispersions (gel_propagate_dispersed*): disp [B][S][GEL_PROP_NDISP] or NULL, valid in all three modes; each factor f is
+ *      used as ONE fp64 product, formed once per (vector, phase):
+ *        index 0  thrust          thrust f: the vacuum thrust; the nozzle term nozzle_area P is untouched
+ *        index 1  mass flow       (-massflow / unit_mass) f
+ *        index 2  reference area  reference_area f (to the dynamics the same thing as a CA or density scale)
+ *        index 3  wind            wn f, we f: the two interpolated wind components (the tables are shared by the vectors of a
+ *                                 workgroup), before the rotation into ECI
+ *      dynamics_velocity against _NoAir is still decided by the HANDLE's reference_area.  A factor of exactly 1.0 changes no bit,
+ *      and gel_propagate* is gel_propagate_dispersed* with NULL.  A non-finite factor makes that vector's outputs non-finite and
+ *      raises the status like any NaN; the other vectors are unaffected.
  *      Outputs: y [B][11 M], laid out like the state part of x (mass M | position 3M | velocity 3M | quaternion 4M): the propagated
  *      state at every state node; node xa of each phase is X_0 copied bit for bit.  err (optional) [B][S][4] in gel_mesh_error's
  *      normalisation: max_{i=1..n} |y_c(i) - x_c(i)| / (1 + max_{i=0..n} |x_c(i)|), then the maximum over each group's components
@@ -584,7 +600,8 @@ int gel_interp_host(const gel_interp_plan* plan, int32_t B, const double* x, dou
  *      the source handle's status (GEL_NONFINITE from gel_propagate, through gel_sync for the device form); the other vectors'
  *      outputs stay valid.  A vector's result depends neither on B, nor on its position in the batch, nor on anything another
  *      vector holds, nor on the slab size.
- *      Refusals (GEL_ERR_ARG): steps[s] < 1; steps[s] n_s > 2^20 (no lane runs longer than that many steps: a launch always ends);
+ *      Refusals (GEL_ERR_ARG): steps[s] < 1; steps[s] n_s > 2^20, and for a chain plan sum_s steps[s] n_s > 2^20 (no lane runs
+ *      longer than that many steps: a launch always ends); both mode flags at once;
  *      control matrices of more than 2^27 doubles in all (sum of Pp n); on a device handle a free-attitude phase of more than 1024
  *      nodes (its controls are staged in a workgroup's LDS) and more than 2^20 stage points of free-attitude phases in all (the
  *      control samples of 64 vectors, 16 bytes per stage point, must fit the 1 GB workspace).
@@ -594,10 +611,12 @@ int gel_interp_host(const gel_interp_plan* plan, int32_t B, const double* x, dou
  *      its source handle.  B = 0 is valid.  There is no host form: the evaluation calls refuse a GEL_DEVICE_NONE handle. ---- */
 typedef struct gel_prop_plan gel_prop_plan; /* opaque */
 #define GEL_PROP_RESTART_NODE 1
+#define GEL_PROP_CHAIN 2
+#define GEL_PROP_NDISP 4
 int gel_prop_plan_create(gel_problem* src, const int32_t* steps /* [S] */, int32_t flags, gel_prop_plan** out);
 int gel_prop_plan_destroy(gel_prop_plan* plan);
-/* info [6]: S, flags, stage points in total (sum of Pp), RK4 steps of the longest lane (max k n, or max k with
- * GEL_PROP_RESTART_NODE), workspace bytes per vector, vectors per slab a call will use NOW (the most the workspace cap holds, a
+/* info [6]: S, flags, stage points in total (sum of Pp), RK4 steps of the longest lane (max k n, max k with
+ * GEL_PROP_RESTART_NODE, sum of k n with GEL_PROP_CHAIN), workspace bytes per vector, vectors per slab a call will use NOW (the most the workspace cap holds, a
  * multiple of 64; GEL_PROP_SLAB in the environment, read per call and rounded up to a multiple of 64, overrides it where it fits) */
 int gel_prop_plan_info(const gel_prop_plan* plan, int64_t* info /* [6] */);
 /* row-major, Pp = 2 steps[phase] n + 1; any pointer may be NULL; works on GEL_DEVICE_NONE handles */
@@ -610,6 +629,10 @@ int gel_propagate(gel_prop_plan* plan, int32_t B, const double* x, double* y, do
  * gel_sync(src, NULL).  A caller working on a NON-BLOCKING stream must have finished writing d_x before the call and must
  * gel_sync(src, NULL) before it consumes the outputs. */
 int gel_propagate_device(gel_prop_plan* plan, int32_t B, const double* d_x, double* d_y, double* d_err /* or NULL */);
+/* the same pair with per-vector, per-phase factors disp [B][S][GEL_PROP_NDISP] (or NULL: exactly the pair above) */
+int gel_propagate_dispersed(gel_prop_plan* plan, int32_t B, const double* x, const double* disp /* or NULL */, double* y, double* err);
+int gel_propagate_dispersed_device(gel_prop_plan* plan, int32_t B, const double* d_x, const double* d_disp /* or NULL */, double* d_y,
+                                   double* d_err /* or NULL */);
 
 /* ---- one optimiser callback = one device round trip: the four defect groups, the knot / terminal / user row table and the
  *      aero path constraints of ONE decision vector launched back to back on the handle's stream, one synchronise

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
-"""Cost of the explicit RK4 propagation (gel_propagate_device), in ONE process on the SAME device buffers (as
-tools/mesh_error_bench.py): for mixed-6x64 and stress-12x128, k = 1 and 4 steps per node interval, section and node restart, at
+"""Cost of the explicit RK4 propagation (gel_propagate_device, gel_propagate_dispersed_device), in ONE process on the SAME device
+buffers (as tools/mesh_error_bench.py): for mixed-6x64 and stress-12x128, k = 1 and 4 steps per node interval, section and node
+restart, the chained flight ("chain") and the chain and the section mode under per-vector dispersions ("chain+disp",
+"section+disp": factors 1 + 0.02 N(0, 1) per vector and phase; PROP_BENCH_MODES=section,node,... selects), at
 B = 1 and B = 65536 -- ns per vector and ns per (vector . RK4 step) from device events after a warm-up, next to the
 residual-only gel_eval_batch_device launch (the same right-hand side once per node: the expected ratio is about 4 k per
 right-hand-side evaluation) and gel_mesh_error_device on the same x, turns alternating.  Prints one JSON line.
@@ -28,12 +30,13 @@ def timed(fn, reps):
 def main():
     import numpy as np
     import torch
-    from gelato_amd import Engine, _lib, con_dynamics, pack_x, problem
+    from gelato_amd import Engine, _lib, con_dynamics, pack_x, problem, propagate
     Bbig = int(sys.argv[1]) if len(sys.argv) > 1 else 65536
     turns = int(sys.argv[2]) if len(sys.argv) > 2 else 3
     if not torch.cuda.is_available():
         raise SystemExit("propagate_bench: no GPU visible")
     only = os.environ.get("PROP_BENCH_ONLY")
+    modes = os.environ.get("PROP_BENCH_MODES", "section,node,chain,chain+disp,section+disp").split(",")
     out = {"B": Bbig, "turns": turns, "cases": [], "build": _lib.build_info()}
     for wl in ("mixed-6x64", "stress-12x128"):
         if only and only.split(",")[0] != wl:
@@ -51,15 +54,17 @@ def main():
             r = torch.empty((B, E.nres), dtype=torch.float64, device="cuda")
             de = torch.empty((B, E.S, 4), dtype=torch.float64, device="cuda")
             dY = torch.empty((B, 11 * E.M), dtype=torch.float64, device="cuda")
+            dD = torch.from_numpy(propagate.sample_dispersion(B, E.S, 0.02, seed=1, per="phase")).cuda()
             reps = 20 if B == 1 else 1
             base = {"residual_only": lambda: E.eval_batch_device(B, dX.data_ptr(), r.data_ptr(), 0, s),
                     "mesh_error": lambda: E.mesh_error_device(B, dX.data_ptr(), de.data_ptr(), 0, s)}
             for k in (1, 4):
-                for restart in ("section", "node"):
+                for restart in modes:
                     if only and only.split(",")[1:] != [str(k), restart, str(B)]:
                         continue
-                    plan = E.propagation_plan(steps=k, restart=restart)
-                    calls = dict(base, propagate=lambda: plan.apply_device(B, dX.data_ptr(), dY.data_ptr(), de.data_ptr()))
+                    plan = E.propagation_plan(steps=k, restart=restart.split("+")[0])
+                    disp = dD.data_ptr() if restart.endswith("+disp") else 0
+                    calls = dict(base, propagate=lambda: plan.apply_device(B, dX.data_ptr(), dY.data_ptr(), de.data_ptr(), disp))
                     if only:
                         calls = {"propagate": calls["propagate"]}
                     per = {name: [] for name in calls}
@@ -82,7 +87,7 @@ def main():
                         rec["propagate_over_mesh_error"] = med["propagate"] / med["mesh_error"]
                     out["cases"].append(rec)
                     plan.close()
-            del dX, r, de, dY
+            del dX, r, de, dY, dD
             torch.cuda.empty_cache()
         E.close()
     print(json.dumps(out))
