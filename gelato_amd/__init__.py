@@ -17,5 +17,6 @@ include/gelato_amd.h; there is no CPU fallback.
 from .engine import Engine, InterpPlan, PropagationPlan, pack_x  # noqa: F401
 from .interp import refine, sample  # noqa: F401
 from .propagate import fly, sample_dispersion, shooting_check  # noqa: F401
+from .montecarlo import flight_envelope  # noqa: F401
 
 __version__ = "0.1.0"

@@ -20,6 +20,7 @@ GEL_FLAG_EXACT_AERO_JAC = 64     # aero path constraints' gradients exact to rou
 GEL_INTERP_UNIT_QUAT = 1         # gel_interp_plan_create*: rows that are not copies get q / sqrt(q . q)
 GEL_PROP_RESTART_NODE = 1        # gel_prop_plan_create: every node interval starts from the collocated state (the local defect)
 GEL_PROP_CHAIN = 2               # gel_prop_plan_create: one integration per vector through all phases, the state carried across the knots (the flight)
+GEL_ENV_NSTAT, GEL_PEAK_NSTAT = 8, 4   # gel_output_table_batch*: statistics per (node, column) and per (vector, column)
 GEL_PROP_NDISP = 4               # gel_propagate_dispersed*: factors per (vector, phase): thrust, mass flow, reference area, wind
 GEL_FLAG_EXACT_ROWS_JAC = 128    # node-function rows' jfn (terminal, user, waypoint rows) exact to rounding instead of forward differences
 NUM_BLOCKS = 13
@@ -160,6 +161,9 @@ SIGNATURES = {
     "gel_propagate_dispersed_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gel_initial_guess": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, _dp, _dp]),
     "gel_output_table": (C.c_int, [C.c_void_p, _dp, _dp, C.c_double, C.c_double, _dp]),
+    "gel_output_table_batch": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, _dp, C.c_double, C.c_double, C.c_int32, _ip, _dp, _dp, _dp]),
+    "gel_output_table_batch_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
+                                                C.c_int32, _ip, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gel_dynamics_velocity": (C.c_int, [C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int32, _dp, C.c_int32,
                                          _dp, C.c_double, _dp]),
     "gel_dynamics_velocity_NoAir": (C.c_int, [C.c_int32, _dp, _dp, _dp, _dp, _dp, C.c_double, _dp]),
@@ -176,7 +180,7 @@ def build(force=False):
     src_dir = os.path.join(_HERE, "csrc")
     if force and os.path.exists(SO_PATH):
         os.remove(SO_PATH)
-    subprocess.check_call(["make", "-s", "-j8", "-C", src_dir])   # eleven translation units (kernels, the AERO instantiation, the three exact Jacobians, the mesh error estimate, the two Jacobian products, the interpolation, the propagation, host side)
+    subprocess.check_call(["make", "-s", "-j8", "-C", src_dir])   # twelve translation units (kernels, the AERO instantiation, the three exact Jacobians, the mesh error estimate, the two Jacobian products, the interpolation, the propagation, the batched output table, host side)
     if not os.path.exists(SO_PATH):
         raise RuntimeError("building %s failed" % SO_PATH)
     _write_build_info()

@@ -24,6 +24,7 @@
 #include "gel_conprod.h"
 #include "gel_interp.h"
 #include "gel_prop.h"
+#include "gel_outbatch.h"
 
 namespace {
 
@@ -357,6 +358,9 @@ struct gel_problem {
   // Both only grow and are kept until the handle is closed.
   DeviceArray<double> d_arena;
   PinnedArray<double> h_arena;
+  // the envelope partials of gel_output_table_batch* (DESIGN.md 3.16): the device form's buffers are the caller's, so the partials
+  // cannot live beside them in the arena; only grows, after a drain
+  DeviceArray<double> d_outws;
   // gel_jac_fd working set: kept between calls; the residuals of all num_vars + 1 perturbed vectors are
   // re-used while x stays the same (the four groups are asked for one after the other)
   DeviceArray<double> jfd_x, jfd_Xp, jfd_res, jfd_J;
@@ -3464,6 +3468,87 @@ int gel_output_table(gel_problem* p, const double* x, const double* tx_res, doub
                        HIPCHK(gel::launch_output(p->dev, M, a[0], a[1], reinterpret_cast<const int32_t*>(a[2]), launch_lat_deg, launch_lon_deg,
                                                  a[3], p->stream.get()));
                        return GEL_OK;
+                     });
+}
+
+// ------------- batched post-processing table with envelope and peaks -------------
+// the argument checks of both forms, before the device check; fills the column map
+static int outbatch_check(gel_problem* p, int32_t B, const void* x, int32_t ncols, const int32_t* cols, const void* out, const void* env,
+                          const void* peaks, gel::OutColsDev& C) {
+  if (!p) return fail(GEL_ERR_ARG, "gel_output_table_batch: null handle");
+  if (B < 0) return fail(GEL_ERR_ARG, "gel_output_table_batch: B < 0");
+  if (B > 0 && !x) return fail(GEL_ERR_ARG, "gel_output_table_batch: x is NULL with B > 0");
+  if (!out && !env && !peaks) return fail(GEL_ERR_ARG, "gel_output_table_batch: no output selected (out, env and peaks are all NULL)");
+  bool seen[gel::kOutputColumns] = {};
+  for (int c = 0; c < gel::kOutputColumns; c++) C.col[c] = (int8_t)c;
+  C.ncols = gel::kOutputColumns;
+  unsigned long long mask = ~0ull;
+  if (cols) {
+    if (ncols < 1 || ncols > gel::kOutputColumns)
+      return fail(GEL_ERR_ARG, "gel_output_table_batch: ncols = " + std::to_string(ncols) + " outside 1 .. " + std::to_string(gel::kOutputColumns));
+    mask = 0;
+    for (int k = 0; k < ncols; k++) {
+      if (cols[k] < 0 || cols[k] >= gel::kOutputColumns)
+        return fail(GEL_ERR_ARG, "gel_output_table_batch: column id " + std::to_string(cols[k]) + " out of range (cols[" + std::to_string(k) + "])");
+      if (seen[cols[k]])
+        return fail(GEL_ERR_ARG, "gel_output_table_batch: column id " + std::to_string(cols[k]) + " repeated (cols[" + std::to_string(k) + "])");
+      seen[cols[k]] = true;
+      C.col[k] = (int8_t)cols[k];
+      mask |= 1ull << cols[k];
+    }
+    C.ncols = ncols;
+  }
+  // what the selected columns need: downrange (5) Vincenty, 7 .. 12 the orbital elements, 3 / 4 the impact point (gel_output_row.h kRow*)
+  C.parts = ((mask >> 5 & 1) ? 1u : 0u) | ((mask >> 7 & 0x3f) ? 2u : 0u) | ((mask >> 3 & 3) ? 4u : 0u);
+  return GEL_OK;
+}
+
+// the launches of one call on the handle's stream
+static int outbatch_enqueue(gel_problem* p, const gel::OutBatchArgs& A, double* d_out, double* d_env, double* d_peaks) {
+  hipStream_t s = p->stream.get();
+  const size_t lds = gel::outbatch_lds_bytes(p->dev.Kw, p->dev.Kc);
+  if (int rc = check_launch_lds("gel_output_table_batch", lds, gel::staged_table_doubles(p->dev.Kw, p->dev.Kc),
+                                gel::padded_table_doubles(p->dev.Kw, p->dev.Kc), true))
+    return rc;
+  if (A.B > 0 && (d_out || d_peaks)) HIPCHK(gel::launch_outbatch_rows(p->dev, A, d_out, d_peaks, s));
+  if (d_env) {
+    const size_t need = gel::outbatch_ws_doubles(A.B, p->dims.M, A.cols.ncols);
+    if (p->d_outws.capacity() < need) {
+      HIPCHK(drain(p));   // an earlier call in flight still reads the old block
+      HIPCHK(p->d_outws.reserve(need));
+    }
+    HIPCHK(gel::launch_outbatch_env(p->dev, A, A.B > 0 ? d_out : nullptr, p->d_outws.get(), d_env, s));
+  }
+  return GEL_OK;
+}
+
+int gel_output_table_batch_device(gel_problem* p, int32_t B, const double* d_x, const double* d_tx, const double* d_disp,
+                                  double launch_lat_deg, double launch_lon_deg, int32_t ncols, const int32_t* cols, double* d_out,
+                                  double* d_env, double* d_peaks) {
+  gel::OutBatchArgs A{};
+  if (int rc = outbatch_check(p, B, d_x, ncols, cols, d_out, d_env, d_peaks, A.cols)) return rc;
+  NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
+  HIPCHK(hipSetDevice(p->device));
+  A.B = B; A.x = d_x; A.tx = d_tx; A.disp = d_disp; A.lat0 = launch_lat_deg; A.lon0 = launch_lon_deg;
+  return outbatch_enqueue(p, A, d_out, d_env, d_peaks);
+}
+
+int gel_output_table_batch(gel_problem* p, int32_t B, const double* x, const double* tx, const double* disp, double launch_lat_deg,
+                           double launch_lon_deg, int32_t ncols, const int32_t* cols, double* out, double* env, double* peaks) {
+  gel::OutBatchArgs A{};
+  if (int rc = outbatch_check(p, B, x, ncols, cols, out, env, peaks, A.cols)) return rc;
+  NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
+  HIPCHK(hipSetDevice(p->device));
+  const size_t M = (size_t)p->dims.M, nc = (size_t)A.cols.ncols, nB = (size_t)B;
+  A.B = B; A.lat0 = launch_lat_deg; A.lon0 = launch_lon_deg;
+  // (B = 0: x may be NULL; nothing is read)
+  return staged_call(p, kStagedNoFlag,
+                     {staged_in(B > 0 ? x : nullptr, nB * p->dims.num_vars), staged_in(B > 0 ? tx : nullptr, nB * M),
+                      staged_out(out, nB * M * nc), staged_out(env, M * nc * gel::kEnvNStat), staged_out(peaks, nB * nc * gel::kPeakNStat),
+                      staged_in(B > 0 ? disp : nullptr, nB * p->dims.S * GEL_PROP_NDISP)},
+                     [&](const gel::ProblemDev&, double* const* a) -> int {
+                       A.x = a[0]; A.tx = a[1]; A.disp = a[5];
+                       return outbatch_enqueue(p, A, a[2], a[3], a[4]);
                      });
 }
 

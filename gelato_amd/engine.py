@@ -751,6 +751,94 @@ class Engine:
         check(lib().gel_output_table(self._h, _d(x), _d(tx), float(launch_lat), float(launch_lon), _d(out)))
         return out
 
+    ENVELOPE_FIELDS = ("count", "mean", "m2", "min", "max", "argmin", "argmax", "first_nonfinite")   # GEL_ENV_NSTAT
+    PEAK_FIELDS = ("min", "argmin", "max", "argmax")                                                     # GEL_PEAK_NSTAT
+
+    def _output_columns(self, columns):
+        """column names or gel_output_column values -> (names, int32 ids | None for all 34 in order)"""
+        if columns is None:
+            return list(self.OUTPUT_COLUMNS), None
+        ids = []
+        for c in columns:
+            if isinstance(c, str):
+                if c not in self.OUTPUT_COLUMNS:
+                    raise ValueError("unknown output column %r" % (c,))
+                ids.append(self.OUTPUT_COLUMNS.index(c))
+            else:
+                ids.append(int(c))
+        if not ids or len(set(ids)) != len(ids) or min(ids) < 0 or max(ids) >= len(self.OUTPUT_COLUMNS):
+            raise ValueError("columns: 1 .. %d distinct columns of OUTPUT_COLUMNS" % len(self.OUTPUT_COLUMNS))
+        return [self.OUTPUT_COLUMNS[i] for i in ids], np.asarray(ids, dtype=np.int32)
+
+    def output_table_batch(self, X, launch_lat, launch_lon, tx=None, dispersion=None, columns=None, table=True, envelope=True,
+                           peaks=True):
+        """The post-processing table of a batch with its envelope and peaks (gel_output_table_batch).
+        X [B, nvars] (or [nvars]); tx None (every vector's node times from its own knots) or [B, M] seconds; dispersion None or
+        float64 [B, S, 4] as PropagationPlan.apply takes it (the mass-flow factor has no reader here); columns None (all of
+        OUTPUT_COLUMNS) or a list of distinct names.
+        -> {"columns": names, "table": [B, M, ncols] | None,
+            "envelope": {name: {count [M] int, mean, std (sqrt(m2 / (count - 1)), NaN where count < 2), m2, min, max [M],
+                                argmin, argmax, first_nonfinite [M] int (-1: none)}} | None   -- per node over the vectors,
+            "peaks": {name: {min, max [B], argmin, argmax [B] int (node; -1: no finite entry)}} | None   -- per vector over the nodes}"""
+        if not (table or envelope or peaks):
+            raise ValueError("output_table_batch: no output selected (table, envelope and peaks are all off)")
+        names, ids = self._output_columns(columns)
+        X = _f64(X)
+        if X.ndim == 1:
+            X = X[None]
+        if X.ndim != 2 or X.shape[1] != self.nvars:
+            raise ValueError("X: [B, nvars] = [B, %d], not %s" % (self.nvars, X.shape))
+        B, M, nc = X.shape[0], self.M, len(names)
+        if tx is not None:
+            tx = _f64(tx)
+            if tx.shape == (M,) and B == 1:
+                tx = tx[None]
+            if tx.shape != (B, M):
+                raise ValueError("tx: [B, M] = %s, not %s" % ((B, M), tx.shape))
+        disp = None
+        if dispersion is not None:
+            disp = np.asarray(dispersion)
+            if disp.dtype != np.float64:
+                raise TypeError("dispersion: float64")
+            if disp.shape == (self.S, _lib.GEL_PROP_NDISP) and B == 1:
+                disp = disp[None]
+            if disp.shape != (B, self.S, _lib.GEL_PROP_NDISP):
+                raise ValueError("dispersion: [B, S, %d] = %s, not %s" % (_lib.GEL_PROP_NDISP, (B, self.S, _lib.GEL_PROP_NDISP), disp.shape))
+            disp = np.ascontiguousarray(disp)
+        out = np.empty((B, M, nc)) if table else None
+        env = np.empty((M, nc, _lib.GEL_ENV_NSTAT)) if envelope else None
+        pk = np.empty((B, nc, _lib.GEL_PEAK_NSTAT)) if peaks else None
+        check(lib().gel_output_table_batch(self._h, B, _d(X), _d(tx) if tx is not None else None, _d(disp) if disp is not None else None,
+                                           float(launch_lat), float(launch_lon), nc, ids.ctypes.data_as(_ip) if ids is not None else None,
+                                           _d(out) if table else None, _d(env) if envelope else None, _d(pk) if peaks else None))
+        res = {"columns": names, "table": out, "envelope": None, "peaks": None}
+        if envelope:
+            res["envelope"] = {}
+            for k, name in enumerate(names):
+                e = {f: env[:, k, j] for j, f in enumerate(self.ENVELOPE_FIELDS)}
+                for f in ("count", "argmin", "argmax", "first_nonfinite"):
+                    e[f] = e[f].astype(np.int64)
+                with np.errstate(invalid="ignore", divide="ignore"):
+                    e["std"] = np.where(e["count"] >= 2, np.sqrt(e["m2"] / np.maximum(e["count"] - 1, 1)), np.nan)
+                res["envelope"][name] = e
+        if peaks:
+            res["peaks"] = {}
+            for k, name in enumerate(names):
+                q = {f: pk[:, k, j] for j, f in enumerate(self.PEAK_FIELDS)}
+                for f in ("argmin", "argmax"):
+                    q[f] = q[f].astype(np.int64)
+                res["peaks"][name] = q
+        return res
+
+    def output_table_batch_device(self, B, d_x, launch_lat, launch_lon, d_tx=0, d_dispersion=0, columns=None, d_out=0, d_env=0,
+                                  d_peaks=0):
+        """device buffers (raw pointers; 0 = not given): d_out [B][M][ncols], d_env [M][ncols][8], d_peaks [B][ncols][4];
+        asynchronous on the engine's own stream; status through Engine.sync()"""
+        names, ids = self._output_columns(columns)
+        check(lib().gel_output_table_batch_device(self._h, int(B), d_x or None, d_tx or None, d_dispersion or None, float(launch_lat),
+                                                  float(launch_lon), len(names), ids.ctypes.data_as(_ip) if ids is not None else None,
+                                                  d_out or None, d_env or None, d_peaks or None))
+
     def initial_guess(self, t_ref, table, knot_times):
         """initialize.py:322-409 behind the C-ABI: reference trajectory (t_ref [n], table [n, 13] = mass | pos 3 | vel 3 |
         quat 4 | body rates y, z) interpolated at the mesh's node times -> packed decision vector"""

@@ -669,6 +669,57 @@ typedef enum {
 int gel_output_table(gel_problem* p, const double* x, const double* tx_res /* [M] */, double launch_lat_deg,
                      double launch_lon_deg, double* out /* [M][GEL_OUTPUT_COLUMNS] */);
 
+/* ---- the post-processing table of a BATCH with its Monte-Carlo envelope and the peaks of every flight: what
+ *      a dispersed batch of gel_propagate_dispersed* (x_flown = [y | u | t]) is looked at with.
+ *      Table: out [B][M][ncols]; out[b][i][c] is what gel_output_table writes for vector b, node i, column cols[c] -- bit for bit,
+ *      NaN pattern included -- when disp is NULL and the same tx is given.  cols: ncols distinct gel_output_column values in any
+ *      order, or NULL = all 34 in order (ncols is then ignored).  With a subset the kernel leaves out the work only unselected
+ *      columns need (Vincenty's iteration, the impact point, the orbital elements); a column that is formed keeps its bits.
+ *      Times: tx [B][M] seconds, or NULL: every vector's node times from its own knots and the handle's tau,
+ *      (tau_x (tf - to) / 2 + (tf + to) / 2) unit_t with tau_x = [-1, tau], operation for operation the expression of
+ *      gelato_amd.output_result.node_times -- the same bits as passing them.
+ *      Dispersions: disp [B][S][GEL_PROP_NDISP] or NULL (= all ones), the factors of gel_propagate_dispersed*, each ONE fp64
+ *      product formed once per (vector, phase); a factor of exactly 1.0 changes no bit:
+ *        index 0  thrust f (column thrust and accel_BODY_X; the nozzle term is untouched)
+ *        index 1  mass flow: nothing in the table reads it; IGNORED
+ *        index 2  reference_area f (aero_BODY_X, accel_BODY_X)
+ *        index 3  wn f, we f on the interpolated wind, before any rotation (dynamic pressure, Q_alpha, the angles of attack, vel_air, M)
+ *      Envelope: env [M][ncols][GEL_ENV_NSTAT] = per (node, column), over the vectors b whose entry is finite: count (a double),
+ *      mean, m2 = sum (v - mean)^2, min, max, argmin, argmax (vector indices as doubles; compared with < / >: the FIRST vector that
+ *      attains the extremum), first_nonfinite (the lowest b whose entry is NaN / Inf, or -1).  count == 0: mean, m2, min, max are
+ *      NaN and both arg fields -1; count == 1: m2 is exactly 0.  THE ORDER, a function of the vector index alone: the batch is cut
+ *      into blocks of 256 consecutive vectors (block k = vectors 256 k .. 256 k + 255).  Inside a block, Welford's update in
+ *      ascending b over the finite entries:  n += 1;  d = v - mean;  mean = mean + d / n;  m2 = fma(d, v - mean, m2).
+ *      The blocks that hold a finite entry are merged in ascending k into a running total (the first one is copied), Chan's form:
+ *        nt = n + nb;  d = mean_b - mean;  mean = mean + d (nb / nt);  m2 = (m2 + m2_b) + (d d) ((n nb) / nt);  n = nt
+ *      each written operation one rounding.  The result does not depend on the stream, the launch geometry or the form (host /
+ *      device) of the call, nor on whether out or peaks are asked for too.  No floating-point atomics.  Angle columns are reduced
+ *      as the numbers they are: a wrap at +-180 / 360 degrees inside a column's spread is the caller's business.
+ *      Peaks: peaks [B][ncols][GEL_PEAK_NSTAT] = per (vector, column), over the nodes in ascending order, finite entries only:
+ *      min, its node, max, its node (nodes as doubles; the first node that attains the extremum); NaN and -1 where no node is finite.
+ *      A vector's table and peaks depend neither on B nor on its place in the batch.
+ *      Status: the table legitimately holds NaN (no impact point), so these calls never return GEL_NONFINITE: count and
+ *      first_nonfinite carry that.  GEL_ERR_ARG, decided before the device is looked at: p NULL; B < 0; x NULL with B > 0; cols
+ *      given and ncols outside 1 .. 34, a column id out of range or repeated; out, env and peaks all NULL.  On a device handle
+ *      also: tables so long that the row tile (64 x 34 doubles) does not fit the workgroup's 64 KB beside them.  A valid call on a
+ *      GEL_DEVICE_NONE handle returns what gel_output_table returns there.  B = 0 succeeds and writes the count == 0 envelope when
+ *      env is given.  The host form copies in, launches, copies out and synchronises once (the handle's arena).  The device form
+ *      takes NO stream argument (a caller-stream form is a later change): like gel_propagate_device it enqueues everything on the
+ *      handle's own stream, which is a blocking stream and so orders itself against the null stream, and reports through
+ *      gel_sync(p, NULL); a caller on a NON-BLOCKING stream must have finished writing its inputs before the call and must
+ *      gel_sync(p, NULL) before it reads the outputs.  cols stays a host pointer in both forms.  The envelope's partials
+ *      ([blocks][M][ncols][8] doubles) are the handle's. ---- */
+#define GEL_ENV_NSTAT 8  /* count, mean, m2, min, max, argmin, argmax, first_nonfinite */
+#define GEL_PEAK_NSTAT 4 /* min, node of min, max, node of max */
+int gel_output_table_batch(gel_problem* p, int32_t B, const double* x /* [B][num_vars] */, const double* tx /* [B][M] or NULL */,
+                           const double* disp /* [B][S][GEL_PROP_NDISP] or NULL */, double launch_lat_deg, double launch_lon_deg,
+                           int32_t ncols, const int32_t* cols /* [ncols] or NULL = all 34 */, double* out /* [B][M][ncols] or NULL */,
+                           double* env /* [M][ncols][GEL_ENV_NSTAT] or NULL */, double* peaks /* [B][ncols][GEL_PEAK_NSTAT] or NULL */);
+int gel_output_table_batch_device(gel_problem* p, int32_t B, const double* d_x, const double* d_tx /* or NULL */,
+                                  const double* d_disp /* or NULL */, double launch_lat_deg, double launch_lon_deg, int32_t ncols,
+                                  const int32_t* cols /* host pointer, or NULL */, double* d_out /* or NULL */,
+                                  double* d_env /* or NULL */, double* d_peaks /* or NULL */);
+
 /* ---- from-file initial guess on the host (replaces initialize.py:322-409 initialize_xdict_6DoF_from_file, LGR mode;
  *      SURVEY.md 8f row f-3): linear interpolation (scipy interp1d with fill_value="extrapolate": the end intervals extend
  *      beyond the table) of a reference trajectory at the state-node times [-1, tau] and the control-node times tau of
