@@ -10,6 +10,8 @@ the start state and the start bound E passed in, so that a flight is the phases 
                           quotient and the same product, so its dF stays 0.  Only the wind differs in form (the scaled table here,
                           the scaled interpolant on the device: one rounding each side, 2u of the wind), which enters F through
                           dF_wind = 2u |F(f_3 (1 + 2^-20)) - F(f_3)| 2^20 from the oracle's own right-hand side.
+  node restart            fly_all(restart="node"): every node interval from the collocated X_j with E = 0 under the phase's factors
+                          (gel_propagate_dispersed on a GEL_PROP_RESTART_NODE plan); the step is rk4_step, the one of the chain
 The tests allow 2 E, as propagate_truth's do.
 
 Three WRONG restatements (`mutate`) give the bound its teeth: "no_jump" carries y across every knot without the collocated jump,
@@ -63,9 +65,35 @@ class _Phase:
         return d
 
 
-def fly_phase(E, plan, prob, x, s, y0, E0, f=None, want_bound=True):
+def rk4_step(ph, s, y, Eb, Sh, p, Us, dUs, pts, to, tf, want_bound=True):
+    """one RK4 step of phase ph from (y, Eb) over S h = Sh, whose stage points are p, p + 1, p + 2 -> (y, Eb) at its end.
+    propagate_truth.propagate_phase's loop body, operation for operation (Eb is returned as it came where want_bound is off)."""
+    k1 = ph.F(y, Us[p], pts[p], to, tf)[0]
+    y2 = y + Sh * 0.5 * k1
+    k2 = ph.F(y2, Us[p + 1], pts[p + 1], to, tf)[0]
+    y3 = y + Sh * 0.5 * k2
+    k3 = ph.F(y3, Us[p + 1], pts[p + 1], to, tf)[0]
+    y4 = y + Sh * k3
+    k4 = ph.F(y4, Us[p + 2], pts[p + 2], to, tf)[0]
+    if want_bound:
+        A = _jac_abs(ph.pd, s, y, Us[p], pts[p], to, tf, k1)
+        if ph.mass is not None:
+            A[0, :] = 0.0    # (k1's mass row is the restated constant, not the oracle's: its derivative is zero)
+        aS = abs(Sh)
+        e1 = A @ Eb + ph.dF(y, y, Us[p], dUs[p], pts[p], to, tf, k1)
+        e2 = A @ (Eb + aS / 2 * e1) + ph.dF(y, y2, Us[p + 1], dUs[p + 1], pts[p + 1], to, tf, k2)
+        e3 = A @ (Eb + aS / 2 * e2) + ph.dF(y, y3, Us[p + 1], dUs[p + 1], pts[p + 1], to, tf, k3)
+        e4 = A @ (Eb + aS * e3) + ph.dF(y, y4, Us[p + 2], dUs[p + 2], pts[p + 2], to, tf, k4)
+    y = y + Sh / 6.0 * (k1 + 2 * k2 + 2 * k3 + k4)
+    if want_bound:
+        Eb = Eb + aS / 6 * (e1 + 2 * e2 + 2 * e3 + e4) + 8 * U * np.abs(y)
+    return y, Eb
+
+
+def fly_phase(E, plan, prob, x, s, y0, E0, f=None, want_bound=True, restart=False):
     """phase s of one vector from the start state y0 [11] with the start bound E0 [11] -> (Y [n+1, 11], bound [n+1, 11] = 2 E at
-    every node, E at the last node).  propagate_truth.propagate_phase's loop, operation for operation."""
+    every node, E at the last node).  restart: every node interval j starts from the collocated X_j with E = 0
+    (GEL_PROP_RESTART_NODE; y0 and E0 serve node 0 alone, where they are X_0 and 0)."""
     m = plan.matrices(s)
     k = plan.steps[s]
     X, Uc, to, tf = mt.phase_state(E, x, s)
@@ -87,28 +115,11 @@ def fly_phase(E, plan, prob, x, s, y0, E0, f=None, want_bound=True):
     y = np.array(y0, dtype=float)
     Eb = np.array(E0, dtype=float)
     for j in range(n):
+        if restart:
+            y, Eb = X[j].copy(), np.zeros(11)
         Sh = S * hs[j]
         for i in range(k):
-            p = 2 * (k * j + i)
-            k1 = ph.F(y, Us[p], pts[p], to, tf)[0]
-            y2 = y + Sh * 0.5 * k1
-            k2 = ph.F(y2, Us[p + 1], pts[p + 1], to, tf)[0]
-            y3 = y + Sh * 0.5 * k2
-            k3 = ph.F(y3, Us[p + 1], pts[p + 1], to, tf)[0]
-            y4 = y + Sh * k3
-            k4 = ph.F(y4, Us[p + 2], pts[p + 2], to, tf)[0]
-            if want_bound:
-                A = _jac_abs(ph.pd, s, y, Us[p], pts[p], to, tf, k1)
-                if ph.mass is not None:
-                    A[0, :] = 0.0    # (k1's mass row is the restated constant, not the oracle's: its derivative is zero)
-                aS = abs(Sh)
-                e1 = A @ Eb + ph.dF(y, y, Us[p], dUs[p], pts[p], to, tf, k1)
-                e2 = A @ (Eb + aS / 2 * e1) + ph.dF(y, y2, Us[p + 1], dUs[p + 1], pts[p + 1], to, tf, k2)
-                e3 = A @ (Eb + aS / 2 * e2) + ph.dF(y, y3, Us[p + 1], dUs[p + 1], pts[p + 1], to, tf, k3)
-                e4 = A @ (Eb + aS * e3) + ph.dF(y, y4, Us[p + 2], dUs[p + 2], pts[p + 2], to, tf, k4)
-            y = y + Sh / 6.0 * (k1 + 2 * k2 + 2 * k3 + k4)
-            if want_bound:
-                Eb = Eb + aS / 6 * (e1 + 2 * e2 + 2 * e3 + e4) + 8 * U * np.abs(y)
+            y, Eb = rk4_step(ph, s, y, Eb, Sh, 2 * (k * j + i), Us, dUs, pts, to, tf, want_bound)
         Y[j + 1] = y
         Bd[j + 1] = 2 * Eb
     return Y, Bd, Eb
@@ -125,14 +136,18 @@ def carry(y, Eb, x_last, x_first):
     return y0, E0
 
 
-def fly_all(E, plan, prob, x, disp=None, want_bound=True, mutate=None, chain=True):
+def fly_all(E, plan, prob, x, disp=None, want_bound=True, mutate=None, chain=True, restart=None):
     """one vector through every phase -> (y [M, 11], bound_y [M, 11], err [S, 4], bound_err [S, 4]).  disp: None or [S, 4];
-    chain=False: every phase from its own X_0 (the section mode, for the dispersed parity there); mutate: see the module"""
+    chain=False: every phase from its own X_0 (the section mode, for the dispersed parity there); restart="node": every node
+    interval of every phase from the collocated X_j with E = 0, under the phase's factors (the node mode; nothing is carried, so
+    chain is moot); mutate: see the module"""
+    assert restart in (None, "node")
+    node = restart == "node"
     ys, bs, es, bes = [], [], [], []
     y_end, E_end, X_prev = None, None, None
     for s in range(E.S):
         X = mt.phase_state(E, x, s)[0]
-        if s == 0 or not chain:
+        if s == 0 or not chain or node:
             y0, E0 = X[0].copy(), np.zeros(11)
         elif mutate == "no_jump":
             y0, E0 = y_end, E_end
@@ -143,7 +158,7 @@ def fly_all(E, plan, prob, x, disp=None, want_bound=True, mutate=None, chain=Tru
             f = np.array(disp[s - 1], dtype=float) if s else None
         if f is not None and mutate == "no_wind_factor":
             f[3] = 1.0
-        Y, Bd, E_end = fly_phase(E, plan, prob, x, s, y0, E0, f=f, want_bound=want_bound)
+        Y, Bd, E_end = fly_phase(E, plan, prob, x, s, y0, E0, f=f, want_bound=want_bound, restart=node)
         y_end, X_prev = Y[-1], X
         e, ec, den = group_err(X, Y)
         bc = Bd[1:].max(axis=0) / den + 4 * U * ec
@@ -178,9 +193,9 @@ def teeth_dispersion(S):
     return d
 
 
-def mutant_miss(E, plan, prob, x, disp, mutate, y, by):
-    """the largest |mutant - y| / bound over the nodes and components where the bound is positive"""
-    wrong = fly_all(E, plan, prob, x, disp=disp, want_bound=False, mutate=mutate)[0]
+def mutant_miss(E, plan, prob, x, disp, mutate, y, by, **mode):
+    """the largest |mutant - y| / bound over the nodes and components where the bound is positive (mode: fly_all's chain / restart)"""
+    wrong = fly_all(E, plan, prob, x, disp=disp, want_bound=False, mutate=mutate, **mode)[0]
     d = np.abs(wrong - y)
     ok = np.isfinite(d) & (by > 0)
     return float((d[ok] / by[ok]).max())

@@ -1,6 +1,7 @@
 """What gel_output_table_batch's reductions are checked against (tests/test_output_batch_cpu.py, tests/test_output_batch.py): the
 exactly rounded statistics of a table, the bound the device's mean and m2 must keep to them, and plain restatements of the peaks
-and of the stated reduction order.  numpy and Python integers only, no GPU.
+and of the stated reduction order -- in Python floats without the fma (welford_merge: inside the bound) and exactly as written, the
+fma in one rounding (welford_merge_exact: what the device gives bit for bit).  numpy, Python integers and fractions only, no GPU.
 
 The order the header states (include/gelato_amd.h): blocks of BLOCK = 256 consecutive vectors; inside a block Welford's update over
 the finite entries in ascending b,
@@ -185,6 +186,54 @@ def welford_merge(v, block=BLOCK):
         nt, d = n + nb, mb - mean
         mean = mean + d * (nb / nt)
         m2 = (m2 + sb) + (d * d) * ((n * nb) / nt)
+        n = nt
+        if lob < lo:
+            lo, alo = lob, alob
+        if hib > hi:
+            hi, ahi = hib, ahib
+    if n == 0:
+        return np.array([0.0, math.nan, math.nan, math.nan, math.nan, -1.0, -1.0, float(fnf)])
+    return np.array([float(n), mean, m2, lo, hi, float(alo), float(ahi), float(fnf)])
+
+
+def fma(a, b, c):
+    """a b + c with ONE rounding (finite arguments): the exact value in fractions.Fraction, rounded to nearest even by float()"""
+    return float(Fraction(a) * Fraction(b) + Fraction(c))
+
+
+def welford_merge_exact(v, block=BLOCK, contract_merge=False):
+    """the stated order EXACTLY as the header writes it -- welford_merge with m2 = fma(d, v - mean, m2) in one rounding, every
+    other written operation one rounding as Python floats give it -> the eight fields, which the device must give bit for bit.
+    contract_merge: a WRONG variant for the teeth, a merge that a compiler has contracted: "mean" Chan's mean + d (nb / nt) as one
+    fma(d, nb / nt, mean) (True means this one); "m2" the merged m2 as fma(d d, (n nb) / nt, m2 + m2_b).  The first shows only where
+    the block means differ by about as much as they are (the product's lost bits lie log2 |mean / d| places below the sum's last
+    bit); the second wherever the spread between the blocks is comparable with the spread inside them."""
+    assert contract_merge in (False, True, "mean", "m2")
+    n, mean, m2, lo, hi, alo, ahi, fnf = 0, 0.0, 0.0, 0.0, 0.0, -1, -1, -1
+    for b0 in range(0, len(v), block):
+        nb, mb, sb, lob, hib, alob, ahib = 0, 0.0, 0.0, 0.0, 0.0, -1, -1
+        for b in range(b0, min(b0 + block, len(v))):
+            x = float(v[b])
+            if not math.isfinite(x):
+                if fnf < 0:
+                    fnf = b
+                continue
+            nb += 1
+            d = x - mb
+            mb = mb + d / nb
+            sb = fma(d, x - mb, sb)
+            if alob < 0 or x < lob:
+                lob, alob = x, b
+            if ahib < 0 or x > hib:
+                hib, ahib = x, b
+        if nb == 0:
+            continue
+        if n == 0:
+            n, mean, m2, lo, hi, alo, ahi = nb, mb, sb, lob, hib, alob, ahib
+            continue
+        nt, d = n + nb, mb - mean
+        mean = fma(d, nb / nt, mean) if contract_merge in (True, "mean") else mean + d * (nb / nt)
+        m2 = fma(d * d, (n * nb) / nt, m2 + sb) if contract_merge == "m2" else (m2 + sb) + (d * d) * ((n * nb) / nt)
         n = nt
         if lob < lo:
             lo, alo = lob, alob

@@ -69,6 +69,33 @@ CASES = {
 MESHES = {"pack": (20, 31, 2), "coop": (40, 65, 2), "slab": (70, 5, 2)}      # tests/states.py table_state(); the tail has no aerodynamics
 
 
+# Every kernel that stages the tables into LDS -> the tests that run it over CASES ("file::test", parametrisation left off).
+# tests/test_table_sizes_cpu.py finds the kernels in gelato_amd/csrc and fails where one has no entry here or a named test is gone.
+# PER_INSTANTIATION: kernels keyed per value of their bool template parameters (each instantiation has a table-staging path of its own)
+PER_INSTANTIATION = {"prop_kernel": ("kDisp", "kChain")}
+_SIZES, _FLIGHT, _OUTBATCH = "test_table_sizes.py::", "test_table_sizes_flight.py::", "test_table_sizes_outbatch.py::"
+TABLE_KERNELS = {
+    "eval_kernel": [_SIZES + "test_defect_groups_against_the_oracle_in_every_form"],
+    "callback_kernel": [_SIZES + "test_defect_groups_against_the_oracle_in_every_form", _SIZES + "test_aero_kinds_dense_records_and_callback"],
+    "aero_kernel": [_SIZES + "test_aero_kinds_dense_records_and_callback"],
+    "aero_sm_kernel": [_SIZES + "test_aero_kinds_dense_records_and_callback"],
+    "aero_wide_kernel": [_SIZES + "test_aero_kinds_dense_records_and_callback"],
+    "rhs_vel_air_kernel": [_SIZES + "test_velocity_rhs_of_every_phase"],
+    "mesh_kernel": [_SIZES + "test_mesh_error_and_propagation"],
+    "output_kernel": [_SIZES + "test_output_table"],
+    "prop_kernel<false,false>": [_SIZES + "test_mesh_error_and_propagation"],
+    "prop_kernel<true,false>": [_FLIGHT + "test_dispersed_node_restart_on_the_table_states", _FLIGHT + "test_bits_of_a_vector_in_a_mixed_batch"],
+    "prop_kernel<false,true>": [_FLIGHT + "test_chain_of_the_example_over_the_tables"],
+    "prop_kernel<true,true>": [_FLIGHT + "test_chain_of_the_example_over_the_tables"],
+    "outbatch_rows_kernel": [_OUTBATCH + "test_table_bits_against_the_single_vector_call", _OUTBATCH + "test_envelope_and_peaks_two_blocks",
+                             _OUTBATCH + "test_dispersed_wind_bits_and_values"],
+    "outbatch_env_kernel": [_OUTBATCH + "test_envelope_and_peaks_two_blocks"],
+    # the exact kernels: LONG alone, in their own suites (exact arithmetic as the truth)
+    "exact_jac_kernel": ["test_exact_jac.py::test_exact_against_the_ground_truth_over_long_tables"],
+    "exact_aero_kernel": ["test_exact_aero_jac.py::test_exact_against_the_ground_truth_over_long_tables"],
+}
+
+
 def with_tables(prob, case):
     """a copy of prob over the case's tables"""
     prob = dict(prob)

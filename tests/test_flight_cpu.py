@@ -1,6 +1,6 @@
 """Chained flight and dispersions, host side (no GPU; host-only handles): the chain plan's flag, its refusals and
 gel_prop_plan_info, the Python argument checks, sample_dispersion, the restatement of tests/flight_truth.py against
-propagate_truth's bits, the teeth of its three wrong restatements, and the plan builder under AddressSanitizer + UBSan in a
+propagate_truth's bits (the chain's phase 0; the node restart as a whole), the teeth of its three wrong restatements, and the plan builder under AddressSanitizer + UBSan in a
 stand-alone program."""
 import os
 import subprocess
@@ -168,6 +168,41 @@ def test_truth_phase0_and_continuous_knots():
     # no dispersion and factors of one: the same bits (x * 1.0 is x)
     y1, _b, _e, _be = ft.fly_all(E, plan, prob, X[1], disp=np.ones((E.S, 4)), want_bound=False)
     assert np.array_equal(_bits(y1), _bits(ft.fly_all(E, plan, prob, X[1], want_bound=False)[0]))
+    plan.close()
+
+
+def test_truth_node_restart():
+    """fly_all(restart="node"): without factors it is propagate_truth.propagate_all(restart=True), bit for bit (y, bound, err);
+    the first node interval of every phase is the section mode's (both start from X_0 with E = 0), with factors too; the later
+    intervals are not (the section mode carries its state on); and the factors reach every interval"""
+    prob, E, X = example()
+    k = 2
+    plan = E.propagation_plan(steps=k, restart="node")
+    nn = [int(v) for v in E.num_nodes]
+    for b in (1, 2):
+        got = ft.fly_all(E, plan, prob, X[b], restart="node")
+        ref = pt.propagate_all(E, plan, prob, X[b], restart=True)
+        for a, r, name in zip(got, ref, ("y", "bound_y", "err", "bound_err")):
+            assert np.array_equal(_bits(a), _bits(r)), (b, name)
+    disp = ft.teeth_dispersion(E.S)
+    for d in (None, disp):
+        yn, bn, _e, _be = ft.fly_all(E, plan, prob, X[1], disp=d, restart="node")
+        ys, bs, _e, _be = ft.fly_all(E, plan, prob, X[1], disp=d, chain=False)
+        later = 0
+        for s in range(E.S):
+            xa = sum(nn[:s]) + s
+            assert np.array_equal(_bits(yn[xa:xa + 2]), _bits(ys[xa:xa + 2])) and np.array_equal(_bits(bn[xa:xa + 2]), _bits(bs[xa:xa + 2])), s
+            later += int(not np.array_equal(_bits(yn[xa + 2:xa + nn[s] + 1]), _bits(ys[xa + 2:xa + nn[s] + 1])))
+        assert later == E.S
+    y0 = ft.fly_all(E, plan, prob, X[1], restart="node", want_bound=False)[0]
+    moved = np.any(_bits(yn) != _bits(y0), axis=1)
+    powered = [s for s in range(E.S) if prob["engine_on"][s]]
+    assert len(powered) >= 6
+    for s in range(E.S):
+        xa = sum(nn[:s]) + s
+        assert not moved[xa], s                                              # node xa is X_0
+        if s in powered:                                                     # (a coast above the air has nothing to scale)
+            assert moved[xa + 1:xa + nn[s] + 1].all(), s                     # every interval feels the phase's factors
     plan.close()
 
 

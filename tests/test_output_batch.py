@@ -6,7 +6,11 @@ tests/output_batch_truth.py; host form = device form = second call, with or with
 gel_rows_eval calls; gelato_amd.montecarlo.flight_envelope.
 
 Batch sizes: 1, 2, 3, 64, 65, 67 (one envelope block), 256 and 257 (the block size and one more), 600 (three blocks: the merge runs
-twice).  Largest share of the bound the device used (MI355X, recorded in DESIGN.md 3.16): mean 0.50, m2 0.26, std 0.18."""
+twice).  Largest share of the bound the device used (MI355X, recorded in DESIGN.md 3.16): mean 0.50, m2 0.26, std 0.18.
+
+The envelope's node groups of 8 also on M = 64 and M = 3, with and without a table; and at B = 600 mean and m2 bit for bit the stated
+order restated with a correctly rounded fma (output_batch_truth.welford_merge_exact): the header's order is the contract, not only a
+bound around the exact statistics.  The long wind and CA tables: tests/test_table_sizes_outbatch.py."""
 import numpy as np
 import pytest
 
@@ -229,6 +233,60 @@ def test_envelope_mean_and_m2(g, engines, full, B):
     if B > 1:
         k = Engine.OUTPUT_COLUMNS.index("altitude")
         assert env[70, k, 7] == 1.0 and env[70, k, 0] == B - 1
+
+
+@pytest.mark.parametrize("B", [1, 9, 257])
+@pytest.mark.parametrize("handle", ["m64", "m3"])
+def test_envelope_mean_and_m2_node_groups(g, engines, handle, B):
+    """the same on M = 64 (every node group of outbatch_env_kernel full) and M = 3 (one group, five idle node lanes), B = 1, 9
+    (a second step of one vector) and 257 (a second block of one vector), in both forms: with a table (outbatch_env_table_kernel)
+    and without one (outbatch_env_kernel) -- each against the exact statistics of the table, and bit for bit each other's"""
+    E = engines[handle]
+    X, TX = _batch(g, handle, B)
+    R = E.output_table_batch(X, LAT, LON, tx=TX)
+    assert R["table"].shape == (B, MS[handle], 34) and same(R["table"][:1], single_tables(g, engines, handle, 1))
+    alone = E.output_table_batch(X, LAT, LON, tx=TX, table=False, peaks=False)
+    for form, r in (("with a table", R), ("without a table", alone)):
+        env = _env_array(r)
+        std = np.stack([r["envelope"][c]["std"] for c in r["columns"]], axis=1)
+        share = obt.check_envelope(R["table"], env, std=std)
+        print("\n%s B = %d %s: largest share of the bound used: mean %.3g, m2 %.3g, std %.3g" % (handle, B, form, share["mean"], share["m2"], share["std"]))
+        fin = np.isfinite(R["table"]).all(axis=0)
+        assert fin.any() and np.all(env[:, :, 0][fin] == float(B))
+        if B == 1:
+            assert np.all(env[:, :, 2][fin] == 0.0)
+    assert same(_env_array(alone), _env_array(R))
+
+
+EXACT_NODES = (0, 1, 5, 63, 64, 70, 127, 128)      # both ends of a node group and of a tile of 64; node 70 holds vector 1's NaN
+
+
+def test_envelope_is_the_stated_order_bit_for_bit(g, engines, full):
+    """B = 600 on the big handle (three blocks, two merges): count, mean, m2 and the other five fields of eight nodes x all 34
+    columns equal output_batch_truth.welford_merge_exact -- the header's order, each written operation one rounding, the fma
+    correctly rounded -- on the device's own table, bit for bit.  tests/test_output_batch_cpu.py shows that this restatement differs
+    in its bits from the order without the fma and from a contracted merge."""
+    B = 600
+    R = full(B)
+    env = _env_array(R)
+    T = R["table"]
+    differ, told_apart, contracted = [], 0, 0
+    for i in EXACT_NODES:
+        for k, c in enumerate(R["columns"]):
+            want = obt.welford_merge_exact(T[:, i, k])
+            # restatement against restatement on this table: the order without the fma, and a merge whose m2 is contracted
+            told_apart += int(not same(obt.welford_merge(T[:, i, k])[2], want[2]))
+            contracted += int(not same(obt.welford_merge_exact(T[:, i, k], contract_merge="m2")[2], want[2]))
+            if not same(env[i, k], want):
+                differ.append((i, c, [f for j, f in enumerate(obt.ENV_FIELDS) if not same(env[i, k, j], want[j])], env[i, k, 1:3].tolist(), want[1:3].tolist()))
+    assert not differ, (len(differ), differ[:5])
+    k = Engine.OUTPUT_COLUMNS.index("altitude")
+    assert env[70, k, 0] == B - 1 and env[70, k, 7] == 1.0
+    print("\nB = %d: %d of %d pairs equal the stated order bit for bit; in m2 the order without the fma differs at %d of them, a "
+          "contracted merge at %d" % (B, len(EXACT_NODES) * 34 - len(differ), len(EXACT_NODES) * 34, told_apart, contracted))
+    # (a contracted MEAN update cannot show on this batch: its block means differ by 1e-7 of their size, so the product's lost bits
+    # lie 23 places below the sum's last one; tests/test_output_batch_cpu.py tells that variant apart on spread-out columns)
+    assert told_apart >= 1 and contracted >= 1, (told_apart, contracted)
 
 
 def test_envelope_count_zero_and_ties(g, engines):

@@ -1,4 +1,8 @@
-"""Every kernel that reads the wind and CA tables, on small problems over the tables of tests/table_cases.py (two rows; 32 | 33 rows:
+"""The kernels that read the wind and CA tables -- the fused kernel, the aero kernels, rhs_vel_air_kernel, mesh_kernel, output_kernel
+and prop_kernel<false, false> here; prop_kernel's dispersed and chained instantiations in tests/test_table_sizes_flight.py; the
+batched output table's outbatch_rows_kernel and outbatch_env_kernel in tests/test_table_sizes_outbatch.py (table_cases.TABLE_KERNELS
+lists kernel by kernel which test runs it; tests/test_table_sizes_cpu.py holds the list to the sources) -- on small problems over
+the tables of tests/table_cases.py (two rows; 32 | 33 rows:
 the two branches of lower_count; 160 wind rows: several passes of every staging loop, both parities of the padded table size that
 the regions behind the tables start at), under the comparisons the suite already makes for the same entry points on the example's
 tables -- imported, not restated; no tolerance of its own.
@@ -279,22 +283,31 @@ def test_output_table(case, mesh):
     measured 8.6e-9 m/s on vel_air against a flat 1e-9.  The term is what the oracle's own column moves by when every node is
     raised or lowered by TOL["altitude"]; the other columns keep TOL as it is."""
     from gelato_amd import Engine
-    from test_output_table import TOL, check_device_column
-    behind_the_wind = ("vel_air", "AOA_total", "AOA_pitch", "AOA_yaw", "dynamic_pressure", "Q_alpha", "M", "aero_BODY_X", "accel_BODY_X")
+    from test_output_table import check_device_column
     prob, _xc = _state(case, mesh, "climb")
     E = Engine(prob)
     for vector in ("climb", "knots"):
         x = _state(case, mesh, vector)[1]
         tx = states.table_node_times(prob, x)
         Tt = states.table_oracle_rows(prob, x)
-        M = E.M
-        moved = []
-        for sign in (1.0, -1.0):
-            xm = x.copy()
-            r = xm[M:4 * M].reshape(-1, 3)
-            r *= 1.0 + sign * TOL["altitude"][0] / (np.linalg.norm(r, axis=1, keepdims=True) * float(prob["units"][1]))
-            moved.append(states.table_oracle_rows(prob, xm))
+        extra = behind_the_wind_extra(prob, x, Tt)
         got = E.output_table(x, tx, 28.5, 0.0)
         for j, c in enumerate(E.OUTPUT_COLUMNS):
-            extra = np.maximum(np.abs(moved[0][c] - Tt[c]), np.abs(moved[1][c] - Tt[c])) if c in behind_the_wind else 0.0
-            check_device_column(c, got[:, j], ((Tt[c], "oracle"),), extra=extra)
+            check_device_column(c, got[:, j], ((Tt[c], "oracle"),), extra=extra[c])
+
+
+BEHIND_THE_WIND = ("vel_air", "AOA_total", "AOA_pitch", "AOA_yaw", "dynamic_pressure", "Q_alpha", "M", "aero_BODY_X", "accel_BODY_X")
+
+
+def behind_the_wind_extra(prob, x, Tt):
+    """{column: the extra term of test_output_table's docstring}: what the oracle's own column (Tt = table_oracle_rows(prob, x))
+    moves by when every node is raised or lowered by TOL["altitude"], for the columns behind the wind lookup; 0.0 for the others"""
+    from test_output_table import TOL
+    M = len(Tt["altitude"])
+    moved = []
+    for sign in (1.0, -1.0):
+        xm = x.copy()
+        r = xm[M:4 * M].reshape(-1, 3)
+        r *= 1.0 + sign * TOL["altitude"][0] / (np.linalg.norm(r, axis=1, keepdims=True) * float(prob["units"][1]))
+        moved.append(states.table_oracle_rows(prob, xm))
+    return {c: (np.maximum(np.abs(moved[0][c] - Tt[c]), np.abs(moved[1][c] - Tt[c])) if c in BEHIND_THE_WIND else 0.0) for c in Tt}
