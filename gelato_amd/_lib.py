@@ -22,6 +22,7 @@ GEL_PROP_RESTART_NODE = 1        # gel_prop_plan_create: every node interval sta
 GEL_PROP_CHAIN = 2               # gel_prop_plan_create: one integration per vector through all phases, the state carried across the knots (the flight)
 GEL_ENV_NSTAT, GEL_PEAK_NSTAT = 8, 4   # gel_output_table_batch*: statistics per (node, column) and per (vector, column)
 GEL_PROP_NDISP = 4               # gel_propagate_dispersed*: factors per (vector, phase): thrust, mass flow, reference area, wind
+GEL_QUANT_MAXQ = 16              # gel_batch_quantiles*: probabilities per call
 GEL_FLAG_EXACT_ROWS_JAC = 128    # node-function rows' jfn (terminal, user, waypoint rows) exact to rounding instead of forward differences
 NUM_BLOCKS = 13
 
@@ -68,6 +69,10 @@ class GelDims(C.Structure):
         ("total_nnz", C.c_int64), ("num_var_entries", C.c_int64), ("algorithmic_bytes", C.c_int64),
         ("stored_bytes", C.c_int64),
     ]
+
+
+class GelQuantilesInfo(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("bins", "cap", "chunk", "slab_cols", "workspace_bytes", "workspace_cap_bytes", "passes", "slabs")]
 
 
 # every symbol include/gelato_amd.h declares, with its signature
@@ -164,6 +169,11 @@ SIGNATURES = {
     "gel_output_table_batch": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, _dp, C.c_double, C.c_double, C.c_int32, _ip, _dp, _dp, _dp]),
     "gel_output_table_batch_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
                                                 C.c_int32, _ip, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gel_batch_quantiles": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, _dp, C.c_int32, _dp, _dp, _dp, _dp]),
+    "gel_batch_quantiles_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, _dp, C.c_void_p, C.c_void_p,
+                                             C.c_void_p]),
+    "gel_batch_quantiles_info": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.POINTER(GelQuantilesInfo)]),
+    "gel_batch_quantiles_last": (C.c_int, [C.c_void_p, _lp]),
     "gel_dynamics_velocity": (C.c_int, [C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int32, _dp, C.c_int32,
                                          _dp, C.c_double, _dp]),
     "gel_dynamics_velocity_NoAir": (C.c_int, [C.c_int32, _dp, _dp, _dp, _dp, _dp, C.c_double, _dp]),
@@ -180,7 +190,7 @@ def build(force=False):
     src_dir = os.path.join(_HERE, "csrc")
     if force and os.path.exists(SO_PATH):
         os.remove(SO_PATH)
-    subprocess.check_call(["make", "-s", "-j8", "-C", src_dir])   # twelve translation units (kernels, the AERO instantiation, the three exact Jacobians, the mesh error estimate, the two Jacobian products, the interpolation, the propagation, the batched output table, host side)
+    subprocess.check_call(["make", "-s", "-j8", "-C", src_dir])   # thirteen translation units (kernels, the AERO instantiation, the three exact Jacobians, the mesh error estimate, the two Jacobian products, the interpolation, the propagation, the batched output table, the batch quantiles, host side)
     if not os.path.exists(SO_PATH):
         raise RuntimeError("building %s failed" % SO_PATH)
     _write_build_info()

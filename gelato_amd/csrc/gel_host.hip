@@ -25,6 +25,7 @@
 #include "gel_interp.h"
 #include "gel_prop.h"
 #include "gel_outbatch.h"
+#include "gel_quant.h"
 
 namespace {
 
@@ -361,6 +362,10 @@ struct gel_problem {
   // the envelope partials of gel_output_table_batch* (DESIGN.md 3.16): the device form's buffers are the caller's, so the partials
   // cannot live beside them in the arena; only grows, after a drain
   DeviceArray<double> d_outws;
+  // the workspace of gel_batch_quantiles* (gel_quant.h quant_layout), capped at gel::kQuantWsCap: only grows, after a
+  // drain.  quant_targets: the (column, rank) pairs of the last call, for gel_batch_quantiles_last
+  DeviceArray<char> d_quantws;
+  int64_t quant_targets = 0;
   // gel_jac_fd working set: kept between calls; the residuals of all num_vars + 1 perturbed vectors are
   // re-used while x stays the same (the four groups are asked for one after the other)
   DeviceArray<double> jfd_x, jfd_Xp, jfd_res, jfd_J;
@@ -3550,6 +3555,105 @@ int gel_output_table_batch(gel_problem* p, int32_t B, const double* x, const dou
                        A.x = a[0]; A.tx = a[1]; A.disp = a[5];
                        return outbatch_enqueue(p, A, a[2], a[3], a[4]);
                      });
+}
+
+// ------------- exact batched quantiles over the vectors of a batch -------------
+// the argument checks of both forms, before the device check
+static int quant_check(gel_problem* p, int32_t B, int64_t W, int64_t ld, const void* src, int32_t nq, const double* probs, const void* q) {
+  if (!p) return fail(GEL_ERR_ARG, "gel_batch_quantiles: null handle");
+  if (B < 0 || W < 0) return fail(GEL_ERR_ARG, "gel_batch_quantiles: B < 0 or W < 0");
+  if (ld < W) return fail(GEL_ERR_ARG, "gel_batch_quantiles: ld = " + std::to_string(ld) + " < W = " + std::to_string(W));
+  if (!src && B > 0 && W > 0) return fail(GEL_ERR_ARG, "gel_batch_quantiles: src is NULL with B W > 0");
+  if (!q) return fail(GEL_ERR_ARG, "gel_batch_quantiles: q is NULL");
+  if (nq < 1 || nq > gel::kQuantMaxQ)
+    return fail(GEL_ERR_ARG, "gel_batch_quantiles: nq = " + std::to_string(nq) + " outside 1 .. " + std::to_string(gel::kQuantMaxQ));
+  if (!probs) return fail(GEL_ERR_ARG, "gel_batch_quantiles: probs is NULL");
+  for (int j = 0; j < nq; j++)
+    if (!(probs[j] >= 0.0 && probs[j] <= 1.0))   // NaN fails both comparisons
+      return fail(GEL_ERR_ARG, "gel_batch_quantiles: probs[" + std::to_string(j) + "] is not a number in [0, 1]");
+  return GEL_OK;
+}
+
+// the launches of one call on the handle's stream: the source is walked in slabs of columns, each through the same workspace
+static int quant_enqueue(gel_problem* p, int32_t B, int64_t W, int64_t ld, const double* d_src, int32_t nq, const double* probs, double* d_q,
+                         double* d_count, double* d_who) {
+  const int T = 2 * nq;
+  p->quant_targets = W * T;
+  if (W == 0) return GEL_OK;
+  hipStream_t s = p->stream.get();
+  const int64_t slab = std::min<int64_t>(gel::quant_slab_cols(T), W);
+  const gel::QuantLayout L = gel::quant_layout(slab, T);
+  if (p->d_quantws.capacity() < L.bytes) {
+    HIPCHK(drain(p));   // an earlier call in flight still uses the old block
+    HIPCHK(p->d_quantws.reserve(L.bytes));
+  }
+  char* ws = p->d_quantws.get();
+  HIPCHK(hipMemsetAsync(ws, 0, 256, s));
+  gel::QuantArgs A{};
+  A.B = B; A.nq = nq; A.T = T; A.ld = ld;
+  A.src = reinterpret_cast<const unsigned long long*>(d_src);
+  for (int j = 0; j < nq; j++) A.probs[j] = probs[j];
+  A.q = d_q; A.count = d_count; A.who = d_who;
+  A.counters = reinterpret_cast<unsigned long long*>(ws + L.counters);
+  A.col = reinterpret_cast<gel::QuantCol*>(ws + L.col);
+  A.hist = reinterpret_cast<uint32_t*>(ws + L.hist);
+  A.tgt = reinterpret_cast<gel::QuantTarget*>(ws + L.tgt);
+  A.cand = reinterpret_cast<unsigned long long*>(ws + L.cand);
+  for (int64_t w0 = 0; w0 < W; w0 += slab) {
+    A.w0 = w0;
+    A.wn = (int32_t)std::min<int64_t>(slab, W - w0);
+    A.chunk = (int32_t)gel::quant_chunk(B, A.wn);
+    HIPCHK(gel::launch_quant_slab(A, s));
+  }
+  return GEL_OK;
+}
+
+int gel_batch_quantiles_device(gel_problem* p, int32_t B, int64_t W, int64_t ld, const double* d_src, int32_t nq, const double* probs,
+                               double* d_q, double* d_count, double* d_who) {
+  if (int rc = quant_check(p, B, W, ld, d_src, nq, probs, d_q)) return rc;
+  NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
+  HIPCHK(hipSetDevice(p->device));
+  return quant_enqueue(p, B, W, ld, d_src, nq, probs, d_q, d_count, d_who);
+}
+
+int gel_batch_quantiles(gel_problem* p, int32_t B, int64_t W, int64_t ld, const double* src, int32_t nq, const double* probs, double* q,
+                        double* count, double* who) {
+  if (int rc = quant_check(p, B, W, ld, src, nq, probs, q)) return rc;
+  NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
+  HIPCHK(hipSetDevice(p->device));
+  // the rows are staged as they lie, [B][ld] up to the last column read: the view stays a view
+  const size_t ns = (B > 0 && W > 0) ? (size_t)(B - 1) * (size_t)ld + (size_t)W : 0, no = (size_t)W * nq * 2;
+  return staged_call(p, kStagedNoFlag, {staged_in(ns ? src : nullptr, ns), staged_out(q, no), staged_out(count, (size_t)W), staged_out(who, no)},
+                     [&](const gel::ProblemDev&, double* const* a) -> int {
+                       return quant_enqueue(p, B, W, ld, a[0], nq, probs, a[1], a[2], a[3]);
+                     });
+}
+
+int gel_batch_quantiles_info(const gel_problem* p, int32_t B, int64_t W, int32_t nq, gel_quantiles_info* info) {
+  if (!p || !info || B < 0 || W < 0 || nq < 1 || nq > gel::kQuantMaxQ) return fail(GEL_ERR_ARG, "gel_batch_quantiles_info: bad argument");
+  const int T = 2 * nq;
+  const int64_t slab = gel::quant_slab_cols(T), used = std::min<int64_t>(slab, W);
+  info->bins = gel::kQuantBins;
+  info->cap = gel::kQuantCap;
+  info->chunk = gel::quant_chunk(B, used);
+  info->slab_cols = slab;
+  info->workspace_bytes = W > 0 ? (int64_t)gel::quant_layout(used, T).bytes : 0;
+  info->workspace_cap_bytes = (int64_t)gel::kQuantWsCap;
+  info->passes = B > 0 && W > 0 ? 3 : 0;
+  info->slabs = W > 0 ? (W + slab - 1) / slab : 0;
+  return GEL_OK;
+}
+
+int gel_batch_quantiles_last(gel_problem* p, int64_t* stats) {
+  if (!p || !stats) return fail(GEL_ERR_ARG, "gel_batch_quantiles_last: null argument");
+  NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
+  HIPCHK(hipSetDevice(p->device));
+  unsigned long long c[4] = {0, 0, 0, 0};
+  HIPCHK(hipStreamSynchronize(p->stream.get()));
+  if (p->d_quantws.get()) HIPCHK(hipMemcpy(c, p->d_quantws.get(), sizeof(c), hipMemcpyDeviceToHost));
+  stats[0] = p->quant_targets;
+  for (int k = 1; k < 4; k++) stats[k] = p->quant_targets ? (int64_t)c[k] : 0;
+  return GEL_OK;
 }
 
 // ------------- from-file initial guess on the host (initialize.py:322-409) -------------

@@ -839,6 +839,77 @@ class Engine:
                                                   float(launch_lon), len(names), ids.ctypes.data_as(_ip) if ids is not None else None,
                                                   d_out or None, d_env or None, d_peaks or None))
 
+    @staticmethod
+    def _quantile_probs(probs):
+        p = np.atleast_1d(np.asarray(probs, dtype=np.float64)).copy()
+        if p.ndim != 1 or not 1 <= p.size <= _lib.GEL_QUANT_MAXQ:
+            raise ValueError("probs: 1 .. %d probabilities, not shape %s" % (_lib.GEL_QUANT_MAXQ, p.shape))
+        if not np.all((p >= 0.0) & (p <= 1.0)):
+            raise ValueError("probs: numbers in [0, 1], not %s" % (p,))
+        return p
+
+    @staticmethod
+    def quantile_value(probs, count, lower, upper):
+        """the interpolated quantile lower + (upper - lower) (h - lo), h = p (count - 1), lo = floor(h); NaN where count = 0.
+        probs [nq]; count [...]; lower, upper [..., nq].  (Where upper - lower overflows, between two ranks 1.8e308 apart, so does
+        the value: lower and upper are the exact answer there.)"""
+        p = np.asarray(probs, dtype=np.float64)
+        n1 = np.maximum(np.asarray(count, dtype=np.int64) - 1, 0).astype(np.float64)[..., None]
+        h = p * n1
+        with np.errstate(invalid="ignore", over="ignore"):
+            v = lower + (upper - lower) * (h - np.floor(h))
+        return np.where(np.asarray(count)[..., None] > 0, v, np.nan)
+
+    def batch_quantiles(self, A, probs, who=False):
+        """Exact quantiles over the first axis of A (gel_batch_quantiles).  A: float64 [B, W], or any C-contiguous
+        [B, ...], flattened behind the first axis; probs: 1 .. 16 probabilities in [0, 1].
+        -> {"probs" [nq], "count" [W] int64 (the finite entries of a column), "lower", "upper" [W, nq]: the floor(h)-th and ceil(h)-th
+            finite entry in key order, h = p (count - 1), bit copies of entries of A (NaN where count = 0),
+            "value" [W, nq]: lower + (upper - lower) (h - floor(h)), formed here,
+            "who_lower", "who_upper" [W, nq] int64 (who=True): the lowest b whose entry is that one; -1 where count = 0}"""
+        p = self._quantile_probs(probs)
+        A = np.asarray(A)
+        if A.dtype != np.float64:
+            raise TypeError("A: float64, not %s" % A.dtype)
+        if A.ndim < 1:
+            raise ValueError("A: [B, ...]")
+        if not A.flags.c_contiguous:
+            raise ValueError("A: C-contiguous")
+        B = A.shape[0]
+        W = int(np.prod(A.shape[1:], dtype=np.int64)) if A.ndim > 1 else 1
+        nq = p.size
+        q = np.empty((W, nq, 2))
+        cnt = np.empty(W)
+        wh = np.empty((W, nq, 2)) if who else None
+        check(lib().gel_batch_quantiles(self._h, B, W, W, _d(A) if A.size else None, nq, _d(p), _d(q), _d(cnt), _d(wh) if who else None))
+        count = cnt.astype(np.int64)
+        lower, upper = np.ascontiguousarray(q[:, :, 0]), np.ascontiguousarray(q[:, :, 1])
+        res = {"probs": p, "count": count, "lower": lower, "upper": upper, "value": self.quantile_value(p, count, lower, upper)}
+        if who:
+            res["who_lower"], res["who_upper"] = wh[:, :, 0].astype(np.int64), wh[:, :, 1].astype(np.int64)
+        return res
+
+    def batch_quantiles_device(self, B, W, ld, d_src, probs, d_q, d_count=0, d_who=0):
+        """device buffers (raw pointers; 0 = not given): d_src [B][ld] of which columns 0 .. W - 1 are read, d_q [W][nq][2], d_count
+        [W], d_who [W][nq][2]; probs stays on the host; asynchronous on the engine's own stream; status through Engine.sync()"""
+        p = self._quantile_probs(probs)
+        check(lib().gel_batch_quantiles_device(self._h, int(B), int(W), int(ld), d_src or None, p.size, _d(p), d_q or None, d_count or None,
+                                               d_who or None))
+
+    def batch_quantiles_info(self, B, W, nq):
+        """-> {"bins", "cap", "chunk", "slab_cols", "workspace_bytes", "workspace_cap_bytes", "passes", "slabs"}: what a call
+        would select (gel_batch_quantiles_info; needs no GPU)"""
+        info = _lib.GelQuantilesInfo()
+        check(lib().gel_batch_quantiles_info(self._h, int(B), int(W), int(nq), C.byref(info)))
+        return {k: int(getattr(info, k)) for k, _t in info._fields_}
+
+    def batch_quantiles_last(self):
+        """-> {"targets", "by_range", "by_candidates", "by_fallback"}: how the (column, rank) pairs of the last batch_quantiles*
+        call were settled (gel_batch_quantiles_last; waits for the engine's stream)"""
+        st = (C.c_int64 * 4)()
+        check(lib().gel_batch_quantiles_last(self._h, st))
+        return dict(zip(("targets", "by_range", "by_candidates", "by_fallback"), (int(v) for v in st)))
+
     def initial_guess(self, t_ref, table, knot_times):
         """initialize.py:322-409 behind the C-ABI: reference trajectory (t_ref [n], table [n, 13] = mass | pos 3 | vel 3 |
         quat 4 | body rates y, z) interpolated at the mesh's node times -> packed decision vector"""

@@ -720,6 +720,57 @@ int gel_output_table_batch_device(gel_problem* p, int32_t B, const double* d_x, 
                                   const int32_t* cols /* host pointer, or NULL */, double* d_out /* or NULL */,
                                   double* d_env /* or NULL */, double* d_peaks /* or NULL */);
 
+/* ---- exact quantiles over the vectors of a batch: what a Monte-Carlo batch is read by -- the 99.865 % value of
+ *      every flight's peak, the 0.135 % / 99.865 % band of the terminal row, the 2.5 .. 97.5 % band of every column along the
+ *      trajectory, and which flight that is.  src [B][ld]: columns 0 .. W - 1 of every row are read.  Everything below is per column
+ *      w, independent of every other column, of W, of ld and of the order of the vectors.
+ *      Key: an entry with bits u (uint64) has the key  u ^ (u >> 63 ? ~0 : 1 << 63).  Ascending keys are ascending doubles, with
+ *      -0.0 before +0.0.  This total order is the contract.
+ *      Which entries count: the finite ones; NaN and +-Inf are left out, as in the envelope.  n = their number; count[w] = n (a double).
+ *      The rank rule, for every probs[j]:  h = probs[j] * (double)(n - 1), one fp64 product, one rounding;  lo = floor(h), hi = ceil(h).
+ *      Outputs: q[w][j][0] = the lo-th and q[w][j][1] = the hi-th finite entry in key order (0-based), both bit copies of source
+ *      entries; n = 0: NaN in both.  who[w][j][.] = the lowest vector index b whose entry has exactly that key, as a double; -1
+ *      where n = 0.  The interpolated quantile lower + (upper - lower) (h - lo) is NOT formed here: that is the caller's (Python's).
+ *      Being order statistics, the results depend on no summation order, launch geometry, stream or form of the call: they are the
+ *      bits a plain sort of the keys gives.  Nothing is sorted and no transposed copy of the source is kept: the call reads the
+ *      source three times (range; histogram of GEL-internal 256 bins per column through a monotone map in value space; gather of
+ *      the bins that hold a rank), a fourth time when who is given, and a target whose bin holds more than 2048 entries (heavy
+ *      ties, one wild vector stretching the range, a range that overflows) is found by bisection on the key over its column, 256
+ *      pivots (one byte of the key) per counting round: at most 8 rounds.  No floating-point atomics.
+ *      Views: ld >= W lets a call read a view -- the whole table of gel_output_table_batch (W = ld = M ncols), its last node's row
+ *      (src + (M - 1) ncols, W = ncols, ld = M ncols), the peaks (W = ld = 4 ncols), err of gel_propagate*, the rows of
+ *      gel_rows_eval_device.  All offsets are 64-bit.
+ *      GEL_ERR_ARG, decided before the device is looked at: p NULL; B < 0, W < 0, ld < W; src NULL with B W > 0; q NULL; nq outside
+ *      1 .. GEL_QUANT_MAXQ; probs NULL, or a probability that is not finite or lies outside [0, 1].  B = 0 succeeds and writes the
+ *      n = 0 pattern; W = 0 succeeds and writes nothing.  The source legitimately holds NaN, so these calls never return
+ *      GEL_NONFINITE: count carries that.  A valid call on a GEL_DEVICE_NONE handle returns what gel_output_table_batch returns there.
+ *      The host form copies rows [B][ld] (up to the last column read) in, launches, copies out and synchronises once (the handle's
+ *      arena).  The device form takes NO stream argument: like gel_output_table_batch_device it enqueues everything on the handle's
+ *      own stream and reports through gel_sync(p, NULL); there is no host round trip in it.  probs stays a host pointer in both.
+ *      Workspace: the handle's, only grows, at most 256 MiB (gel_quantiles_info.workspace_cap_bytes): per column 1048 bytes and
+ *      per (column, rank) 16416 bytes; a source wider than fits is walked in slabs of columns (a multiple of 64) on the stream.
+ *      gel_batch_quantiles_info (needs no GPU) reports what a call would select.  gel_batch_quantiles_last waits for the handle's
+ *      stream and reports how the (column, rank) pairs of the LAST call were settled: stats[0] = their number (2 nq W), [1] by the
+ *      range pass alone (n = 0, or a constant column), [2] from a candidate buffer, [3] by the bisection over the column. ---- */
+#define GEL_QUANT_MAXQ 16
+typedef struct {
+  int64_t bins;                /* bins of a column's histogram */
+  int64_t cap;                 /* keys a candidate buffer holds: a fuller bin goes to the bisection over the column */
+  int64_t chunk;               /* vectors per workgroup of the passes over the source (1024; 256 below 16 column blocks) */
+  int64_t slab_cols;           /* columns per slab: the most the workspace cap holds for this nq, a multiple of 64 */
+  int64_t workspace_bytes;     /* what this call needs of the handle's workspace */
+  int64_t workspace_cap_bytes; /* the cap */
+  int64_t passes;              /* reads of the source without who (who adds one); the bisection's rounds are not counted */
+  int64_t slabs;               /* slabs this call walks */
+} gel_quantiles_info;
+int gel_batch_quantiles(gel_problem* p, int32_t B, int64_t W, int64_t ld, const double* src /* [B][ld], columns 0 .. W-1 read */,
+                        int32_t nq, const double* probs /* [nq], host */, double* q /* [W][nq][2] */,
+                        double* count /* [W] or NULL */, double* who /* [W][nq][2] or NULL */);
+int gel_batch_quantiles_device(gel_problem* p, int32_t B, int64_t W, int64_t ld, const double* d_src, int32_t nq,
+                               const double* probs /* host */, double* d_q, double* d_count /* or NULL */, double* d_who /* or NULL */);
+int gel_batch_quantiles_info(const gel_problem* p, int32_t B, int64_t W, int32_t nq, gel_quantiles_info* info);
+int gel_batch_quantiles_last(gel_problem* p, int64_t* stats /* [4] */);
+
 /* ---- from-file initial guess on the host (replaces initialize.py:322-409 initialize_xdict_6DoF_from_file, LGR mode;
  *      SURVEY.md 8f row f-3): linear interpolation (scipy interp1d with fill_value="extrapolate": the end intervals extend
  *      beyond the table) of a reference trajectory at the state-node times [-1, tau] and the control-node times tau of
