@@ -75,6 +75,11 @@ class GelQuantilesInfo(C.Structure):
     _fields_ = [(k, C.c_int64) for k in ("bins", "cap", "chunk", "slab_cols", "workspace_bytes", "workspace_cap_bytes", "passes", "slabs")]
 
 
+class GelComomentsInfo(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("block", "tile_a", "tile_b", "slab_rows", "slab_cols", "slabs", "workspace_bytes",
+                                         "workspace_cap_bytes", "passes_a", "passes_b")]
+
+
 # every symbol include/gelato_amd.h declares, with its signature
 SIGNATURES = {
     "gel_lgr_nodes": (C.c_int, [C.c_int32, _dp]),
@@ -174,6 +179,11 @@ SIGNATURES = {
                                              C.c_void_p]),
     "gel_batch_quantiles_info": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int32, C.POINTER(GelQuantilesInfo)]),
     "gel_batch_quantiles_last": (C.c_int, [C.c_void_p, _lp]),
+    "gel_batch_comoments": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, _dp, C.c_int64, C.c_int64, C.c_int64, _dp,
+                                      _dp, _dp, _dp, _dp]),
+    "gel_batch_comoments_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64,
+                                             C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gel_batch_comoments_info": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int32, C.POINTER(GelComomentsInfo)]),
     "gel_dynamics_velocity": (C.c_int, [C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp, _dp, C.c_int32, _dp, C.c_int32,
                                          _dp, C.c_double, _dp]),
     "gel_dynamics_velocity_NoAir": (C.c_int, [C.c_int32, _dp, _dp, _dp, _dp, _dp, C.c_double, _dp]),
@@ -190,7 +200,7 @@ def build(force=False):
     src_dir = os.path.join(_HERE, "csrc")
     if force and os.path.exists(SO_PATH):
         os.remove(SO_PATH)
-    subprocess.check_call(["make", "-s", "-j8", "-C", src_dir])   # thirteen translation units (kernels, the AERO instantiation, the three exact Jacobians, the mesh error estimate, the two Jacobian products, the interpolation, the propagation, the batched output table, the batch quantiles, host side)
+    subprocess.check_call(["make", "-s", "-j8", "-C", src_dir])   # fourteen translation units (kernels, the AERO instantiation, the three exact Jacobians, the mesh error estimate, the two Jacobian products, the interpolation, the propagation, the batched output table, the batch quantiles, the batch co-moments, host side)
     if not os.path.exists(SO_PATH):
         raise RuntimeError("building %s failed" % SO_PATH)
     _write_build_info()

@@ -26,6 +26,7 @@
 #include "gel_prop.h"
 #include "gel_outbatch.h"
 #include "gel_quant.h"
+#include "gel_comom.h"
 
 namespace {
 
@@ -366,6 +367,8 @@ struct gel_problem {
   // drain.  quant_targets: the (column, rank) pairs of the last call, for gel_batch_quantiles_last
   DeviceArray<char> d_quantws;
   int64_t quant_targets = 0;
+  // the workspace of gel_batch_comoments* (gel_comom.h com_layout), capped at gel::kComWsCap: only grows, after a drain
+  DeviceArray<char> d_comws;
   // gel_jac_fd working set: kept between calls; the residuals of all num_vars + 1 perturbed vectors are
   // re-used while x stays the same (the four groups are asked for one after the other)
   DeviceArray<double> jfd_x, jfd_Xp, jfd_res, jfd_J;
@@ -3653,6 +3656,127 @@ int gel_batch_quantiles_last(gel_problem* p, int64_t* stats) {
   if (p->d_quantws.get()) HIPCHK(hipMemcpy(c, p->d_quantws.get(), sizeof(c), hipMemcpyDeviceToHost));
   stats[0] = p->quant_targets;
   for (int k = 1; k < 4; k++) stats[k] = p->quant_targets ? (int64_t)c[k] : 0;
+  return GEL_OK;
+}
+
+// ------------- batched co-moments over the vectors of a batch -------------
+// the argument checks of both forms, before the device check
+static int comom_check(const gel_problem* p, int32_t B, int64_t Wa, int64_t inca, int64_t lda, const void* a, int64_t Wb, int64_t incb,
+                       int64_t ldb, const void* b, const void* C, const void* stat_b, const void* info) {
+  if (!p) return fail(GEL_ERR_ARG, "gel_batch_comoments: null handle");
+  if (B < 0) return fail(GEL_ERR_ARG, "gel_batch_comoments: B < 0");
+  if (Wa < 0 || (b && Wb < 0)) return fail(GEL_ERR_ARG, "gel_batch_comoments: W < 0");
+  if (inca < 1 || (b && incb < 1)) return fail(GEL_ERR_ARG, "gel_batch_comoments: inc < 1");
+  const auto too_small = [](int64_t W, int64_t inc, int64_t ld) { return W > 0 && (ld < 1 || (W - 1) > (ld - 1) / inc); };   // ld < (W - 1) inc + 1
+  if (too_small(Wa, inca, lda)) return fail(GEL_ERR_ARG, "gel_batch_comoments: lda = " + std::to_string(lda) + " < (Wa - 1) inca + 1");
+  if (b && too_small(Wb, incb, ldb)) return fail(GEL_ERR_ARG, "gel_batch_comoments: ldb = " + std::to_string(ldb) + " < (Wb - 1) incb + 1");
+  if (!a && B > 0 && Wa > 0) return fail(GEL_ERR_ARG, "gel_batch_comoments: a is NULL with B Wa > 0");
+  if (!info) return fail(GEL_ERR_ARG, "gel_batch_comoments: info is NULL");
+  if (!b && stat_b) return fail(GEL_ERR_ARG, "gel_batch_comoments: stat_b given in the self form (b is NULL)");
+  const int64_t wb = b ? Wb : Wa;
+  if (!C && Wa > 0 && wb > 0) return fail(GEL_ERR_ARG, "gel_batch_comoments: C is NULL with Wa Wb > 0");
+  return GEL_OK;
+}
+
+// columns per slab at the most: GEL_COMOM_SLAB (b columns) and GEL_COMOM_SLAB_ROWS (a columns), measurement switches read per call;
+// 0 / unset = what the cap holds.  The results do not depend on them.
+static int64_t comom_max_slab(const char* name) {
+  if (const char* e = getenv(name)) {
+    const long long w = atoll(e);
+    if (w >= 1) return w;
+  }
+  return 0;
+}
+static int comom_plan(int32_t B, int64_t Wa, int64_t Wb, gel::ComSlabs& S) {
+  S = gel::com_slabs(B, Wa, Wb, comom_max_slab("GEL_COMOM_SLAB_ROWS"), comom_max_slab("GEL_COMOM_SLAB"));
+  if (!S.ok)
+    return fail(GEL_ERR_ARG, "gel_batch_comoments: B = " + std::to_string(B) + " vectors of " + std::to_string(Wa) + " + " + std::to_string(Wb) +
+                                 " columns leave no room for one tile of pairs in the 256 MiB workspace: fewer columns or vectors per call");
+  return GEL_OK;
+}
+
+// the launches of one call on the handle's stream: mask and info, the pairs in slabs through the same workspace, the statistics
+static int comom_enqueue(gel_problem* p, int32_t B, int64_t Wa, int64_t inca, int64_t lda, const double* d_a, int64_t Wb, int64_t incb,
+                         int64_t ldb, const double* d_b, bool self, double* d_C, double* d_stat_a, double* d_stat_b, double* d_info) {
+  gel::ComSlabs S;
+  if (int rc = comom_plan(B, Wa, Wb, S)) return rc;
+  hipStream_t s = p->stream.get();
+  const gel::ComLayout L = gel::com_layout(B, Wa, S.an, S.bn);
+  if (p->d_comws.capacity() < L.bytes) {
+    HIPCHK(drain(p));   // an earlier call in flight still uses the old block
+    HIPCHK(p->d_comws.reserve(L.bytes));
+  }
+  char* ws = p->d_comws.get();
+  gel::ComArgs A{};
+  A.B = B; A.self = self ? 1 : 0;
+  A.Wa = Wa; A.inca = inca; A.lda = lda; A.a = d_a;
+  A.Wb = Wb; A.incb = incb; A.ldb = ldb; A.b = d_b;
+  A.C = d_C; A.stat_a = d_stat_a; A.stat_b = d_stat_b; A.info = d_info;
+  A.cnt = reinterpret_cast<int32_t*>(ws + L.cnt);
+  A.fe = reinterpret_cast<int32_t*>(ws + L.fe);
+  A.mask = reinterpret_cast<unsigned char*>(ws + L.mask);
+  A.sa = reinterpret_cast<double*>(ws + L.sa);
+  A.sb = reinterpret_cast<double*>(ws + L.sb);
+  A.cp = reinterpret_cast<double*>(ws + L.cp);
+  HIPCHK(gel::launch_comom_mask(A, s));
+  if (Wa == 0 || Wb == 0) return GEL_OK;
+  for (int64_t a0 = 0; a0 < Wa; a0 += S.an)
+    for (int64_t b0 = 0; b0 < Wb; b0 += S.bn) {
+      const int64_t bn = std::min<int64_t>(S.bn, Wb - b0);
+      HIPCHK(gel::launch_comom_slab(A, a0, std::min<int64_t>(S.an, Wa - a0), b0, bn, s));
+      if (a0 == 0 && d_stat_b) HIPCHK(gel::launch_comom_stats(A, bn, A.sb, d_stat_b + 2 * b0, s));   // the slab's b columns, before the next slab
+    }
+  HIPCHK(gel::launch_comom_stats(A, Wa, A.sa, d_stat_a, s));
+  return GEL_OK;
+}
+
+int gel_batch_comoments_device(gel_problem* p, int32_t B, int64_t Wa, int64_t inca, int64_t lda, const double* d_a, int64_t Wb, int64_t incb,
+                               int64_t ldb, const double* d_b, double* d_C, double* d_stat_a, double* d_stat_b, double* d_info) {
+  if (int rc = comom_check(p, B, Wa, inca, lda, d_a, Wb, incb, ldb, d_b, d_C, d_stat_b, d_info)) return rc;
+  NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
+  HIPCHK(hipSetDevice(p->device));
+  const bool self = !d_b;
+  if (self) return comom_enqueue(p, B, Wa, inca, lda, d_a, Wa, inca, lda, d_a, true, d_C, d_stat_a, nullptr, d_info);
+  return comom_enqueue(p, B, Wa, inca, lda, d_a, Wb, incb, ldb, d_b, false, d_C, d_stat_a, d_stat_b, d_info);
+}
+
+int gel_batch_comoments(gel_problem* p, int32_t B, int64_t Wa, int64_t inca, int64_t lda, const double* a, int64_t Wb, int64_t incb,
+                        int64_t ldb, const double* b, double* C, double* stat_a, double* stat_b, double* info) {
+  if (int rc = comom_check(p, B, Wa, inca, lda, a, Wb, incb, ldb, b, C, stat_b, info)) return rc;
+  NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
+  HIPCHK(hipSetDevice(p->device));
+  const bool self = !b;
+  if (self) { Wb = Wa; incb = inca; ldb = lda; }
+  // the rows are staged as they lie, up to the last entry read: the views stay views
+  const auto span = [&](int64_t W, int64_t inc, int64_t ld) { return (B > 0 && W > 0) ? (size_t)(B - 1) * (size_t)ld + (size_t)(W - 1) * (size_t)inc + 1 : 0; };
+  const size_t na = span(Wa, inca, lda), nb = self ? 0 : span(Wb, incb, ldb);
+  const bool pairs = Wa > 0 && Wb > 0;   // Wa = 0 or Wb = 0: info only, nothing else is written
+  return staged_call(p, kStagedNoFlag,
+                     {staged_in(na ? a : nullptr, na), staged_in(nb ? b : nullptr, nb), staged_out(pairs ? C : nullptr, (size_t)Wa * (size_t)Wb),
+                      staged_out(pairs ? stat_a : nullptr, (size_t)Wa * 2), staged_out(pairs && !self ? stat_b : nullptr, (size_t)Wb * 2),
+                      staged_out(info, 2)},
+                     [&](const gel::ProblemDev&, double* const* d) -> int {
+                       return comom_enqueue(p, B, Wa, inca, lda, d[0], Wb, incb, ldb, self ? d[0] : d[1], self, d[2], d[3], d[4], d[5]);
+                     });
+}
+
+int gel_batch_comoments_info(const gel_problem* p, int32_t B, int64_t Wa, int64_t Wb, int32_t self, gel_comoments_info* out) {
+  if (!p || !out || B < 0 || Wa < 0 || (!self && Wb < 0)) return fail(GEL_ERR_ARG, "gel_batch_comoments_info: bad argument");
+  if (self) Wb = Wa;
+  gel::ComSlabs S;
+  if (int rc = comom_plan(B, Wa, Wb, S)) return rc;
+  const bool pairs = Wa > 0 && Wb > 0;
+  out->block = gel::kComBlock;
+  out->tile_a = gel::kComTileA;
+  out->tile_b = gel::kComTileB;
+  out->slab_rows = S.an;
+  out->slab_cols = S.bn;
+  out->slabs = pairs ? ((Wa + S.an - 1) / S.an) * ((Wb + S.bn - 1) / S.bn) : 0;
+  out->workspace_bytes = (int64_t)gel::com_layout(B, Wa, S.an, S.bn).bytes;
+  out->workspace_cap_bytes = (int64_t)gel::kComWsCap;
+  // reads of a source entry: the mask pass, then once per tile of the other view's columns (from the caches after the first)
+  out->passes_a = B > 0 && Wa > 0 ? 1 + (pairs ? (Wb + gel::kComTileB - 1) / gel::kComTileB : 0) : 0;
+  out->passes_b = B > 0 && Wb > 0 && !self ? 1 + (pairs ? (Wa + gel::kComTileA - 1) / gel::kComTileA : 0) : 0;
   return GEL_OK;
 }
 

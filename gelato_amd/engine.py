@@ -910,6 +910,68 @@ class Engine:
         check(lib().gel_batch_quantiles_last(self._h, st))
         return dict(zip(("targets", "by_range", "by_candidates", "by_fallback"), (int(v) for v in st)))
 
+    @staticmethod
+    def comoment_ratios(count, C_, m2_a, m2_b):
+        """-> (cov, corr): cov = C / (count - 1), NaN below a count of 2; corr = C / sqrt(m2_a m2_b), NaN where an m2 is 0.  numpy."""
+        C_, m2_a, m2_b = np.asarray(C_, dtype=np.float64), np.asarray(m2_a, dtype=np.float64), np.asarray(m2_b, dtype=np.float64)
+        with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+            cov = C_ / (count - 1) if count >= 2 else np.full(C_.shape, np.nan)
+            den = np.sqrt(m2_a[:, None] * m2_b[None, :])
+            corr = np.where(den > 0.0, C_ / np.where(den > 0.0, den, 1.0), np.nan)
+        return cov, corr
+
+    def batch_comoments(self, A, Bv=None):
+        """Co-moments over the first axis (gel_batch_comoments).  A: C-contiguous float64 [B, Wa]; Bv: [B, Wb], or
+        None = the self form (Bv is A; only the pairs i <= j are formed, C is symmetric in bits).  A flight counts iff every entry
+        of its rows of A and Bv is finite (listwise).
+        -> {"count" int, "first_excluded" int (-1: none), "C" [Wa, Wb] = sum (a_i - mean a_i)(b_j - mean b_j) over the counted
+            flights, "mean_a", "m2_a" [Wa], "mean_b", "m2_b" [Wb] (the self form: those of a), "cov" = C / (count - 1) (NaN below
+            2), "corr" = C / sqrt(m2_a m2_b) (NaN where an m2 is 0) -- cov and corr formed here in numpy}"""
+        def arr(X, name):
+            X = np.asarray(X)
+            if X.dtype != np.float64:
+                raise TypeError("%s: float64, not %s" % (name, X.dtype))
+            if X.ndim != 2:
+                raise ValueError("%s: [B, W]" % name)
+            if not X.flags.c_contiguous:
+                raise ValueError("%s: C-contiguous" % name)
+            return X
+        A = arr(A, "A")
+        B, Wa = A.shape
+        self_form = Bv is None
+        if self_form:
+            Wb = Wa
+        else:
+            Bv = arr(Bv, "Bv")
+            if Bv.shape[0] != B:
+                raise ValueError("Bv: %d rows, A has %d" % (Bv.shape[0], B))
+            Wb = Bv.shape[1]
+        Cm = np.full((Wa, Wb), np.nan)
+        sa, sb, info = np.full((Wa, 2), np.nan), np.full((Wb, 2), np.nan), np.empty(2)
+        check(lib().gel_batch_comoments(self._h, B, Wa, 1, max(Wa, 1), _d(A) if A.size else None, Wb, 1, max(Wb, 1),
+                                        None if self_form else _d(Bv), _d(Cm) if Cm.size else None, _d(sa) if Wa else None,
+                                        None if self_form or not Wb else _d(sb), _d(info)))
+        if self_form:
+            sb = sa
+        count = int(info[0])
+        cov, corr = self.comoment_ratios(count, Cm, sa[:, 1], sb[:, 1])
+        return {"count": count, "first_excluded": int(info[1]), "C": Cm, "mean_a": sa[:, 0].copy(), "m2_a": sa[:, 1].copy(),
+                "mean_b": sb[:, 0].copy(), "m2_b": sb[:, 1].copy(), "cov": cov, "corr": corr}
+
+    def batch_comoments_device(self, B, Wa, inca, lda, d_a, Wb, incb, ldb, d_b, d_C, d_stat_a=0, d_stat_b=0, d_info=0):
+        """device buffers (raw pointers; 0 = not given): column i of flight r of a is d_a[r lda + i inca] (b likewise; d_b = 0: the
+        self form), d_C [Wa][Wb], d_stat_a [Wa][2], d_stat_b [Wb][2], d_info [2] (required); asynchronous on the engine's own
+        stream; status through Engine.sync()"""
+        check(lib().gel_batch_comoments_device(self._h, int(B), int(Wa), int(inca), int(lda), d_a or None, int(Wb), int(incb), int(ldb),
+                                               d_b or None, d_C or None, d_stat_a or None, d_stat_b or None, d_info or None))
+
+    def batch_comoments_info(self, B, Wa, Wb=None):
+        """-> {"block", "tile_a", "tile_b", "slab_rows", "slab_cols", "slabs", "workspace_bytes", "workspace_cap_bytes", "passes_a",
+        "passes_b"}: what a call would select (gel_batch_comoments_info; needs no GPU).  Wb = None: the self form"""
+        info = _lib.GelComomentsInfo()
+        check(lib().gel_batch_comoments_info(self._h, int(B), int(Wa), int(Wa if Wb is None else Wb), 1 if Wb is None else 0, C.byref(info)))
+        return {k: int(getattr(info, k)) for k, _t in info._fields_}
+
     def initial_guess(self, t_ref, table, knot_times):
         """initialize.py:322-409 behind the C-ABI: reference trajectory (t_ref [n], table [n, 13] = mass | pos 3 | vel 3 |
         quat 4 | body rates y, z) interpolated at the mesh's node times -> packed decision vector"""

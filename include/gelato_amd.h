@@ -771,6 +771,67 @@ int gel_batch_quantiles_device(gel_problem* p, int32_t B, int64_t W, int64_t ld,
 int gel_batch_quantiles_info(const gel_problem* p, int32_t B, int64_t W, int32_t nq, gel_quantiles_info* info);
 int gel_batch_quantiles_last(gel_problem* p, int64_t* stats /* [4] */);
 
+/* ---- co-moments over the vectors of a batch: how two columns move together -- the covariance matrix of the
+ *      insertion state, the correlation of max-Q with the terminal miss, the regression of the outputs on the dispersion factors
+ *      the flights were flown with.  C[i][j] = sum over the counted flights r of (a_i[r] - mean a_i) (b_j[r] - mean b_j).
+ *      Views: column i of flight r of a is a[r lda + i inca] (b likewise), inc >= 1, ld >= (W - 1) inc + 1, all offsets 64-bit.  One
+ *      call reads without a copy: disp (W = ld = 4 S); the last node's row of the batch table (src + (M - 1) ncols, W = ncols,
+ *      ld = M ncols); the whole table; every flight's maximum out of peaks [B][ncols][4] (src + 2, inc = 4, W = ncols, ld = 4 ncols);
+ *      err's last row; the row table.
+ *      Which flights count: LISTWISE.  Flight r counts if and only if every entry the call reads of it, in both views, is finite.
+ *      (A matrix assembled from pairwise-complete pairs need not be positive semidefinite; the caller chooses columns that are
+ *      finite, as cols of gel_output_table_batch lets them.)  info[0] = the count (a double), info[1] = the lowest r left out, or -1.
+ *      With a count of 0, C and stat are NaN; with a count of 1 they are C = 0, m2 = 0.  These calls never return GEL_NONFINITE: a
+ *      product that overflows is the result.
+ *      THE ORDER, a function of the vector index and the set of counted flights alone.  Blocks k = vectors 256 k .. 256 k + 255.
+ *      Inside a block, over the counted flights in ascending r, with n, every m, s and C starting at 0:
+ *        n += 1
+ *        every a column i:  da_i = a_i - ma_i;  ma_i = ma_i + da_i / n;  ea_i = a_i - ma_i;  sa_i = fma(da_i, ea_i, sa_i)
+ *        every b column j:  db_j = b_j - mb_j;  mb_j = mb_j + db_j / n;  eb_j = b_j - mb_j;  sb_j = fma(db_j, eb_j, sb_j)
+ *        every pair:        C_ij = fma(da_i, eb_j, C_ij)
+ *      The blocks that hold a counted flight are merged in ascending k into a running total (the first such block is copied);
+ *      every d is formed from the means BEFORE this merge's own mean update:
+ *        nt = n + nb;  da_i = ma_b,i - ma_i;  db_j = mb_b,j - mb_j;  w = (n nb) / nt
+ *        C_ij = (C_ij + Cb_ij) + (da_i db_j) w
+ *        sa_i = (sa_i + sab_i) + (da_i da_i) w          (sb likewise)
+ *        ma_i = ma_i + da_i (nb / nt)                   (mb likewise);   n = nt
+ *      each written operation one rounding.  stat_a[i] = {ma_i, sa_i}, stat_b[j] = {mb_j, sb_j}: the envelope's mean and m2 of that
+ *      column, bit for bit, whenever the counted flights are exactly the column's finite ones.
+ *      Self form (b == NULL; Wb, incb, ldb ignored): b is a.  Only the pairs i <= j are formed, C[j][i] is a bit copy of C[i][j], so
+ *      C [Wa][Wa] is symmetric in bits, and its diagonal is sa_i by construction.  stat_b must be NULL.
+ *      The result does not depend on the stream, the launch geometry, the tile sizes, the slab walk, the workspace size or the form
+ *      (host / device) of the call, nor on Wa and Wb beyond the listwise rule: a pair's value depends only on its two columns and
+ *      on the set of counted flights.  No floating-point atomics.
+ *      GEL_ERR_ARG, decided before the device is looked at: p NULL; B < 0; W < 0; inc < 1; ld < (W - 1) inc + 1 (W > 0); a NULL with
+ *      B Wa > 0; C NULL with Wa Wb > 0; info NULL; stat_b given in the self form.  B = 0 succeeds and writes the count = 0 pattern;
+ *      Wa = 0 or Wb = 0 succeeds and writes info only.  A valid call on a GEL_DEVICE_NONE handle returns what gel_output_table_batch
+ *      returns there.  The host form copies the rows of both views in as they lie (up to the last entry read), launches, copies out
+ *      and synchronises once (the handle's arena).  The device form takes NO stream argument: like gel_batch_quantiles_device it
+ *      enqueues everything on the handle's own stream and reports through gel_sync(p, NULL).
+ *      Workspace: the handle's, only grows, at most 256 MiB (gel_comoments_info.workspace_cap_bytes): one byte per vector, per block
+ *      of 256 vectors 16 bytes per column and 8 bytes per pair of the slab.  A product wider than that holds is walked in slabs of
+ *      b columns (and, where all a columns beside one tile of b still do not fit, of a columns) on the stream; a call whose fixed
+ *      part leaves no room for one tile of pairs is refused (GEL_ERR_ARG).  gel_batch_comoments_info (needs no GPU) reports what a
+ *      call would select. ---- */
+typedef struct {
+  int64_t block;               /* vectors per block of the stated order (256) */
+  int64_t tile_a, tile_b;      /* columns of a and of b per workgroup */
+  int64_t slab_rows;           /* a columns per slab (Wa unless the cap binds) */
+  int64_t slab_cols;           /* b columns per slab */
+  int64_t slabs;               /* slabs this call walks */
+  int64_t workspace_bytes;     /* what this call needs of the handle's workspace */
+  int64_t workspace_cap_bytes; /* the cap */
+  int64_t passes_a, passes_b;  /* reads of an entry of a / of b: the mask pass and one per tile of the other view's columns */
+} gel_comoments_info;
+int gel_batch_comoments(gel_problem* p, int32_t B, int64_t Wa, int64_t inca, int64_t lda, const double* a, int64_t Wb, int64_t incb,
+                        int64_t ldb, const double* b /* or NULL = the self form */, double* C /* [Wa][Wb]; self form [Wa][Wa] */,
+                        double* stat_a /* [Wa][2] mean, m2, or NULL */, double* stat_b /* [Wb][2] or NULL */,
+                        double* info /* [2] count, first_excluded */);
+int gel_batch_comoments_device(gel_problem* p, int32_t B, int64_t Wa, int64_t inca, int64_t lda, const double* d_a, int64_t Wb,
+                               int64_t incb, int64_t ldb, const double* d_b, double* d_C, double* d_stat_a, double* d_stat_b,
+                               double* d_info);
+int gel_batch_comoments_info(const gel_problem* p, int32_t B, int64_t Wa, int64_t Wb, int32_t self, gel_comoments_info* out);
+
 /* ---- from-file initial guess on the host (replaces initialize.py:322-409 initialize_xdict_6DoF_from_file, LGR mode;
  *      SURVEY.md 8f row f-3): linear interpolation (scipy interp1d with fill_value="extrapolate": the end intervals extend
  *      beyond the table) of a reference trajectory at the state-node times [-1, tau] and the control-node times tau of
