@@ -14,7 +14,7 @@ Host-side mirror of the reference interface for the hot path only:
 All numerics run in hand-written HIP kernels (gelato_amd/csrc) through the C-ABI in
 include/gelato_amd.h; there is no CPU fallback.
 """
-from .engine import Engine, InterpPlan, PropagationPlan, pack_x  # noqa: F401
+from .engine import Engine, InterpPlan, PropagationPlan, WindEnsemble, pack_x  # noqa: F401
 from .interp import refine, sample  # noqa: F401
 from .propagate import fly, sample_dispersion, shooting_check  # noqa: F401
 from .montecarlo import flight_envelope  # noqa: F401

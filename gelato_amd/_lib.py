@@ -174,6 +174,17 @@ SIGNATURES = {
     "gel_output_table_batch": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, _dp, C.c_double, C.c_double, C.c_int32, _ip, _dp, _dp, _dp]),
     "gel_output_table_batch_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_double,
                                                 C.c_int32, _ip, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gel_wind_ensemble_create": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _dp, C.POINTER(C.c_void_p)]),
+    "gel_wind_ensemble_destroy": (C.c_int, [C.c_void_p]),
+    "gel_wind_ensemble_info": (C.c_int, [C.c_void_p, _lp]),
+    "gel_wind_ensemble_member": (C.c_int, [C.c_void_p, C.c_int32, _dp]),
+    "gel_wind_ensemble_assign": (C.c_int, [C.c_void_p, C.c_int32, _ip]),
+    "gel_propagate_ensemble": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, C.c_void_p, _dp, _dp]),
+    "gel_propagate_ensemble_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gel_output_table_batch_ensemble": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, _dp, C.c_void_p, C.c_double, C.c_double, C.c_int32, _ip,
+                                                  _dp, _dp, _dp]),
+    "gel_output_table_batch_ensemble_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,
+                                                         C.c_double, C.c_int32, _ip, C.c_void_p, C.c_void_p, C.c_void_p]),
     "gel_batch_quantiles": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, _dp, C.c_int32, _dp, _dp, _dp, _dp]),
     "gel_batch_quantiles_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, _dp, C.c_void_p, C.c_void_p,
                                              C.c_void_p]),

@@ -3168,9 +3168,114 @@ int gel_prop_matrices(const gel_prop_plan* plan, int32_t phase, double* pts, dou
   return GEL_OK;
 }
 
+// ------------- wind ensemble of a Monte-Carlo batch -------------
+// E member tables, each staged like a handle's own wind table, resident in device memory, and one assignment member [B] that the
+// flight (gel_propagate_ensemble*) and the table (gel_output_table_batch_ensemble*) of a batch read alike.  It refers to the source
+// handle for the device and the stream and is destroyed before it.
+struct gel_wind_ensemble {
+  gel_problem* src = nullptr;
+  int32_t E = 0, Kw = 0;
+  int64_t stride = 0;             // doubles per member: 5 Kw - 2
+  std::vector<double> staged;     // [E][stride]: rows | slopes of every member (gel_wind_ensemble_member)
+  int32_t assigned = -1;          // vectors of the current assignment, -1 before the first
+  DeviceArray<double> d_tables;
+  DeviceArray<int32_t> d_member;
+};
+
+// what a call hands its launches: nothing without an ensemble; v0 = the first vector of the slab
+static gel::EnsDev ens_dev(const gel_wind_ensemble* ens, int64_t v0) {
+  gel::EnsDev e{};
+  if (!ens) return e;
+  e.tables = ens->d_tables.get(); e.member = ens->d_member.get() + v0;
+  e.E = ens->E; e.Kw = ens->Kw; e.stride = ens->stride;
+  return e;
+}
+// an evaluation call's ensemble: of the same source handle, and assigned exactly the call's B vectors
+static int ens_check(const char* what, const gel_wind_ensemble* ens, const gel_problem* src, int32_t B) {
+  if (!ens) return GEL_OK;
+  if (ens->src != src) return fail(GEL_ERR_ARG, std::string(what) + ": the wind ensemble belongs to another handle");
+  if (ens->assigned != B)
+    return fail(GEL_ERR_ARG, std::string(what) + ": the wind ensemble is assigned " +
+                                 (ens->assigned < 0 ? std::string("no vectors yet") : std::to_string(ens->assigned) + " vectors") +
+                                 ", the call has B = " + std::to_string(B) + " (gel_wind_ensemble_assign)");
+  return GEL_OK;
+}
+
+int gel_wind_ensemble_create(gel_problem* src, int32_t E, int32_t Kw, const double* tables, gel_wind_ensemble** out) {
+  if (!src || !out) return fail(GEL_ERR_ARG, "gel_wind_ensemble_create: null handle or result pointer");
+  if (E < 1) return fail(GEL_ERR_ARG, "gel_wind_ensemble_create: E = " + std::to_string(E) + " < 1");
+  if (Kw < 2) return fail(GEL_ERR_ARG, "gel_wind_ensemble_create: Kw = " + std::to_string(Kw) + " < 2 (wind and CA tables need at least two rows)");
+  if (Kw > gel::kEnsMaxRows) return fail(GEL_ERR_ARG, "gel_wind_ensemble_create: Kw = " + std::to_string(Kw) + " exceeds 2^20 rows");
+  const int64_t stride = 5 * (int64_t)Kw - 2;
+  if ((int64_t)E * stride > gel::kEnsMaxDoubles)
+    return fail(GEL_ERR_ARG, "gel_wind_ensemble_create: E (5 Kw - 2) = " + std::to_string((int64_t)E * stride) + " doubles exceed 2^27 (1 GB)");
+  if (!tables) return fail(GEL_ERR_ARG, "gel_wind_ensemble_create: tables is NULL");
+  const double ca2[4] = {0.0, 0.0, 1.0, 0.0};   // (check_tables looks at both tables: a valid two-row CA table beside the member)
+  for (int e = 0; e < E; e++)
+    if (const char* bad = gel::check_tables(tables + (size_t)e * 3 * (size_t)Kw, Kw, ca2, 2))
+      return fail(GEL_ERR_ARG, "gel_wind_ensemble_create: member " + std::to_string(e) + ": " + bad);
+  std::unique_ptr<gel_wind_ensemble> en(new gel_wind_ensemble);
+  en->src = src; en->E = E; en->Kw = Kw; en->stride = stride;
+  en->staged.reserve((size_t)E * (size_t)stride);
+  for (int e = 0; e < E; e++) {
+    std::vector<double> slopes;
+    gel::append_rows_and_slopes(en->staged, slopes, tables + (size_t)e * 3 * (size_t)Kw, Kw, 3);
+    en->staged.insert(en->staged.end(), slopes.begin(), slopes.end());
+  }
+  if (src->device != GEL_DEVICE_NONE) {
+    HIPCHK(hipSetDevice(src->device));
+    HIPCHK(en->d_tables.upload(en->staged));
+  }
+  *out = en.release();
+  return GEL_OK;
+}
+
+int gel_wind_ensemble_destroy(gel_wind_ensemble* ens) {
+  if (!ens) return GEL_OK;
+  if (ens->src->device != GEL_DEVICE_NONE) {
+    hipSetDevice(ens->src->device);
+    (void)drain(ens->src);   // a device call in flight still reads the members and the assignment
+  }
+  delete ens;
+  return GEL_OK;
+}
+
+int gel_wind_ensemble_info(const gel_wind_ensemble* ens, int64_t* info) {
+  if (!ens || !info) return fail(GEL_ERR_ARG, "null argument");
+  info[0] = ens->E; info[1] = ens->Kw; info[2] = ens->stride;
+  info[3] = (int64_t)(ens->d_tables.capacity() * sizeof(double) + ens->d_member.capacity() * sizeof(int32_t));
+  info[4] = ens->assigned;
+  return GEL_OK;
+}
+
+int gel_wind_ensemble_member(const gel_wind_ensemble* ens, int32_t e, double* staged) {
+  if (!ens || !staged) return fail(GEL_ERR_ARG, "null argument");
+  if (e < 0 || e >= ens->E) return fail(GEL_ERR_ARG, "gel_wind_ensemble_member: member " + std::to_string(e) + " outside 0 .. " + std::to_string(ens->E - 1));
+  std::memcpy(staged, ens->staged.data() + (size_t)e * (size_t)ens->stride, (size_t)ens->stride * 8);
+  return GEL_OK;
+}
+
+int gel_wind_ensemble_assign(gel_wind_ensemble* ens, int32_t B, const int32_t* member) {
+  if (!ens) return fail(GEL_ERR_ARG, "gel_wind_ensemble_assign: null ensemble");
+  if (B < 0) return fail(GEL_ERR_ARG, "gel_wind_ensemble_assign: B < 0");
+  if (B > 0 && !member) return fail(GEL_ERR_ARG, "gel_wind_ensemble_assign: member is NULL with B > 0");
+  for (int32_t b = 0; b < B; b++)
+    if (member[b] < -1 || member[b] >= ens->E)
+      return fail(GEL_ERR_ARG, "gel_wind_ensemble_assign: member[" + std::to_string(b) + "] = " + std::to_string(member[b]) + " outside -1 .. " +
+                                   std::to_string(ens->E - 1));
+  if (ens->src->device != GEL_DEVICE_NONE) {
+    HIPCHK(hipSetDevice(ens->src->device));
+    HIPCHK(drain(ens->src));   // a call in flight still reads the old assignment
+    ens->assigned = -1;        // (a failed upload leaves no assignment)
+    HIPCHK(ens->d_member.upload(member, (size_t)B));
+  }
+  ens->assigned = B;
+  return GEL_OK;
+}
+
 // the launches of one call on stream s: slab after slab the control samples and the integration, then err of all B vectors
 static int prop_enqueue(gel_prop_plan* plan, int32_t B, const double* d_x, double* d_y, double* d_err, const double* d_disp,
-                        hipStream_t s) {
+                        const gel_wind_ensemble* ens, hipStream_t s) {
   gel_problem* p = plan->src;
   const int64_t vs = prop_slab(plan), ldv = std::min<int64_t>(vs, ((int64_t)B + 63) / 64 * 64);
   const size_t need = (size_t)ldv * 2 * (size_t)plan->sampled_pts;
@@ -3182,35 +3287,49 @@ static int prop_enqueue(gel_prop_plan* plan, int32_t B, const double* d_x, doubl
   for (int64_t v0 = 0; v0 < B; v0 += vs) {
     const int nb = (int)std::min<int64_t>(vs, B - v0);
     HIPCHK(gel::launch_prop_slab(p->dev, plan->dev, plan->ph.data(), plan->n_max_sampled, nb, d_x + (size_t)v0 * nv,
-                                 d_y + (size_t)v0 * ny, plan->d_ws.get(), ldv, d_disp ? d_disp + (size_t)v0 * nd : nullptr, s));
+                                 d_y + (size_t)v0 * ny, plan->d_ws.get(), ldv, d_disp ? d_disp + (size_t)v0 * nd : nullptr,
+                                 ens_dev(ens, v0), s));
   }
   if (d_err) HIPCHK(gel::launch_prop_err(p->dev, plan->dev, B, d_x, d_y, d_err, s));
   return GEL_OK;
 }
 
-int gel_propagate_dispersed_device(gel_prop_plan* plan, int32_t B, const double* d_x, const double* d_disp, double* d_y,
-                                   double* d_err) {
+int gel_propagate_ensemble_device(gel_prop_plan* plan, int32_t B, const double* d_x, const double* d_disp, gel_wind_ensemble* ens,
+                                  double* d_y, double* d_err) {
   if (!plan || B < 0 || (B > 0 && (!d_x || !d_y))) return fail(GEL_ERR_ARG, "bad argument");
   gel_problem* p = plan->src;
+  if (int rc = ens_check("gel_propagate_ensemble", ens, p, B)) return rc;
   NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
   if (B == 0) return GEL_OK;
   HIPCHK(hipSetDevice(p->device));
-  return prop_enqueue(plan, B, d_x, d_y, d_err, d_disp, p->stream.get());
+  return prop_enqueue(plan, B, d_x, d_y, d_err, d_disp, ens, p->stream.get());
+}
+
+int gel_propagate_dispersed_device(gel_prop_plan* plan, int32_t B, const double* d_x, const double* d_disp, double* d_y,
+                                   double* d_err) {
+  return gel_propagate_ensemble_device(plan, B, d_x, d_disp, nullptr, d_y, d_err);
 }
 
 int gel_propagate_device(gel_prop_plan* plan, int32_t B, const double* d_x, double* d_y, double* d_err) {
   return gel_propagate_dispersed_device(plan, B, d_x, nullptr, d_y, d_err);
 }
 
-int gel_propagate_dispersed(gel_prop_plan* plan, int32_t B, const double* x, const double* disp, double* y, double* err) {
+int gel_propagate_ensemble(gel_prop_plan* plan, int32_t B, const double* x, const double* disp, gel_wind_ensemble* ens, double* y,
+                           double* err) {
   if (!plan || B < 0 || (B > 0 && (!x || !y))) return fail(GEL_ERR_ARG, "bad argument");
   gel_problem* p = plan->src;
+  if (int rc = ens_check("gel_propagate_ensemble", ens, p, B)) return rc;
   NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
   if (B == 0) return GEL_OK;
   HIPCHK(hipSetDevice(p->device));
+  // (the ensemble's members and assignment are resident: the arena holds what it held)
   return staged_call(p, 0, {staged_in(x, (size_t)B * p->dims.num_vars), staged_out(y, (size_t)B * 11 * p->dims.M), staged_out(err, (size_t)B * p->dims.S * 4),
                             staged_in(disp, (size_t)B * p->dims.S * GEL_PROP_NDISP)},
-                     [&](const gel::ProblemDev&, double* const* a) { return prop_enqueue(plan, B, a[0], a[1], a[2], a[3], p->stream.get()); });
+                     [&](const gel::ProblemDev&, double* const* a) { return prop_enqueue(plan, B, a[0], a[1], a[2], a[3], ens, p->stream.get()); });
+}
+
+int gel_propagate_dispersed(gel_prop_plan* plan, int32_t B, const double* x, const double* disp, double* y, double* err) {
+  return gel_propagate_ensemble(plan, B, x, disp, nullptr, y, err);
 }
 
 int gel_propagate(gel_prop_plan* plan, int32_t B, const double* x, double* y, double* err) {
@@ -3512,39 +3631,51 @@ static int outbatch_check(gel_problem* p, int32_t B, const void* x, int32_t ncol
 }
 
 // the launches of one call on the handle's stream
-static int outbatch_enqueue(gel_problem* p, const gel::OutBatchArgs& A, double* d_out, double* d_env, double* d_peaks) {
+static int outbatch_enqueue(gel_problem* p, const gel::OutBatchArgs& A, const gel_wind_ensemble* ens, double* d_out, double* d_env,
+                            double* d_peaks) {
   hipStream_t s = p->stream.get();
+  const gel::EnsDev E = ens_dev(ens, 0);
   const size_t lds = gel::outbatch_lds_bytes(p->dev.Kw, p->dev.Kc);
   if (int rc = check_launch_lds("gel_output_table_batch", lds, gel::staged_table_doubles(p->dev.Kw, p->dev.Kc),
                                 gel::padded_table_doubles(p->dev.Kw, p->dev.Kc), true))
     return rc;
-  if (A.B > 0 && (d_out || d_peaks)) HIPCHK(gel::launch_outbatch_rows(p->dev, A, d_out, d_peaks, s));
+  if (A.B > 0 && (d_out || d_peaks)) HIPCHK(gel::launch_outbatch_rows(p->dev, A, E, d_out, d_peaks, s));
   if (d_env) {
     const size_t need = gel::outbatch_ws_doubles(A.B, p->dims.M, A.cols.ncols);
     if (p->d_outws.capacity() < need) {
       HIPCHK(drain(p));   // an earlier call in flight still reads the old block
       HIPCHK(p->d_outws.reserve(need));
     }
-    HIPCHK(gel::launch_outbatch_env(p->dev, A, A.B > 0 ? d_out : nullptr, p->d_outws.get(), d_env, s));
+    HIPCHK(gel::launch_outbatch_env(p->dev, A, E, A.B > 0 ? d_out : nullptr, p->d_outws.get(), d_env, s));
   }
   return GEL_OK;
+}
+
+int gel_output_table_batch_ensemble_device(gel_problem* p, int32_t B, const double* d_x, const double* d_tx, const double* d_disp,
+                                           gel_wind_ensemble* ens, double launch_lat_deg, double launch_lon_deg, int32_t ncols,
+                                           const int32_t* cols, double* d_out, double* d_env, double* d_peaks) {
+  gel::OutBatchArgs A{};
+  if (int rc = outbatch_check(p, B, d_x, ncols, cols, d_out, d_env, d_peaks, A.cols)) return rc;
+  if (int rc = ens_check("gel_output_table_batch_ensemble", ens, p, B)) return rc;
+  NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
+  HIPCHK(hipSetDevice(p->device));
+  A.B = B; A.x = d_x; A.tx = d_tx; A.disp = d_disp; A.lat0 = launch_lat_deg; A.lon0 = launch_lon_deg;
+  return outbatch_enqueue(p, A, ens, d_out, d_env, d_peaks);
 }
 
 int gel_output_table_batch_device(gel_problem* p, int32_t B, const double* d_x, const double* d_tx, const double* d_disp,
                                   double launch_lat_deg, double launch_lon_deg, int32_t ncols, const int32_t* cols, double* d_out,
                                   double* d_env, double* d_peaks) {
-  gel::OutBatchArgs A{};
-  if (int rc = outbatch_check(p, B, d_x, ncols, cols, d_out, d_env, d_peaks, A.cols)) return rc;
-  NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
-  HIPCHK(hipSetDevice(p->device));
-  A.B = B; A.x = d_x; A.tx = d_tx; A.disp = d_disp; A.lat0 = launch_lat_deg; A.lon0 = launch_lon_deg;
-  return outbatch_enqueue(p, A, d_out, d_env, d_peaks);
+  return gel_output_table_batch_ensemble_device(p, B, d_x, d_tx, d_disp, nullptr, launch_lat_deg, launch_lon_deg, ncols, cols, d_out, d_env,
+                                                d_peaks);
 }
 
-int gel_output_table_batch(gel_problem* p, int32_t B, const double* x, const double* tx, const double* disp, double launch_lat_deg,
-                           double launch_lon_deg, int32_t ncols, const int32_t* cols, double* out, double* env, double* peaks) {
+int gel_output_table_batch_ensemble(gel_problem* p, int32_t B, const double* x, const double* tx, const double* disp,
+                                    gel_wind_ensemble* ens, double launch_lat_deg, double launch_lon_deg, int32_t ncols,
+                                    const int32_t* cols, double* out, double* env, double* peaks) {
   gel::OutBatchArgs A{};
   if (int rc = outbatch_check(p, B, x, ncols, cols, out, env, peaks, A.cols)) return rc;
+  if (int rc = ens_check("gel_output_table_batch_ensemble", ens, p, B)) return rc;
   NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
   HIPCHK(hipSetDevice(p->device));
   const size_t M = (size_t)p->dims.M, nc = (size_t)A.cols.ncols, nB = (size_t)B;
@@ -3556,8 +3687,13 @@ int gel_output_table_batch(gel_problem* p, int32_t B, const double* x, const dou
                       staged_in(B > 0 ? disp : nullptr, nB * p->dims.S * GEL_PROP_NDISP)},
                      [&](const gel::ProblemDev&, double* const* a) -> int {
                        A.x = a[0]; A.tx = a[1]; A.disp = a[5];
-                       return outbatch_enqueue(p, A, a[2], a[3], a[4]);
+                       return outbatch_enqueue(p, A, ens, a[2], a[3], a[4]);
                      });
+}
+
+int gel_output_table_batch(gel_problem* p, int32_t B, const double* x, const double* tx, const double* disp, double launch_lat_deg,
+                           double launch_lon_deg, int32_t ncols, const int32_t* cols, double* out, double* env, double* peaks) {
+  return gel_output_table_batch_ensemble(p, B, x, tx, disp, nullptr, launch_lat_deg, launch_lon_deg, ncols, cols, out, env, peaks);
 }
 
 // ------------- exact batched quantiles over the vectors of a batch -------------

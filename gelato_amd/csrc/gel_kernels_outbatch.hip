@@ -30,9 +30,13 @@ __device__ __forceinline__ bool finite_d(double v) { return __builtin_fabs(v) <=
 
 // row (vector b, node i) into dst[0 .. kOutputColumns): a row of the LDS tile; the columns of a part the call leaves out stay stale
 // there and are never read
-template <bool kDisp>
-__device__ __forceinline__ void row_to_tile(const ProblemDev& P, const Tables& tb, const OutBatchArgs& A, long long b, int i,
-                                            double* __restrict__ dst) {
+// kEns = 1 (gel_output_table_batch_ensemble*; with kDisp only, the other instantiations do not read Ens): the row's wind comes from
+// the table vector b is assigned (ens_lane_tables: global memory), through the same wind_ned2 of output_row; A.disp may then be
+// null: factors of one.  An int like prop_kernel's, not a branch inside the dispersed instantiation: with both rows in one kernel
+// the dispersed call without an ensemble was 2 - 3 % slower than before.
+template <bool kDisp, int kEns = 0>
+__device__ __forceinline__ void row_to_tile(const ProblemDev& P, const Tables& tb, const OutBatchArgs& A, const EnsDev& Ens, long long b,
+                                            int i, double* __restrict__ dst) {
   const int M = P.M, N = P.N;
   // the node's phase: section s owns the state nodes xa_s .. xa_s + n_s (output_result.py:121-143)
   int sec = 0;
@@ -53,13 +57,16 @@ __device__ __forceinline__ void row_to_tile(const ProblemDev& P, const Tables& t
     t = sum * P.ut;
   }
   double fw = 1.0;
-  if constexpr (kDisp) {
+  if (kDisp && (!kEns || A.disp)) {   // (null only under an ensemble)
     const double* const fac = A.disp + ((size_t)b * P.S + sec) * 4;   // thrust, (mass flow: no reader here), reference area, wind
     ph.thrust = ph.thrust * fac[0];
     ph.area = ph.area * fac[2];
     fw = fac[3];
   }
-  output_row<kDisp>(P, tb, ph, M, i, xb, t, A.lat0, A.lon0, dst, A.cols.parts, fw);
+  if constexpr (kEns) {
+    const Tables tbe = ens_lane_tables(P, tb, Ens, Ens.member[b]);
+    output_row<true>(P, tbe, ph, M, i, xb, t, A.lat0, A.lon0, dst, A.cols.parts, fw);
+  } else output_row<kDisp>(P, tb, ph, M, i, xb, t, A.lat0, A.lon0, dst, A.cols.parts, fw);
 }
 
 // the column map col[j] = gel_output_column of selected column j into LDS (a lane cannot index the kernel argument by its id
@@ -94,9 +101,9 @@ __device__ __forceinline__ void env_store(const EnvStat& e, double* __restrict__
 }
 }  // namespace
 
-template <bool kDisp>
+template <bool kDisp, int kEns = 0>
 __global__ __launch_bounds__(64) void outbatch_rows_kernel(ProblemDev P, OutBatchArgs A, double* __restrict__ out,
-                                                           double* __restrict__ peaks) {
+                                                           double* __restrict__ peaks, EnsDev Ens) {
   extern __shared__ double lds[];
   const Tables tb = stage_tables(P, lds);
   double* const tile = lds + ((table_doubles(P.Kw, P.Kc) + 1) & ~1);
@@ -108,7 +115,7 @@ __global__ __launch_bounds__(64) void outbatch_rows_kernel(ProblemDev P, OutBatc
   int imin = -1, imax = -1;
   for (int t0 = 0; t0 < M; t0 += 64) {
     const int nrows = min(64, M - t0);
-    if (lane < nrows) row_to_tile<kDisp>(P, tb, A, b, t0 + lane, tile + lane * kW);
+    if (lane < nrows) row_to_tile<kDisp, kEns>(P, tb, A, Ens, b, t0 + lane, tile + lane * kW);
     __syncthreads();
     if (out) {
       double* const dst = out + ((size_t)b * M + t0) * nc;
@@ -138,8 +145,8 @@ __global__ __launch_bounds__(64) void outbatch_rows_kernel(ProblemDev P, OutBatc
 }
 
 constexpr int kEnvPairs = (kEnvNodes * kOutputColumns + 63) / 64;   // (node, column) pairs per lane: 5
-template <bool kDisp>
-__global__ __launch_bounds__(64) void outbatch_env_kernel(ProblemDev P, OutBatchArgs A, int ngroups, double* __restrict__ ws) {
+template <bool kDisp, int kEns = 0>
+__global__ __launch_bounds__(64) void outbatch_env_kernel(ProblemDev P, OutBatchArgs A, int ngroups, double* __restrict__ ws, EnsDev Ens) {
   extern __shared__ double lds[];
   const Tables tb = stage_tables(P, lds);
   double* const tile = lds + ((table_doubles(P.Kw, P.Kc) + 1) & ~1);
@@ -157,7 +164,7 @@ __global__ __launch_bounds__(64) void outbatch_env_kernel(ProblemDev P, OutBatch
     const int bs = b0 + st * 8;      // first vector of the step
     if (bs >= B) break;
     const int nv = min(8, B - bs);
-    if (vv < nv && i < M) row_to_tile<kDisp>(P, tb, A, bs + vv, i, tile + lane * kW);
+    if (vv < nv && i < M) row_to_tile<kDisp, kEns>(P, tb, A, Ens, bs + vv, i, tile + lane * kW);
     __syncthreads();
 #pragma unroll
     for (int j = 0; j < kEnvPairs; j++) {
@@ -224,17 +231,18 @@ __global__ __launch_bounds__(256) void outbatch_merge_kernel(long long npairs, i
   e[5] = amin; e[6] = amax; e[7] = fnf;
 }
 
-hipError_t launch_outbatch_rows(const ProblemDev& P, const OutBatchArgs& A, double* d_out, double* d_peaks, hipStream_t s) {
+hipError_t launch_outbatch_rows(const ProblemDev& P, const OutBatchArgs& A, const EnsDev& ens, double* d_out, double* d_peaks,
+                                hipStream_t s) {
   if (A.B <= 0 || (!d_out && !d_peaks)) return hipSuccess;
   const size_t lds = outbatch_lds_bytes(P.Kw, P.Kc);
   if (lds > kLaunchMaxLds) return hipErrorInvalidValue;
-  auto* const kern = A.disp ? outbatch_rows_kernel<true> : outbatch_rows_kernel<false>;
-  hipLaunchKernelGGL(kern, dim3((unsigned)A.B), dim3(64), lds, s, P, A, d_out, d_peaks);
+  auto* const kern = ens.tables ? outbatch_rows_kernel<true, 1> : A.disp ? outbatch_rows_kernel<true> : outbatch_rows_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3((unsigned)A.B), dim3(64), lds, s, P, A, d_out, d_peaks, ens);
   return hipGetLastError();
 }
 
-hipError_t launch_outbatch_env(const ProblemDev& P, const OutBatchArgs& A, const double* d_table, double* d_ws, double* d_env,
-                               hipStream_t s) {
+hipError_t launch_outbatch_env(const ProblemDev& P, const OutBatchArgs& A, const EnsDev& ens, const double* d_table, double* d_ws,
+                               double* d_env, hipStream_t s) {
   const int nblk = (A.B + kEnvBlock - 1) / kEnvBlock, ngroups = (P.M + kEnvNodes - 1) / kEnvNodes;
   const long long npairs = (long long)P.M * A.cols.ncols;
   if (nblk > 0 && d_table) {
@@ -246,8 +254,8 @@ hipError_t launch_outbatch_env(const ProblemDev& P, const OutBatchArgs& A, const
     const size_t lds = outbatch_lds_bytes(P.Kw, P.Kc);
     const long long grid = (long long)nblk * ngroups;
     if (lds > kLaunchMaxLds || grid > 0x7fffffffLL) return hipErrorInvalidValue;
-    auto* const kern = A.disp ? outbatch_env_kernel<true> : outbatch_env_kernel<false>;
-    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64), lds, s, P, A, ngroups, d_ws);
+    auto* const kern = ens.tables ? outbatch_env_kernel<true, 1> : A.disp ? outbatch_env_kernel<true> : outbatch_env_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64), lds, s, P, A, ngroups, d_ws, ens);
     if (const hipError_t e = hipGetLastError()) return e;
   }
   hipLaunchKernelGGL(outbatch_merge_kernel, dim3((unsigned)((npairs + 255) / 256)), dim3(256), 0, s, npairs, nblk, d_ws, d_env);

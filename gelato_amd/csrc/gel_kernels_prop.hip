@@ -12,7 +12,8 @@
 //                        creation bounds (k n <= 2^20): a launch always ends.
 //                        Template parameters: kChain (GEL_PROP_CHAIN) one lane = one vector through ALL phases, the state carried
 //                        across the knots; kDisp (gel_propagate_dispersed*) per (vector, phase) factors of thrust, mass flow,
-//                        reference area and wind.  <false, false> is the kernel as it was before the template.
+//                        reference area and wind.  <false, false> is the kernel as it was before the template.  kEns = 1
+//                        (gel_propagate_ensemble*): every lane's wind table is the one its vector is assigned.
 //   prop_err_kernel      err [B][S][4] from x and y: one lane = one (vector, phase), nodes in ascending order
 // fp64 throughout; the right-hand side is section_rhs (gel_section_rhs.h), the one mesh_kernel evaluates.
 #include <hip/hip_runtime.h>
@@ -100,10 +101,14 @@ __global__ __launch_bounds__(kPropSampleThreads) void prop_sample_kernel(Problem
 // mass flow, reference area: one product each) and the interpolated wind inside section_rhs.
 // kChain (GEL_PROP_CHAIN): one lane = one vector, which walks the phases in order and carries its state across the knots; a
 // workgroup = kPropThreads consecutive vectors, so the phase stays wave-uniform.  Without either the code is the one-segment body.
-template <bool kDisp, bool kChain>
+// kEns = 1 (gel_propagate_ensemble*; with kDisp only, the other instantiations do not read Ens): the lane looks the wind up in the
+// table its vector is assigned (ens_lane_tables: global memory) and keeps that table's altitude interval across stages, steps and
+// phases.  disp may then be null: factors of one.  An int, not a branch on Ens.tables inside the dispersed instantiations: with both
+// right-hand sides in one kernel the dispersed instantiations took 194 / 202 VGPRs (2 waves/SIMD) instead of 148 / 154.
+template <bool kDisp, bool kChain, int kEns = 0>
 __global__ __launch_bounds__(kPropThreads) void prop_kernel(ProblemDev P, PropDev Pd, int nb, const double* __restrict__ x,
                                                             double* __restrict__ y, const double* __restrict__ ws, long long ld,
-                                                            const double* __restrict__ disp) {
+                                                            const double* __restrict__ disp, EnsDev Ens) {
   extern __shared__ double lds[];
   // workgroup -> (segment, group of kPropThreads vectors); chain mode: the group alone
   const int ngrp = (nb + kPropThreads - 1) / kPropThreads;
@@ -113,6 +118,10 @@ __global__ __launch_bounds__(kPropThreads) void prop_kernel(ProblemDev P, PropDe
   if (seg >= Pd.nseg || v >= nb) return;   // (idle lanes leave: they stay out of the calm-air vote of wind_eci_or_calm; no barrier follows)
   bool bad = false;
   double yv[11];
+  // under an ensemble: the lane's view of the tables (its wind part in global memory) and its kept altitude interval
+  Tables tbe = tb;
+  Bracket2 wbr = no_bracket2();
+  if constexpr (kEns) tbe = ens_lane_tables(P, tb, Ens, Ens.member[v]);
   int s = kChain ? 0 : load_const(&Pd.seg_phase[seg]);
   do {
     PhaseDev ph = load_phase(P.phases + s);
@@ -127,7 +136,7 @@ __global__ __launch_bounds__(kPropThreads) void prop_kernel(ProblemDev P, PropDe
     const double to = xb[11 * M + 2 * N + s], tf = xb[11 * M + 2 * N + s + 1];
     const double S = (tf - to) * P.ut / 2.0;
     double fw = 1.0;
-    if constexpr (kDisp) {
+    if (kDisp && (!kEns || disp)) {   // (null only under an ensemble: factors of one, which change no bit)
       const double* const fac = disp + ((size_t)v * Pd.S + s) * kPropNDisp;
       const double f_thrust = fac[0], f_mf = fac[1], f_area = fac[2];
       fw = fac[3];
@@ -172,7 +181,8 @@ __global__ __launch_bounds__(kPropThreads) void prop_kernel(ProblemDev P, PropDe
             u0 = us[(size_t)pp * 2 * (size_t)ld];
             u1 = us[((size_t)pp * 2 + 1) * (size_t)ld];
           }
-          if constexpr (kDisp) section_rhs<true>(P, ph, tb, Pd.vp, sig[pp], to, tf, yt, u0, u1, F, fw);
+          if constexpr (kEns) section_rhs<true, true>(P, ph, tbe, Pd.vp, sig[pp], to, tf, yt, u0, u1, F, fw, &wbr);
+          else if constexpr (kDisp) section_rhs<true>(P, ph, tb, Pd.vp, sig[pp], to, tf, yt, u0, u1, F, fw);
           else section_rhs(P, ph, tb, Pd.vp, sig[pp], to, tf, yt, u0, u1, F);
 #pragma unroll
           for (int c = 0; c < 11; c++) acc[c] = st ? __builtin_fma(w, F[c], acc[c]) : F[c];
@@ -224,7 +234,8 @@ __global__ __launch_bounds__(256) void prop_err_kernel(ProblemDev P, PropDev Pd,
 }
 
 hipError_t launch_prop_slab(const ProblemDev& P, const PropDev& Pd, const PropPhaseDev* host_ph, int n_max_sampled, int nb,
-                            const double* d_x, double* d_y, double* d_ws, int64_t ld, const double* d_disp, hipStream_t s) {
+                            const double* d_x, double* d_y, double* d_ws, int64_t ld, const double* d_disp, const EnsDev& ens,
+                            hipStream_t s) {
   if (nb <= 0) return hipSuccess;
   if (ld < nb) return hipErrorInvalidValue;
   const long long ng = ((long long)nb + kPropSampleVB - 1) / kPropSampleVB;
@@ -242,9 +253,10 @@ hipError_t launch_prop_slab(const ProblemDev& P, const PropDev& Pd, const PropPh
   if (grid <= 0) return hipSuccess;
   if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
   const size_t lds = table_lds_bytes(P.Kw, P.Kc);
-  auto* const kern = Pd.chain ? (d_disp ? prop_kernel<true, true> : prop_kernel<false, true>)
-                              : (d_disp ? prop_kernel<true, false> : prop_kernel<false, false>);
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kPropThreads), lds, s, P, Pd, nb, d_x, d_y, d_ws, (long long)ld, d_disp);
+  auto* const kern = ens.tables ? (Pd.chain ? prop_kernel<true, true, 1> : prop_kernel<true, false, 1>)
+                     : Pd.chain ? (d_disp ? prop_kernel<true, true> : prop_kernel<false, true>)
+                                : (d_disp ? prop_kernel<true, false> : prop_kernel<false, false>);
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kPropThreads), lds, s, P, Pd, nb, d_x, d_y, d_ws, (long long)ld, d_disp, ens);
   return hipGetLastError();
 }
 

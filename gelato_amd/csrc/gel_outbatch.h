@@ -5,6 +5,7 @@
 
 #include "gel_device.h"
 #include "gel_launch.h"
+#include "gel_ensemble.h"
 
 namespace gel {
 
@@ -41,11 +42,14 @@ inline size_t outbatch_ws_doubles(int B, int M, int ncols) {
 }
 
 // table [B][M][ncols] and / or peaks [B][ncols][4] (either may be null, not both): one workgroup per vector
-hipError_t launch_outbatch_rows(const ProblemDev& P, const OutBatchArgs& A, double* d_out, double* d_peaks, hipStream_t s);
+// ens: the wind ensemble with the assignment of all B vectors, or ens.tables == null (the same for launch_outbatch_env); with an
+// ensemble the kernels' kEns instantiation runs, with factors of one where A.disp is null
+hipError_t launch_outbatch_rows(const ProblemDev& P, const OutBatchArgs& A, const EnsDev& ens, double* d_out, double* d_peaks,
+                                hipStream_t s);
 // envelope [M][ncols][8] through the partials ws (outbatch_ws_doubles).  d_table = the [B][M][ncols] table launch_outbatch_rows has
 // written on the same stream for the same arguments: the partials are read from it; null: the rows are formed again, nothing of a
 // table is written or read.  The same bits either way.
-hipError_t launch_outbatch_env(const ProblemDev& P, const OutBatchArgs& A, const double* d_table, double* d_ws, double* d_env,
-                               hipStream_t s);
+hipError_t launch_outbatch_env(const ProblemDev& P, const OutBatchArgs& A, const EnsDev& ens, const double* d_table, double* d_ws,
+                               double* d_env, hipStream_t s);
 
 }  // namespace gel

@@ -28,6 +28,7 @@
 #include <stdint.h>
 
 #include "gel_device.h"
+#include "gel_ensemble.h"
 
 namespace gel {
 
@@ -67,9 +68,12 @@ inline size_t prop_sample_lds_bytes(int n) { return (size_t)16 * n * kPropSample
 
 // One slab of nb vectors (x, y: the slab's first vector; ws: [stage point][2][ld] with ld >= nb):
 // control samples into ws, then y [nb][11 M] from x [nb][nvars].  n_max_sampled sizes the sample kernel's LDS.  d_disp: the slab's
-// factors [nb][S][kPropNDisp], or null (the undispersed instantiation).
+// factors [nb][S][kPropNDisp], or null (the undispersed instantiation).  ens: the wind ensemble with the SLAB's part of the
+// assignment (ens.member = the entry of the slab's first vector), or ens.tables == null; with an ensemble the kernel's kEns
+// instantiation runs, with factors of one where d_disp is null.
 hipError_t launch_prop_slab(const ProblemDev& P, const PropDev& Pd, const PropPhaseDev* host_ph, int n_max_sampled, int nb,
-                            const double* d_x, double* d_y, double* d_ws, int64_t ld, const double* d_disp, hipStream_t s);
+                            const double* d_x, double* d_y, double* d_ws, int64_t ld, const double* d_disp, const EnsDev& ens,
+                            hipStream_t s);
 // err [B][S][4] from x and y (all B vectors in one launch)
 hipError_t launch_prop_err(const ProblemDev& P, const PropDev& Pd, int B, const double* d_x, const double* d_y, double* d_err,
                            hipStream_t s);

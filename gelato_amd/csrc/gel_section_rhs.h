@@ -17,9 +17,12 @@ namespace gel {
 // kDisp (gel_propagate_dispersed): the caller has already scaled ph.thrust, ph.mf_um and ph.area by its lane's factors (one product
 // each, once per phase); fw scales the two wind components AFTER the interpolation -- the tables in LDS are the workgroup's --
 // and before wind_eci_or_calm.  ph.air stays the handle's.  Without kDisp fw is not read: the code is what it was.
-template <bool kDisp = false>
+// kEns (gel_propagate_ensemble*, with kDisp): tb is the LANE's view of the tables (ens_lane_tables, gel_ensemble.h: its wind part
+// lies in global memory) and wbr the lane's kept altitude interval of that table, carried by the caller across stages and steps:
+// wind_ned2_cached gives wind_ned2's bits from it and searches again on a miss.  Without kEns wbr is not read.
+template <bool kDisp = false, bool kEns = false>
 GEL_DEV void section_rhs(const ProblemDev& P, const PhaseDev& ph, const Tables& tb, double vp, double sig, double to, double tf,
-                         const double xt[11], double u0, double u1, double F[11], double fw = 1.0) {
+                         const double xt[11], double u0, double u1, double F[11], double fw = 1.0, Bracket2* wbr = nullptr) {
   F[0] = ph.engine_on ? ph.mf_um : 0.0;   // mass: the m[1:] - m[0] form when the engine is off
 #pragma unroll
   for (int c = 0; c < 3; c++) F[1 + c] = xt[4 + c] * vp;
@@ -31,7 +34,7 @@ GEL_DEV void section_rhs(const ProblemDev& P, const PhaseDev& ph, const Tables& 
   if (ph.air) {
     // dynamics_velocity at the normalised time of the point (PSparams.time_nodes, as the defect kernels take it)
     const double v3[3] = {xt[4] * P.uv, xt[5] * P.uv, xt[6] * P.uv};
-    const PosPart pp = pos_part(r, tb, P.barC20);
+    const PosPart pp = pos_part(r, tb, P.barC20, kEns ? wbr : nullptr);
     const EarthAngle ea = earth_angle(sig * (tf - to) / 2 + (tf + to) / 2);
     double w[3], Fa[3];
     if constexpr (kDisp) {

@@ -178,13 +178,16 @@ class PropagationPlan:
         check(lib().gel_prop_matrices(self._p, int(phase), _d(out["pts"]), _d(out["Wu"]), out["copy_u"].ctypes.data_as(_ip)))
         return out
 
-    def apply(self, X, want_err=True, dispersion=None):
+    def apply(self, X, want_err=True, dispersion=None, ensemble=None):
         """X [B, nvars] (or [nvars]) -> (Y [B, 11 M]: the propagated state at every state node, laid out like the state part of
         x; err [B, S, 4] (mass, position, velocity, quaternion) | None; status).  dispersion: None, or float64 [B, S, 4] ([S, 4]
-        for one vector): per vector and phase the factors of thrust, mass flow, reference area and wind (gel_propagate_dispersed)"""
+        for one vector): per vector and phase the factors of thrust, mass flow, reference area and wind (gel_propagate_dispersed).
+        ensemble: None, or a WindEnsemble of this engine assigned B vectors: every vector flies under the wind table its entry
+        selects (gel_propagate_ensemble)"""
         self._live()
         X = _f64(X).reshape(-1, self.nvars)
         B = X.shape[0]
+        ens = _ensemble_ptr(ensemble, self._owner)
         disp = None
         if dispersion is not None:
             disp = np.asarray(dispersion)
@@ -197,15 +200,86 @@ class PropagationPlan:
             disp = np.ascontiguousarray(disp)
         Y = np.empty((B, 11 * self.M))
         err = np.empty((B, self.S, 4)) if want_err else None
-        rc = check(lib().gel_propagate_dispersed(self._p, B, _d(X), _d(disp) if disp is not None else None, _d(Y),
-                                                 _d(err) if want_err else None))
+        rc = check(lib().gel_propagate_ensemble(self._p, B, _d(X), _d(disp) if disp is not None else None, ens, _d(Y),
+                                                _d(err) if want_err else None))
         return Y, err, rc
 
-    def apply_device(self, B, d_x, d_y, d_err=0, d_dispersion=0):
-        """device buffers: d_y [B][11 M], d_err [B][S][4] or 0, d_dispersion [B][S][4] or 0; asynchronous on the engine's own
-        stream; status through Engine.sync()"""
+    def apply_device(self, B, d_x, d_y, d_err=0, d_dispersion=0, ensemble=None):
+        """device buffers: d_y [B][11 M], d_err [B][S][4] or 0, d_dispersion [B][S][4] or 0; ensemble: None or a WindEnsemble of
+        this engine assigned B vectors; asynchronous on the engine's own stream; status through Engine.sync()"""
         self._live()
-        check(lib().gel_propagate_dispersed_device(self._p, int(B), d_x, d_dispersion or None, d_y, d_err or None))
+        check(lib().gel_propagate_ensemble_device(self._p, int(B), d_x, d_dispersion or None, _ensemble_ptr(ensemble, self._owner), d_y,
+                                                  d_err or None))
+
+
+def _ensemble_ptr(ensemble, owner):
+    """the raw pointer of a live WindEnsemble (None for None); an ensemble of another engine is refused here, by name"""
+    if ensemble is None:
+        return None
+    if not isinstance(ensemble, WindEnsemble):
+        raise TypeError("ensemble: a WindEnsemble (Engine.wind_ensemble) or None")
+    ensemble._live()
+    if ensemble._owner is not owner:
+        raise ValueError("ensemble: created by another engine")
+    return ensemble._p
+
+
+class WindEnsemble:
+    """A wind ensemble of one engine (include/gelato_amd.h gel_wind_ensemble_*): E member tables [Kw, 3] resident on
+    the device and one assignment member [B] (-1: the engine's own table) that the flight and the table of a batch read alike.  It
+    holds the engine's handle owner, so the handle outlives it; close() destroys the ensemble."""
+
+    INFO = ("E", "Kw", "member_doubles", "device_bytes", "assigned")
+
+    def __init__(self, owner, ptr, E, Kw):
+        self._owner = owner
+        self._p = ptr
+        self.E, self.Kw = int(E), int(Kw)
+
+    def close(self):
+        if self._p:
+            ptr, self._p = self._p, None
+            if self._owner.ptr:     # (a handle closed first has taken the device down with it: the ensemble's host memory leaks)
+                lib().gel_wind_ensemble_destroy(ptr)
+        self._owner = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _live(self):
+        if not (self._p and self._owner.ptr):
+            raise _lib.GelatoAmdError("wind ensemble: closed, or its engine was closed first")
+
+    def info(self):
+        """{"E", "Kw", "member_doubles": 5 Kw - 2, "device_bytes", "assigned": vectors of the current assignment or -1}"""
+        self._live()
+        info = (C.c_int64 * 5)()
+        check(lib().gel_wind_ensemble_info(self._p, info))
+        return dict(zip(self.INFO, (int(v) for v in info)))
+
+    def member(self, e):
+        """member e as staged -> {"rows" [Kw, 3], "slopes" [Kw - 1, 2]} (works on host-only handles)"""
+        self._live()
+        st = np.empty(5 * self.Kw - 2)
+        check(lib().gel_wind_ensemble_member(self._p, int(e), _d(st)))
+        return {"rows": st[:3 * self.Kw].reshape(self.Kw, 3), "slopes": st[3 * self.Kw:].reshape(self.Kw - 1, 2)}
+
+    def assign(self, members):
+        """members: integers [B], each -1 (the engine's own wind table) or 0 .. E - 1; validated by the library"""
+        self._live()
+        m = np.asarray(members)
+        if m.ndim != 1:
+            raise ValueError("members: one entry per vector, [B]")
+        if m.size and not np.issubdtype(m.dtype, np.integer):
+            raise TypeError("members: integers")
+        if m.size and (int(m.min()) < -1 or int(m.max()) >= self.E):
+            raise ValueError("members: -1 or 0 .. %d, not %d .. %d" % (self.E - 1, int(m.min()), int(m.max())))
+        m = np.ascontiguousarray(m, dtype=np.int32)
+        check(lib().gel_wind_ensemble_assign(self._p, int(m.size), m.ctypes.data_as(_ip)))
+        return self
 
 
 class Engine:
@@ -771,11 +845,12 @@ class Engine:
         return [self.OUTPUT_COLUMNS[i] for i in ids], np.asarray(ids, dtype=np.int32)
 
     def output_table_batch(self, X, launch_lat, launch_lon, tx=None, dispersion=None, columns=None, table=True, envelope=True,
-                           peaks=True):
+                           peaks=True, ensemble=None):
         """The post-processing table of a batch with its envelope and peaks (gel_output_table_batch).
         X [B, nvars] (or [nvars]); tx None (every vector's node times from its own knots) or [B, M] seconds; dispersion None or
         float64 [B, S, 4] as PropagationPlan.apply takes it (the mass-flow factor has no reader here); columns None (all of
-        OUTPUT_COLUMNS) or a list of distinct names.
+        OUTPUT_COLUMNS) or a list of distinct names; ensemble None or a WindEnsemble of this engine assigned B vectors: every
+        vector's rows take the wind of the table its entry selects (gel_output_table_batch_ensemble).
         -> {"columns": names, "table": [B, M, ncols] | None,
             "envelope": {name: {count [M] int, mean, std (sqrt(m2 / (count - 1)), NaN where count < 2), m2, min, max [M],
                                 argmin, argmax, first_nonfinite [M] int (-1: none)}} | None   -- per node over the vectors,
@@ -808,9 +883,11 @@ class Engine:
         out = np.empty((B, M, nc)) if table else None
         env = np.empty((M, nc, _lib.GEL_ENV_NSTAT)) if envelope else None
         pk = np.empty((B, nc, _lib.GEL_PEAK_NSTAT)) if peaks else None
-        check(lib().gel_output_table_batch(self._h, B, _d(X), _d(tx) if tx is not None else None, _d(disp) if disp is not None else None,
-                                           float(launch_lat), float(launch_lon), nc, ids.ctypes.data_as(_ip) if ids is not None else None,
-                                           _d(out) if table else None, _d(env) if envelope else None, _d(pk) if peaks else None))
+        check(lib().gel_output_table_batch_ensemble(self._h, B, _d(X), _d(tx) if tx is not None else None,
+                                                    _d(disp) if disp is not None else None, _ensemble_ptr(ensemble, self._owner),
+                                                    float(launch_lat), float(launch_lon), nc,
+                                                    ids.ctypes.data_as(_ip) if ids is not None else None, _d(out) if table else None,
+                                                    _d(env) if envelope else None, _d(pk) if peaks else None))
         res = {"columns": names, "table": out, "envelope": None, "peaks": None}
         if envelope:
             res["envelope"] = {}
@@ -831,13 +908,15 @@ class Engine:
         return res
 
     def output_table_batch_device(self, B, d_x, launch_lat, launch_lon, d_tx=0, d_dispersion=0, columns=None, d_out=0, d_env=0,
-                                  d_peaks=0):
+                                  d_peaks=0, ensemble=None):
         """device buffers (raw pointers; 0 = not given): d_out [B][M][ncols], d_env [M][ncols][8], d_peaks [B][ncols][4];
-        asynchronous on the engine's own stream; status through Engine.sync()"""
+        ensemble: None or a WindEnsemble of this engine assigned B vectors; asynchronous on the engine's own stream; status
+        through Engine.sync()"""
         names, ids = self._output_columns(columns)
-        check(lib().gel_output_table_batch_device(self._h, int(B), d_x or None, d_tx or None, d_dispersion or None, float(launch_lat),
-                                                  float(launch_lon), len(names), ids.ctypes.data_as(_ip) if ids is not None else None,
-                                                  d_out or None, d_env or None, d_peaks or None))
+        check(lib().gel_output_table_batch_ensemble_device(self._h, int(B), d_x or None, d_tx or None, d_dispersion or None,
+                                                           _ensemble_ptr(ensemble, self._owner), float(launch_lat), float(launch_lon),
+                                                           len(names), ids.ctypes.data_as(_ip) if ids is not None else None,
+                                                           d_out or None, d_env or None, d_peaks or None))
 
     @staticmethod
     def _quantile_probs(probs):
@@ -1105,6 +1184,23 @@ class Engine:
         h = C.c_void_p()
         check(lib().gel_prop_plan_create(self._h, st.ctypes.data_as(_ip), {"section": 0, "node": _lib.GEL_PROP_RESTART_NODE, "chain": _lib.GEL_PROP_CHAIN}[restart], C.byref(h)))
         return PropagationPlan(self._owner, h, self.num_nodes, st, (self.S, self.M, self.nvars))
+
+    # ------------------------------------------------------------------
+    # a Monte-Carlo batch against an ensemble of wind profiles (include/gelato_amd.h gel_wind_ensemble_*)
+    def wind_ensemble(self, tables):
+        """tables: float64 [E, Kw, 3] (one member: [Kw, 3]), the columns of prob["wind_table"]; every member's altitudes increase
+        strictly -> WindEnsemble (assign() it before a call takes it)"""
+        t = np.asarray(tables)
+        if t.dtype != np.float64:
+            raise TypeError("tables: float64")
+        if t.ndim == 2:
+            t = t[None]
+        if t.ndim != 3 or t.shape[2] != 3:
+            raise ValueError("tables: [E, Kw, 3], not %s" % (t.shape,))
+        t = np.ascontiguousarray(t)
+        h = C.c_void_p()
+        check(lib().gel_wind_ensemble_create(self._h, int(t.shape[0]), int(t.shape[1]), _d(t), C.byref(h)))
+        return WindEnsemble(self._owner, h, t.shape[0], t.shape[1])
 
     # ------------------------------------------------------------------
     # Jacobian products from the compact values (include/gelato_amd.h gel_jac_*; DESIGN.md 3.10)

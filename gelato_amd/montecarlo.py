@@ -15,11 +15,12 @@ from . import con_dynamics
 from .engine import Engine, pack_x
 
 
-def flight_envelope(xdict_or_X, pdict, unitdict, dispersion=None, steps=4, columns=None, engine=None):
+def flight_envelope(xdict_or_X, pdict, unitdict, dispersion=None, steps=4, columns=None, engine=None, ensemble=None):
     """xdict_or_X: a solution xdict or packed vectors [B, nvars] / [nvars]; dispersion: None or [B, S, 4]
     (propagate.sample_dispersion); steps: as propagate.fly; ONE chain run with 2 * steps RK4 steps per node interval, the run fly's y and err
     come from; columns: None (all of Engine.OUTPUT_COLUMNS) or a list of names; engine: an Engine of the same problem (one is
-    created on device 0 otherwise).
+    created on device 0 otherwise); ensemble: None, or a WindEnsemble of that engine assigned B vectors: the flight AND the table of
+    every vector take the wind table its entry selects (flight_quantiles and flight_covariance take it alike).
     -> {"steps": 2 * steps, "status": 0 or GEL_NONFINITE (of the flight and the row table; the output table reports its own
         non-finite entries through count / first_nonfinite), "columns": names,
         "envelope", "peaks": as Engine.output_table_batch returns them, at x_flown,
@@ -38,13 +39,13 @@ def flight_envelope(xdict_or_X, pdict, unitdict, dispersion=None, steps=4, colum
     # fly's chain plan, the run that counts alone (fly's second run only estimates the integrator's share of err)
     plan = engine.propagation_plan(steps=2 * steps, restart="chain")
     try:
-        Y, err, status = plan.apply(X, dispersion=dispersion)
+        Y, err, status = plan.apply(X, dispersion=dispersion, ensemble=ensemble)
     finally:
         plan.close()
     x_flown = X.copy()
     x_flown[:, :11 * engine.M] = Y
     lc = pdict["LaunchCondition"]
-    T = engine.output_table_batch(x_flown, lc["lat"], lc["lon"], dispersion=dispersion, columns=columns, table=False)
+    T = engine.output_table_batch(x_flown, lc["lat"], lc["lon"], dispersion=dispersion, columns=columns, table=False, ensemble=ensemble)
     out = {"steps": 2 * steps, "status": int(status), "columns": T["columns"], "envelope": T["envelope"], "peaks": T["peaks"],
            "terminal_miss": err[:, -1], "x_flown": x_flown}
     if engine._nlin + engine._nfn:
@@ -54,7 +55,7 @@ def flight_envelope(xdict_or_X, pdict, unitdict, dispersion=None, steps=4, colum
     return out
 
 
-def flight_quantiles(xdict_or_X, pdict, unitdict, probs, dispersion=None, steps=4, columns=None, engine=None):
+def flight_quantiles(xdict_or_X, pdict, unitdict, probs, dispersion=None, steps=4, columns=None, engine=None, ensemble=None):
     """The same flight as flight_envelope, read by exact quantiles over the flights (Engine.batch_quantiles_device, include/gelato_amd.h
     gel_batch_quantiles).  The flown states, the table [B, M, ncols] and the peaks stay on the device; only results of
     the size [M][ncols][nq] come back.  probs: 1 .. 16 probabilities in [0, 1]; the other arguments as flight_envelope takes them.
@@ -99,11 +100,11 @@ def flight_quantiles(xdict_or_X, pdict, unitdict, probs, dispersion=None, steps=
     dptr = d_disp.data_ptr() if d_disp is not None else 0
     plan = engine.propagation_plan(steps=2 * steps, restart="chain")
     try:
-        plan.apply_device(B, d_x.data_ptr(), d_y.data_ptr(), d_err.data_ptr(), dptr)
+        plan.apply_device(B, d_x.data_ptr(), d_y.data_ptr(), d_err.data_ptr(), dptr, ensemble=ensemble)
         d_x[:, :11 * M] = d_y          # x_flown; the null stream orders itself against the engine's blocking stream
         lc = pdict["LaunchCondition"]
         engine.output_table_batch_device(B, d_x.data_ptr(), lc["lat"], lc["lon"], d_dispersion=dptr, columns=columns,
-                                         d_out=d_table.data_ptr(), d_peaks=d_peaks.data_ptr())
+                                         d_out=d_table.data_ptr(), d_peaks=d_peaks.data_ptr(), ensemble=ensemble)
         engine.batch_quantiles_device(B, M * nc, M * nc, d_table.data_ptr(), p, q_node.data_ptr(), c_node.data_ptr())
         engine.batch_quantiles_device(B, nc * 4, nc * 4, d_peaks.data_ptr(), p, q_peak.data_ptr(), c_peak.data_ptr(), w_peak.data_ptr())
         engine.batch_quantiles_device(B, 4, S * 4, d_err.data_ptr() + 8 * (S - 1) * 4, p, q_miss.data_ptr(), c_miss.data_ptr())
@@ -154,7 +155,7 @@ def dispersion_sensitivity(count, C_dd, C_dy, m2_y):
     return {"count": int(count), "active": act, "beta": beta, "explained": explained, "share": share}
 
 
-def flight_covariance(xdict_or_X, pdict, unitdict, dispersion, steps=4, columns=None, engine=None):
+def flight_covariance(xdict_or_X, pdict, unitdict, dispersion, steps=4, columns=None, engine=None, ensemble=None):
     """The same flight as flight_quantiles, read by co-moments over the flights (Engine.batch_comoments_device, include/gelato_amd.h
     gel_batch_comoments).  The flown states, the table and the peaks stay on the device; the calls read them as
     views.  dispersion: [B, S, 4], required; the other arguments as flight_envelope takes them.
@@ -209,11 +210,11 @@ def flight_covariance(xdict_or_X, pdict, unitdict, dispersion, steps=4, columns=
     outs = {}
     plan = engine.propagation_plan(steps=2 * steps, restart="chain")
     try:
-        plan.apply_device(B, d_x.data_ptr(), d_y.data_ptr(), d_err.data_ptr(), d_disp.data_ptr())
+        plan.apply_device(B, d_x.data_ptr(), d_y.data_ptr(), d_err.data_ptr(), d_disp.data_ptr(), ensemble=ensemble)
         d_x[:, :11 * M] = d_y          # x_flown; the null stream orders itself against the engine's blocking stream
         lc = pdict["LaunchCondition"]
         engine.output_table_batch_device(B, d_x.data_ptr(), lc["lat"], lc["lon"], d_dispersion=d_disp.data_ptr(), columns=columns,
-                                         d_out=d_table.data_ptr(), d_peaks=d_peaks.data_ptr())
+                                         d_out=d_table.data_ptr(), d_peaks=d_peaks.data_ptr(), ensemble=ensemble)
         for key, (va, vb) in views.items():
             Wa, Wb = va[1], (va[1] if vb is None else vb[1])
             o = (buf(Wa, Wb), buf(Wa, 2), None if vb is None else buf(Wb, 2), buf(2))
@@ -240,4 +241,136 @@ def flight_covariance(xdict_or_X, pdict, unitdict, dispersion, steps=4, columns=
         sens = dispersion_sensitivity(r["count"], res["dispersion"]["C"], r["C"], r["m2_b"])
         r.update({k: sens[k] for k in ("active", "beta", "explained", "share")})
         out["sensitivity"][g] = r
+    return out
+
+
+def availability_from_peaks(peaks, members, limits, E=None):
+    """The launch-availability record of a batch flown against a wind ensemble, from every flight's peaks (host numpy; no GPU).
+    peaks: {column: {"min", "argmin", "max", "argmax" [B]}} as Engine.output_table_batch returns them; members: int [B], the member
+    0 .. E - 1 every flight flew under (several flights per member: its replicas); limits: {column: upper} or {column: (lower,
+    upper)}, either bound None for none; E: the number of members (default: max(members) + 1).  Every member needs a flight.
+    Per limited column and member, over the member's flights in ascending order: the worst (largest) maximum and the worst
+    (smallest) minimum, NaN peaks left out, with the FIRST flight that holds each and its node.  A member is ok when every one of
+    its flights has finite peaks in every limited column, worst_max <= upper and worst_min >= lower.
+    -> {"columns": the limited columns, "limits": {column: (lower | None, upper | None)},
+        "worst_max", "worst_min": {column: [E]}, "flight_max", "node_max", "flight_min", "node_min": {column: [E] int (-1: none)},
+        "ok" [E] bool, "ok_by_column": {column: [E] bool}, "availability": ok.sum() / E, "failing": the members that are not ok}"""
+    members = np.asarray(members)
+    if members.ndim != 1 or (members.size and not np.issubdtype(members.dtype, np.integer)):
+        raise ValueError("members: integers [B]")
+    B = members.size
+    if B == 0 or members.min() < 0:
+        raise ValueError("members: at least one flight, every flight under a member 0 .. E - 1")
+    E = int(members.max()) + 1 if E is None else int(E)
+    if members.max() >= E:
+        raise ValueError("members: an entry >= E = %d" % E)
+    if np.bincount(members, minlength=E).min() == 0:
+        raise ValueError("members: every member needs at least one flight")
+    if not limits:
+        raise ValueError("limits: at least one limited column")
+    lim = {}
+    for name, v in limits.items():
+        if name not in peaks:
+            raise ValueError("limits: no peaks of column %r" % (name,))
+        lo, up = v if isinstance(v, (tuple, list)) else (None, v)
+        lo, up = (None if lo is None else float(lo)), (None if up is None else float(up))
+        if (lo is not None and lo != lo) or (up is not None and up != up) or (lo is None and up is None):
+            raise ValueError("limits[%r]: upper, or (lower, upper), numbers, at least one of them" % (name,))
+        lim[name] = (lo, up)
+    out = {"columns": list(lim), "limits": lim, "ok_by_column": {}}
+    for k in ("worst_max", "worst_min", "flight_max", "node_max", "flight_min", "node_min"):
+        out[k] = {}
+    ok = np.ones(E, dtype=bool)
+    flights = np.arange(B)
+    for name, (lo, up) in lim.items():
+        pk = peaks[name]
+        vmax, vmin = np.asarray(pk["max"], dtype=np.float64), np.asarray(pk["min"], dtype=np.float64)
+        if vmax.shape != (B,) or vmin.shape != (B,):
+            raise ValueError("peaks[%r]: [B] = [%d]" % (name, B))
+        wmax, wmin = np.full(E, np.nan), np.full(E, np.nan)
+        fmax, fmin = np.full(E, -1, dtype=np.int64), np.full(E, -1, dtype=np.int64)
+        nmax, nmin = fmax.copy(), fmin.copy()
+        okc = np.ones(E, dtype=bool)
+        for e in range(E):
+            fl = flights[members == e]
+            fin = np.isfinite(vmax[fl]) & np.isfinite(vmin[fl])
+            okc[e] = bool(fin.all())
+            if fin.any():
+                g = fl[fin]
+                i, j = g[np.argmax(vmax[g])], g[np.argmin(vmin[g])]      # (argmax / argmin: the first that attains it)
+                wmax[e], fmax[e], nmax[e] = vmax[i], i, int(np.asarray(pk["argmax"])[i])
+                wmin[e], fmin[e], nmin[e] = vmin[j], j, int(np.asarray(pk["argmin"])[j])
+                if up is not None and not wmax[e] <= up:
+                    okc[e] = False
+                if lo is not None and not wmin[e] >= lo:
+                    okc[e] = False
+        out["worst_max"][name], out["worst_min"][name] = wmax, wmin
+        out["flight_max"][name], out["node_max"][name], out["flight_min"][name], out["node_min"][name] = fmax, nmax, fmin, nmin
+        out["ok_by_column"][name] = okc
+        ok &= okc
+    out["ok"] = ok
+    out["availability"] = float(ok.sum()) / E
+    out["failing"] = np.flatnonzero(~ok)
+    return out
+
+
+def wind_availability(xdict_or_x, pdict, unitdict, wind_tables, limits, replicas=1, sigma=0.0, seed=0, steps=4, engine=None):
+    """Launch availability of ONE trajectory over an ensemble of wind profiles: the share of profiles under which the flight keeps
+    its limits.  xdict_or_x: a solution xdict or one packed vector [nvars]; wind_tables: float64 [E, Kw, 3] (Engine.wind_ensemble);
+    limits: {column of Engine.OUTPUT_COLUMNS: upper} or {column: (lower, upper)}; replicas: flights per member, B = E replicas
+    flights blocked by member (propagate.assign_members); sigma, seed: the factors of propagate.sample_dispersion(B, S, sigma,
+    seed) -- none at all with sigma == 0 and replicas == 1; steps: as flight_envelope (ONE chain run, 2 * steps RK4 steps per node
+    interval); engine: an Engine of the same problem (one is created on device 0 otherwise).  The flown states stay on the device and
+    only the peaks of the limited columns come back.
+    -> the record of availability_from_peaks(peaks, members, limits, E), and "steps": 2 * steps, "status": 0 or GEL_NONFINITE (of
+       the flight), "members" [B], "peaks": {column: {"min", "argmin", "max", "argmax" [B]}}, "dispersion": [B, S, 4] | None"""
+    import torch
+    from .propagate import assign_members, sample_dispersion
+    if engine is None:
+        S = pdict["num_sections"]
+        ps = pdict["ps_params"]
+        engine = Engine(con_dynamics.problem_arrays(pdict, unitdict), D=[ps.D(i) for i in range(S)],
+                        tau=[ps.tau(i) for i in range(S)])
+    steps, replicas = int(steps), int(replicas)
+    if steps < 1 or replicas < 1:
+        raise ValueError("steps and replicas: at least 1")
+    if not limits:
+        raise ValueError("limits: at least one limited column")
+    names, _ids = engine._output_columns(list(limits))
+    x = pack_x(xdict_or_x) if isinstance(xdict_or_x, dict) else np.asarray(xdict_or_x, dtype=np.float64)
+    if x.size != engine.nvars:
+        raise ValueError("wind_availability takes ONE decision vector [nvars = %d]" % engine.nvars)
+    ens = engine.wind_ensemble(wind_tables)
+    try:
+        E = ens.E
+        B, M, S, nc = E * replicas, engine.M, engine.S, len(names)
+        members = assign_members(B, E, order="blocked")
+        ens.assign(members)
+        disp = None if (replicas == 1 and np.all(np.asarray(sigma) == 0)) else sample_dispersion(B, S, sigma, seed)
+        d_disp = torch.from_numpy(disp).cuda() if disp is not None else None
+        dptr = d_disp.data_ptr() if d_disp is not None else 0
+        d_x = torch.from_numpy(np.ascontiguousarray(np.broadcast_to(x.reshape(1, -1), (B, engine.nvars)))).cuda()
+        d_y = torch.empty((B, 11 * M), dtype=torch.float64, device="cuda")
+        d_peaks = torch.empty((B, nc, 4), dtype=torch.float64, device="cuda")
+        plan = engine.propagation_plan(steps=2 * steps, restart="chain")
+        try:
+            plan.apply_device(B, d_x.data_ptr(), d_y.data_ptr(), 0, dptr, ensemble=ens)
+            d_x[:, :11 * M] = d_y          # x_flown; the null stream orders itself against the engine's blocking stream
+            lc = pdict["LaunchCondition"]
+            engine.output_table_batch_device(B, d_x.data_ptr(), lc["lat"], lc["lon"], d_dispersion=dptr, columns=names,
+                                             d_peaks=d_peaks.data_ptr(), ensemble=ens)
+            status = engine.sync()
+        finally:
+            plan.close()
+    finally:
+        ens.close()
+    pk = d_peaks.cpu().numpy()
+    peaks = {}
+    for k, name in enumerate(names):
+        q = {f: pk[:, k, j].copy() for j, f in enumerate(engine.PEAK_FIELDS)}
+        for f in ("argmin", "argmax"):
+            q[f] = q[f].astype(np.int64)
+        peaks[name] = q
+    out = availability_from_peaks(peaks, members, limits, E)
+    out.update({"steps": 2 * steps, "status": int(status), "members": members, "peaks": peaks, "dispersion": disp})
     return out

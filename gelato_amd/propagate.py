@@ -88,11 +88,35 @@ def sample_dispersion(B, S, sigma, seed, per="vector"):
     return np.array(np.broadcast_to(1.0 + sg * z, (B, S, 4)), order="C")   # (an array of its own: writable, contiguous)
 
 
-def fly(xdict_or_X, pdict, unitdict, steps=4, dispersion=None, engine=None):
+def assign_members(B, E, order="blocked", seed=0, own=0):
+    """An assignment int32 [B] for WindEnsemble.assign: the first `own` flights get -1 (the engine's own wind table), the other
+    B - own are spread over the E members so that the counts per member differ by at most one.
+    order="blocked": flight j of those gets member j // ceil((B - own) / E) -- consecutive flights share a table, so a workgroup's
+    lanes read few of them; "cyclic": j % E; "random": the cyclic assignment permuted, deterministic in seed.  numpy only."""
+    if order not in ("blocked", "cyclic", "random"):
+        raise ValueError("order: 'blocked', 'cyclic' or 'random'")
+    B, E, own = int(B), int(E), int(own)
+    if B < 0 or E < 1 or not 0 <= own <= B:
+        raise ValueError("B >= 0, E >= 1 and 0 <= own <= B")
+    n = B - own
+    j = np.arange(n)
+    if order == "blocked":
+        # the first n % E members take ceil(n / E) flights, the others floor(n / E): with n a multiple of E this is j // (n / E)
+        q, r = divmod(n, E)
+        m = np.where(j < r * (q + 1), j // (q + 1), r + (j - r * (q + 1)) // max(q, 1))
+    else:
+        m = j % E
+        if order == "random":
+            m = np.random.default_rng(seed).permutation(m)
+    return np.concatenate([np.full(own, -1), m]).astype(np.int32)
+
+
+def fly(xdict_or_X, pdict, unitdict, steps=4, dispersion=None, engine=None, ensemble=None):
     """The flight of every decision vector: the controls integrated from lift-off to the last node in ONE chain
     (Engine.propagation_plan(restart="chain")), RK4 with 2 * steps steps per node interval.  xdict_or_X: a solution xdict, or
     packed vectors [B, nvars] / [nvars]; dispersion: None or [B, S, 4] (sample_dispersion); engine: an Engine of the same
-    problem (one is created on device 0 from pdict / unitdict otherwise, which may be None when it is given).
+    problem (one is created on device 0 from pdict / unitdict otherwise, which may be None when it is given); ensemble: None, or
+    a WindEnsemble of that engine assigned B vectors (Engine.wind_ensemble, assign_members): every flight under its own wind table.
     -> {"steps": 2 * steps, "status": 0 or GEL_NONFINITE (a non-finite vector does not stop the others),
         "y" [B, 11 M]: the flown state at every state node, laid out like the state part of x,
         "err" [B, S, 4]: the accumulated flight error per section (mass, position, velocity, quaternion), |y - x| / (1 + max |x|);
@@ -117,7 +141,7 @@ def fly(xdict_or_X, pdict, unitdict, steps=4, dispersion=None, engine=None):
     for k in (steps, 2 * steps):
         plan = engine.propagation_plan(steps=k, restart="chain")
         try:
-            Y, err, rc = plan.apply(X, dispersion=dispersion)
+            Y, err, rc = plan.apply(X, dispersion=dispersion, ensemble=ensemble)
         finally:
             plan.close()
         status = max(status, rc)

@@ -720,6 +720,54 @@ int gel_output_table_batch_device(gel_problem* p, int32_t B, const double* d_x, 
                                   const int32_t* cols /* host pointer, or NULL */, double* d_out /* or NULL */,
                                   double* d_env /* or NULL */, double* d_peaks /* or NULL */);
 
+/* ---- a Monte-Carlo batch against an ENSEMBLE of wind profiles: a month of soundings, a synthetic ensemble, the
+ *      members of a forecast, one per flight, where gel_propagate_dispersed* can only scale the handle's single profile.
+ *      Ensemble: tables [E][Kw][3], E >= 1 members of Kw >= 2 rows each, columns (altitude, wind north, wind east) as in
+ *      gel_problem_desc.wind_table; every member has its own altitudes, which must increase strictly (the rule of wind_table; the
+ *      first offending member is named in gel_last_error).  Each member is staged as a handle's own table is: its rows followed by
+ *      its 2 (Kw - 1) slopes (y[k+1] - y[k]) / (x[k+1] - x[k]), 5 Kw - 2 doubles -- bit for bit the wind part of the tables of a
+ *      handle created with that member as wind_table (gel_wind_ensemble_member returns it).  The members live in DEVICE memory, not
+ *      in a workgroup's LDS: the table limits of a handle (gel_table_limits) do not apply; E (5 Kw - 2) <= 2^27 doubles and
+ *      Kw <= 2^20, beyond which creation returns GEL_ERR_ARG.
+ *      Assignment: member [B] (host pointer), one entry per vector of the batch: 0 .. E - 1 selects a member, -1 the handle's own
+ *      wind table.  gel_wind_ensemble_assign validates it on the host (GEL_ERR_ARG names the first offending vector; nothing is
+ *      enqueued), waits for the calls in flight on the source handle and uploads it to a buffer the ensemble owns: the flight and the
+ *      table of a batch read the same assignment, and no kernel forms an address from an unchecked index.
+ *      Flight b under member e: every wind lookup of that vector runs through the handle's own expression with the member's rows,
+ *      slopes and Kw; atmosphere, CA table, the phase's air switch and everything else stay the handle's, and the dispersion factor
+ *      of the wind still multiplies the interpolated components afterwards.  THE CONTRACT, for y, err, out, peaks and env, without a
+ *      tolerance: a vector with member[b] = e gets bit for bit what the call without an ensemble returns for the same x and disp row
+ *      on a handle created from the same problem with wind_table = tables[e]; a vector with member[b] = -1 gets that call's bits on
+ *      this handle; and a vector's result depends neither on B, nor on its place in the batch, nor on the slab size, nor on what its
+ *      neighbours are assigned.  Valid in all three propagation modes, with or without disp.
+ *      Calls: ens == NULL is exactly gel_propagate_dispersed* / gel_output_table_batch*.  With ens, its assignment must hold exactly
+ *      B vectors and it must have been created on the plan's / the call's handle, else GEL_ERR_ARG (decided before the device is
+ *      looked at).  B = 0 is valid.  Create, info, member and assign work on a GEL_DEVICE_NONE handle (assign validates and keeps the
+ *      count); the four evaluation calls refuse such a handle as gel_propagate* does.  The device forms take NO stream argument:
+ *      they enqueue on the handle's own stream and report through gel_sync(p, NULL), like gel_propagate_device and
+ *      gel_output_table_batch_device.  Status as in those calls: a non-finite wind entry of a member makes its own flights
+ *      non-finite and raises GEL_NONFINITE for the flight; the table calls never return it.  An ensemble is destroyed BEFORE its
+ *      source handle. ---- */
+typedef struct gel_wind_ensemble gel_wind_ensemble; /* opaque */
+int gel_wind_ensemble_create(gel_problem* src, int32_t E, int32_t Kw, const double* tables /* [E][Kw][3] */, gel_wind_ensemble** out);
+int gel_wind_ensemble_destroy(gel_wind_ensemble* ens);
+/* info [5]: E, Kw, doubles per member (5 Kw - 2), device bytes the ensemble holds, vectors of the current assignment or -1 */
+int gel_wind_ensemble_info(const gel_wind_ensemble* ens, int64_t* info /* [5] */);
+/* member e as staged: rows [Kw][3] | slopes [Kw - 1][2]; works on GEL_DEVICE_NONE handles */
+int gel_wind_ensemble_member(const gel_wind_ensemble* ens, int32_t e, double* staged /* [5 Kw - 2] */);
+int gel_wind_ensemble_assign(gel_wind_ensemble* ens, int32_t B, const int32_t* member /* host [B] */);
+int gel_propagate_ensemble(gel_prop_plan* plan, int32_t B, const double* x, const double* disp /* or NULL */, gel_wind_ensemble* ens /* or NULL */,
+                           double* y, double* err /* or NULL */);
+int gel_propagate_ensemble_device(gel_prop_plan* plan, int32_t B, const double* d_x, const double* d_disp /* or NULL */,
+                                  gel_wind_ensemble* ens /* or NULL */, double* d_y, double* d_err /* or NULL */);
+int gel_output_table_batch_ensemble(gel_problem* p, int32_t B, const double* x, const double* tx /* or NULL */, const double* disp /* or NULL */,
+                                    gel_wind_ensemble* ens /* or NULL */, double launch_lat_deg, double launch_lon_deg, int32_t ncols,
+                                    const int32_t* cols /* or NULL */, double* out, double* env, double* peaks);
+int gel_output_table_batch_ensemble_device(gel_problem* p, int32_t B, const double* d_x, const double* d_tx /* or NULL */,
+                                           const double* d_disp /* or NULL */, gel_wind_ensemble* ens /* or NULL */, double launch_lat_deg,
+                                           double launch_lon_deg, int32_t ncols, const int32_t* cols /* host pointer, or NULL */,
+                                           double* d_out /* or NULL */, double* d_env /* or NULL */, double* d_peaks /* or NULL */);
+
 /* ---- exact quantiles over the vectors of a batch: what a Monte-Carlo batch is read by -- the 99.865 % value of
  *      every flight's peak, the 0.135 % / 99.865 % band of the terminal row, the 2.5 .. 97.5 % band of every column along the
  *      trajectory, and which flight that is.  src [B][ld]: columns 0 .. W - 1 of every row are read.  Everything below is per column
