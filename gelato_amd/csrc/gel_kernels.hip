@@ -206,7 +206,8 @@ __global__ void point_kernel(int kind, int n, const double* in, const double* au
   // aux table (wind [K][3] or generic [K][2]) and the atmosphere table are staged in LDS
   // kinds 5 / 6: rows followed by the per-interval slopes (built by the host entry point)
   const int naux = (kind == 5 || kind == 10) ? 3 * aux_rows + 2 * (aux_rows - 1)
-                   : (kind == 6 || kind == 9) ? 2 * aux_rows + (aux_rows - 1) : (kind == 0 ? kAtmDoubles : 0);
+                   : (kind == 6 || kind == 9) ? 2 * aux_rows + (aux_rows - 1)
+                   : (kind == 15) ? kAtmDoubles + 3 * aux_rows + 2 * (aux_rows - 1) : (kind == 0 ? kAtmDoubles : 0);
   for (int i = threadIdx.x; i < naux; i += blockDim.x) lds[i] = aux[i];
   __syncthreads();
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -301,6 +302,25 @@ __global__ void point_kernel(int kind, int n, const double* in, const double* au
       for (int c = 0; c < 3; c++) out[7 * i + 4 + c] = d[c];
     } break;
     case 14: out[2 * i] = fexp(in[i]); out[2 * i + 1] = exp(in[i]); break;   // the path's exp beside the library's, for the bit-identity test
+    case 15: {  // a position sweep in exact-difference form as the fused kernel chains it: in = r[3] (m), kk, dlt; the atmosphere table,
+                // the wind rows and their slopes in LDS
+      Tables tb;
+      tb.atm = lds; tb.wind = lds + kAtmDoubles; tb.winds = tb.wind + 3 * aux_rows; tb.ca = nullptr; tb.cas = nullptr;
+      tb.Kw = aux_rows; tb.Kc = 0;
+      const double* a = in + 5 * i;
+      const double r[3] = {a[0], a[1], a[2]};
+      const int kk = min(max((int)a[3], 0), 2);
+      PosCentre pc;
+      PosCentreTail pt;
+      PosPart pp = pos_part<true, PosCentreSink, false>(r, tb, 0.0, nullptr, PosCentreSink{&pc}, &pt);
+      pos_centre_tail(pt, pp.rho, pp.P, tb, pc, pp.wn, pp.we);
+      PosPart pq;
+      const bool ok = pos_delta(r, kk, a[4], pp, pc, tb, pq);
+      double* o = out + 18 * i;
+      o[0] = pp.rho; o[1] = pp.P; o[2] = pp.inv_a; o[3] = pp.wn; o[4] = pp.we; o[5] = pp.shp; o[6] = pp.chp; o[7] = pp.inv_p;
+      o[8] = pq.rho; o[9] = pq.P; o[10] = pq.inv_a; o[11] = pq.wn; o[12] = pq.we; o[13] = pq.shp; o[14] = pq.chp; o[15] = pq.inv_p;
+      o[16] = ok ? 1.0 : 0.0; o[17] = pc.margin;
+    } break;
     default: break;
   }
 }

@@ -566,7 +566,8 @@ GEL_DEV void wind_piece(double h, int piece, const double* tab, const double* sl
 //   rho = P/(R T)                         rho'/rho = (1 + uP)/(1 + uT);   1/a = (1.4 R T)^-1/2: (1 + uT)^-1/2
 // with the series of log1p / expm1 / (1 + u)^-1/2 cut where the next term is below 1e-13 of the change for |dh| <= 1 m
 // (gel_host.hip selects the recomputing form for larger steps).  The result differs from the reference's recomputation
-// by the rounding noise of THAT (1e-16 of the value = 1e-8 .. 1e-4 of the change); tests/test_delta_model.py has the model.
+// by the rounding noise of THAT (1e-16 of the value = 1e-8 .. 1e-4 of the change); tests/delta_model.py has the model (a numpy
+// restatement and a 40-digit truth), tests/test_delta_model.py holds it and the device to the accuracy stated here.
 // ---------------------------------------------------------------------------
 struct AirCentre { double iT, h; int k; };   // what the difference form needs besides Air: 1/T, geopotential altitude, layer
 // geopotential altitude of 86 km geometric, the end of the geopotential branch (src/Air.cpp:47-54), rounded DOWN: a node of layer 6

@@ -142,6 +142,15 @@ GEL_DEV void pos_centre_tail(const PosCentreTail& t, double rho, double P, const
 // with every series cut where the next term is below 1e-13 of the change for |dlt| <= 1 m.  ~130 fp64 operations instead
 // of ~450, and the change is accurate to ~1e-12 of itself, where the recomputation's is accurate to 1e-16 of the VALUE
 // (1e-8 .. 1e-4 of the change: the reference's own finite-difference noise).  Gravity is recomputed by the caller.
+// Two exceptions, both within kilometres of the polar axis (tests/test_delta_model.py measures them on the formulas in plain fp64;
+// stated here at twice the measured figure, tests/delta_model.py rel_at()):
+//   1/p             1e-12 + 1.25 u^2 of its change: (1 + u)^-1/2 - 1 is cut after u^2, and the next term is 5/8 u^2 of the change --
+//                   6.2e-9 at the limit |u| = 1e-4 of the predicate below, under 1e-12 where |u| < 9e-7 (beyond 2200 km from the
+//                   axis at 1 m).  1/p only scales the longitude pair of the wind's rotation: 6e-13 of the VALUE at worst;
+//   altitude        d(p / cos lat) = (dp cos lat - p dcos) / (cos lat cos lat') cancels, so what its terms are off (roundings; at
+//                   1 m the v^3 that 1 / (1 + v) drops) weighs 1 / cos^2 lat: 1e-12 + min(1.54e-8, 108 eps / cos^2 lat) of the
+//                   change -- under 2e-12 below 80 degrees, 1.54e-8 within 8 km of the axis.  Density, pressure and wind follow
+//                   the altitude; their own output rounding (eps of the value) is larger wherever they are not zero.
 // Returns false for a lane whose perturbed point leaves the centre's atmosphere layer / table piece / geopotential branch
 // or sits too close to the polar axis for the series: the caller then recomputes the wavefront's sweep in full.
 // ---------------------------------------------------------------------------

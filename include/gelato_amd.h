@@ -921,6 +921,11 @@ int gel_dynamics_quaternion(int32_t n, const double* quat_eci2body, const double
  *  kind 13: q            -> [conj(q), thrust direction quatrot(conj(q), (1, 0, 0))]  in [n][4]  out [n][7]  (:59-61,
  *           src/pybind_dynamics.cpp:62-63)
  *  kind 14: x            -> [fexp(x), exp(x)]                    in [n][1]   out [n][2]  self-check of the path's exp
+ *  kind 15: (r, kk, dlt)  -> one position sweep in exact-difference form as the fused kernel chains it (csrc/gel_rhs_parts.h:
+ *           pos_part of the centre r [m], pos_centre_tail, pos_delta for component kk = 0, 1, 2 moved by dlt [m]), wind table in
+ *           aux [K][3]: [rho, P, 1/a, wn, we, sin(lat/2), cos(lat/2), 1/p] of the centre, the same eight of the perturbed point,
+ *           pos_delta's return value (1.0: the difference form holds, 0.0: the caller recomputes), the centre's margin [m]
+ *                                                                   in [n][5]   out [n][18]
  */
 int gel_point_eval(int32_t kind, int32_t n, const double* in, const double* aux, int32_t aux_rows, double* out);
 
@@ -932,7 +937,7 @@ int gel_point_eval(int32_t kind, int32_t n, const double* in, const double* aux,
  *  rows), which also covers the launches that keep nothing behind the tables (exact Jacobians, propagation, output table:
  *  T <= 8192); gel_mesh_error[_device] for the estimate, whose workgroup takes as many vectors of a phase as fit beside the
  *  tables and needs room for one (T <= 8170 - 13 n, below the aero limit only from n = 491 on; the handle stays usable for
- *  everything else); gel_dynamics_velocity (T <= 8192) and gel_point_eval kinds 5, 6, 9, 10 (88 + 5 aux_rows <= 8192) for theirs.
+ *  everything else); gel_dynamics_velocity (T <= 8192) and gel_point_eval kinds 5, 6, 9, 10, 15 (88 + 5 aux_rows <= 8192) for theirs.
  *  gel_table_limits (needs no GPU): info[0] = T, info[1] = the T that fits the fused kernel, [2] the aero and callback kernels,
  *  [3] one vector of the collocation error estimate of a phase of n nodes (-1 if n is outside 2 .. 511), [4] the launches with nothing
  *  behind the tables, [5] = the cap in bytes, [6] the vectors a workgroup of the estimate takes of such a phase beside these tables

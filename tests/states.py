@@ -143,16 +143,30 @@ def with_coast_tail(build, n_tail=2):
                                  quat, np.tile(quat[-4:], rep), u, np.zeros(2 * n_tail), t, [t[-1] + 0.01]])
 
 
-def layer_break_state(n_max=None):
+BREAK_STEP_OFFSETS = ((-0.06, 0.6, -1.2, 2.5), (0.06, -0.6, 1.2, -2.5))
+
+
+def layer_break_state(n_max=None, step=None):
     """One aerodynamic phase whose nodes sit within a few centimetres of the breaks of the atmosphere layers (geopotential 11, 20, 32, 47,
     51, 71 km), of the geopotential branch (86 km geometric) and of the wind table's pieces (1, 3, 11, 15, 16, 23 km): the position
     step of a sweep (dx * unit = 6.4 cm) carries some of them across -- what the exact-difference forms hand back to the recomputing
-    sweeps.  Mid latitudes, 400 .. 3000 m/s."""
+    sweeps.  Mid latitudes, 400 .. 3000 m/s.
+
+    step (m; None: the vector above, bit for bit): the nodes scale with the position step of the problem the vector is made for.
+    The breaks gain 91, 110 and 120 km (where the ellipse and the exponential of the temperature begin and end); every break has
+    two nodes below and two above it, at 0.06, 0.6, 1.2 and 2.5 steps in geopotential altitude (geometric at the 86 km branch and
+    above) -- the signs alternate from break to break (BREAK_STEP_OFFSETS), which keeps the 15 breaks within one 64-node phase.
+    A negative step gives the mirrored vector (every offset on the other side of its break): the two together put a node at each
+    of the eight offsets +-0.06 .. +-2.5 steps of every break."""
     prob = _example_prob()
     rng = np.random.default_rng(5)
     r0 = 6356766.0
     breaks_h = [11000.0, 20000.0, 32000.0, 47000.0, 51000.0, 71000.0, 1000.0, 3000.0, 15000.0, 16000.0, 23000.0]
-    alt = [r0 * h / (r0 - h) + off for h in breaks_h for off in (-0.04, -0.004, 0.004, 0.04)] + [86000.0 + off for off in (-0.04, -0.004, 0.004, 0.04)]
+    if step is None:
+        alt = [r0 * h / (r0 - h) + off for h in breaks_h for off in (-0.04, -0.004, 0.004, 0.04)] + [86000.0 + off for off in (-0.04, -0.004, 0.004, 0.04)]
+    else:
+        alt = [r0 * (h + off * step) / (r0 - (h + off * step)) for i, h in enumerate(breaks_h) for off in BREAK_STEP_OFFSETS[i % 2]]
+        alt += [z + off * step for i, z in enumerate([86000.0, 91000.0, 110000.0, 120000.0]) for off in BREAK_STEP_OFFSETS[(i + 1) % 2]]
     alt = np.array(alt + [5000.0])
     if n_max is not None:            # a phase that fits two-vectors-per-wavefront launches: the first n_max + 1 of them
         alt = alt[:n_max + 1]
