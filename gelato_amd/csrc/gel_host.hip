@@ -24,6 +24,7 @@
 #include "gel_conprod.h"
 #include "gel_interp.h"
 #include "gel_prop.h"
+#include "gel_proptan.h"
 #include "gel_outbatch.h"
 #include "gel_quant.h"
 #include "gel_comom.h"
@@ -3334,6 +3335,120 @@ int gel_propagate_dispersed(gel_prop_plan* plan, int32_t B, const double* x, con
 
 int gel_propagate(gel_prop_plan* plan, int32_t B, const double* x, double* y, double* err) {
   return gel_propagate_dispersed(plan, B, x, nullptr, y, err);
+}
+
+// ------------- tangent-linear propagation: exact flight sensitivities -------------
+// The workspace holds one sample set (16 bytes per sampled stage point) per vector of a slab and one per seed: per lane
+// (vector, direction), or per direction when the seeds are shared.  Vectors per slab: as many as the plan's 1 GB cap then holds, a
+// multiple of 64, at least 64; GEL_PROP_SLAB as in prop_slab().
+static int64_t proptan_slab(const gel_prop_plan* pl, int64_t P, bool shared) {
+  const int64_t set = 16 * pl->sampled_pts;
+  const int64_t per_vec = shared ? set : set * (1 + P), fixed = shared ? set * ((P + 63) / 64 * 64) : 0;
+  int64_t vs = per_vec ? std::min<int64_t>(kPropMaxSlab, std::max<int64_t>(0, kPropWsBytes - fixed) / per_vec / 64 * 64) : kPropMaxSlab;
+  vs = std::min<int64_t>(vs, (int64_t)0x7fffffff / P / 64 * 64);   // (a slab's lanes fit an int32)
+  if (vs < 64) vs = 64;
+  if (const char* e = getenv("GEL_PROP_SLAB")) {
+    const long long w = (atoll(e) + 63) / 64 * 64;
+    if (w >= 64 && w <= vs) vs = w;
+  }
+  return vs;
+}
+
+static int proptan_check(const char* who, const gel_prop_plan* plan, int32_t B, int32_t P, int32_t shared, const void* x, const void* dx,
+                         const void* ddisp, const void* y, const void* dy) {
+  const std::string w(who);
+  if (!plan) return fail(GEL_ERR_ARG, w + ": null plan");
+  if (B < 0) return fail(GEL_ERR_ARG, w + ": B < 0");
+  if (P < 1) return fail(GEL_ERR_ARG, w + ": P < 1");
+  if ((int64_t)B * P > 0x7fffffffLL) return fail(GEL_ERR_ARG, w + ": B P exceeds 2^31 - 1 lanes");
+  if (shared != 0 && shared != 1) return fail(GEL_ERR_ARG, w + ": shared is neither 0 nor 1");
+  if (!dx && !ddisp) return fail(GEL_ERR_ARG, w + ": both seeds (dx, ddisp) are NULL");
+  if (B > 0 && (!x || !y || !dy)) return fail(GEL_ERR_ARG, w + ": x, y or dy is NULL with B > 0");
+  if (plan->src->device == GEL_DEVICE_NONE) return fail(GEL_ERR_ARG, w + ": the plan's handle is host-only (GEL_DEVICE_NONE)");
+  const int64_t set = 16 * plan->sampled_pts;
+  if ((shared ? set * (((int64_t)P + 63) / 64 * 64 + 64) : set * 64 * (1 + (int64_t)P)) > kPropWsBytes)
+    return fail(GEL_ERR_ARG, w + ": the control samples of 64 vectors and their seeds exceed the 1 GB workspace");
+  return GEL_OK;
+}
+
+int gel_prop_tangent_info(const gel_prop_plan* plan, int32_t B, int32_t P, int32_t shared, int64_t* info) {
+  if (!plan || !info || B < 0 || P < 1 || (int64_t)B * P > 0x7fffffffLL || (shared != 0 && shared != 1))
+    return fail(GEL_ERR_ARG, "gel_prop_tangent_info: bad argument");
+  const int64_t vs = proptan_slab(plan, P, shared != 0);
+  info[0] = 16 * plan->sampled_pts;
+  info[1] = vs * P;
+  info[2] = (B + vs - 1) / vs;
+  return GEL_OK;
+}
+
+// the launches of one call on stream s, slab after slab: the control samples of the slab's vectors, those of its seeds (the shared
+// seeds' once, before the first slab), the integration
+static int proptan_enqueue(gel_prop_plan* plan, int32_t B, int32_t P, int32_t shared, const double* d_x, const double* d_disp,
+                           const double* d_dx, const double* d_ddisp, double* d_y, double* d_dy, hipStream_t s) {
+  gel_problem* p = plan->src;
+  const int64_t vs = proptan_slab(plan, P, shared != 0), ldv = std::min<int64_t>(vs, ((int64_t)B + 63) / 64 * 64);
+  const int64_t dld = d_dx ? (shared ? ((int64_t)P + 63) / 64 * 64 : ldv * P) : 0;
+  const size_t set = 2 * (size_t)plan->sampled_pts, need = (size_t)(ldv + dld) * set;
+  if (plan->d_ws.capacity() < need) {
+    HIPCHK(drain(p));   // an earlier call in flight still reads the old block
+    HIPCHK(plan->d_ws.reserve(need));
+  }
+  double* const ws = plan->d_ws.get();
+  double* const dws = ws + (size_t)ldv * set;   // the second region: the seeds' samples
+  // prop_sample_kernel alone: launch_prop_slab on a copy of the plan's tables that has no segment to integrate
+  gel::PropDev sample_only = plan->dev;
+  sample_only.chain = 0;
+  sample_only.restart = 0;
+  sample_only.nseg = 0;
+  const size_t nv = (size_t)p->dims.num_vars, ny = (size_t)11 * p->dims.M, nd = (size_t)p->dims.S * GEL_PROP_NDISP;
+  const gel::EnsDev no_ens{};
+  if (d_dx && shared)
+    HIPCHK(gel::launch_prop_slab(p->dev, sample_only, plan->ph.data(), plan->n_max_sampled, P, d_dx, nullptr, dws, dld, nullptr, no_ens, s));
+  for (int64_t v0 = 0; v0 < B; v0 += vs) {
+    const int nb = (int)std::min<int64_t>(vs, B - v0);
+    HIPCHK(gel::launch_prop_slab(p->dev, sample_only, plan->ph.data(), plan->n_max_sampled, nb, d_x + (size_t)v0 * nv, nullptr, ws, ldv,
+                                 nullptr, no_ens, s));
+    const size_t l0 = (size_t)v0 * P;   // the slab's first lane
+    if (d_dx && !shared)
+      HIPCHK(gel::launch_prop_slab(p->dev, sample_only, plan->ph.data(), plan->n_max_sampled, nb * P, d_dx + l0 * nv, nullptr, dws, dld,
+                                   nullptr, no_ens, s));
+    gel::PropTanArgs a{};
+    a.nb = nb; a.P = P; a.shared = shared;
+    a.x = d_x + (size_t)v0 * nv;
+    a.disp = d_disp ? d_disp + (size_t)v0 * nd : nullptr;
+    a.dx = d_dx ? (shared ? d_dx : d_dx + l0 * nv) : nullptr;
+    a.ddisp = d_ddisp ? (shared ? d_ddisp : d_ddisp + l0 * nd) : nullptr;
+    a.y = d_y + (size_t)v0 * ny;
+    a.dy = d_dy + l0 * ny;
+    a.ws = ws; a.dws = dws; a.ld = ldv; a.dld = dld;
+    HIPCHK(gel::launch_proptan_slab(p->dev, plan->dev, a, s));
+  }
+  return GEL_OK;
+}
+
+int gel_propagate_tangent_device(gel_prop_plan* plan, int32_t B, int32_t P, int32_t shared, const double* d_x, const double* d_disp,
+                                 const double* d_dx, const double* d_ddisp, double* d_y, double* d_dy) {
+  if (int rc = proptan_check("gel_propagate_tangent_device", plan, B, P, shared, d_x, d_dx, d_ddisp, d_y, d_dy)) return rc;
+  if (B == 0) return GEL_OK;
+  gel_problem* p = plan->src;
+  HIPCHK(hipSetDevice(p->device));
+  return proptan_enqueue(plan, B, P, shared, d_x, d_disp, d_dx, d_ddisp, d_y, d_dy, p->stream.get());
+}
+
+int gel_propagate_tangent(gel_prop_plan* plan, int32_t B, int32_t P, int32_t shared, const double* x, const double* disp, const double* dx,
+                          const double* ddisp, double* y, double* dy) {
+  if (int rc = proptan_check("gel_propagate_tangent", plan, B, P, shared, x, dx, ddisp, y, dy)) return rc;
+  if (B == 0) return GEL_OK;
+  gel_problem* p = plan->src;
+  HIPCHK(hipSetDevice(p->device));
+  const size_t nv = (size_t)p->dims.num_vars, ny = (size_t)11 * p->dims.M, nd = (size_t)p->dims.S * GEL_PROP_NDISP;
+  const size_t seeds = shared ? (size_t)P : (size_t)B * P;
+  // (x, y, disp as gel_propagate_dispersed lays them out; the new buffers behind them)
+  return staged_call(p, 0, {staged_in(x, (size_t)B * nv), staged_out(y, (size_t)B * ny), staged_in(disp, (size_t)B * nd),
+                            staged_in(dx, seeds * nv), staged_in(ddisp, seeds * nd), staged_out(dy, (size_t)B * P * ny)},
+                     [&](const gel::ProblemDev&, double* const* a) {
+                       return proptan_enqueue(plan, B, P, shared, a[0], a[2], a[3], a[4], a[1], a[5], p->stream.get());
+                     });
 }
 
 // ------------- Jacobian products from the compact values -------------

@@ -1,0 +1,187 @@
+// gel_kernels_proptan.hip -- the tangent-linear propagation (gel_propagate_tangent*): the flight of
+// gel_propagate_dispersed* together with the derivative of that discrete RK4 map along P seed directions per vector.
+//
+//   proptan_kernel<kChain>   one lane = one (vector, direction, segment): lane l of a slab is direction l % P of vector l / P, so
+//                            dy [B][P][11 M] is lane-major.  A workgroup = kPropThreads consecutive lanes of ONE segment: the phase,
+//                            n and k are wave-uniform.  The atmosphere, wind and CA tables are read where the handle keeps
+//                            them, in global memory (the layout the other kernels copy into LDS: the same entries, hence
+//                            the same bits): the rows a lookup compares against are the same addresses in every lane, and the
+//                            kernel has no staging pass whose length depends on the tables' row counts.  Every lane recomputes its
+//                            vector's value trajectory -- direction p's bits do not depend on P, and the extra lanes are the
+//                            wavefronts a chain call lacks -- and direction 0 stores it: y has
+//                            gel_propagate_dispersed*'s bits (the factors are applied as prop_kernel<true, .> applies them; a
+//                            factor of one changes no bit).
+// The control directions are sampled by prop_sample_kernel (gel_kernels_prop.hip), which is linear in the controls, pointed at dx.
+// Loop lengths come from the plan's tables (k n <= 2^20): a launch always ends.  The right-hand side and its tangent are
+// section_rhs_tangent (gel_section_rhs_tan.h).
+//
+// THE STEP'S TANGENT, in this order (value lines: gel_prop.h; F, dF: the previous stage's):
+//   dS   = (dtf - dto) * unit_t / 2.0;  dSh = dS * hs[j];  dSh2 = dSh * 0.5;  dSh6 = dSh / 6.0
+//   dyt  = fma(da, F, fma(a, dF, dy))          a = Sh2, Sh2, Sh and da = dSh2, dSh2, dSh for stages 2, 3, 4; stage 1: dyt = dy
+//   dacc = fma(w, dF, dacc)                    w = 2, 2, 1; stage 1: dacc = dF
+//   dy   = fma(dSh6, acc, fma(Sh6, dacc, dy))  with acc of the value line, before y is updated
+// Knot (chain): djump = dx(first node of s + 1) - dx(last node of s); dy where djump == 0, else dy + djump.
+#include <hip/hip_runtime.h>
+
+#include "gel_tables.h"
+#include "gel_section_rhs_tan.h"
+#include "gel_prop.h"
+#include "gel_proptan.h"
+
+namespace gel {
+
+namespace {
+__device__ __forceinline__ bool nonfinite(double v) { return !(__builtin_fabs(v) <= 1.79769313486231570815e308); }
+__device__ __forceinline__ size_t state_index(int M, int xi, int c) {
+  return (c == 0) ? (size_t)xi : (c < 4) ? (size_t)M + 3 * (size_t)xi + (c - 1) : (c < 7) ? 4 * (size_t)M + 3 * (size_t)xi + (c - 4)
+                                                                                      : 7 * (size_t)M + 4 * (size_t)xi + (c - 7);
+}
+}  // namespace
+
+template <bool kChain>
+__global__ __launch_bounds__(kPropThreads) void proptan_kernel(ProblemDev P, PropDev Pd, PropTanArgs A) {
+  const long long nl = (long long)A.nb * A.P;
+  const long long ngrp = (nl + kPropThreads - 1) / kPropThreads;
+  const int seg = kChain ? 0 : (int)(blockIdx.x / ngrp);
+  const long long grp = blockIdx.x - seg * ngrp;
+  const Tables tb = table_view(P.tables, P.Kw, P.Kc);   // the handle's tables where they lie (global memory): no LDS copy
+  const long long l = grp * kPropThreads + (long long)threadIdx.x;
+  if (seg >= Pd.nseg || l >= nl) return;   // (idle lanes leave: they stay out of the calm-air vote of wind_eci_or_calm; no barrier follows)
+  const int v = (int)(l / A.P), p = (int)(l - (long long)v * A.P);
+  const size_t ls = A.shared ? (size_t)p : (size_t)l;   // the lane's seed set
+  bool bad = false;
+  double yv[11], dyv[11];
+  const int M = P.M, N = P.N;
+  const double* const xb = A.x + (size_t)v * P.nvars;
+  const double* const dxb = A.dx ? A.dx + ls * P.nvars : nullptr;
+  double* const yb = A.y + (size_t)v * 11 * (size_t)M;
+  double* const dyb = A.dy + (size_t)l * 11 * (size_t)M;
+  int s = kChain ? 0 : load_const(&Pd.seg_phase[seg]);
+  do {
+    PhaseDev ph = load_phase(P.phases + s);
+    const int n = load_const(&Pd.ph[s].n), k = load_const(&Pd.ph[s].k), sampled = load_const(&Pd.ph[s].sampled);
+    const int j0 = (!kChain && Pd.restart) ? seg - load_const(&Pd.ph[s].seg0) : 0, j1 = (!kChain && Pd.restart) ? j0 + 1 : n;
+    const double* const sig = Pd.mat + load_const(&Pd.ph[s].sg);
+    const double* const hs = Pd.mat + load_const(&Pd.ph[s].hs);
+    const size_t pt0 = (size_t)load_const(&Pd.ph[s].pt0);
+    const double* const us = A.ws + pt0 * 2 * (size_t)A.ld + v;
+    const double* const dus = A.dws + pt0 * 2 * (size_t)A.dld + ls;
+    const double to = xb[11 * M + 2 * N + s], tf = xb[11 * M + 2 * N + s + 1];
+    const double S = (tf - to) * P.ut / 2.0;
+    double dS = 0.0;
+    if (dxb) dS = (dxb[11 * M + 2 * N + s + 1] - dxb[11 * M + 2 * N + s]) * P.ut / 2.0;
+    double fw = 1.0;
+    RhsDirection d;
+    d.du0 = d.du1 = d.dthrust = d.dmf = d.darea = d.dfw = 0.0;
+    if (A.ddisp) {   // (before the factors scale the record: the tangents of thrust f0, mf_um f1 and area f2 along df)
+      const double* const df = A.ddisp + (ls * Pd.S + s) * kPropNDisp;
+      d.dthrust = ph.thrust * df[0];
+      d.dmf = ph.mf_um * df[1];
+      d.darea = ph.area * df[2];
+      d.dfw = df[3];
+    }
+    if (A.disp) {
+      const double* const fac = A.disp + ((size_t)v * Pd.S + s) * kPropNDisp;
+      const double f_thrust = fac[0], f_mf = fac[1], f_area = fac[2];
+      fw = fac[3];
+      ph.thrust = ph.thrust * f_thrust;
+      ph.mf_um = ph.mf_um * f_mf;
+      ph.area = ph.area * f_area;
+    }
+
+    if (kChain && s > 0) {
+#pragma unroll
+      for (int c = 0; c < 11; c++) {
+        const size_t i1 = state_index(M, ph.xa, c), i0 = state_index(M, ph.xa - 1, c);
+        const double jump = xb[i1] - xb[i0];
+        yv[c] = (jump == 0.0) ? yv[c] : yv[c] + jump;
+        const double djump = dxb ? dxb[i1] - dxb[i0] : 0.0;
+        dyv[c] = (djump == 0.0) ? dyv[c] : dyv[c] + djump;
+      }
+    } else {
+#pragma unroll
+      for (int c = 0; c < 11; c++) {
+        const size_t i = state_index(M, ph.xa + j0, c);
+        yv[c] = xb[i];
+        dyv[c] = dxb ? dxb[i] : 0.0;
+      }
+    }
+    if (j0 == 0) {
+#pragma unroll
+      for (int c = 0; c < 11; c++) {
+        const size_t i = state_index(M, ph.xa, c);
+        if (p == 0) yb[i] = yv[c];
+        dyb[i] = dyv[c];
+        bad |= nonfinite(yv[c]);
+        bad |= nonfinite(dyv[c]);
+      }
+    }
+    for (int j = j0; j < j1; j++) {
+      const double Sh = S * hs[j], Sh2 = Sh * 0.5, Sh6 = Sh / 6.0;
+      const double dSh = dS * hs[j], dSh2 = dSh * 0.5, dSh6 = dSh / 6.0;
+      for (int i = 0; i < k; i++) {
+        const int pb = 2 * (k * j + i);
+        double acc[11], F[11], dacc[11], dF[11];
+#pragma unroll
+        for (int c = 0; c < 11; c++) acc[c] = F[c] = dacc[c] = dF[c] = 0.0;
+#pragma nounroll
+        for (int st = 0; st < 4; st++) {
+          const int pp = pb + ((st + 1) >> 1);                 // stage points p, p + 1, p + 1, p + 2
+          const double a = (st == 3) ? Sh : Sh2, da = (st == 3) ? dSh : dSh2;
+          const double w = (st == 3) ? 1.0 : 2.0;
+          double yt[11], dyt[11];
+#pragma unroll
+          for (int c = 0; c < 11; c++) {
+            yt[c] = st ? __builtin_fma(a, F[c], yv[c]) : yv[c];
+            dyt[c] = st ? __builtin_fma(da, F[c], __builtin_fma(a, dF[c], dyv[c])) : dyv[c];
+          }
+          double u0 = 0.0, u1 = 0.0;
+          d.du0 = d.du1 = 0.0;
+          if (sampled) {
+            u0 = us[(size_t)pp * 2 * (size_t)A.ld];
+            u1 = us[((size_t)pp * 2 + 1) * (size_t)A.ld];
+            if (dxb) {
+              d.du0 = dus[(size_t)pp * 2 * (size_t)A.dld];
+              d.du1 = dus[((size_t)pp * 2 + 1) * (size_t)A.dld];
+            }
+          }
+          section_rhs_tangent(P, ph, tb, Pd.vp, sig[pp], to, tf, yt, u0, u1, fw, dyt, d, F, dF);
+#pragma unroll
+          for (int c = 0; c < 11; c++) {
+            acc[c] = st ? __builtin_fma(w, F[c], acc[c]) : F[c];
+            dacc[c] = st ? __builtin_fma(w, dF[c], dacc[c]) : dF[c];
+          }
+        }
+#pragma unroll
+        for (int c = 0; c < 11; c++) {
+          dyv[c] = __builtin_fma(dSh6, acc[c], __builtin_fma(Sh6, dacc[c], dyv[c]));
+          yv[c] = __builtin_fma(Sh6, acc[c], yv[c]);
+        }
+      }
+#pragma unroll
+      for (int c = 0; c < 11; c++) {
+        const size_t i = state_index(M, ph.xa + j + 1, c);
+        if (p == 0) yb[i] = yv[c];
+        dyb[i] = dyv[c];
+        bad |= nonfinite(yv[c]);
+        bad |= nonfinite(dyv[c]);
+      }
+    }
+  } while (kChain && ++s < Pd.S);
+  if (bad) *(volatile int32_t*)P.flag = 1;
+}
+
+hipError_t launch_proptan_slab(const ProblemDev& P, const PropDev& Pd, const PropTanArgs& A, hipStream_t s) {
+  if (A.nb <= 0 || A.P <= 0) return hipSuccess;
+  const long long nl = (long long)A.nb * A.P;
+  if (A.ld < A.nb || (A.dx && A.dld < (A.shared ? (long long)A.P : nl))) return hipErrorInvalidValue;
+  const long long ngrp = (nl + kPropThreads - 1) / kPropThreads;
+  const long long grid = Pd.chain ? ngrp : ngrp * Pd.nseg;
+  if (grid <= 0) return hipSuccess;
+  if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
+  auto* const kern = Pd.chain ? proptan_kernel<true> : proptan_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kPropThreads), 0, s, P, Pd, A);
+  return hipGetLastError();
+}
+
+}  // namespace gel

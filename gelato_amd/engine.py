@@ -212,6 +212,69 @@ class PropagationPlan:
                                                   d_err or None))
 
 
+    def _seed(self, a, name, B, P, shared, tail):
+        """a seed array as the library takes it: [P, *tail] when shared, else [B, P, *tail]; None stays None"""
+        if a is None:
+            return None
+        a = np.asarray(a)
+        if a.dtype != np.float64:
+            raise TypeError("%s: float64" % name)
+        want = ((P,) if shared else (B, P)) + tail
+        if a.shape != want:
+            raise ValueError("%s: %s, not %s" % (name, want, a.shape))
+        return np.ascontiguousarray(a)
+
+    def tangent(self, X, dX=None, dispersion=None, ddispersion=None, shared=False):
+        """The flight of apply() and its exact derivative along seed directions (gel_propagate_tangent).
+        X [B, nvars] (or [nvars]); dX: None, or the directions in x, [B, P, nvars] ([P, nvars] with shared=True: one set for every
+        vector); dispersion: None or [B, S, 4]; ddispersion: None, or the directions in the factors, [B, P, S, 4] ([P, S, 4] shared).
+        At least one of dX / ddispersion.  -> (Y [B, 11 M]: apply()'s Y bit for bit, dY [B, P, 11 M], status)"""
+        self._live()
+        X = _f64(X).reshape(-1, self.nvars)
+        B = X.shape[0]
+        if dX is None and ddispersion is None:
+            raise ValueError("tangent: at least one of dX and ddispersion")
+        shared = bool(shared)
+        lead = np.asarray(dX if dX is not None else ddispersion)
+        if lead.ndim < (2 if shared else 3):
+            raise ValueError("tangent: seeds are [P, ...] with shared=True, else [B, P, ...]")
+        P = int(lead.shape[0] if shared else lead.shape[1])
+        if P < 1:
+            raise ValueError("tangent: at least one direction")
+        nd = _lib.GEL_PROP_NDISP
+        dx = self._seed(dX, "dX", B, P, shared, (self.nvars,))
+        dd = self._seed(ddispersion, "ddispersion", B, P, shared, (self.S, nd))
+        disp = None
+        if dispersion is not None:
+            disp = np.asarray(dispersion)
+            if disp.dtype != np.float64:
+                raise TypeError("dispersion: float64")
+            if disp.shape == (self.S, nd) and B == 1:
+                disp = disp[None]
+            if disp.shape != (B, self.S, nd):
+                raise ValueError("dispersion: [B, S, %d] = %s, not %s" % (nd, (B, self.S, nd), disp.shape))
+            disp = np.ascontiguousarray(disp)
+        Y = np.empty((B, 11 * self.M))
+        dY = np.empty((B, P, 11 * self.M))
+        opt = lambda a: _d(a) if a is not None else None   # noqa: E731
+        rc = check(lib().gel_propagate_tangent(self._p, B, P, int(shared), _d(X), opt(disp), opt(dx), opt(dd), _d(Y), _d(dY)))
+        return Y, dY, rc
+
+    def tangent_device(self, B, P, d_x, d_y, d_dy, d_dx=0, d_dispersion=0, d_ddispersion=0, shared=False):
+        """device buffers: d_y [B][11 M], d_dy [B][P][11 M], d_dx / d_ddispersion as tangent() lays them out or 0 (not both),
+        d_dispersion [B][S][4] or 0; asynchronous on the engine's own stream; status through Engine.sync()"""
+        self._live()
+        check(lib().gel_propagate_tangent_device(self._p, int(B), int(P), int(bool(shared)), d_x, d_dispersion or None, d_dx or None,
+                                                 d_ddispersion or None, d_y, d_dy))
+
+    def tangent_info(self, B, P, shared=False):
+        """{"sample_set_bytes", "lanes_per_slab", "slabs"} of a tangent call NOW (works on host-only handles)"""
+        self._live()
+        info = (C.c_int64 * 3)()
+        check(lib().gel_prop_tangent_info(self._p, int(B), int(P), int(bool(shared)), info))
+        return dict(zip(("sample_set_bytes", "lanes_per_slab", "slabs"), (int(v) for v in info)))
+
+
 def _ensemble_ptr(ensemble, owner):
     """the raw pointer of a live WindEnsemble (None for None); an ensemble of another engine is refused here, by name"""
     if ensemble is None:

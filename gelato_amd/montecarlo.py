@@ -374,3 +374,19 @@ def wind_availability(xdict_or_x, pdict, unitdict, wind_tables, limits, replicas
     out = availability_from_peaks(peaks, members, limits, E)
     out.update({"steps": 2 * steps, "status": int(status), "members": members, "peaks": peaks, "dispersion": disp})
     return out
+
+
+def linear_covariance(J, sigma):
+    """J diag(sigma^2) J^T: the covariance of outputs whose Jacobian with respect to independent inputs of standard deviations sigma
+    is J -- the linear-covariance counterpart of flight_covariance, fed by propagate.flight_jacobian where that one needs a dispersed
+    batch.  J [..., R, P], sigma [P] (or one number) -> [..., R, R], symmetric bit for bit.  Host numpy."""
+    J = np.asarray(J, dtype=np.float64)
+    if J.ndim < 2:
+        raise ValueError("J: [..., R, P]")
+    sg = np.asarray(sigma, dtype=np.float64)
+    if sg.shape not in ((), (J.shape[-1],)) or not np.all(sg >= 0):
+        raise ValueError("sigma: one non-negative number, or one per column of J (%d)" % J.shape[-1])
+    A = J * sg                      # (J sigma)(J sigma)^T: every entry and its mirror are the same sum of the same products
+    C = np.einsum("...ip,...jp->...ij", A, A)
+    lo = np.tril(np.ones(C.shape[-2:], dtype=bool))
+    return np.where(lo, C, np.swapaxes(C, -1, -2))

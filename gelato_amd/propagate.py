@@ -173,3 +173,95 @@ def fly(xdict_or_X, pdict, unitdict, steps=4, dispersion=None, engine=None, ense
         out["rows"] = con
         out["status"] = max(out["status"], int(rc))
     return out
+
+
+JACOBIAN_GROUPS = ("initial", "dispersion", "times", "controls_bias")
+_STATE_NAMES = ("mass", "x", "y", "z", "vx", "vy", "vz", "q0", "q1", "q2", "q3")
+_FACTOR_NAMES = ("thrust", "massflow", "area", "wind")
+
+
+def jacobian_seeds(num_nodes, attitude_hold, wrt=("initial", "dispersion", "times")):
+    """The shared unit seeds of flight_jacobian for phases of num_nodes nodes -> (columns [P] names, dX [P, nvars], dD [P, S, 4]).
+    "initial": the 11 lift-off components (state row 0); "dispersion": the 4 S factors, phase-major; "times": the S + 1 knot
+    times; "controls_bias": per free-attitude phase and control one constant direction (all its nodes 1).  numpy only."""
+    nn = [int(v) for v in num_nodes]
+    S, N = len(nn), sum(nn)
+    M = N + S
+    nvars = 11 * M + 2 * N + S + 1
+    wrt = tuple(wrt)
+    if not wrt or any(g not in JACOBIAN_GROUPS for g in wrt) or len(set(wrt)) != len(wrt):
+        raise ValueError("wrt: distinct groups of %r" % (JACOBIAN_GROUPS,))
+    cols, rows = [], []          # rows: (index array into dx or None, (phase, factor) or None)
+    for g in wrt:
+        if g == "initial":
+            off = (0, M, M + 1, M + 2, 4 * M, 4 * M + 1, 4 * M + 2, 7 * M, 7 * M + 1, 7 * M + 2, 7 * M + 3)
+            for c in range(11):
+                cols.append("initial:%s" % _STATE_NAMES[c]); rows.append((np.array([off[c]]), None))
+        elif g == "dispersion":
+            for s in range(S):
+                for f in range(4):
+                    cols.append("dispersion:%s[%d]" % (_FACTOR_NAMES[f], s)); rows.append((None, (s, f)))
+        elif g == "times":
+            for i in range(S + 1):
+                cols.append("time[%d]" % i); rows.append((np.array([11 * M + 2 * N + i]), None))
+        else:
+            for s in range(S):
+                if attitude_hold[s]:
+                    continue
+                ua = sum(nn[:s])
+                for c in range(2):
+                    cols.append("u%d_bias[%d]" % (c, s)); rows.append((11 * M + 2 * (ua + np.arange(nn[s])) + c, None))
+    P = len(cols)
+    dX, dD = np.zeros((P, nvars)), np.zeros((P, S, 4))
+    for p, (ix, sf) in enumerate(rows):
+        if ix is not None:
+            dX[p, ix] = 1.0
+        else:
+            dD[p, sf[0], sf[1]] = 1.0
+    return cols, dX, dD
+
+
+def flight_jacobian(xdict_or_X, pdict, unitdict, steps=4, wrt=("initial", "dispersion", "times"), dispersion=None, engine=None):
+    """The exact Jacobian of the flight fly() reports (one chain, RK4 with 2 * steps steps per node interval) with respect to the
+    lift-off state, the 4 S dispersion factors, the S + 1 knot times and optionally a constant bias of every free phase's controls
+    (wrt; jacobian_seeds): the tangent-linear propagation (PropagationPlan.tangent) along shared unit seeds --
+    derivatives of the discrete map, without sampling noise, where montecarlo.dispersion_sensitivity regresses over a batch.
+    -> {"columns": names [P], "status", "y" [B, 11 M], "dy" [B, P, 11 M], "x_flown" [B, nvars],
+        "terminal": {group: [B, 1 | 3 | 3 | 4, P]}: the last state node's derivative in physical units (kg, m, m/s, 1),
+        "rows" [B, R, P]: the engine's row table's derivative, Engine.con_matvec applied to [dy | du | dt] at x_flown -- only
+                          where a row table is configured}"""
+    steps = int(steps)
+    if steps < 1:
+        raise ValueError("steps: at least 1")
+    if engine is None:
+        S = pdict["num_sections"]
+        ps = pdict["ps_params"]
+        engine = Engine(con_dynamics.problem_arrays(pdict, unitdict), D=[ps.D(i) for i in range(S)],
+                        tau=[ps.tau(i) for i in range(S)])
+    X = pack_x(xdict_or_X) if isinstance(xdict_or_X, dict) else np.asarray(xdict_or_X, dtype=np.float64)
+    X = np.ascontiguousarray(X).reshape(-1, engine.nvars)
+    B, M = X.shape[0], engine.M
+    cols, dX, dD = jacobian_seeds(engine.num_nodes, engine.prob["attitude_hold"], wrt)
+    P = len(cols)
+    plan = engine.propagation_plan(steps=2 * steps, restart="chain")
+    try:
+        Y, dY, rc = plan.tangent(X, dX=dX if dX.any() else None, dispersion=dispersion, ddispersion=dD if dD.any() else None, shared=True)
+    finally:
+        plan.close()
+    x_flown = X.copy()
+    x_flown[:, :11 * M] = Y
+    u = engine.units
+    scale = (u[0], u[1], u[2], 1.0)
+    last = M - 1
+    idx = ([last], [M + 3 * last + c for c in range(3)], [4 * M + 3 * last + c for c in range(3)], [7 * M + 4 * last + c for c in range(4)])
+    out = {"columns": cols, "status": int(rc), "y": Y, "dy": dY, "x_flown": x_flown,
+           "terminal": {k: np.swapaxes(dY[:, :, ix], 1, 2) * sc for k, ix, sc in zip(GROUPS, idx, scale)}}
+    if engine._nlin + engine._nfn:
+        _con, jfn, rc2 = engine.rows_eval(x_flown, want_jac=True)
+        V = np.broadcast_to(dX[None], (B, P, engine.nvars)).copy()    # [dy | du | dt]: the seeds' own control and time parts
+        V[:, :, :11 * M] = dY
+        jf = np.ascontiguousarray(np.broadcast_to(jfn[:, None], (B, P) + jfn.shape[1:]))
+        r, rc3 = engine.con_matvec(V, jfn=jf)
+        out["rows"] = np.swapaxes(r, 1, 2)
+        out["status"] = max(out["status"], int(rc2), int(rc3))
+    return out

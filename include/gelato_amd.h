@@ -634,6 +634,41 @@ int gel_propagate_dispersed(gel_prop_plan* plan, int32_t B, const double* x, con
 int gel_propagate_dispersed_device(gel_prop_plan* plan, int32_t B, const double* d_x, const double* d_disp /* or NULL */, double* d_y,
                                    double* d_err /* or NULL */);
 
+/* ---- tangent-linear propagation: exact flight sensitivities.  gel_propagate_tangent* returns the y of
+ *      gel_propagate_dispersed* on the same plan, x and disp -- bit for bit -- and dy [B][P][11 M]: for every vector b and direction
+ *      p the derivative of that discrete RK4 map (the step above, as it is coded) along a seed (dx, ddisp).  All three plan modes.
+ *      Seeds: dx is laid out like a decision vector [nvars]; only what the value call reads from x is read from dx: the state row
+ *      a segment starts from (chain: phase 0's X_0; section mode: every section's first node; node mode: every node), in chain
+ *      mode both state rows of every knot (djump = dx(first node of s + 1) - dx(last node of s)), the controls of the
+ *      free-attitude phases and the knot times.  ddisp [S][GEL_PROP_NDISP] is the direction in the four factors (disp == NULL:
+ *      the factors are one).  Either seed may be NULL (zero), not both.  shared = 0: per (vector, direction), dx [B][P][nvars] and
+ *      ddisp [B][P][S][4]; shared = 1: one set [P][...] serves every vector (its control directions are sampled once).
+ *      Tangent of a step, term by term in this order (F, dF: the previous stage's):  dS = (dtf - dto) unit_t / 2, dSh = dS h_j;
+ *        dyt = fma(da, F, fma(a, dF, dy)) for the stages with a = Sh/2, Sh/2, Sh and da = dSh/2, dSh/2, dSh (stage 1: dyt = dy);
+ *        dF = J dyt + dF/du dU + dF/dfactors df, dU the control direction sampled like U (Wu du, a node copied), the factors
+ *        as the value applies them (thrust df0, mf_um df1, area df2, d(wn fw) = wn dfw + fw dwn);
+ *        dacc = fma(w, dF, dacc), w = 2, 2, 1 (stage 1: dacc = dF);  dy <- fma(dSh / 6, acc, fma(Sh / 6, dacc, dy)).
+ *      J and the partials are the hand-written fp64 tangents of GEL_FLAG_EXACT_DEFECT_JAC with their conventions at kinks (the
+ *      derivative of the branch the value took); the explicit time dependence of F (the Earth angle, read on the polar axis only)
+ *      has tangent zero, as in that flag's t columns.  Knot (chain): dy where djump == 0, else dy + djump.  Quaternions are not
+ *      renormalised; a hold phase has zero quaternion rows, an engine-off phase a zero mass row.  The tangent is linear in the
+ *      seed with no additive constant: a zero seed gives dy == 0, a seed times 2^k gives dy times 2^k bit for bit.  Direction p's
+ *      bits depend neither on P, nor on B, nor on the slab size.  There is no err output.
+ *      Status: a non-finite y or dy raises the source handle's status as gel_propagate* does; the other (vector, direction)
+ *      slices stay valid.  Refusals (GEL_ERR_ARG): P < 1; B P > 2^31 - 1; both seeds NULL; shared not 0 or 1; a host-only handle;
+ *      seeds whose control samples for 64 vectors do not fit the plan's 1 GB workspace.  B = 0 succeeds and touches nothing.
+ *      The workspace holds 1 + P sample sets per vector (shared: 1 per vector and P in all); a larger batch is walked in slabs,
+ *      GEL_PROP_SLAB (vectors) as above.  The device form takes no stream argument: it enqueues on the handle's own stream and
+ *      reports through gel_sync(src, NULL), like gel_propagate_device. ---- */
+int gel_propagate_tangent(gel_prop_plan* plan, int32_t B, int32_t P, int32_t shared, const double* x, const double* disp /* or NULL */,
+                          const double* dx /* or NULL */, const double* ddisp /* or NULL */, double* y, double* dy);
+int gel_propagate_tangent_device(gel_prop_plan* plan, int32_t B, int32_t P, int32_t shared, const double* d_x,
+                                 const double* d_disp /* or NULL */, const double* d_dx /* or NULL */, const double* d_ddisp /* or NULL */,
+                                 double* d_y, double* d_dy);
+/* info [3]: bytes of one sample set (per vector of a slab, and per seed: per lane, or per direction when shared), lanes
+ * (vector, direction) per slab a call will use NOW, slabs of a call of B vectors; works on GEL_DEVICE_NONE handles */
+int gel_prop_tangent_info(const gel_prop_plan* plan, int32_t B, int32_t P, int32_t shared, int64_t* info /* [3] */);
+
 /* ---- one optimiser callback = one device round trip: the four defect groups, the knot / terminal / user row table and the
  *      aero path constraints of ONE decision vector launched back to back on the handle's stream, one synchronise
  *      (what objfunc / sens of Trajectory_Optimization.py:194-312 need from the device).  Every output pointer may be
