@@ -1,5 +1,5 @@
 """LGR nodes and differentiation matrix (replaces lib/PSfunctions.py:149-168,182-208 of the
-reference).  Computed by the C++ generator in csrc/gel_host.hip (Newton on P_{n-1}+P_n in extended precision +
+reference).  Computed by the C++ generator in csrc/gel_host_lgr.hip (Newton on P_{n-1}+P_n in extended precision +
 barycentric weights) for the flipped Radau set (reverse=True, the one on GELATO's hot path); the unflipped set is its
 mirror image: tau = -tau_flipped reversed, and with t = -s the Lagrange derivatives obey D[k, i] = -D_flipped[n-1-k, n-i]."""
 import ctypes as C

@@ -214,7 +214,7 @@ def build(force=False):
     src_dir = os.path.join(_HERE, "csrc")
     if force and os.path.exists(SO_PATH):
         os.remove(SO_PATH)
-    subprocess.check_call(["make", "-s", "-j8", "-C", src_dir])   # fifteen translation units (kernels, the AERO instantiation, the three exact Jacobians, the mesh error estimate, the two Jacobian products, the interpolation, the propagation and its tangent, the batched output table, the batch quantiles, the batch co-moments, host side)
+    subprocess.check_call(["make", "-s", "-j8", "-C", src_dir])   # fourteen translation units with kernels (the fused kernels, the AERO instantiation, the three exact Jacobians, the mesh error estimate, the two Jacobian products, the interpolation, the propagation and its tangent, the batched output table, the batch quantiles, the batch co-moments) and the host side, gel_host*.hip
     if not os.path.exists(SO_PATH):
         raise RuntimeError("building %s failed" % SO_PATH)
     _write_build_info()

@@ -1,5 +1,6 @@
-// gel_host.hip -- host side of the engine: LGR generator, fixed sparsity pattern,
-// device-resident problem, and the C-ABI of include/gelato_amd.h.
+// gel_host.hip -- host side of the engine: fixed sparsity pattern, device-resident problem, and the C-ABI of
+// include/gelato_amd.h.  The extended-precision generators (LGR nodes, D, the mesh estimate's matrices) are gel_host_lgr.hip;
+// what the host files share is gel_host_internal.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -28,14 +29,22 @@
 #include "gel_outbatch.h"
 #include "gel_quant.h"
 #include "gel_comom.h"
+#include "gel_host_internal.h"
 
+// the calling thread's message: g_err, fail() and gel_last_error stay together in this file (no thread_local crosses a translation unit)
+namespace gelhost {
 namespace {
-
 thread_local std::string g_err;
+}
 int fail(int code, const std::string& msg) {
   g_err = msg;
   return code;
 }
+}  // namespace gelhost
+using namespace gelhost;
+
+namespace {
+
 #define HIPCHK(expr)                                                                         \
   do {                                                                                       \
     hipError_t _e = (expr);                                                                  \
@@ -100,170 +109,6 @@ class Stream {
   hipStream_t s_ = nullptr;
 };
 
-// ---------------------------------------------------------------------------
-// LGR nodes / differentiation matrix.
-// What: lib/PSfunctions.py:149-168 (flipped LGR nodes, ending at +1) and :182-208
-// (D[k][i] = l_i'(tau_x[k+1]) on tau_x = [-1, tau]).  How: the flipped LGR points
-// are the negated roots of P_{n-1}(x) + P_n(x) (Legendre), found by Newton in
-// extended precision from the classic -cos(2 pi k/(2n-1)) guesses; D comes from
-// barycentric weights in O(n^2) instead of the reference's O(n^4) products.
-// ---------------------------------------------------------------------------
-typedef long double ld;
-
-void legendre_pair(int n, ld x, ld& Pn, ld& Pn1) {  // P_n, P_{n-1}
-  ld p0 = 1.0L, p1 = x;
-  if (n == 0) { Pn = 1.0L; Pn1 = 0.0L; return; }
-  for (int k = 2; k <= n; k++) {
-    const ld p2 = ((2 * k - 1) * x * p1 - (k - 1) * p0) / k;
-    p0 = p1; p1 = p2;
-  }
-  Pn = p1; Pn1 = p0;
-}
-
-int lgr_nodes_ld(int n, std::vector<ld>& tau) {
-  if (n < 2) return -1;
-  std::vector<ld> xs(n);
-  xs[0] = -1.0L;  // the Radau end point of the un-flipped set
-  const ld pi = 3.141592653589793238462643383279502884L;
-  for (int k = 1; k < n; k++) {
-    ld x = -cosl(2.0L * pi * k / (2 * n - 1));
-    for (int it = 0; it < 100; it++) {
-      ld Pn, Pn1;
-      legendre_pair(n, x, Pn, Pn1);  // P_n, P_{n-1}
-      ld Pm, Pm1;
-      legendre_pair(n - 1, x, Pm, Pm1);  // P_{n-1}, P_{n-2}
-      const ld f = Pn1 + Pn;
-      // P_k'(x) = k (x P_k - P_{k-1}) / (x^2 - 1)
-      const ld dPn = n * (x * Pn - Pn1) / (x * x - 1.0L);
-      const ld dPn1 = (n - 1) * (x * Pm - Pm1) / (x * x - 1.0L);
-      // deflate the known root at -1: g = f/(1+x)
-      const ld gval = f / (1.0L + x);
-      const ld dg = (dPn + dPn1) / (1.0L + x) - f / ((1.0L + x) * (1.0L + x));
-      const ld step = gval / dg;
-      x -= step;
-      if (fabsl(step) < 1e-19L) break;
-    }
-    xs[k] = x;
-  }
-  tau.resize(n);
-  for (int k = 0; k < n; k++) tau[k] = -xs[k];
-  std::sort(tau.begin(), tau.end());
-  tau[n - 1] = 1.0L;
-  return 0;
-}
-
-int lgr_diffmat_ld(int n, std::vector<double>& D, std::vector<double>& tau_out) {
-  std::vector<ld> tau;
-  if (lgr_nodes_ld(n, tau)) return -1;
-  std::vector<ld> t(n + 1), w(n + 1);
-  t[0] = -1.0L;
-  for (int k = 0; k < n; k++) t[k + 1] = tau[k];
-  for (int i = 0; i <= n; i++) {
-    ld p = 1.0L;
-    for (int m = 0; m <= n; m++)
-      if (m != i) p *= (t[i] - t[m]);
-    w[i] = 1.0L / p;
-  }
-  D.assign((size_t)n * (n + 1), 0.0);
-  for (int k = 0; k < n; k++) {
-    ld diag = 0.0L;
-    for (int i = 0; i <= n; i++) {
-      if (i == k + 1) continue;
-      const ld v = (w[i] / w[k + 1]) / (t[k + 1] - t[i]);
-      D[(size_t)k * (n + 1) + i] = (double)v;
-      diag -= v;
-    }
-    D[(size_t)k * (n + 1) + k + 1] = (double)diag;
-  }
-  tau_out.resize(n);
-  for (int k = 0; k < n; k++) tau_out[k] = (double)tau[k];
-  return 0;
-}
-
-// ---------------------------------------------------------------------------
-// Collocation error estimate (gel_mesh_*): per phase of n nodes, on the fine grid sigma = the flipped LGR points
-// of n + 1 (sigma_0 = -1), the Lagrange bases of the phase's support tau_x = [-1, tau] (Lx) and of its collocation points tau
-// (Lu) at sigma_1 .. sigma_{n+1}, and the fine grid's Radau integration matrix I = (D^[:, 1:])^-1, D^ = lgr_diffmat(n + 1):
-// barycentric weights and Gauss-Jordan elimination in extended precision, rounded once.
-// ---------------------------------------------------------------------------
-std::vector<ld> bary_weights(const std::vector<ld>& t) {
-  std::vector<ld> w(t.size());
-  for (size_t i = 0; i < t.size(); i++) {
-    ld p = 1.0L;
-    for (size_t m = 0; m < t.size(); m++)
-      if (m != i) p *= (t[i] - t[m]);
-    w[i] = 1.0L / p;
-  }
-  return w;
-}
-// the Lagrange basis of support t (weights w) at z, second barycentric form; exactly 1 / 0 at a support point
-void lagrange_row(const std::vector<ld>& t, const std::vector<ld>& w, ld z, ld* out) {
-  for (size_t i = 0; i < t.size(); i++)
-    if (z == t[i]) {
-      for (size_t k = 0; k < t.size(); k++) out[k] = (k == i) ? 1.0L : 0.0L;
-      return;
-    }
-  ld sum = 0.0L;
-  for (size_t i = 0; i < t.size(); i++) { out[i] = w[i] / (z - t[i]); sum += out[i]; }
-  for (size_t i = 0; i < t.size(); i++) out[i] /= sum;
-}
-// sigma [P], Lx [P][n+1], Lu [P][n], I [P][P] (row-major, P = n + 1) of a phase whose collocation points are tau [n]
-int mesh_matrices_ld(const std::vector<double>& tau, std::vector<double>& out) {
-  const int n = (int)tau.size(), P = n + 1;
-  std::vector<ld> sg;
-  if (lgr_nodes_ld(P, sg)) return -1;
-  std::vector<ld> tx(P), tc(n);
-  tx[0] = -1.0L;
-  for (int k = 0; k < n; k++) tx[k + 1] = tc[k] = (ld)tau[k];
-  const std::vector<ld> wx = bary_weights(tx), wc = bary_weights(tc);
-  // D^ on the fine support s = [-1, sigma]: D^[k][i] = l_i'(s[k+1]); A = its columns 1 .. P, inverted in place
-  std::vector<ld> sup(P + 1);
-  sup[0] = -1.0L;
-  for (int k = 0; k < P; k++) sup[k + 1] = sg[k];
-  const std::vector<ld> ws = bary_weights(sup);
-  std::vector<ld> A((size_t)P * P), Inv((size_t)P * P, 0.0L);
-  for (int k = 0; k < P; k++) {
-    ld diag = 0.0L;
-    for (int i = 0; i <= P; i++) {
-      if (i == k + 1) continue;
-      const ld v = (ws[i] / ws[k + 1]) / (sup[k + 1] - sup[i]);
-      if (i > 0) A[(size_t)k * P + i - 1] = v;
-      diag -= v;
-    }
-    A[(size_t)k * P + k] = diag;
-    Inv[(size_t)k * P + k] = 1.0L;
-  }
-  for (int c = 0; c < P; c++) {   // Gauss-Jordan, partial pivoting
-    int piv = c;
-    for (int r = c + 1; r < P; r++)
-      if (fabsl(A[(size_t)r * P + c]) > fabsl(A[(size_t)piv * P + c])) piv = r;
-    if (!(fabsl(A[(size_t)piv * P + c]) > 0.0L)) return -1;
-    if (piv != c)
-      for (int k = 0; k < P; k++) { std::swap(A[(size_t)c * P + k], A[(size_t)piv * P + k]); std::swap(Inv[(size_t)c * P + k], Inv[(size_t)piv * P + k]); }
-    const ld ip = 1.0L / A[(size_t)c * P + c];
-    for (int k = 0; k < P; k++) { A[(size_t)c * P + k] *= ip; Inv[(size_t)c * P + k] *= ip; }
-    for (int r = 0; r < P; r++) {
-      if (r == c) continue;
-      const ld f = A[(size_t)r * P + c];
-      if (f == 0.0L) continue;
-      for (int k = 0; k < P; k++) { A[(size_t)r * P + k] -= f * A[(size_t)c * P + k]; Inv[(size_t)r * P + k] -= f * Inv[(size_t)c * P + k]; }
-    }
-  }
-  out.clear();
-  out.reserve((size_t)P * (1 + P + n + P));
-  for (int l = 0; l < P; l++) out.push_back((double)sg[l]);
-  std::vector<ld> row(P);
-  for (int l = 0; l < P; l++) {
-    lagrange_row(tx, wx, sg[l], row.data());
-    for (int i = 0; i < P; i++) out.push_back((double)row[i]);
-  }
-  for (int l = 0; l < P; l++) {
-    lagrange_row(tc, wc, sg[l], row.data());
-    for (int j = 0; j < n; j++) out.push_back((double)row[j]);
-  }
-  for (size_t k = 0; k < (size_t)P * P; k++) out.push_back((double)Inv[k]);
-  return 0;
-}
 // doubles of one phase's block in the host table: sigma | Lx | Lu | I
 inline size_t mesh_block_doubles(int n) { return (size_t)(n + 1) * (1 + (n + 1) + n + (n + 1)); }
 
@@ -372,47 +217,55 @@ struct gel_problem {
   DeviceArray<char> d_comws;
   // gel_jac_fd working set: kept between calls; the residuals of all num_vars + 1 perturbed vectors are
   // re-used while x stays the same (the four groups are asked for one after the other)
-  DeviceArray<double> jfd_x, jfd_Xp, jfd_res, jfd_J;
-  // every phase as its own one-phase problem (gel_jac_fd differences phase by phase)
-  DeviceArray<gel::PhaseDev> d_subphases;                     // [S] the phase records with ua = xa = 0
-  DeviceArray<int4> d_subchunks;                              // the phase-ordered work items with phase index 0
-  DeviceArray<int32_t> d_colmap;                              // per phase: local column -> global column
-  std::vector<int32_t> sub_chunk0, sub_nchunks, sub_col0;     // [S] first work item, work items, first colmap entry
-  std::vector<size_t> sub_res0;                               // [S] first double of the phase's residuals in jfd_res
-  std::vector<double> jfd_last_x;                             // empty = nothing cached
-  DeviceArray<int32_t> d_done;                                // self-signalling one-vector launches (ProblemDev::done_flag): device counter,
-  PinnedArray<volatile int32_t> h_done;                       // pinned host word, sequence number of the last armed launch
-  int32_t done_seq = 0;
-  long long done_ema_us = 100;                                // running estimate of a self-signalling launch's wait (sets the spin budget)
-  int jfd_status = GEL_OK;
+  struct JacFd {
+    DeviceArray<double> x, Xp, res, J;
+    // every phase as its own one-phase problem (gel_jac_fd differences phase by phase)
+    DeviceArray<gel::PhaseDev> d_subphases;                     // [S] the phase records with ua = xa = 0
+    DeviceArray<int4> d_subchunks;                              // the phase-ordered work items with phase index 0
+    DeviceArray<int32_t> d_colmap;                              // per phase: local column -> global column
+    std::vector<int32_t> sub_chunk0, sub_nchunks, sub_col0;     // [S] first work item, work items, first colmap entry
+    std::vector<size_t> sub_res0;                               // [S] first double of the phase's residuals in res
+    std::vector<double> last_x;                                 // empty = nothing cached
+    int status = GEL_OK;
+  } jfd;
+  struct Done {
+    DeviceArray<int32_t> d_ctr;                                 // self-signalling one-vector launches (ProblemDev::done_flag): device counter,
+    PinnedArray<volatile int32_t> h_word;                       // pinned host word, sequence number of the last armed launch
+    int32_t seq = 0;
+    long long ema_us = 100;                                     // running estimate of a self-signalling launch's wait (sets the spin budget)
+  } done;
   // knot / terminal / user rows (gel_rows_configure)
   std::vector<gel::LinRowDev> lin_rows;
   std::vector<gel::FnRowDev> fn_rows;
   DeviceArray<gel::LinRowDev> d_lin_rows;
   DeviceArray<gel::FnRowDev> d_fn_rows;
-  // collocation error estimate (gel_mesh_*): per phase the host block sigma | Lx | Lu | I (row-major) at mesh_hoff[i], the device
+  // collocation error estimate (gel_mesh_*): per phase the host block sigma | Lx | Lu | I (row-major) at hoff[i], the device
   // copy transposed (gel_mesh.h); none when a phase has more nodes than mesh_kernel's workgroup has lanes
-  std::vector<double> mesh_host;
-  std::vector<size_t> mesh_hoff;
-  std::vector<gel::MeshPhaseDev> mesh_ph;
-  int32_t mesh_npts = 0;
-  size_t mesh_lds_max = 0;     // LDS of the widest phase's workgroup (gel::mesh_lds_bytes), host-only handles included
-  gel::MeshDev mesh_dev{};
-  DeviceArray<double> d_mesh_mat;
-  DeviceArray<gel::MeshPhaseDev> d_mesh_ph;
+  struct Mesh {
+    std::vector<double> host;
+    std::vector<size_t> hoff;
+    std::vector<gel::MeshPhaseDev> ph;
+    int32_t npts = 0;
+    size_t lds_max = 0;     // LDS of the widest phase's workgroup (gel::mesh_lds_bytes), host-only handles included
+    gel::MeshDev dev{};
+    DeviceArray<double> d_mat;
+    DeviceArray<gel::MeshPhaseDev> d_ph;
+  } mesh;
   // Jacobian products from the compact values (gel_jac_*): the operator tables of gel_jprod.h, built from the
   // pattern walk (host-only handles included; the host product reads the same arrays), and their device copies
-  std::vector<int32_t> jp_it;
-  std::vector<double> jp_dt;
-  std::vector<gel::JprodPhaseDev> jp_ph;
-  int64_t jp_info[4] = {0, 0, 0, 0};                          // non-zero constant entries, variable entries, longest row, longest column
-  int jp_threads = 512;                                       // lanes per workgroup (GEL_JPROD_THREADS = 256 when the handle is created: measurement switch)
-  int32_t jp_nin_max[2] = {0, 0};                             // largest local input count of a phase: J v, J^T lambda
-  gel::JprodDev jp_dev{};
-  DeviceArray<int32_t> d_jp_it;
-  DeviceArray<double> d_jp_dt;
-  DeviceArray<gel::JprodPhaseDev> d_jp_ph;
-  DeviceArray<double> d_jp_tpart;                             // [B][S][2] partial sums of the time columns of J^T lambda
+  struct Jprod {
+    std::vector<int32_t> it;
+    std::vector<double> dt;
+    std::vector<gel::JprodPhaseDev> ph;
+    int64_t info[4] = {0, 0, 0, 0};                           // non-zero constant entries, variable entries, longest row, longest column
+    int threads = 512;                                        // lanes per workgroup (GEL_JPROD_THREADS = 256 when the handle is created: measurement switch)
+    int32_t nin_max[2] = {0, 0};                              // largest local input count of a phase: J v, J^T lambda
+    gel::JprodDev dev{};
+    DeviceArray<int32_t> d_it;
+    DeviceArray<double> d_dt;
+    DeviceArray<gel::JprodPhaseDev> d_ph;
+    DeviceArray<double> d_tpart;                              // [B][S][2] partial sums of the time columns of J^T lambda
+  } jp;
   // Products with K, the Jacobian of every row that is not a defect row (gel_con_*): the operator tables of
   // gel_conprod.h in both directions (0: by row, K v; 1: by column, K^T lambda), rebuilt as a whole by gel_rows_configure and
   // gel_aero_configure and swapped in with the tables they come from (host-only handles included; the host product reads the
@@ -670,15 +523,15 @@ const char* build_jprod_tables(gel_problem& P) {
     rlen[(size_t)gr]++; clen[(size_t)gc]++;
   });
   if (err) return err;
-  P.jp_info[0] = nconst; P.jp_info[1] = nvarent;
-  P.jp_info[2] = *std::max_element(rlen.begin(), rlen.end());
-  P.jp_info[3] = *std::max_element(clen.begin(), clen.end());
+  P.jp.info[0] = nconst; P.jp.info[1] = nvarent;
+  P.jp.info[2] = *std::max_element(rlen.begin(), rlen.end());
+  P.jp.info[3] = *std::max_element(clen.begin(), clen.end());
 
-  std::vector<int32_t>& it = P.jp_it;
-  std::vector<double>& dt = P.jp_dt;
+  std::vector<int32_t>& it = P.jp.it;
+  std::vector<double>& dt = P.jp.dt;
   it.clear(); dt.clear();
-  P.jp_ph.assign((size_t)S, gel::JprodPhaseDev{});
-  P.jp_nin_max[0] = P.jp_nin_max[1] = 0;
+  P.jp.ph.assign((size_t)S, gel::JprodPhaseDev{});
+  P.jp.nin_max[0] = P.jp.nin_max[1] = 0;
   auto emit = [&](const std::vector<std::vector<Ent>>& rows, const std::vector<int32_t>& omap, const std::vector<int32_t>& imap,
                   size_t nin, gel::JprodOpDev& op) {
     const size_t nout = rows.size();
@@ -724,7 +577,7 @@ const char* build_jprod_tables(gel_problem& P) {
     }
   };
   for (int i = 0; i < S; i++) {
-    gel::JprodPhaseDev& q = P.jp_ph[i];
+    gel::JprodPhaseDev& q = P.jp.ph[i];
     q.voff = P.ph[i].voff;
     emit(fw[i], rowmap[i], colmap[i], colmap[i].size(), q.fw);
     emit(bw[i], colmap[i], rowmap[i], rowmap[i].size(), q.bw);
@@ -736,10 +589,10 @@ const char* build_jprod_tables(gel_problem& P) {
       d.tslot = (int64_t)it.size(); for (const Ent& e : t) it.push_back(e.slot);
       d.tval = (int64_t)dt.size(); for (const Ent& e : t) dt.push_back(e.slot < 0 ? e.cv : 0.0);
     }
-    P.jp_nin_max[0] = std::max(P.jp_nin_max[0], q.fw.nin);
-    P.jp_nin_max[1] = std::max(P.jp_nin_max[1], q.bw.nin);
+    P.jp.nin_max[0] = std::max(P.jp.nin_max[0], q.fw.nin);
+    P.jp.nin_max[1] = std::max(P.jp.nin_max[1], q.bw.nin);
   }
-  gel::JprodDev& jd = P.jp_dev;
+  gel::JprodDev& jd = P.jp.dev;
   jd.S = S; jd.V = (int32_t)P.dims.num_var_entries; jd.nvars = nvars; jd.nres = 11 * N; jd.tcol0 = tcol0; jd.pad = 0;
   jd.ph = nullptr; jd.it = nullptr; jd.dt = nullptr;
   return nullptr;
@@ -747,8 +600,8 @@ const char* build_jprod_tables(gel_problem& P) {
 
 // One operator of one phase on the host, from the same tables and in the same order as a lane of jprod_kernel
 void jprod_host_op(const gel_problem& P, const gel::JprodOpDev& op, int64_t voff, const double* jv, const double* in, double* out) {
-  const int32_t* it = P.jp_it.data();
-  const double* dt = P.jp_dt.data();
+  const int32_t* it = P.jp.it.data();
+  const double* dt = P.jp.dt.data();
   const size_t nout = (size_t)op.nout;
   for (size_t o = 0; o < nout; o++) {
     double acc = 0.0;
@@ -964,10 +817,10 @@ static bool done_flag_on() {
   return on;
 }
 static void arm_done(gel_problem* p, gel::ProblemDev& dv) {
-  if (!p->d_done.get() || !p->h_done.get() || !done_flag_on()) return;
-  dv.done_ctr = p->d_done.get();
-  dv.done_flag = const_cast<int32_t*>(p->h_done.get());
-  dv.done_seq = ++p->done_seq;
+  if (!p->done.d_ctr.get() || !p->done.h_word.get() || !done_flag_on()) return;
+  dv.done_ctr = p->done.d_ctr.get();
+  dv.done_flag = const_cast<int32_t*>(p->done.h_word.get());
+  dv.done_seq = ++p->done.seq;
 }
 static hipError_t spin_wait(hipStream_t s);
 static inline void cpu_relax() {
@@ -985,18 +838,18 @@ static hipError_t wait_done(gel_problem* p, const gel::ProblemDev& dv) {
     // processes taking turns on the GPU, or a preempted queue, a fixed 5 ms burnt a core per call before the runtime's wait was
     // taken anyway.  A launch that never signals (it should not happen) falls back to that wait as well.
     const auto t0 = std::chrono::steady_clock::now();
-    const auto budget = std::chrono::microseconds(std::min<long long>(5000, std::max<long long>(200, 8 * p->done_ema_us)));
+    const auto budget = std::chrono::microseconds(std::min<long long>(5000, std::max<long long>(200, 8 * p->done.ema_us)));
     for (unsigned it = 1;; it++) {
-      if (*p->h_done.get() == dv.done_seq) {
+      if (*p->done.h_word.get() == dv.done_seq) {
         std::atomic_thread_fence(std::memory_order_acquire);
         const long long us = std::chrono::duration_cast<std::chrono::microseconds>(std::chrono::steady_clock::now() - t0).count();
-        p->done_ema_us = (3 * p->done_ema_us + us + 3) / 4;
+        p->done.ema_us = (3 * p->done.ema_us + us + 3) / 4;
         return hipSuccess;
       }
       cpu_relax();
       if ((it & 1023u) == 0 && std::chrono::steady_clock::now() - t0 > budget) break;
     }
-    p->done_ema_us = std::min<long long>(5000, 2 * p->done_ema_us + 50);   // the wait outlasted the budget: a longer one next time
+    p->done.ema_us = std::min<long long>(5000, 2 * p->done.ema_us + 50);   // the wait outlasted the budget: a longer one next time
   }
   return spin_wait(p->stream.get());
 }
@@ -1265,27 +1118,10 @@ std::vector<double> build_tables(const double* wind, int Kw, const double* ca, i
 }
 }  // namespace gel
 
-extern "C" {
+namespace {
 
-const char* gel_last_error(void) { return g_err.c_str(); }
-const char* gel_version(void) { return "gelato_amd 0.1 (gfx950, fp64)"; }
-
-int gel_lgr_nodes(int32_t n, double* tau) {
-  std::vector<ld> t;
-  if (!tau || lgr_nodes_ld(n, t)) return fail(GEL_ERR_ARG, "gel_lgr_nodes: n >= 2 required");
-  for (int k = 0; k < n; k++) tau[k] = (double)t[k];
-  return GEL_OK;
-}
-
-int gel_lgr_diffmat(int32_t n, double* D) {
-  std::vector<double> d, t;
-  if (!D || lgr_diffmat_ld(n, d, t)) return fail(GEL_ERR_ARG, "gel_lgr_diffmat: n >= 2 required");
-  std::memcpy(D, d.data(), d.size() * 8);
-  return GEL_OK;
-}
-
-int gel_problem_create(const gel_problem_desc* d, gel_problem** out) {
-  if (!d || !out) return fail(GEL_ERR_ARG, "null argument");
+// ---- the steps of gel_problem_create, in the order it takes them; each returns a gel_* status ----
+int create_validate(const gel_problem_desc* d) {
   if (d->num_sections < 1 || !d->num_nodes || !d->thrust || !d->massflow || !d->reference_area || !d->nozzle_area ||
       !d->engine_on || !d->attitude_hold || !d->wind_table || !d->ca_table || d->wind_rows < 2 || d->ca_rows < 2)
     return fail(GEL_ERR_ARG, "incomplete problem description");
@@ -1313,8 +1149,11 @@ int gel_problem_create(const gel_problem_desc* d, gel_problem** out) {
       return fail(GEL_ERR_HIP, "no HIP device: the engine has no CPU fallback");
     if (d->device < 0 || d->device >= ndev) return fail(GEL_ERR_ARG, "device ordinal out of range");
   }
+  return GEL_OK;
+}
 
-  std::unique_ptr<gel_problem> p(new gel_problem());   // released to the caller on success only
+// flags, units, the phases' layout and the dims
+int create_layout(gel_problem* p, const gel_problem_desc* d) {
   p->device = d->device;
   p->um = d->unit_mass; p->up = d->unit_position; p->uv = d->unit_velocity; p->uu = d->unit_u; p->ut = d->unit_t;
   p->dx = d->dx;
@@ -1385,7 +1224,13 @@ int gel_problem_create(const gel_problem_desc* d, gel_problem** out) {
     dm.algorithmic_bytes = 8 * ((int64_t)dm.num_vars + 11 * (int64_t)N + Vref);
     dm.stored_bytes = 8 * (11 * (int64_t)N + V);
   }
+  return GEL_OK;
+}
 
+// the gather map (constants, sources, first use of every compact slot) and its constant-stride runs
+int create_gather_map(gel_problem* p, const gel_problem_desc*) {
+  const int S = p->dims.S;
+  const int64_t V = p->dims.num_var_entries, tot = p->dims.total_nnz;
   // pattern-derived host arrays
   p->cval.assign((size_t)tot, 0.0);
   p->src.assign((size_t)tot, -1);
@@ -1423,7 +1268,12 @@ int gel_problem_create(const gel_problem_desc* d, gel_problem** out) {
       i = j;
     }
   }
+  return GEL_OK;
+}
 
+int create_coo_direct(gel_problem* p, const gel_problem_desc*) {
+  const int S = p->dims.S;
+  const int64_t tot = p->dims.total_nnz;
   if (!p->fd_recompute) {
     // COO-direct groups: where the runs of the all-x-dependent blocks start in the full value vector (the emission order of
     // walk_pattern() = the reference's), checked against the gather map itself -- any surprise switches the mode off
@@ -1469,7 +1319,11 @@ int gel_problem_create(const gel_problem_desc* d, gel_problem** out) {
       }
     }
   }
+  return GEL_OK;
+}
 
+int create_mesh_host(gel_problem* p, const gel_problem_desc* d) {
+  const int S = p->dims.S;
   {
     // collocation error estimate: every phase's block, built aside and committed once all are there (a phase that repeats an
     // earlier one's n and tau repeats its block)
@@ -1487,24 +1341,28 @@ int gel_problem_create(const gel_problem_desc* d, gel_problem** out) {
       else if (mesh_matrices_ld(h.tau, blk)) return fail(GEL_ERR_ARG, "collocation error tables: singular integration matrix");
       mh.insert(mh.end(), blk.begin(), blk.end());
     }
-    p->mesh_host = std::move(mh);
-    p->mesh_hoff = std::move(hoff);
-    p->mesh_npts = npts;
-    for (int i = 0; fits && i < S; i++) p->mesh_lds_max = std::max(p->mesh_lds_max, gel::mesh_lds_bytes(d->wind_rows, d->ca_rows, p->ph[i].n));
+    p->mesh.host = std::move(mh);
+    p->mesh.hoff = std::move(hoff);
+    p->mesh.npts = npts;
+    for (int i = 0; fits && i < S; i++) p->mesh.lds_max = std::max(p->mesh.lds_max, gel::mesh_lds_bytes(d->wind_rows, d->ca_rows, p->ph[i].n));
   }
+  return GEL_OK;
+}
+
+// the Jacobian products' tables and the work partition
+int create_products_host(gel_problem* p, const gel_problem_desc* d) {
+  const int S = p->dims.S;
   p->dev.Kw = d->wind_rows; p->dev.Kc = d->ca_rows;
   if (const char* e = build_jprod_tables(*p)) return fail(GEL_ERR_ARG, e);
-  if (const char* e = getenv("GEL_JPROD_THREADS")) { if (atoi(e) == 256) p->jp_threads = 256; }   // host-only handles report it too
+  if (const char* e = getenv("GEL_JPROD_THREADS")) { if (atoi(e) == 256) p->jp.threads = 256; }   // host-only handles report it too
   for (int i = 0; i < S; i++)
     for (int j0 = 0; j0 < p->ph[i].n; j0 += 64) p->chunk_phase.push_back(i);
-  if (p->device == GEL_DEVICE_NONE) {
-    p->dev.nchunks = (int32_t)p->chunk_phase.size();
-    *out = p.release();
-    return GEL_OK;
-  }
+  return GEL_OK;
+}
 
-  // device side
-  if (hipSetDevice(p->device) != hipSuccess) return fail(GEL_ERR_HIP, "hipSetDevice failed");
+// the device's phase records, the work items and D in the matrix pipe's feed orders, built on the host and uploaded
+int create_device_tables(gel_problem* p, const gel_problem_desc* d) {
+  const int S = p->dims.S, N = p->dims.N;
   std::vector<gel::PhaseDev> dph(S);
   std::vector<int32_t> node_phase(N);
   std::vector<double> Dt, tau;
@@ -1585,27 +1443,36 @@ int gel_problem_create(const gel_problem_desc* d, gel_problem** out) {
     int c0 = 0;
     for (int i = 0; i < S; i++) {
       sub[i].ua = 0; sub[i].xa = 0; sub[i].voff = 0;
-      p->sub_chunk0.push_back(c0);
+      p->jfd.sub_chunk0.push_back(c0);
       int cnt = 0;
       while (c0 + cnt < (int)chunks.size() && chunks[c0 + cnt].x == i) { subchunks[c0 + cnt].x = 0; cnt++; }
-      p->sub_nchunks.push_back(cnt);
+      p->jfd.sub_nchunks.push_back(cnt);
       c0 += cnt;
-      p->sub_col0.push_back((int32_t)colmap.size());
-      phase_columns(p.get(), i, colmap);
+      p->jfd.sub_col0.push_back((int32_t)colmap.size());
+      phase_columns(p, i, colmap);
     }
-    HIPCHK(p->d_subphases.upload(sub)); HIPCHK(p->d_subchunks.upload(subchunks)); HIPCHK(p->d_colmap.upload(colmap));
+    HIPCHK(p->jfd.d_subphases.upload(sub)); HIPCHK(p->jfd.d_subchunks.upload(subchunks)); HIPCHK(p->jfd.d_colmap.upload(colmap));
   }
   if (p->d_flag.reserve(1) != hipSuccess || hipMemset(p->d_flag.get(), 0, 4) != hipSuccess ||
-      p->d_done.reserve(1) != hipSuccess || hipMemset(p->d_done.get(), 0, 4) != hipSuccess || p->h_done.reserve(1) != hipSuccess ||
+      p->done.d_ctr.reserve(1) != hipSuccess || hipMemset(p->done.d_ctr.get(), 0, 4) != hipSuccess || p->done.h_word.reserve(1) != hipSuccess ||
       p->h_flag.reserve(1) != hipSuccess || p->stream.create() != hipSuccess)
     return fail(GEL_ERR_HIP, "device allocation failed");
   *p->h_flag.get() = 0;
+  return GEL_OK;
+}
+
+int create_problem_dev(gel_problem* p, const gel_problem_desc* d) {
+  const int S = p->dims.S, N = p->dims.N, M = p->dims.M;
+  const int64_t V = p->dims.num_var_entries;
+  const gel_dims& dm = p->dims;
   gel::ProblemDev& dv = p->dev;
   dv.S = S; dv.N = N; dv.M = M; dv.nvars = dm.num_vars; dv.Kw = d->wind_rows; dv.Kc = d->ca_rows; dv.V = V;
   dv.phases = p->d_phases.get(); dv.node_phase = p->d_node_phase.get(); dv.Dt = p->d_Dt.get(); dv.tau = p->d_tau.get();
   dv.tables = p->d_tables.get(); dv.flag = p->d_flag.get();
-  dv.nchunks = (int32_t)chunks.size(); dv.chunks = p->d_chunks_sorted.get(); dv.Dsw = p->d_Dsw.get(); dv.Dst = p->d_Dst.get();
+  dv.nchunks = (int32_t)p->chunk_phase.size(); dv.chunks = p->d_chunks_sorted.get(); dv.Dsw = p->d_Dsw.get(); dv.Dst = p->d_Dst.get();
   dv.park_off = (int32_t)gel::padded_table_doubles(d->wind_rows, d->ca_rows);
+  int nmax = 0;
+  for (int i = 0; i < S; i++) nmax = std::max(nmax, p->ph[i].n);
   {
     // D.X path.  fp64 MFMA and fp64 VALU instructions share the SIMD's fp64 datapath on this part (measured: their busy
     // times add up), so the matrix pipe is not free throughput; what it buys is fewer issue slots and the
@@ -1616,29 +1483,28 @@ int gel_problem_create(const gel_problem_desc* d, gel_problem** out) {
     // 161 M vs 91 M, 6x64 31.3 M vs 21.4 M.  Between 33 and 63 nodes per phase the matrix pipe wins as well (one vector per
     // wavefront).  Only a mesh that mixes phases above 32 nodes with many tiny ones would prefer the dot-products; none
     // of the reference's configurations does.  GEL_FLAG_DX_VALU / _MFMA force a path.
-    int nmax = 0;
-    for (int i = 0; i < S; i++) nmax = std::max(nmax, p->ph[i].n);
     dv.use_mfma = (d->flags & GEL_FLAG_DX_VALU) ? 0 : 1;
     dv.pack = (nmax <= 32) && !(d->flags & GEL_FLAG_NO_PACK);
     dv.longp = (nmax >= gel::kLongPhaseFrom) ? 1 : 0;
   }
   dv.fd_recompute = p->fd_recompute ? 1 : 0;
-  {
-    int nmax = 0;
-    for (int i = 0; i < S; i++) nmax = std::max(nmax, p->ph[i].n);
-    // measured (same box): 3 x 32 +4 % (fused and residual-only), 6 x 64 -1..2 %: only the small-phase meshes, whose rows share most lines
-    dv.vmajor = (nmax <= 32 && !(d->flags & GEL_FLAG_ITEM_MAJOR)) ? 1 : 0;
-  }
+  // measured (same box): 3 x 32 +4 % (fused and residual-only), 6 x 64 -1..2 %: only the small-phase meshes, whose rows share most lines
+  dv.vmajor = (nmax <= 32 && !(d->flags & GEL_FLAG_ITEM_MAJOR)) ? 1 : 0;
   dv.um = p->um; dv.up = p->up; dv.uv = p->uv; dv.uu = p->uu; dv.ut = p->ut; dv.dx = p->dx; dv.barC20 = p->barC20;
   dv.inv_uv = 1.0 / p->uv; dv.inv_dx = 1.0 / p->dx; dv.kpt = p->uv * p->ut / 2.0 / p->up; dv.hT = p->ut * 0.5;
-  if (!p->mesh_hoff.empty()) {
+  return GEL_OK;
+}
+
+int create_mesh_device(gel_problem* p, const gel_problem_desc* d) {
+  const int S = p->dims.S;
+  if (!p->mesh.hoff.empty()) {
     // the estimate's device tables: each phase's matrices transposed (point index fastest), LDS per workgroup of vpb vectors
     std::vector<double> mat;
     std::vector<gel::MeshPhaseDev> mph(S);
     int32_t pt0 = 0;
     for (int i = 0; i < S; i++) {
       const int n = p->ph[i].n, P = n + 1;
-      const double* hb = p->mesh_host.data() + p->mesh_hoff[i];
+      const double* hb = p->mesh.host.data() + p->mesh.hoff[i];
       const double *sg = hb, *Lx = sg + P, *Lu = Lx + (size_t)P * P, *I = Lu + (size_t)P * n;
       gel::MeshPhaseDev& q = mph[i];
       q.n = n; q.pt0 = pt0; q.pad = 0;
@@ -1655,13 +1521,49 @@ int gel_problem_create(const gel_problem_desc* d, gel_problem** out) {
       for (int l = 0; l < P; l++) mat.push_back(sg[l]);
       q.lds = (int64_t)gel::mesh_lds_bytes(d->wind_rows, d->ca_rows, n);
     }
-    HIPCHK(p->d_mesh_mat.upload(mat)); HIPCHK(p->d_mesh_ph.upload(mph));
-    p->mesh_ph = std::move(mph);
-    gel::MeshDev& md = p->mesh_dev;
-    md.S = S; md.npts = p->mesh_npts; md.ph = p->d_mesh_ph.get(); md.mat = p->d_mesh_mat.get(); md.vp = p->uv / p->up;
+    HIPCHK(p->mesh.d_mat.upload(mat)); HIPCHK(p->mesh.d_ph.upload(mph));
+    p->mesh.ph = std::move(mph);
+    gel::MeshDev& md = p->mesh.dev;
+    md.S = S; md.npts = p->mesh.npts; md.ph = p->mesh.d_ph.get(); md.mat = p->mesh.d_mat.get(); md.vp = p->uv / p->up;
   }
-  HIPCHK(p->d_jp_it.upload(p->jp_it)); HIPCHK(p->d_jp_dt.upload(p->jp_dt)); HIPCHK(p->d_jp_ph.upload(p->jp_ph));
-  p->jp_dev.ph = p->d_jp_ph.get(); p->jp_dev.it = p->d_jp_it.get(); p->jp_dev.dt = p->d_jp_dt.get();
+  return GEL_OK;
+}
+
+int create_products_device(gel_problem* p, const gel_problem_desc*) {
+  HIPCHK(p->jp.d_it.upload(p->jp.it)); HIPCHK(p->jp.d_dt.upload(p->jp.dt)); HIPCHK(p->jp.d_ph.upload(p->jp.ph));
+  p->jp.dev.ph = p->jp.d_ph.get(); p->jp.dev.it = p->jp.d_it.get(); p->jp.dev.dt = p->jp.d_dt.get();
+  return GEL_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* gel_last_error(void) { return g_err.c_str(); }
+const char* gel_version(void) { return "gelato_amd 0.1 (gfx950, fp64)"; }
+
+int gel_problem_create(const gel_problem_desc* d, gel_problem** out) {
+  if (!d || !out) return fail(GEL_ERR_ARG, "null argument");
+  if (int rc = create_validate(d)) return rc;
+  std::unique_ptr<gel_problem> p(new gel_problem());   // released to the caller on success only
+  gel_problem* const h = p.get();
+  if (int rc = create_layout(h, d)) return rc;
+  if (int rc = create_gather_map(h, d)) return rc;
+  if (int rc = create_coo_direct(h, d)) return rc;
+  if (int rc = create_mesh_host(h, d)) return rc;
+  if (int rc = create_products_host(h, d)) return rc;
+  if (p->device == GEL_DEVICE_NONE) {
+    p->dev.nchunks = (int32_t)p->chunk_phase.size();
+    *out = p.release();
+    return GEL_OK;
+  }
+
+  // device side
+  if (hipSetDevice(p->device) != hipSuccess) return fail(GEL_ERR_HIP, "hipSetDevice failed");
+  if (int rc = create_device_tables(h, d)) return rc;
+  if (int rc = create_problem_dev(h, d)) return rc;
+  if (int rc = create_mesh_device(h, d)) return rc;
+  if (int rc = create_products_device(h, d)) return rc;
   *out = p.release();
   return GEL_OK;
 }
@@ -2026,20 +1928,20 @@ int gel_sync(gel_problem* p, void* stream) {
 // working set: x, the perturbed local vectors of the LARGEST phase (reused phase after phase), the residuals of every phase's
 // perturbed vectors (kept while x stays the same: the four groups are asked for one after the other)
 static int jfd_allocate(gel_problem* p) {
-  if (p->jfd_x.get()) return GEL_OK;
+  if (p->jfd.x.get()) return GEL_OK;
   const size_t nv = (size_t)p->dims.num_vars;
   size_t xp_max = 0, res_tot = 0;
-  p->sub_res0.clear();
+  p->jfd.sub_res0.clear();
   for (int i = 0; i < p->dims.S; i++) {
     const size_t n = p->ph[i].n, nloc = 13 * n + 13;
     xp_max = std::max(xp_max, (nloc + 1) * nloc);
-    p->sub_res0.push_back(res_tot);
+    p->jfd.sub_res0.push_back(res_tot);
     res_tot += (nloc + 1) * 11 * n;
   }
   DeviceArray<double> jx, jxp, jres;   // all or nothing: a later call must not find a partial set
   if (jx.reserve(nv) != hipSuccess || jxp.reserve(xp_max) != hipSuccess || jres.reserve(res_tot) != hipSuccess)
     return fail(GEL_ERR_ALLOC, "gel_jac_fd: device allocation failed");
-  p->jfd_x = std::move(jx); p->jfd_Xp = std::move(jxp); p->jfd_res = std::move(jres);
+  p->jfd.x = std::move(jx); p->jfd.Xp = std::move(jxp); p->jfd.res = std::move(jres);
   return GEL_OK;
 }
 
@@ -2049,10 +1951,10 @@ static int jfd_evaluate(gel_problem* p, const double* d_x, hipStream_t s) {
     const int n = p->ph[i].n, nloc = 13 * n + 13;
     gel::ProblemDev dv = p->dev;   // the phase as a one-phase problem: same tables, D, tau; local index space
     dv.S = 1; dv.N = n; dv.M = n + 1; dv.nvars = nloc; dv.V = 0;
-    dv.phases = p->d_subphases.get() + i;
-    dv.chunks = p->d_subchunks.get() + p->sub_chunk0[i]; dv.nchunks = p->sub_nchunks[i]; dv.chunk0 = 0;
-    HIPCHK(gel::launch_perturb_local(nloc, p->dx, d_x, p->d_colmap.get() + p->sub_col0[i], p->jfd_Xp.get(), s));
-    HIPCHK(gel::launch_eval(dv, nloc + 1, p->jfd_Xp.get(), p->jfd_res.get() + p->sub_res0[i], nullptr, s));
+    dv.phases = p->jfd.d_subphases.get() + i;
+    dv.chunks = p->jfd.d_subchunks.get() + p->jfd.sub_chunk0[i]; dv.nchunks = p->jfd.sub_nchunks[i]; dv.chunk0 = 0;
+    HIPCHK(gel::launch_perturb_local(nloc, p->dx, d_x, p->jfd.d_colmap.get() + p->jfd.sub_col0[i], p->jfd.Xp.get(), s));
+    HIPCHK(gel::launch_eval(dv, nloc + 1, p->jfd.Xp.get(), p->jfd.res.get() + p->jfd.sub_res0[i], nullptr, s));
   }
   return GEL_OK;
 }
@@ -2070,11 +1972,11 @@ static int jfd_quotients(gel_problem* p, int group, int blocks, double* d_J, hip
     const int n = p->ph[i].n, nloc = 13 * n + 13;
     const int roff_loc = (group == 0) ? 0 : (group == 1) ? n : (group == 2) ? 4 * n : 7 * n;
     if (blocks)
-      HIPCHK(gel::launch_quotient_local(nloc, 11 * n, roff_loc, w * n, p->dx, p->jfd_res.get() + p->sub_res0[i], d_J + off, (long long)nloc, 0,
+      HIPCHK(gel::launch_quotient_local(nloc, 11 * n, roff_loc, w * n, p->dx, p->jfd.res.get() + p->jfd.sub_res0[i], d_J + off, (long long)nloc, 0,
                                         nullptr, s));
     else
-      HIPCHK(gel::launch_quotient_local(nloc, 11 * n, roff_loc, w * n, p->dx, p->jfd_res.get() + p->sub_res0[i], d_J, (long long)nv,
-                                        w * p->ph[i].ua, p->d_colmap.get() + p->sub_col0[i], s));
+      HIPCHK(gel::launch_quotient_local(nloc, 11 * n, roff_loc, w * n, p->dx, p->jfd.res.get() + p->jfd.sub_res0[i], d_J, (long long)nv,
+                                        w * p->ph[i].ua, p->jfd.d_colmap.get() + p->jfd.sub_col0[i], s));
     off += (size_t)w * n * nloc;
   }
   *count = blocks ? off : nrows * nv;
@@ -2096,20 +1998,20 @@ static int jfd_host(gel_problem* p, int32_t group, const double* x, double* J, i
   if ((rc = jfd_allocate(p))) return rc;
   const size_t nv = (size_t)p->dims.num_vars, nrows = (size_t)p->dims.num_rows[group];
   const size_t need = blocks ? jfd_block_doubles(p, group) : nrows * nv;
-  HIPCHK(p->jfd_J.reserve(need));
+  HIPCHK(p->jfd.J.reserve(need));
   // the perturbed evaluations -- unless the same x was just differenced
-  if (p->jfd_last_x.size() != nv || std::memcmp(p->jfd_last_x.data(), x, nv * 8) != 0) {
-    p->jfd_last_x.clear();
-    HIPCHK(hipMemcpyAsync(p->jfd_x.get(), x, nv * 8, hipMemcpyHostToDevice, p->stream.get()));
-    if ((rc = jfd_evaluate(p, p->jfd_x.get(), p->stream.get()))) return rc;
+  if (p->jfd.last_x.size() != nv || std::memcmp(p->jfd.last_x.data(), x, nv * 8) != 0) {
+    p->jfd.last_x.clear();
+    HIPCHK(hipMemcpyAsync(p->jfd.x.get(), x, nv * 8, hipMemcpyHostToDevice, p->stream.get()));
+    if ((rc = jfd_evaluate(p, p->jfd.x.get(), p->stream.get()))) return rc;
     HIPCHK(hipMemcpyAsync(p->h_flag.get(), p->d_flag.get(), 4, hipMemcpyDeviceToHost, p->stream.get()));
     HIPCHK(hipStreamSynchronize(p->stream.get()));
-    p->jfd_status = GEL_OK;
-    if (*p->h_flag.get()) { *p->h_flag.get() = 0; HIPCHK(clear_flag(p, p->stream.get())); p->jfd_status = GEL_NONFINITE; }
-    p->jfd_last_x.assign(x, x + nv);
+    p->jfd.status = GEL_OK;
+    if (*p->h_flag.get()) { *p->h_flag.get() = 0; HIPCHK(clear_flag(p, p->stream.get())); p->jfd.status = GEL_NONFINITE; }
+    p->jfd.last_x.assign(x, x + nv);
   }
   size_t total = 0;
-  if ((rc = jfd_quotients(p, group, blocks, p->jfd_J.get(), p->stream.get(), &total))) return rc;
+  if ((rc = jfd_quotients(p, group, blocks, p->jfd.J.get(), p->stream.get(), &total))) return rc;
   HIPCHK(hipStreamSynchronize(p->stream.get()));
   // J -> caller through the two pinned slots: D2H of piece i+1 overlaps the host copy of piece i
   const size_t piece = (size_t)p->pipe_evals * (size_t)std::max<int64_t>(p->dims.num_var_entries, 1);
@@ -2123,12 +2025,12 @@ static int jfd_host(gel_problem* p, int32_t group, const double* x, double* J, i
     }
     if (off < total) {
       const size_t n = std::min(piece, total - off);
-      HIPCHK(hipMemcpyAsync(sl.h_jv.get(), p->jfd_J.get() + off, n * 8, hipMemcpyDeviceToHost, sl.stream.get()));
+      HIPCHK(hipMemcpyAsync(sl.h_jv.get(), p->jfd.J.get() + off, n * 8, hipMemcpyDeviceToHost, sl.stream.get()));
       pend_off[i & 1] = off; pend_n[i & 1] = n;
       off += n;
     }
   }
-  return p->jfd_status;
+  return p->jfd.status;
 }
 
 int gel_jac_fd(gel_problem* p, int32_t group, const double* x, double* J) { return jfd_host(p, group, x, J, 0); }
@@ -2165,21 +2067,19 @@ int gel_jac_fd_device(gel_problem* p, int32_t group, const double* d_x, double* 
   int rc = jfd_allocate(p);
   if (rc) return rc;
   hipStream_t s = stream_of(p, stream);
-  p->jfd_last_x.clear();   // the residuals kept for gel_jac_fd's host callers are overwritten
+  p->jfd.last_x.clear();   // the residuals kept for gel_jac_fd's host callers are overwritten
   if ((rc = jfd_evaluate(p, d_x, s))) return rc;
   size_t total = 0;
   return jfd_quotients(p, group, blocks ? 1 : 0, d_J, s, &total);
 }
 
 // --------------------------- RHS / point hooks ---------------------------
-namespace {
-int need_device() {
+static int need_device() {
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
     return fail(GEL_ERR_HIP, "no HIP device: the engine has no CPU fallback");
   return GEL_OK;
 }
-}  // namespace
 
 int gel_dynamics_velocity(int32_t n, const double* mass_e, const double* pos_e, const double* vel_e, const double* quat,
                           const double* t, const double* param, const double* wind, int32_t Kw, const double* ca,
@@ -2231,11 +2131,10 @@ int gel_dynamics_quaternion(int32_t n, const double* quat, const double* u_e, do
   return GEL_OK;
 }
 
-namespace {
 // The two walks that describe the aero gradients of a configuration `a` of handle p (gel_aero_pattern, gel_aero_record_map and
 // the tables of the K products all go through them: there is no second description of the layout).
 // emission order of inequality_jac_max_*: con_aero.py:437-463
-void aero_pattern_of(const gel_problem* p, const gel_problem::Aero& a, int kind, int var, int32_t* rows, int32_t* cols) {
+static void aero_pattern_of(const gel_problem* p, const gel_problem::Aero& a, int kind, int var, int32_t* rows, int32_t* cols) {
   const auto& A = a.rows[kind];
   int64_t o = 0;
   for (size_t r0 = 0; r0 < A.size(); r0 += A[r0].nk) {
@@ -2252,7 +2151,7 @@ void aero_pattern_of(const gel_problem* p, const gel_problem::Aero& a, int kind,
 }
 // record index of every entry of gel_eval_aero_all's arrays: var = -1 the constraint vector [nrows], var 0..3 the position /
 // velocity / quaternion / t block of the gradient values (in the order of aero_pattern_of)
-void aero_record_map_of(const gel_problem* p, const gel_problem::Aero& a, int kind, int var, int64_t* idx) {
+static void aero_record_map_of(const gel_problem* p, const gel_problem::Aero& a, int kind, int var, int64_t* idx) {
   const auto& A = a.rows[kind];
   const int nq = (kind == 1) ? 0 : 4;
   int64_t o = 0;
@@ -2285,7 +2184,7 @@ void aero_record_map_of(const gel_problem* p, const gel_problem::Aero& a, int ki
 // copies, into `out` (a local of the configure call that swaps it in).  Rows [linear | node-function | alpha | q | q-alpha];
 // a row's entries in the order of its definition (linear: idx0, idx1; node-function: jfn column 0 .. 6; aero: var 0 .. 3, inside
 // a var the pattern's order); a column's entries by ascending row, equal rows in the row's own order.
-int conprod_build(const gel_problem* p, const std::vector<gel::LinRowDev>& lin, const std::vector<gel::FnRowDev>& fn,
+static int conprod_build(const gel_problem* p, const std::vector<gel::LinRowDev>& lin, const std::vector<gel::FnRowDev>& fn,
                   const gel_problem::Aero& a, gel_problem::Conprod& out) {
   struct Entry { int32_t row, col, src; int64_t offd, offr; double cval; };
   const int M = p->dims.M, N = p->dims.N, nvars = p->dims.num_vars;
@@ -2352,7 +2251,6 @@ int conprod_build(const gel_problem* p, const std::vector<gel::LinRowDev>& lin, 
   }
   return GEL_OK;
 }
-}  // namespace
 
 // ------------------ aero path constraints (lib/con_aero.py) ------------------
 int gel_aero_configure(gel_problem* p, int32_t kind, int32_t nspec, const int32_t* phase, const int32_t* range_all,
@@ -2570,9 +2468,7 @@ int gel_aero_pattern(const gel_problem* p, int32_t kind, int32_t var, int32_t* r
   return GEL_OK;
 }
 
-namespace {
-size_t aero_jac_len(const gel_problem* p, int kind) { return p->aero.rows[kind].size() * ((kind == 1) ? 8 : 12); }
-}  // namespace
+static size_t aero_jac_len(const gel_problem* p, int kind) { return p->aero.rows[kind].size() * ((kind == 1) ? 8 : 12); }
 
 int gel_eval_aero_all_device(gel_problem* p, int32_t B, const double* d_x, double* const* d_con, double* const* d_jac,
                              void* stream) {
@@ -2686,20 +2582,20 @@ int gel_rows_eval(gel_problem* p, int32_t B, const double* x, double* con, doubl
 // ------------- collocation error estimate per section -------------
 #define MESH_FITS(p)                                                                                                   \
   do {                                                                                                                 \
-    if (int rc_ = check_launch_lds("collocation error estimate", (p)->mesh_lds_max,                                    \
+    if (int rc_ = check_launch_lds("collocation error estimate", (p)->mesh.lds_max,                                    \
                                    gel::staged_table_doubles((p)->dev.Kw, (p)->dev.Kc),                                \
                                    gel::padded_table_doubles((p)->dev.Kw, (p)->dev.Kc), true))                         \
       return rc_;                                                                                                      \
   } while (0)
 #define NEED_MESH(p)                                                                                                   \
   do {                                                                                                                 \
-    if ((p)->mesh_hoff.empty())                                                                                        \
+    if ((p)->mesh.hoff.empty())                                                                                        \
       return fail(GEL_ERR_ARG, "collocation error estimate: a phase has more than 511 nodes (one workgroup per point set)"); \
   } while (0)
 
 int gel_mesh_dims(const gel_problem* p, int32_t* npts) {
   if (!p || !npts) return fail(GEL_ERR_ARG, "null argument");
-  *npts = p->mesh_npts;
+  *npts = p->mesh.npts;
   return GEL_OK;
 }
 
@@ -2707,7 +2603,7 @@ int gel_mesh_matrices(const gel_problem* p, int32_t phase, double* sigma, double
   if (!p || phase < 0 || phase >= p->dims.S) return fail(GEL_ERR_ARG, "bad argument");
   NEED_MESH(p);
   const int n = p->ph[phase].n, P = n + 1;
-  const double* hb = p->mesh_host.data() + p->mesh_hoff[phase];
+  const double* hb = p->mesh.host.data() + p->mesh.hoff[phase];
   if (sigma) std::memcpy(sigma, hb, (size_t)P * 8);
   if (Lx) std::memcpy(Lx, hb + P, (size_t)P * P * 8);
   if (Lu) std::memcpy(Lu, hb + P + (size_t)P * P, (size_t)P * n * 8);
@@ -2720,7 +2616,7 @@ int gel_mesh_error_device(gel_problem* p, int32_t B, const double* d_x, double* 
   MESH_FITS(p);
   NEED_DEVICE(p, GEL_ERR_HIP, kNoGpu);
   NEED_MESH(p);
-  HIPCHK(gel::launch_mesh(p->dev, p->mesh_dev, p->mesh_ph.data(), B, d_x, d_err, d_diff, stream_of(p, stream)));
+  HIPCHK(gel::launch_mesh(p->dev, p->mesh.dev, p->mesh.ph.data(), B, d_x, d_err, d_diff, stream_of(p, stream)));
   return GEL_OK;
 }
 
@@ -2731,9 +2627,9 @@ int gel_mesh_error(gel_problem* p, int32_t B, const double* x, double* err, doub
   NEED_MESH(p);
   HIPCHK(hipSetDevice(p->device));
   return staged_call(p, kStagedZeroCopy,
-                     {staged_in(x, (size_t)B * p->dims.num_vars), staged_out(err, (size_t)B * p->dims.S * 4), staged_out(diff, (size_t)B * p->mesh_npts * 11)},
+                     {staged_in(x, (size_t)B * p->dims.num_vars), staged_out(err, (size_t)B * p->dims.S * 4), staged_out(diff, (size_t)B * p->mesh.npts * 11)},
                      [&](const gel::ProblemDev& dv, double* const* a) -> int {
-                       HIPCHK(gel::launch_mesh(dv, p->mesh_dev, p->mesh_ph.data(), B, a[0], a[1], a[2], p->stream.get()));
+                       HIPCHK(gel::launch_mesh(dv, p->mesh.dev, p->mesh.ph.data(), B, a[0], a[1], a[2], p->stream.get()));
                        return GEL_OK;
                      });
 }
@@ -3454,13 +3350,13 @@ int gel_propagate_tangent(gel_prop_plan* plan, int32_t B, int32_t P, int32_t sha
 // ------------- Jacobian products from the compact values -------------
 #define NEED_JPROD(p, t)                                                                                                  \
   do {                                                                                                                    \
-    if (!gel::jprod_vectors_per_group((p)->jp_nin_max[(t) ? 1 : 0], (t) != 0))                                             \
+    if (!gel::jprod_vectors_per_group((p)->jp.nin_max[(t) ? 1 : 0], (t) != 0))                                             \
       return fail(GEL_ERR_ARG, "Jacobian products: a phase's slice of the input does not fit a workgroup's LDS");          \
   } while (0)
 
 int gel_jac_products_info(const gel_problem* p, int64_t* info) {
   if (!p || !info) return fail(GEL_ERR_ARG, "null argument");
-  for (int k = 0; k < 4; k++) info[k] = p->jp_info[k];
+  for (int k = 0; k < 4; k++) info[k] = p->jp.info[k];
   return GEL_OK;
 }
 
@@ -3468,24 +3364,24 @@ int gel_jac_products_host(const gel_problem* p, int32_t B, const double* jvar, c
   if (!p || B < 1 || !jvar || !in || !out) return fail(GEL_ERR_ARG, "bad argument");
   const size_t V = (size_t)p->dims.num_var_entries, nv = (size_t)p->dims.num_vars, nr = (size_t)11 * p->dims.N;
   const int S = p->dims.S;
-  const int32_t* it = p->jp_it.data();
-  const double* dt = p->jp_dt.data();
+  const int32_t* it = p->jp.it.data();
+  const double* dt = p->jp.dt.data();
   int rc = GEL_OK;
   for (int32_t b = 0; b < B; b++) {
     const double* jv = jvar + (size_t)b * V;
     const double* ib = in + (size_t)b * (transpose ? nr : nv);
     double* ob = out + (size_t)b * (transpose ? nv : nr);
     for (int i = 0; i < S; i++) {
-      const gel::JprodPhaseDev& q = p->jp_ph[i];
+      const gel::JprodPhaseDev& q = p->jp.ph[i];
       jprod_host_op(*p, transpose ? q.bw : q.fw, q.voff, jv, ib, ob);
     }
     if (transpose) {
       // the time columns: the tf side of phase i - 1, then the to side of phase i, each summed in table order
-      double* g = ob + p->jp_dev.tcol0;
+      double* g = ob + p->jp.dev.tcol0;
       for (int i = 0; i <= S; i++) g[i] = 0.0;
       for (int i = 0; i < S; i++)
         for (int side = 0; side < 2; side++) {
-          const gel::JprodPhaseDev& q = p->jp_ph[i];
+          const gel::JprodPhaseDev& q = p->jp.ph[i];
           const gel::JprodTcolDev& t = q.tc[side];
           double acc = 0.0;
           for (int e = 0; e < t.nt; e++) {
@@ -3509,7 +3405,7 @@ int gel_jac_products_host(const gel_problem* p, int32_t B, const double* jvar, c
 // GEL_JPROD_VB = 1 / 2 / 4 / 8 (measurement switch, read per call; a value whose staged inputs do not fit is ignored).  The results
 // do not depend on it.  0: not even one vector fits (NEED_JPROD).
 static int jprod_vb(const gel_problem* p, int transpose) {
-  const int nin = p->jp_nin_max[transpose ? 1 : 0];
+  const int nin = p->jp.nin_max[transpose ? 1 : 0];
   if (const char* e = getenv("GEL_JPROD_VB")) {
     const int w = atoi(e);
     if ((w == 1 || w == 2 || w == 4 || w == 8) && gel::jprod_lds_bytes(nin, w, transpose != 0) <= gel::kJprodMaxLds) return w;
@@ -3518,18 +3414,18 @@ static int jprod_vb(const gel_problem* p, int transpose) {
 }
 
 static int jprod_device(gel_problem* p, int32_t B, const double* d_jvar, const double* d_in, double* d_out, int transpose, hipStream_t s) {
-  if (transpose && p->d_jp_tpart.capacity() < (size_t)B * p->dims.S * 2) {
-    if (p->d_jp_tpart.get()) HIPCHK(drain(p));   // an earlier product in flight still sums through the old workspace
-    HIPCHK(p->d_jp_tpart.reserve((size_t)B * p->dims.S * 2));
+  if (transpose && p->jp.d_tpart.capacity() < (size_t)B * p->dims.S * 2) {
+    if (p->jp.d_tpart.get()) HIPCHK(drain(p));   // an earlier product in flight still sums through the old workspace
+    HIPCHK(p->jp.d_tpart.reserve((size_t)B * p->dims.S * 2));
   }
-  HIPCHK(gel::launch_jprod(p->jp_dev, p->jp_nin_max[transpose ? 1 : 0], B, d_jvar, d_in, d_out, p->d_jp_tpart.get(), p->d_flag.get(),
-                           transpose, jprod_vb(p, transpose), p->jp_threads, s));
+  HIPCHK(gel::launch_jprod(p->jp.dev, p->jp.nin_max[transpose ? 1 : 0], B, d_jvar, d_in, d_out, p->jp.d_tpart.get(), p->d_flag.get(),
+                           transpose, jprod_vb(p, transpose), p->jp.threads, s));
   return GEL_OK;
 }
 
 int gel_jac_products_launch_info(const gel_problem* p, int32_t* info) {
   if (!p || !info) return fail(GEL_ERR_ARG, "null argument");
-  for (int t = 0; t < 2; t++) { info[2 * t] = jprod_vb(p, t); info[2 * t + 1] = p->jp_threads; }
+  for (int t = 0; t < 2; t++) { info[2 * t] = jprod_vb(p, t); info[2 * t + 1] = p->jp.threads; }
   return GEL_OK;
 }
 

@@ -5,7 +5,6 @@ and from the textbook formula -- montecarlo.dispersion_sensitivity on a designed
 UBSan in a stand-alone program."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -13,7 +12,7 @@ import pytest
 import comoment_truth as ct
 import interp_truth as it
 import output_batch_truth as obt
-from conftest import ROOT
+import sanitized_lib
 from gelato_amd import Engine, _lib, montecarlo
 
 GEL_ERR_ARG, GEL_ERR_HIP = -1, -2          # include/gelato_amd.h
@@ -279,24 +278,8 @@ def test_dispersion_sensitivity_on_a_designed_batch():
 
 
 # ---------------------------------------------------------------- the refusals under sanitizers, stand-alone
-HIPCC = "/opt/rocm/bin/hipcc"
-CLANG = "/opt/rocm/lib/llvm/bin/clang"
-
-
-@pytest.mark.skipif(not (os.path.exists(HIPCC) and os.path.exists(CLANG)), reason="ROCm toolchain not present")
+@sanitized_lib.needs_toolchain
 def test_refusals_and_info_under_asan_ubsan(tmp_path):
     """every refusal of both forms and gel_batch_comoments_info on a host-only handle, in a stand-alone program
     (tests/comoments_sanitize.c) under AddressSanitizer + UBSan + LeakSanitizer; nothing is launched"""
-    csrc = os.path.join(ROOT, "gelato_amd", "csrc")
-    lib = tmp_path / "libgelato_amd_asan.so"
-    flags = ["-O1", "-g", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fno-fast-math", "-ffp-contract=on",
-             "-mllvm", "-disable-machine-licm", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-w"]
-    subprocess.run([HIPCC, *flags, "-shared", "-o", str(lib), "gel_kernels.hip", "gel_host.hip"], cwd=csrc, check=True, capture_output=True, timeout=280)
-    exe = tmp_path / "comoments_sanitize"
-    subprocess.run([CLANG, "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-o", str(exe),
-                    os.path.join(ROOT, "tests", "comoments_sanitize.c"), str(lib), "-lm",
-                    "-Wl,-rpath,%s" % tmp_path, "-Wl,-rpath,/opt/rocm/lib"], check=True, capture_output=True, timeout=120)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    r = subprocess.run([str(exe)], env=env, capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "COMOMENTS_SANITIZE_OK" in r.stdout, (r.stdout + r.stderr)[-4000:]
-    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-4000:]
+    sanitized_lib.run_program(tmp_path, sanitized_lib.build(tmp_path), "comoments_sanitize")

@@ -2,9 +2,6 @@
 gel_prop_plan_info, the Python argument checks, sample_dispersion, the restatement of tests/flight_truth.py against
 propagate_truth's bits (the chain's phase 0; the node restart as a whole), the teeth of its three wrong restatements, and the plan builder under AddressSanitizer + UBSan in a
 stand-alone program."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
@@ -12,7 +9,7 @@ import flight_truth as ft
 import interp_truth as it
 import mesh_truth as mt
 import propagate_truth as pt
-from conftest import ROOT
+import sanitized_lib
 
 
 def _bits(a):
@@ -219,24 +216,8 @@ def test_truth_rejects_wrong_restatements(mutate):
     plan.close()
 
 
-HIPCC = "/opt/rocm/bin/hipcc"
-CLANG = "/opt/rocm/lib/llvm/bin/clang"
-
-
-@pytest.mark.skipif(not (os.path.exists(HIPCC) and os.path.exists(CLANG)), reason="ROCm toolchain not present")
+@sanitized_lib.needs_toolchain
 def test_chain_plan_builder_under_asan_ubsan(tmp_path):
     """the plan builder in all three modes, its refusals and gel_prop_matrices on a host-only handle, in a stand-alone program
     (tests/flight_sanitize.c) under AddressSanitizer + UBSan + LeakSanitizer; nothing is launched"""
-    csrc = os.path.join(ROOT, "gelato_amd", "csrc")
-    lib = tmp_path / "libgelato_amd_asan.so"
-    flags = ["-O1", "-g", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fno-fast-math", "-ffp-contract=on",
-             "-mllvm", "-disable-machine-licm", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-w"]
-    subprocess.run([HIPCC, *flags, "-shared", "-o", str(lib), "gel_kernels.hip", "gel_host.hip"], cwd=csrc, check=True, capture_output=True, timeout=280)
-    exe = tmp_path / "flight_sanitize"
-    subprocess.run([CLANG, "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-o", str(exe),
-                    os.path.join(ROOT, "tests", "flight_sanitize.c"), str(lib), "-lm",
-                    "-Wl,-rpath,%s" % tmp_path, "-Wl,-rpath,/opt/rocm/lib"], check=True, capture_output=True, timeout=120)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    r = subprocess.run([str(exe)], env=env, capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "FLIGHT_SANITIZE_OK" in r.stdout, (r.stdout + r.stderr)[-4000:]
-    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-4000:]
+    sanitized_lib.run_program(tmp_path, sanitized_lib.build(tmp_path), "flight_sanitize")

@@ -3,14 +3,13 @@ refusals of the new entry points and gel_prop_tangent_info, the Python argument 
 linear_covariance, and the entry points' validation under AddressSanitizer + UBSan in a stand-alone program."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import flight_tangent_truth as tt
 import interp_truth as it
-from conftest import ROOT
+import sanitized_lib
 
 
 def _bits(a):
@@ -202,24 +201,8 @@ def test_linear_covariance_hand_case():
     assert np.array_equal(montecarlo.linear_covariance(J, np.zeros(3)), np.zeros((2, 2)))
 
 
-HIPCC = "/opt/rocm/bin/hipcc"
-CLANG = "/opt/rocm/lib/llvm/bin/clang"
-
-
-@pytest.mark.skipif(not (os.path.exists(HIPCC) and os.path.exists(CLANG)), reason="ROCm toolchain not present")
+@sanitized_lib.needs_toolchain
 def test_entry_points_under_asan_ubsan(tmp_path):
     """the new entry points' validation and gel_prop_tangent_info on a host-only handle, in a stand-alone program
     (tests/flight_tangent_sanitize.c) under AddressSanitizer + UBSan + LeakSanitizer; nothing is launched, nothing preloaded"""
-    csrc = os.path.join(ROOT, "gelato_amd", "csrc")
-    lib = tmp_path / "libgelato_amd_asan.so"
-    flags = ["-O1", "-g", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fno-fast-math", "-ffp-contract=on",
-             "-mllvm", "-disable-machine-licm", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-w"]
-    subprocess.run([HIPCC, *flags, "-shared", "-o", str(lib), "gel_kernels.hip", "gel_host.hip"], cwd=csrc, check=True, capture_output=True, timeout=280)
-    exe = tmp_path / "flight_tangent_sanitize"
-    subprocess.run([CLANG, "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-o", str(exe),
-                    os.path.join(ROOT, "tests", "flight_tangent_sanitize.c"), str(lib), "-lm",
-                    "-Wl,-rpath,%s" % tmp_path, "-Wl,-rpath,/opt/rocm/lib"], check=True, capture_output=True, timeout=120)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    r = subprocess.run([str(exe)], env=env, capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "FLIGHT_TANGENT_SANITIZE_OK" in r.stdout, (r.stdout + r.stderr)[-4000:]
-    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-4000:]
+    sanitized_lib.run_program(tmp_path, sanitized_lib.build(tmp_path), "flight_tangent_sanitize")

@@ -5,15 +5,13 @@ reduction on hand-made peaks, and the ensemble's host code under AddressSanitize
 (The library exposes no handle's staged tables, so "the wind part of a handle created with that member" is held here through the
 restatement of the one staging function both go through; the GPU suite holds the flights to such handles bit for bit.)"""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import interp_truth as it
+import sanitized_lib
 import table_cases as TC
-from conftest import ROOT
 
 
 def _bits(a):
@@ -271,25 +269,9 @@ def test_availability_reduction_on_hand_made_peaks():
             availability_from_peaks(peaks, np.asarray(kw.pop("members"), dtype=np.int64), **kw)
 
 
-HIPCC = "/opt/rocm/bin/hipcc"
-CLANG = "/opt/rocm/lib/llvm/bin/clang"
-
-
-@pytest.mark.skipif(not (os.path.exists(HIPCC) and os.path.exists(CLANG)), reason="ROCm toolchain not present")
+@sanitized_lib.needs_toolchain
 def test_ensemble_host_code_under_asan_ubsan(tmp_path):
     """create, member, info, assign, every refusal and destroy on host-only handles, in a stand-alone program
     (tests/ensemble_sanitize.c) under AddressSanitizer + UBSan + LeakSanitizer, linked against the sanitized library directly;
     nothing is preloaded and nothing is launched"""
-    csrc = os.path.join(ROOT, "gelato_amd", "csrc")
-    lib = tmp_path / "libgelato_amd_asan.so"
-    flags = ["-O1", "-g", "-std=c++17", "-fPIC", "--offload-arch=gfx950", "-fno-fast-math", "-ffp-contract=on",
-             "-mllvm", "-disable-machine-licm", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-w"]
-    subprocess.run([HIPCC, *flags, "-shared", "-o", str(lib), "gel_kernels.hip", "gel_host.hip"], cwd=csrc, check=True, capture_output=True, timeout=280)
-    exe = tmp_path / "ensemble_sanitize"
-    subprocess.run([CLANG, "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-o", str(exe),
-                    os.path.join(ROOT, "tests", "ensemble_sanitize.c"), str(lib), "-lm",
-                    "-Wl,-rpath,%s" % tmp_path, "-Wl,-rpath,/opt/rocm/lib"], check=True, capture_output=True, timeout=120)
-    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="halt_on_error=1:print_stacktrace=1")
-    r = subprocess.run([str(exe)], env=env, capture_output=True, text=True, timeout=120)
-    assert r.returncode == 0 and "ENSEMBLE_SANITIZE_OK" in r.stdout, (r.stdout + r.stderr)[-4000:]
-    assert "runtime error" not in r.stderr and "AddressSanitizer" not in r.stderr, r.stderr[-4000:]
+    sanitized_lib.run_program(tmp_path, sanitized_lib.build(tmp_path), "ensemble_sanitize")

@@ -14,8 +14,8 @@ for spec in "$@"; do
   ( d=$(mktemp -d /tmp/gelvar.XXXXXX)
     { /opt/rocm/bin/hipcc $BASE -mllvm -amdgpu-sched-strategy=max-ilp $flags -c -o $d/k.o gel_kernels.hip \
       && /opt/rocm/bin/hipcc $BASE $KA $flags -c -o $d/a.o gel_kernels_aero.hip \
-      && /opt/rocm/bin/hipcc $BASE -mllvm -amdgpu-sched-strategy=max-ilp $flags -c -o $d/h.o gel_host.hip \
-      && /opt/rocm/bin/hipcc $BASE -shared -o ../../build/variants/libgel_$name.so $d/k.o $d/a.o $d/h.o ; } > ../../build/variants/$name.log 2>&1 \
+      && ( for h in gel_host*.hip; do /opt/rocm/bin/hipcc $BASE -mllvm -amdgpu-sched-strategy=max-ilp $flags -c -o $d/${h%.hip}.o $h || exit 1; done ) \
+      && /opt/rocm/bin/hipcc $BASE -shared -o ../../build/variants/libgel_$name.so $d/k.o $d/a.o $d/gel_host*.o ; } > ../../build/variants/$name.log 2>&1 \
      && echo "built $name [$flags]" || { echo "FAILED $name (build/variants/$name.log):"; tail -5 ../../build/variants/$name.log; }
     rm -rf $d ) &
 done
