@@ -172,6 +172,9 @@ SIGNATURES = {
     "gel_propagate_tangent": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp]),
     "gel_propagate_tangent_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 6),
     "gel_prop_tangent_info": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _lp]),
+    "gel_propagate_adjoint": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "gel_propagate_adjoint_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 6),
+    "gel_prop_adjoint_info": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _lp]),
     "gel_initial_guess": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, _dp, _dp]),
     "gel_output_table": (C.c_int, [C.c_void_p, _dp, _dp, C.c_double, C.c_double, _dp]),
     "gel_output_table_batch": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, _dp, C.c_double, C.c_double, C.c_int32, _ip, _dp, _dp, _dp]),
@@ -214,7 +217,7 @@ def build(force=False):
     src_dir = os.path.join(_HERE, "csrc")
     if force and os.path.exists(SO_PATH):
         os.remove(SO_PATH)
-    subprocess.check_call(["make", "-s", "-j8", "-C", src_dir])   # fourteen translation units with kernels (the fused kernels, the AERO instantiation, the three exact Jacobians, the mesh error estimate, the two Jacobian products, the interpolation, the propagation and its tangent, the batched output table, the batch quantiles, the batch co-moments) and the host side, gel_host*.hip
+    subprocess.check_call(["make", "-s", "-j8", "-C", src_dir])   # fifteen translation units with kernels (the fused kernels, the AERO instantiation, the three exact Jacobians, the mesh error estimate, the two Jacobian products, the interpolation, the propagation, its tangent and its adjoint, the batched output table, the batch quantiles, the batch co-moments) and the host side, gel_host*.hip
     if not os.path.exists(SO_PATH):
         raise RuntimeError("building %s failed" % SO_PATH)
     _write_build_info()

@@ -26,6 +26,7 @@
 #include "gel_interp.h"
 #include "gel_prop.h"
 #include "gel_proptan.h"
+#include "gel_propadj.h"
 #include "gel_outbatch.h"
 #include "gel_quant.h"
 #include "gel_comom.h"
@@ -3344,6 +3345,132 @@ int gel_propagate_tangent(gel_prop_plan* plan, int32_t B, int32_t P, int32_t sha
                             staged_in(dx, seeds * nv), staged_in(ddisp, seeds * nd), staged_out(dy, (size_t)B * P * ny)},
                      [&](const gel::ProblemDev&, double* const* a) {
                        return proptan_enqueue(plan, B, P, shared, a[0], a[2], a[3], a[4], a[1], a[5], p->stream.get());
+                     });
+}
+
+// ------------- adjoint flight: gradients of the flown trajectory in one pass -------------
+// The workspace holds per vector of a slab one sample set (16 bytes per sampled stage point) and per lane (vector, functional) the
+// stage points' control multipliers (as many bytes again), one double per phase (the multiplier of S) and the inner checkpoints of
+// one node interval (11 doubles per step but the first, for the largest steps[s]).  Vectors per slab: as many
+// as the plan's 1 GB cap holds and as the transposed sampler's grid (one workgroup per 256 lanes and control node) allows, a multiple
+// of 64; 0 where 64 vectors do not fit.  GEL_PROP_SLAB as in prop_slab().
+static int64_t propadj_kmax(const gel_prop_plan* pl) {
+  int64_t k = 1;
+  for (const gel::PropPhaseDev& q : pl->ph) k = std::max<int64_t>(k, q.k);
+  return k;
+}
+static int64_t propadj_lane_bytes(const gel_prop_plan* pl) { return 16 * pl->sampled_pts + 8 * (int64_t)pl->dev.S + 88 * (propadj_kmax(pl) - 1); }
+
+static int64_t propadj_slab(const gel_prop_plan* pl, int64_t Q) {
+  const int64_t per_vec = 16 * pl->sampled_pts + Q * propadj_lane_bytes(pl);
+  int64_t vs = std::min<int64_t>(kPropMaxSlab, kPropWsBytes / per_vec / 64 * 64);
+  const int64_t grid_lanes = (int64_t)0x7fffffff / ((int64_t)pl->src->dims.N + 1) * gel::kPropAdjSampleThreads;
+  vs = std::min<int64_t>(vs, std::min<int64_t>(grid_lanes, 0x7fffffff) / Q / 64 * 64);
+  if (vs < 64) return 0;
+  if (const char* e = getenv("GEL_PROP_SLAB")) {
+    const long long w = (atoll(e) + 63) / 64 * 64;
+    if (w >= 64 && w <= vs) vs = w;
+  }
+  return vs;
+}
+
+// every refusal that is decided before a buffer is looked at
+static int propadj_refuse(const char* who, const gel_prop_plan* plan, int32_t B, int32_t Q, int32_t shared) {
+  const std::string w(who);
+  if (!plan) return fail(GEL_ERR_ARG, w + ": null plan");
+  if (B < 0) return fail(GEL_ERR_ARG, w + ": B < 0");
+  if (Q < 1) return fail(GEL_ERR_ARG, w + ": Q < 1");
+  if ((int64_t)B * Q > 0x7fffffffLL) return fail(GEL_ERR_ARG, w + ": B Q exceeds 2^31 - 1 lanes");
+  if (shared != 0 && shared != 1) return fail(GEL_ERR_ARG, w + ": shared is neither 0 nor 1");
+  if (plan->flags & GEL_PROP_RESTART_NODE)
+    return fail(GEL_ERR_ARG, w + ": a GEL_PROP_RESTART_NODE plan has no adjoint flight (neighbouring node segments share a stage point)");
+  if (!propadj_slab(plan, Q))
+    return fail(GEL_ERR_ARG, w + ": the workspace of 64 vectors (control samples, and per functional the stage points' multipliers) exceeds the 1 GB cap");
+  return GEL_OK;
+}
+
+static int propadj_check(const char* who, const gel_prop_plan* plan, int32_t B, int32_t Q, int32_t shared, const void* x, const void* lam,
+                         const void* y, const void* gx) {
+  const std::string w(who);
+  if (plan && !lam) return fail(GEL_ERR_ARG, w + ": lam is NULL");
+  if (int rc = propadj_refuse(who, plan, B, Q, shared)) return rc;
+  if (plan->src->device == GEL_DEVICE_NONE) return fail(GEL_ERR_ARG, w + ": the plan's handle is host-only (GEL_DEVICE_NONE)");
+  if (B > 0 && (!x || !y || !gx)) return fail(GEL_ERR_ARG, w + ": x, y or gx is NULL with B > 0");
+  return GEL_OK;
+}
+
+int gel_prop_adjoint_info(const gel_prop_plan* plan, int32_t B, int32_t Q, int32_t shared, int64_t* info) {
+  if (!info) return fail(GEL_ERR_ARG, "gel_prop_adjoint_info: info is NULL");
+  if (int rc = propadj_refuse("gel_prop_adjoint_info", plan, B, Q, shared)) return rc;
+  const int64_t vs = propadj_slab(plan, Q);
+  info[0] = propadj_lane_bytes(plan);
+  info[1] = vs * Q;
+  info[2] = (B + vs - 1) / vs;
+  return GEL_OK;
+}
+
+// the launches of one call on stream s, slab after slab: the control samples and the value flight (y: the checkpoints), the backward
+// walk, the transposed sampler with the knot times
+static int propadj_enqueue(gel_prop_plan* plan, int32_t B, int32_t Q, int32_t shared, const double* d_x, const double* d_disp,
+                           const double* d_lam, double* d_y, double* d_gx, double* d_gdisp, hipStream_t s) {
+  gel_problem* p = plan->src;
+  const int64_t vs = propadj_slab(plan, Q), ldv = std::min<int64_t>(vs, ((int64_t)B + 63) / 64 * 64);
+  const int64_t gld = ldv * Q;
+  const size_t set = 2 * (size_t)plan->sampled_pts;
+  const size_t nck = 11 * (size_t)(propadj_kmax(plan) - 1);
+  const size_t need = (size_t)ldv * set + (size_t)gld * (set + (size_t)plan->dev.S + nck) + 1;   // (+ 1: ck is a valid pointer at k = 1 too)
+  if (plan->d_ws.capacity() < need) {
+    HIPCHK(drain(p));   // an earlier call in flight still reads the old block
+    HIPCHK(plan->d_ws.reserve(need));
+  }
+  double* const ws = plan->d_ws.get();
+  double* const gws = ws + (size_t)ldv * set;    // the second region: the stage points' control multipliers
+  double* const gS = gws + (size_t)gld * set;    // the third: the multiplier of S per (phase, lane)
+  double* const ck = gS + (size_t)gld * (size_t)plan->dev.S;   // the fourth: the inner checkpoints of the interval in hand
+  const size_t nv = (size_t)p->dims.num_vars, ny = (size_t)11 * p->dims.M, nd = (size_t)p->dims.S * GEL_PROP_NDISP;
+  const gel::EnsDev no_ens{};
+  for (int64_t v0 = 0; v0 < B; v0 += vs) {
+    const int nb = (int)std::min<int64_t>(vs, B - v0);
+    const double* const disp = d_disp ? d_disp + (size_t)v0 * nd : nullptr;
+    HIPCHK(gel::launch_prop_slab(p->dev, plan->dev, plan->ph.data(), plan->n_max_sampled, nb, d_x + (size_t)v0 * nv, d_y + (size_t)v0 * ny, ws,
+                                 ldv, disp, no_ens, s));
+    const size_t l0 = (size_t)v0 * Q;   // the slab's first lane
+    gel::PropAdjArgs a{};
+    a.nb = nb; a.Q = Q; a.shared = shared;
+    a.x = d_x + (size_t)v0 * nv;
+    a.disp = disp;
+    a.lam = shared ? d_lam : d_lam + l0 * ny;
+    a.y = d_y + (size_t)v0 * ny;
+    a.gx = d_gx + l0 * nv;
+    a.gdisp = d_gdisp ? d_gdisp + l0 * nd : nullptr;
+    a.ws = ws; a.gws = gws; a.gS = gS; a.ck = ck; a.ld = ldv; a.gld = gld;
+    HIPCHK(gel::launch_propadj_slab(p->dev, plan->dev, a, s));
+  }
+  return GEL_OK;
+}
+
+int gel_propagate_adjoint_device(gel_prop_plan* plan, int32_t B, int32_t Q, int32_t shared, const double* d_x, const double* d_disp,
+                                 const double* d_lam, double* d_y, double* d_gx, double* d_gdisp) {
+  if (int rc = propadj_check("gel_propagate_adjoint_device", plan, B, Q, shared, d_x, d_lam, d_y, d_gx)) return rc;
+  if (B == 0) return GEL_OK;
+  gel_problem* p = plan->src;
+  HIPCHK(hipSetDevice(p->device));
+  return propadj_enqueue(plan, B, Q, shared, d_x, d_disp, d_lam, d_y, d_gx, d_gdisp, p->stream.get());
+}
+
+int gel_propagate_adjoint(gel_prop_plan* plan, int32_t B, int32_t Q, int32_t shared, const double* x, const double* disp, const double* lam,
+                          double* y, double* gx, double* gdisp) {
+  if (int rc = propadj_check("gel_propagate_adjoint", plan, B, Q, shared, x, lam, y, gx)) return rc;
+  if (B == 0) return GEL_OK;
+  gel_problem* p = plan->src;
+  HIPCHK(hipSetDevice(p->device));
+  const size_t nv = (size_t)p->dims.num_vars, ny = (size_t)11 * p->dims.M, nd = (size_t)p->dims.S * GEL_PROP_NDISP;
+  const size_t lanes = (size_t)B * Q;
+  // (x, y, disp as gel_propagate_dispersed lays them out; the new buffers behind them)
+  return staged_call(p, 0, {staged_in(x, (size_t)B * nv), staged_out(y, (size_t)B * ny), staged_in(disp, (size_t)B * nd),
+                            staged_in(lam, (shared ? (size_t)Q : lanes) * ny), staged_out(gx, lanes * nv), staged_out(gdisp, lanes * nd)},
+                     [&](const gel::ProblemDev&, double* const* a) {
+                       return propadj_enqueue(plan, B, Q, shared, a[0], a[2], a[3], a[1], a[4], a[5], p->stream.get());
                      });
 }
 

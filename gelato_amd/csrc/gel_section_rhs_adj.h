@@ -1,0 +1,167 @@
+// gel_section_rhs_adj.h -- the right-hand side F of gel_section_rhs.h together with the TRANSPOSE of its tangent (gel_section_rhs_tan.h)
+// applied to one multiplier lF [11], for the adjoint flight (gel_kernels_propadj.hip).
+//
+// Values: the lines of section_rhs_tangent, on the same arguments in the same order, so F has section_rhs<true>'s bits.  Partials:
+// the ones section_rhs_tangent forms (dg, dw3, dh, AirTangent, the quadratic thrust direction, the bilinear quaternion rate), with
+// gel_exact.h's conventions at kinks; every line of the tangent is transposed where it stands, the 3 x 3 blocks contracted from the
+// other side (over the component instead of over the position direction).  aero_force_tangent() is linear in (da, drho, dinv_a): its
+// transpose is WRITTEN OUT here (not probed with unit inputs), term by term:
+//   dF_i = -(dk a_i + kk da_i)                 ->  l_dk = -<lFa, a>;  l_da_i = -kk lFa_i
+//   dk   = area / 2 (drho ca s + rho cas dM s + rho ca ds)   (0 where |a| = 0)
+//                                              ->  l_drho = h ca s;  l_dM = h rho cas s;  l_ds = h rho ca,   h = area / 2 l_dk
+//   dM   = ds inv_a + s dinv_a                 ->  l_ds += inv_a l_dM;  l_dinv_a = s l_dM
+//   ds   = <a, da> / s                         ->  l_da_i += (a_i / s) l_ds
+// The time has no adjoint here: the tangent of F along the time is taken as zero (gel_section_rhs_tan.h).
+//
+// Out: lxt [11] = J^T lF in the units of the value call's state, and in RhsAdjoint the multipliers of the controls and of
+// ph.thrust, ph.mf_um, ph.area AS THE VALUE CALL HOLDS THEM (the caller multiplies by the handle's unscaled values, as the tangent
+// forms d.dthrust from them) and of the wind factor.
+#pragma once
+#include "gel_exact.h"
+#include "gel_section_rhs.h"
+
+namespace gel {
+
+struct RhsAdjoint {
+  double u0, u1;
+  double thrust, mf, area, fw;
+};
+
+GEL_DEV void section_rhs_adjoint(const ProblemDev& P, const PhaseDev& ph, const Tables& tb, double vp, double sig, double to,
+                                 double tf, const double xt[11], double u0, double u1, double fw, const double lF[11],
+                                 double F[11], double lxt[11], RhsAdjoint& g) {
+  F[0] = ph.engine_on ? ph.mf_um : 0.0;
+  g.mf = ph.engine_on ? lF[0] : 0.0;
+#pragma unroll
+  for (int c = 0; c < 3; c++) F[1 + c] = xt[4 + c] * vp;
+  const double m = xt[0] * P.um;
+  const double r[3] = {xt[1] * P.up, xt[2] * P.up, xt[3] * P.up};
+  const double q[4] = {xt[7], xt[8], xt[9], xt[10]};
+  double dir[3], f[3];
+  thrust_dir(q, dir);
+  const double inv_m = 1.0 / m;
+  double dg[3][3];
+  gravity_tangent(r, P.barC20, dg);
+  // df_c = (X_c / m - (tm_c / m) dm + dg_c) / uv:  mu = the bracket's multiplier, nu = X's
+  const double mu[3] = {lF[4] * P.inv_uv, lF[5] * P.inv_uv, lF[6] * P.inv_uv};
+  const double nu[3] = {mu[0] * inv_m, mu[1] * inv_m, mu[2] * inv_m};
+  double ldr[3], ldir[3], lv[3] = {0.0, 0.0, 0.0}, ldm;
+#pragma unroll
+  for (int k = 0; k < 3; k++) ldr[k] = dg[k][0] * mu[0] + dg[k][1] * mu[1] + dg[k][2] * mu[2];
+  g.area = 0.0;
+  g.fw = 0.0;
+  if (ph.air) {
+    const double v3[3] = {xt[4] * P.uv, xt[5] * P.uv, xt[6] * P.uv};
+    PosCentre pc;
+    PosCentreTail tail;
+    const PosPart pp = pos_part<true, PosCentreSink>(r, tb, P.barC20, nullptr, PosCentreSink{&pc}, &tail);
+    const EarthAngle ea = earth_angle(sig * (tf - to) / 2 + (tf + to) / 2);
+    double w[3], Fa[3];
+    const double wn = pp.wn * fw, we = pp.we * fw;
+    wind_eci_or_calm(r, ea, pp.shp, pp.chp, pp.inv_p, wn, we, w);
+    aero_force(r, v3, pp.rho, pp.inv_a, w, ph.area, tb, Fa);
+    const double T = ph.thrust - ph.nozzle * pp.P;
+    const double Td[3] = {T * dir[0], T * dir[1], T * dir[2]};
+    accel(Td, Fa, inv_m, pp.g, P.inv_uv, f);
+    // ---- the partials, as section_rhs_tangent forms them ----
+    const double a[3] = {(v3[0] + kOmega * r[1]) - w[0], (v3[1] - kOmega * r[0]) - w[1], v3[2] - w[2]};
+    const double s2 = a[0] * a[0] + a[1] * a[1] + a[2] * a[2];
+    const double s = fsqrt(fmax(s2, 1.0e-200));
+    const double mach = s * pp.inv_a;
+    const double ca = interp_tab(mach, tb.ca, tb.cas, tb.Kc, 2, 1);
+    const double cas = interp_tab_slope(mach, tb.ca, tb.cas, tb.Kc, 2);
+    const double kk = (s2 > 0.0) ? 0.5 * pp.rho * ph.area * ca * s : 0.0;
+    double dsl[3], dcl[3], dalt[3], dh[3];
+    geodetic_tangent(r, pp.inv_p, pc, dsl, dcl, dalt);
+#pragma unroll
+    for (int k = 0; k < 3; k++) dh[k] = (pc.G * pc.G) * dalt[k];
+    const double Tk = pp.P / (pp.rho * tb.atm[33 + tail.k]);
+    const AirTangent at = atmosphere_tangent(tail.h, Tk, pp.P, pp.rho, pp.inv_a, tb.atm);
+    const bool in = tail.piece >= 0;
+    const double s0 = in ? tb.winds[2 * tail.piece] * fw : 0.0, s1 = in ? tb.winds[2 * tail.piece + 1] * fw : 0.0;
+    const double clon = (pp.inv_p > 0.0) ? r[0] * pp.inv_p : ea.c, slon = (pp.inv_p > 0.0) ? r[1] * pp.inv_p : ea.s;
+    double dw3[3][3];
+    wind_eci_tangent(r, pp.inv_p, clon, slon, pc.sl, pc.cl, wn, we, s0, s1, dh, dsl, dcl, dw3);
+    // ---- the transpose ----
+    // df_c: -(tm_c / m) dm
+    ldm = 0.0;
+#pragma unroll
+    for (int c = 0; c < 3; c++) ldm -= (((Td[c] + Fa[c]) * inv_m) * inv_m) * mu[c];
+    // X_c = (dT dir_c + T ddir_c) + (dFa_c - dka a_c)
+    const double lT = nu[0] * dir[0] + nu[1] * dir[1] + nu[2] * dir[2];
+    const double na = nu[0] * a[0] + nu[1] * a[1] + nu[2] * a[2];
+#pragma unroll
+    for (int c = 0; c < 3; c++) ldir[c] = T * nu[c];
+    // dka = rho darea ca s / 2;  dT = dthrust - nozzle dP dhd
+    g.area = (s2 > 0.0) ? (0.5 * pp.rho * ca * s) * (-na) : 0.0;
+    g.thrust = lT;
+    double lhd = -(ph.nozzle * at.dP) * lT;
+    // aero_force_tangent transposed (the head of this file); lFa = nu
+    double lda[3] = {-kk * nu[0], -kk * nu[1], -kk * nu[2]};
+    if (s2 > 0.0) {
+      const double h = 0.5 * ph.area * (-na);
+      const double lrho = h * (ca * s), lM = h * (pp.rho * cas * s);
+      const double ls = h * (pp.rho * ca) + pp.inv_a * lM;
+      const double linv_a = s * lM;
+#pragma unroll
+      for (int i = 0; i < 3; i++) lda[i] += (a[i] / s) * ls;
+      // drho = at.drho dhd, dinv_a = at.dinv_a dhd
+      lhd += at.drho * lrho + at.dinv_a * linv_a;
+    }
+    // da = (dv uv + Omega x dr) - dw
+#pragma unroll
+    for (int i = 0; i < 3; i++) lv[i] = P.uv * lda[i];
+    ldr[1] += kOmega * lda[0];
+    ldr[0] -= kOmega * lda[1];
+    const double ldw[3] = {-lda[0], -lda[1], -lda[2]};
+    // dw_i = sum_k dw3[k][i] dr_k + (dwn N_i + dwe E_i);  dhd = <dh, dr>
+#pragma unroll
+    for (int k = 0; k < 3; k++) ldr[k] += (dw3[k][0] * ldw[0] + dw3[k][1] * ldw[1] + dw3[k][2] * ldw[2]) + dh[k] * lhd;
+    const double lwn = (-pc.sl * clon) * ldw[0] + (-pc.sl * slon) * ldw[1] + pc.cl * ldw[2];
+    const double lwe = (-slon) * ldw[0] + clon * ldw[1];
+    // dwn = wn dfw, dwe = we dfw with the interpolated (unscaled) wind
+    g.fw = pp.wn * lwn + pp.we * lwe;
+  } else {
+    double gv[3];
+    gravity_eci(r, P.barC20, gv);
+    const double Td[3] = {ph.thrust * dir[0], ph.thrust * dir[1], ph.thrust * dir[2]};
+    accel_noair(Td, inv_m, gv, P.inv_uv, f);
+    ldm = 0.0;
+#pragma unroll
+    for (int c = 0; c < 3; c++) ldm -= ((Td[c] * inv_m) * inv_m) * mu[c];
+    g.thrust = nu[0] * dir[0] + nu[1] * dir[1] + nu[2] * dir[2];
+#pragma unroll
+    for (int c = 0; c < 3; c++) ldir[c] = ph.thrust * nu[c];
+  }
+#pragma unroll
+  for (int c = 0; c < 3; c++) F[4 + c] = f[c];
+  lxt[0] = ldm * P.um;
+#pragma unroll
+  for (int k = 0; k < 3; k++) lxt[1 + k] = ldr[k] * P.up;
+#pragma unroll
+  for (int c = 0; c < 3; c++) lxt[4 + c] = lF[1 + c] * vp + lv[c];
+  // the thrust direction's quadratic form, transposed (ddir of section_rhs_tangent read by columns)
+  double lq[4] = {2.0 * (q[0] * ldir[0] + q[3] * ldir[1] - q[2] * ldir[2]), 2.0 * (q[1] * ldir[0] + q[2] * ldir[1] + q[3] * ldir[2]),
+                  2.0 * (q[1] * ldir[1] - q[2] * ldir[0] - q[0] * ldir[2]), 2.0 * (q[0] * ldir[1] - q[3] * ldir[0] + q[1] * ldir[2])};
+  double fq[4] = {0.0, 0.0, 0.0, 0.0};
+  g.u0 = g.u1 = 0.0;
+  if (!ph.hold) {
+    quat_rate(q, u0, u1, P.uu, fq);
+    // bilinear in (q, u) (quat_rate()): the rate of dq under u read by columns, then the rate of q under du
+    const double d2r = 0.017453292519943295769;
+    const double oy = (u0 * P.uu) * d2r, oz = (u1 * P.uu) * d2r;
+    const double l0 = lF[7], l1 = lF[8], l2 = lF[9], l3 = lF[10];
+    lq[0] += 0.5 * (oy * l2 + oz * l3);
+    lq[1] += 0.5 * (oy * l3 - oz * l2);
+    lq[2] += 0.5 * (oz * l1 - oy * l0);
+    lq[3] += 0.5 * (-oz * l0 - oy * l1);
+    const double loy = 0.5 * (((q[0] * l2 + q[1] * l3) - q[2] * l0) - q[3] * l1);
+    const double loz = 0.5 * (((q[0] * l3 + q[2] * l1) - q[1] * l2) - q[3] * l0);
+    g.u0 = (loy * d2r) * P.uu;
+    g.u1 = (loz * d2r) * P.uu;
+  }
+#pragma unroll
+  for (int c = 0; c < 4; c++) { F[7 + c] = fq[c]; lxt[7 + c] = lq[c]; }
+}
+
+}  // namespace gel

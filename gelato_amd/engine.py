@@ -274,6 +274,56 @@ class PropagationPlan:
         check(lib().gel_prop_tangent_info(self._p, int(B), int(P), int(bool(shared)), info))
         return dict(zip(("sample_set_bytes", "lanes_per_slab", "slabs"), (int(v) for v in info)))
 
+    def adjoint(self, X, Lam, dispersion=None, shared=False):
+        """The flight of apply() and the gradients of Q functionals of it in one backward pass (gel_propagate_adjoint):
+        the transpose of the linear map tangent() applies.  X [B, nvars] (or [nvars]); Lam: the functionals as weights on Y,
+        [B, Q, 11 M] ([Q, 11 M] with shared=True: one set for every vector); dispersion: None or [B, S, 4].  Chain and section plans.
+        -> (Y [B, 11 M]: apply()'s Y bit for bit, GX [B, Q, nvars], GD [B, Q, S, 4], status)"""
+        self._live()
+        X = _f64(X).reshape(-1, self.nvars)
+        B = X.shape[0]
+        shared = bool(shared)
+        lam = np.asarray(Lam)
+        if lam.dtype != np.float64:
+            raise TypeError("Lam: float64")
+        if lam.ndim != (2 if shared else 3):
+            raise ValueError("adjoint: Lam is [Q, 11 M] with shared=True, else [B, Q, 11 M]")
+        Q = int(lam.shape[0] if shared else lam.shape[1])
+        if Q < 1:
+            raise ValueError("adjoint: at least one functional")
+        lam = self._seed(lam, "Lam", B, Q, shared, (11 * self.M,))
+        nd = _lib.GEL_PROP_NDISP
+        disp = None
+        if dispersion is not None:
+            disp = np.asarray(dispersion)
+            if disp.dtype != np.float64:
+                raise TypeError("dispersion: float64")
+            if disp.shape == (self.S, nd) and B == 1:
+                disp = disp[None]
+            if disp.shape != (B, self.S, nd):
+                raise ValueError("dispersion: [B, S, %d] = %s, not %s" % (nd, (B, self.S, nd), disp.shape))
+            disp = np.ascontiguousarray(disp)
+        Y = np.empty((B, 11 * self.M))
+        GX = np.empty((B, Q, self.nvars))
+        GD = np.empty((B, Q, self.S, nd))
+        rc = check(lib().gel_propagate_adjoint(self._p, B, Q, int(shared), _d(X), _d(disp) if disp is not None else None, _d(lam), _d(Y),
+                                               _d(GX), _d(GD)))
+        return Y, GX, GD, rc
+
+    def adjoint_device(self, B, Q, d_x, d_lam, d_y, d_gx, d_gdisp=0, d_dispersion=0, shared=False):
+        """device buffers: d_lam as adjoint() lays Lam out, d_y [B][11 M], d_gx [B][Q][nvars], d_gdisp [B][Q][S][4] or 0,
+        d_dispersion [B][S][4] or 0; asynchronous on the engine's own stream; status through Engine.sync()"""
+        self._live()
+        check(lib().gel_propagate_adjoint_device(self._p, int(B), int(Q), int(bool(shared)), d_x, d_dispersion or None, d_lam or None, d_y,
+                                                 d_gx, d_gdisp or None))
+
+    def adjoint_info(self, B, Q, shared=False):
+        """{"lane_bytes", "lanes_per_slab", "slabs"} of an adjoint call NOW (works on host-only handles)"""
+        self._live()
+        info = (C.c_int64 * 3)()
+        check(lib().gel_prop_adjoint_info(self._p, int(B), int(Q), int(bool(shared)), info))
+        return dict(zip(("lane_bytes", "lanes_per_slab", "slabs"), (int(v) for v in info)))
+
 
 def _ensemble_ptr(ensemble, owner):
     """the raw pointer of a live WindEnsemble (None for None); an ensemble of another engine is refused here, by name"""

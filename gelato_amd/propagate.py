@@ -265,3 +265,81 @@ def flight_jacobian(xdict_or_X, pdict, unitdict, steps=4, wrt=("initial", "dispe
         out["rows"] = np.swapaxes(r, 1, 2)
         out["status"] = max(out["status"], int(rc2), int(rc3))
     return out
+
+
+GRADIENT_OF = ("terminal", "rows")
+
+
+def flight_gradient(xdict_or_X, pdict, unitdict, steps=4, of=("terminal",), dispersion=None, engine=None):
+    """The gradients of functionals of the flight fly() reports (one chain, RK4 with 2 * steps steps per node interval) with respect to
+    EVERY input in one backward pass: the adjoint flight (PropagationPlan.adjoint), where flight_jacobian pays one
+    lane per column.  of = ("terminal",): the 11 components of the last state node in physical units (kg, m, m/s, 1);
+    of = ("rows", mu): mu [R] or [Q, R] multipliers on the engine's row table at x_flown -- Engine.con_rmatvec carries them to
+    [dy | du | dt]: the state part becomes the functional's weights on y, the u and t parts are added to the result (the mirror of
+    what flight_jacobian does with con_matvec).
+    -> {"functionals": names [Q], "status", "y" [B, 11 M], "x_flown" [B, nvars],
+        "gx" [B, Q, nvars]: the gradient with respect to the decision vector (its own units): the lift-off state, both state rows of
+                            every knot, ALL controls and the knot times; +0.0 where the flight does not read x,
+        "gdisp" [B, Q, S, 4]: with respect to the factors,
+        "columns" names [P] and "jacobian" [B, Q, P]: the entries flight_jacobian's columns name (jacobian_seeds with all four groups:
+                            "initial:*", "dispersion:*[s]", "time[i]", and "u*_bias[s]" = the sum over the phase's nodes)}"""
+    steps = int(steps)
+    if steps < 1:
+        raise ValueError("steps: at least 1")
+    of = tuple(of) if isinstance(of, (tuple, list)) else (of,)
+    if not of or of[0] not in GRADIENT_OF or len(of) != (1 if of[0] == "terminal" else 2):
+        raise ValueError('of: ("terminal",) or ("rows", mu)')
+    if engine is None:
+        S = pdict["num_sections"]
+        ps = pdict["ps_params"]
+        engine = Engine(con_dynamics.problem_arrays(pdict, unitdict), D=[ps.D(i) for i in range(S)],
+                        tau=[ps.tau(i) for i in range(S)])
+    X = pack_x(xdict_or_X) if isinstance(xdict_or_X, dict) else np.asarray(xdict_or_X, dtype=np.float64)
+    X = np.ascontiguousarray(X).reshape(-1, engine.nvars)
+    B, M, nv = X.shape[0], engine.M, engine.nvars
+    plan = engine.propagation_plan(steps=2 * steps, restart="chain")
+    try:
+        status, extra = 0, None
+        if of[0] == "terminal":
+            u = engine.units
+            last = M - 1
+            idx = [last] + [M + 3 * last + c for c in range(3)] + [4 * M + 3 * last + c for c in range(3)] + [7 * M + 4 * last + c for c in range(4)]
+            scale = np.array([u[0]] + [u[1]] * 3 + [u[2]] * 3 + [1.0] * 4)
+            names = ["terminal:%s" % n for n in _STATE_NAMES]
+            lam = np.zeros((11, 11 * M))
+            lam[np.arange(11), idx] = 1.0
+            shared = True
+        else:
+            if not engine._nlin + engine._nfn:
+                raise ValueError('of=("rows", mu): the engine has no row table')
+            mu = np.asarray(of[1], dtype=np.float64)
+            R = engine._nlin + engine._nfn
+            if mu.ndim not in (1, 2) or mu.shape[-1] != R:
+                raise ValueError("mu: [R] or [Q, R] with R = %d rows" % R)
+            mu = mu.reshape(-1, R)
+            Q = mu.shape[0]
+            names = ["rows:mu[%d]" % q for q in range(Q)]
+            Y0, _err, rc0 = plan.apply(X, want_err=False, dispersion=dispersion)
+            x_fl = X.copy()
+            x_fl[:, :11 * M] = Y0
+            _con, jfn, rc1 = engine.rows_eval(x_fl, want_jac=True)
+            jf = np.ascontiguousarray(np.broadcast_to(jfn[:, None], (B, Q) + jfn.shape[1:]))
+            g, rc2 = engine.con_rmatvec(np.ascontiguousarray(np.broadcast_to(mu[None], (B, Q, R))), jfn=jf)
+            status = max(int(rc0), int(rc1), int(rc2))
+            lam = np.ascontiguousarray(g[:, :, :11 * M])
+            extra = g[:, :, 11 * M:]          # the rows' own dependence on u and t
+            scale = np.ones(Q)
+            shared = False
+        Y, GX, GD, rc = plan.adjoint(X, lam, dispersion=dispersion, shared=shared)
+    finally:
+        plan.close()
+    GX = GX * scale[None, :, None]
+    GD = GD * scale[None, :, None, None]
+    if extra is not None:
+        GX[:, :, 11 * M:] += extra
+    x_flown = X.copy()
+    x_flown[:, :11 * M] = Y
+    cols, dX, dD = jacobian_seeds(engine.num_nodes, engine.prob["attitude_hold"], JACOBIAN_GROUPS)
+    jac = np.einsum("bqv,pv->bqp", GX, dX) + np.einsum("bqsf,psf->bqp", GD, dD)
+    return {"functionals": names, "status": max(status, int(rc)), "y": Y, "x_flown": x_flown, "gx": GX, "gdisp": GD, "columns": cols,
+            "jacobian": jac}

@@ -669,6 +669,52 @@ int gel_propagate_tangent_device(gel_prop_plan* plan, int32_t B, int32_t P, int3
  * (vector, direction) per slab a call will use NOW, slabs of a call of B vectors; works on GEL_DEVICE_NONE handles */
 int gel_prop_tangent_info(const gel_prop_plan* plan, int32_t B, int32_t P, int32_t shared, int64_t* info /* [3] */);
 
+/* ---- adjoint flight: gradients of the flown trajectory in one pass.  Let T = [T_x | T_d] be the linear map
+ *      gel_propagate_tangent* applies, dy = T_x dx + T_d ddisp, as it is coded (its conventions at kinks, the zero time tangent of
+ *      F, djump, dS = (dtf - dto) unit_t / 2).  gel_propagate_adjoint* returns the y of gel_propagate_dispersed* on the same plan, x
+ *      and disp -- bit for bit -- and, for Q functionals per vector given as weights lam on y,
+ *        gx [B][Q][nvars] = T_x^T lam        gdisp [B][Q][S][GEL_PROP_NDISP] = T_d^T lam   (gdisp may be NULL: not wanted).
+ *      lam is laid out like y: [B][Q][11 M], or with shared = 1 one set [Q][11 M] for every vector.  Any node's rows may carry
+ *      weight; a terminal functional is a lam that is zero except in the last node's rows.  Entries of gx for inputs the value call
+ *      does not read (state rows that start no segment and lie at no chain knot, a hold phase's controls) are +0.0; every element
+ *      of gx and gdisp is written by every call.
+ *      Chain (GEL_PROP_CHAIN) and section plans.  GEL_PROP_RESTART_NODE plans are refused: neighbouring node segments share a stage
+ *      point, whose control multiplier would need a second accumulation path.  Wind ensembles are out of scope.
+ *      The value flight runs first; its y(node j) is the checkpoint interval j restarts from.  Then every (vector, functional) walks
+ *      backwards -- phases S - 1 .. 0 (chain), intervals n - 1 .. 0, steps k - 1 .. 0 -- and every step is the transpose of the
+ *      tangent's step, term by term in this order (l = the multiplier of the step's end state; F1 .. F3 recomputed with the value's
+ *      own lines from the step's start: the node's checkpoint, or an inner checkpoint -- per node interval the k - 1 value steps to
+ *      the starts of its later steps are integrated once more and kept per lane):
+ *        lacc = (Sh / 6) l;   lF4 = lacc;  lF3 = fma(Sh, lyt4, 2 lacc);  lF2 = fma(Sh/2, lyt3, 2 lacc);  lF1 = fma(Sh/2, lyt2, lacc)
+ *        with (lyt_i, lu_i, lfactors_i) = (J^T, (dF/du)^T, (dF/dfactors)^T) lF_i at stage i's point, the same partials as the tangent;
+ *        l <- l + (((lyt4 + lyt3) + lyt2) + lyt1);
+ *        gS <- fma(h_j, <l, acc> / 6 + <lyt4, F3> + <lyt3, F2> / 2 + <lyt2, F1> / 2, gS)      (l before its update, acc the value's)
+ *      lam's rows of a node are added to l where the walk passes the node.  A segment's start row gets l; across a chain knot
+ *      gx(first node of s + 1) = l, gx(last node of s) = 0 - l, and l carries on.  The factors' multipliers are summed over a
+ *      phase's stages in walk order and multiplied by the handle's thrust, mf_um and area (the wind factor's by 1).  The stage
+ *      points' control multipliers are stored once each (a step's end point: stage 4's plus stage 1's of the step after it; its
+ *      midpoint: stage 2's + stage 3's) and carried to the nodes by the transposed sampler: gu(node j) = one fma chain over the
+ *      stage points in ascending order of Wu[p][j] lu(p), in which a point that IS a node is skipped (the value call copies the
+ *      node there) and added to that node's result instead.  Knot times: gt(s) = ((gS(s - 1) - gS(s)) unit_t) / 2, gS(-1) = gS(S) = 0.
+ *      No atomic operation anywhere: every output has one writer and the order above.  The result is linear in lam with no additive
+ *      constant: lam == 0 gives zeros, lam times 2^k gives the outputs times 2^k bit for bit.  Functional q's bits depend neither on
+ *      Q, nor on B, nor on the vector's position in the batch, nor on the slab size, nor on shared.
+ *      Status: a non-finite y, gx or gdisp raises the source handle's status as gel_propagate* does; the other (vector, functional)
+ *      slices stay valid.  Refusals (GEL_ERR_ARG, decided before a buffer is looked at, the reason in gel_last_error): Q < 1;
+ *      B Q > 2^31 - 1; lam == NULL; shared not 0 or 1; a host-only handle; a GEL_PROP_RESTART_NODE plan; a workspace that does not fit
+ *      the plan's 1 GB cap for 64 vectors.  B = 0 succeeds and touches nothing.
+ *      The workspace holds one sample set per vector and, per (vector, functional), the stage points' control multipliers (as many
+ *      bytes again), one double per phase and 88 (max steps[s] - 1) bytes of inner checkpoints; a larger batch is walked in slabs, GEL_PROP_SLAB (vectors) as above.  The device form
+ *      takes no stream argument: it enqueues on the handle's own stream and reports through gel_sync(src, NULL). ---- */
+int gel_propagate_adjoint(gel_prop_plan* plan, int32_t B, int32_t Q, int32_t shared, const double* x, const double* disp /* or NULL */,
+                          const double* lam, double* y, double* gx, double* gdisp /* or NULL */);
+int gel_propagate_adjoint_device(gel_prop_plan* plan, int32_t B, int32_t Q, int32_t shared, const double* d_x,
+                                 const double* d_disp /* or NULL */, const double* d_lam, double* d_y, double* d_gx,
+                                 double* d_gdisp /* or NULL */);
+/* info [3]: workspace bytes per lane (vector, functional), lanes per slab a call will use NOW, slabs of a call of B vectors;
+ * refuses what the calls refuse, except that it works on GEL_DEVICE_NONE handles */
+int gel_prop_adjoint_info(const gel_prop_plan* plan, int32_t B, int32_t Q, int32_t shared, int64_t* info /* [3] */);
+
 /* ---- one optimiser callback = one device round trip: the four defect groups, the knot / terminal / user row table and the
  *      aero path constraints of ONE decision vector launched back to back on the handle's stream, one synchronise
  *      (what objfunc / sens of Trajectory_Optimization.py:194-312 need from the device).  Every output pointer may be
