@@ -187,6 +187,10 @@ SIGNATURES = {
     "gel_wind_ensemble_assign": (C.c_int, [C.c_void_p, C.c_int32, _ip]),
     "gel_propagate_ensemble": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, C.c_void_p, _dp, _dp]),
     "gel_propagate_ensemble_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "gel_propagate_tangent_ensemble": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp, C.c_void_p, _dp, _dp]),
+    "gel_propagate_tangent_ensemble_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 7),
+    "gel_propagate_adjoint_ensemble": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp, C.c_void_p, _dp, _dp, _dp]),
+    "gel_propagate_adjoint_ensemble_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 7),
     "gel_output_table_batch_ensemble": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, _dp, C.c_void_p, C.c_double, C.c_double, C.c_int32, _ip,
                                                   _dp, _dp, _dp]),
     "gel_output_table_batch_ensemble_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,

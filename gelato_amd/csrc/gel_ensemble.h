@@ -33,6 +33,12 @@ GEL_DEV Tables ens_lane_tables(const ProblemDev& P, const Tables& tb, const EnsD
   t.winds = w + (own ? 3 * P.Kw + 2 * P.Kc : 3 * E.Kw);
   return t;
 }
+// The same view for the lane of vector v of the launch (v counts from the slab's first vector, as member does): what the tangent
+// and the adjoint flight take.  Their tb already lies in global memory, atmosphere and CA included; only the wind
+// part changes.
+GEL_DEV Tables ens_lane_view(const ProblemDev& P, const Tables& tb, int v, const EnsDev& E) {
+  return ens_lane_tables(P, tb, E, E.member[v]);
+}
 #endif
 
 }  // namespace gel

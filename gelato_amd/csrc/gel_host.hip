@@ -3252,7 +3252,7 @@ static int64_t proptan_slab(const gel_prop_plan* pl, int64_t P, bool shared) {
 }
 
 static int proptan_check(const char* who, const gel_prop_plan* plan, int32_t B, int32_t P, int32_t shared, const void* x, const void* dx,
-                         const void* ddisp, const void* y, const void* dy) {
+                         const void* ddisp, const gel_wind_ensemble* ens, const void* y, const void* dy) {
   const std::string w(who);
   if (!plan) return fail(GEL_ERR_ARG, w + ": null plan");
   if (B < 0) return fail(GEL_ERR_ARG, w + ": B < 0");
@@ -3261,6 +3261,7 @@ static int proptan_check(const char* who, const gel_prop_plan* plan, int32_t B, 
   if (shared != 0 && shared != 1) return fail(GEL_ERR_ARG, w + ": shared is neither 0 nor 1");
   if (!dx && !ddisp) return fail(GEL_ERR_ARG, w + ": both seeds (dx, ddisp) are NULL");
   if (B > 0 && (!x || !y || !dy)) return fail(GEL_ERR_ARG, w + ": x, y or dy is NULL with B > 0");
+  if (int rc = ens_check(who, ens, plan->src, B)) return rc;
   if (plan->src->device == GEL_DEVICE_NONE) return fail(GEL_ERR_ARG, w + ": the plan's handle is host-only (GEL_DEVICE_NONE)");
   const int64_t set = 16 * plan->sampled_pts;
   if ((shared ? set * (((int64_t)P + 63) / 64 * 64 + 64) : set * 64 * (1 + (int64_t)P)) > kPropWsBytes)
@@ -3281,7 +3282,8 @@ int gel_prop_tangent_info(const gel_prop_plan* plan, int32_t B, int32_t P, int32
 // the launches of one call on stream s, slab after slab: the control samples of the slab's vectors, those of its seeds (the shared
 // seeds' once, before the first slab), the integration
 static int proptan_enqueue(gel_prop_plan* plan, int32_t B, int32_t P, int32_t shared, const double* d_x, const double* d_disp,
-                           const double* d_dx, const double* d_ddisp, double* d_y, double* d_dy, hipStream_t s) {
+                           const double* d_dx, const double* d_ddisp, const gel_wind_ensemble* ens, double* d_y, double* d_dy,
+                           hipStream_t s) {
   gel_problem* p = plan->src;
   const int64_t vs = proptan_slab(plan, P, shared != 0), ldv = std::min<int64_t>(vs, ((int64_t)B + 63) / 64 * 64);
   const int64_t dld = d_dx ? (shared ? ((int64_t)P + 63) / 64 * 64 : ldv * P) : 0;
@@ -3318,34 +3320,56 @@ static int proptan_enqueue(gel_prop_plan* plan, int32_t B, int32_t P, int32_t sh
     a.y = d_y + (size_t)v0 * ny;
     a.dy = d_dy + l0 * ny;
     a.ws = ws; a.dws = dws; a.ld = ldv; a.dld = dld;
-    HIPCHK(gel::launch_proptan_slab(p->dev, plan->dev, a, s));
+    HIPCHK(gel::launch_proptan_slab(p->dev, plan->dev, a, ens_dev(ens, v0), s));
   }
   return GEL_OK;
 }
 
-int gel_propagate_tangent_device(gel_prop_plan* plan, int32_t B, int32_t P, int32_t shared, const double* d_x, const double* d_disp,
-                                 const double* d_dx, const double* d_ddisp, double* d_y, double* d_dy) {
-  if (int rc = proptan_check("gel_propagate_tangent_device", plan, B, P, shared, d_x, d_dx, d_ddisp, d_y, d_dy)) return rc;
+// (the refusals name the entry point the caller used: with an ensemble the _ensemble one)
+static int proptan_device(const char* who, gel_prop_plan* plan, int32_t B, int32_t P, int32_t shared, const double* d_x, const double* d_disp,
+                          const double* d_dx, const double* d_ddisp, gel_wind_ensemble* ens, double* d_y, double* d_dy) {
+  if (int rc = proptan_check(who, plan, B, P, shared, d_x, d_dx, d_ddisp, ens, d_y, d_dy)) return rc;
   if (B == 0) return GEL_OK;
   gel_problem* p = plan->src;
   HIPCHK(hipSetDevice(p->device));
-  return proptan_enqueue(plan, B, P, shared, d_x, d_disp, d_dx, d_ddisp, d_y, d_dy, p->stream.get());
+  return proptan_enqueue(plan, B, P, shared, d_x, d_disp, d_dx, d_ddisp, ens, d_y, d_dy, p->stream.get());
 }
 
-int gel_propagate_tangent(gel_prop_plan* plan, int32_t B, int32_t P, int32_t shared, const double* x, const double* disp, const double* dx,
-                          const double* ddisp, double* y, double* dy) {
-  if (int rc = proptan_check("gel_propagate_tangent", plan, B, P, shared, x, dx, ddisp, y, dy)) return rc;
+int gel_propagate_tangent_ensemble_device(gel_prop_plan* plan, int32_t B, int32_t P, int32_t shared, const double* d_x, const double* d_disp,
+                                          const double* d_dx, const double* d_ddisp, gel_wind_ensemble* ens, double* d_y, double* d_dy) {
+  return proptan_device("gel_propagate_tangent_ensemble_device", plan, B, P, shared, d_x, d_disp, d_dx, d_ddisp, ens, d_y, d_dy);
+}
+
+int gel_propagate_tangent_device(gel_prop_plan* plan, int32_t B, int32_t P, int32_t shared, const double* d_x, const double* d_disp,
+                                 const double* d_dx, const double* d_ddisp, double* d_y, double* d_dy) {
+  return proptan_device("gel_propagate_tangent_device", plan, B, P, shared, d_x, d_disp, d_dx, d_ddisp, nullptr, d_y, d_dy);
+}
+
+static int proptan_host(const char* who, gel_prop_plan* plan, int32_t B, int32_t P, int32_t shared, const double* x, const double* disp,
+                        const double* dx, const double* ddisp, gel_wind_ensemble* ens, double* y, double* dy) {
+  if (int rc = proptan_check(who, plan, B, P, shared, x, dx, ddisp, ens, y, dy)) return rc;
   if (B == 0) return GEL_OK;
   gel_problem* p = plan->src;
   HIPCHK(hipSetDevice(p->device));
   const size_t nv = (size_t)p->dims.num_vars, ny = (size_t)11 * p->dims.M, nd = (size_t)p->dims.S * GEL_PROP_NDISP;
   const size_t seeds = shared ? (size_t)P : (size_t)B * P;
-  // (x, y, disp as gel_propagate_dispersed lays them out; the new buffers behind them)
+  // (x, y, disp as gel_propagate_dispersed lays them out; the new buffers behind them; the ensemble's members and assignment are
+  // resident: the arena holds what it held)
   return staged_call(p, 0, {staged_in(x, (size_t)B * nv), staged_out(y, (size_t)B * ny), staged_in(disp, (size_t)B * nd),
                             staged_in(dx, seeds * nv), staged_in(ddisp, seeds * nd), staged_out(dy, (size_t)B * P * ny)},
                      [&](const gel::ProblemDev&, double* const* a) {
-                       return proptan_enqueue(plan, B, P, shared, a[0], a[2], a[3], a[4], a[1], a[5], p->stream.get());
+                       return proptan_enqueue(plan, B, P, shared, a[0], a[2], a[3], a[4], ens, a[1], a[5], p->stream.get());
                      });
+}
+
+int gel_propagate_tangent_ensemble(gel_prop_plan* plan, int32_t B, int32_t P, int32_t shared, const double* x, const double* disp,
+                                   const double* dx, const double* ddisp, gel_wind_ensemble* ens, double* y, double* dy) {
+  return proptan_host("gel_propagate_tangent_ensemble", plan, B, P, shared, x, disp, dx, ddisp, ens, y, dy);
+}
+
+int gel_propagate_tangent(gel_prop_plan* plan, int32_t B, int32_t P, int32_t shared, const double* x, const double* disp, const double* dx,
+                          const double* ddisp, double* y, double* dy) {
+  return proptan_host("gel_propagate_tangent", plan, B, P, shared, x, disp, dx, ddisp, nullptr, y, dy);
 }
 
 // ------------- adjoint flight: gradients of the flown trajectory in one pass -------------
@@ -3390,10 +3414,11 @@ static int propadj_refuse(const char* who, const gel_prop_plan* plan, int32_t B,
 }
 
 static int propadj_check(const char* who, const gel_prop_plan* plan, int32_t B, int32_t Q, int32_t shared, const void* x, const void* lam,
-                         const void* y, const void* gx) {
+                         const gel_wind_ensemble* ens, const void* y, const void* gx) {
   const std::string w(who);
   if (plan && !lam) return fail(GEL_ERR_ARG, w + ": lam is NULL");
   if (int rc = propadj_refuse(who, plan, B, Q, shared)) return rc;
+  if (int rc = ens_check(who, ens, plan->src, B)) return rc;
   if (plan->src->device == GEL_DEVICE_NONE) return fail(GEL_ERR_ARG, w + ": the plan's handle is host-only (GEL_DEVICE_NONE)");
   if (B > 0 && (!x || !y || !gx)) return fail(GEL_ERR_ARG, w + ": x, y or gx is NULL with B > 0");
   return GEL_OK;
@@ -3409,10 +3434,11 @@ int gel_prop_adjoint_info(const gel_prop_plan* plan, int32_t B, int32_t Q, int32
   return GEL_OK;
 }
 
-// the launches of one call on stream s, slab after slab: the control samples and the value flight (y: the checkpoints), the backward
-// walk, the transposed sampler with the knot times
+// the launches of one call on stream s, slab after slab: the control samples and the value flight (y: the checkpoints; under an
+// ensemble gel_propagate_ensemble*'s launch, so that the checkpoints are that flight's bits), the backward walk, the transposed
+// sampler with the knot times
 static int propadj_enqueue(gel_prop_plan* plan, int32_t B, int32_t Q, int32_t shared, const double* d_x, const double* d_disp,
-                           const double* d_lam, double* d_y, double* d_gx, double* d_gdisp, hipStream_t s) {
+                           const double* d_lam, const gel_wind_ensemble* ens, double* d_y, double* d_gx, double* d_gdisp, hipStream_t s) {
   gel_problem* p = plan->src;
   const int64_t vs = propadj_slab(plan, Q), ldv = std::min<int64_t>(vs, ((int64_t)B + 63) / 64 * 64);
   const int64_t gld = ldv * Q;
@@ -3428,12 +3454,12 @@ static int propadj_enqueue(gel_prop_plan* plan, int32_t B, int32_t Q, int32_t sh
   double* const gS = gws + (size_t)gld * set;    // the third: the multiplier of S per (phase, lane)
   double* const ck = gS + (size_t)gld * (size_t)plan->dev.S;   // the fourth: the inner checkpoints of the interval in hand
   const size_t nv = (size_t)p->dims.num_vars, ny = (size_t)11 * p->dims.M, nd = (size_t)p->dims.S * GEL_PROP_NDISP;
-  const gel::EnsDev no_ens{};
   for (int64_t v0 = 0; v0 < B; v0 += vs) {
     const int nb = (int)std::min<int64_t>(vs, B - v0);
     const double* const disp = d_disp ? d_disp + (size_t)v0 * nd : nullptr;
+    const gel::EnsDev e = ens_dev(ens, v0);   // the slab's part of the assignment, for the value flight and the walk alike
     HIPCHK(gel::launch_prop_slab(p->dev, plan->dev, plan->ph.data(), plan->n_max_sampled, nb, d_x + (size_t)v0 * nv, d_y + (size_t)v0 * ny, ws,
-                                 ldv, disp, no_ens, s));
+                                 ldv, disp, e, s));
     const size_t l0 = (size_t)v0 * Q;   // the slab's first lane
     gel::PropAdjArgs a{};
     a.nb = nb; a.Q = Q; a.shared = shared;
@@ -3444,23 +3470,33 @@ static int propadj_enqueue(gel_prop_plan* plan, int32_t B, int32_t Q, int32_t sh
     a.gx = d_gx + l0 * nv;
     a.gdisp = d_gdisp ? d_gdisp + l0 * nd : nullptr;
     a.ws = ws; a.gws = gws; a.gS = gS; a.ck = ck; a.ld = ldv; a.gld = gld;
-    HIPCHK(gel::launch_propadj_slab(p->dev, plan->dev, a, s));
+    HIPCHK(gel::launch_propadj_slab(p->dev, plan->dev, a, e, s));
   }
   return GEL_OK;
 }
 
-int gel_propagate_adjoint_device(gel_prop_plan* plan, int32_t B, int32_t Q, int32_t shared, const double* d_x, const double* d_disp,
-                                 const double* d_lam, double* d_y, double* d_gx, double* d_gdisp) {
-  if (int rc = propadj_check("gel_propagate_adjoint_device", plan, B, Q, shared, d_x, d_lam, d_y, d_gx)) return rc;
+static int propadj_device(const char* who, gel_prop_plan* plan, int32_t B, int32_t Q, int32_t shared, const double* d_x, const double* d_disp,
+                          const double* d_lam, gel_wind_ensemble* ens, double* d_y, double* d_gx, double* d_gdisp) {
+  if (int rc = propadj_check(who, plan, B, Q, shared, d_x, d_lam, ens, d_y, d_gx)) return rc;
   if (B == 0) return GEL_OK;
   gel_problem* p = plan->src;
   HIPCHK(hipSetDevice(p->device));
-  return propadj_enqueue(plan, B, Q, shared, d_x, d_disp, d_lam, d_y, d_gx, d_gdisp, p->stream.get());
+  return propadj_enqueue(plan, B, Q, shared, d_x, d_disp, d_lam, ens, d_y, d_gx, d_gdisp, p->stream.get());
 }
 
-int gel_propagate_adjoint(gel_prop_plan* plan, int32_t B, int32_t Q, int32_t shared, const double* x, const double* disp, const double* lam,
-                          double* y, double* gx, double* gdisp) {
-  if (int rc = propadj_check("gel_propagate_adjoint", plan, B, Q, shared, x, lam, y, gx)) return rc;
+int gel_propagate_adjoint_ensemble_device(gel_prop_plan* plan, int32_t B, int32_t Q, int32_t shared, const double* d_x, const double* d_disp,
+                                          const double* d_lam, gel_wind_ensemble* ens, double* d_y, double* d_gx, double* d_gdisp) {
+  return propadj_device("gel_propagate_adjoint_ensemble_device", plan, B, Q, shared, d_x, d_disp, d_lam, ens, d_y, d_gx, d_gdisp);
+}
+
+int gel_propagate_adjoint_device(gel_prop_plan* plan, int32_t B, int32_t Q, int32_t shared, const double* d_x, const double* d_disp,
+                                 const double* d_lam, double* d_y, double* d_gx, double* d_gdisp) {
+  return propadj_device("gel_propagate_adjoint_device", plan, B, Q, shared, d_x, d_disp, d_lam, nullptr, d_y, d_gx, d_gdisp);
+}
+
+static int propadj_host(const char* who, gel_prop_plan* plan, int32_t B, int32_t Q, int32_t shared, const double* x, const double* disp,
+                        const double* lam, gel_wind_ensemble* ens, double* y, double* gx, double* gdisp) {
+  if (int rc = propadj_check(who, plan, B, Q, shared, x, lam, ens, y, gx)) return rc;
   if (B == 0) return GEL_OK;
   gel_problem* p = plan->src;
   HIPCHK(hipSetDevice(p->device));
@@ -3470,8 +3506,18 @@ int gel_propagate_adjoint(gel_prop_plan* plan, int32_t B, int32_t Q, int32_t sha
   return staged_call(p, 0, {staged_in(x, (size_t)B * nv), staged_out(y, (size_t)B * ny), staged_in(disp, (size_t)B * nd),
                             staged_in(lam, (shared ? (size_t)Q : lanes) * ny), staged_out(gx, lanes * nv), staged_out(gdisp, lanes * nd)},
                      [&](const gel::ProblemDev&, double* const* a) {
-                       return propadj_enqueue(plan, B, Q, shared, a[0], a[2], a[3], a[1], a[4], a[5], p->stream.get());
+                       return propadj_enqueue(plan, B, Q, shared, a[0], a[2], a[3], ens, a[1], a[4], a[5], p->stream.get());
                      });
+}
+
+int gel_propagate_adjoint_ensemble(gel_prop_plan* plan, int32_t B, int32_t Q, int32_t shared, const double* x, const double* disp,
+                                   const double* lam, gel_wind_ensemble* ens, double* y, double* gx, double* gdisp) {
+  return propadj_host("gel_propagate_adjoint_ensemble", plan, B, Q, shared, x, disp, lam, ens, y, gx, gdisp);
+}
+
+int gel_propagate_adjoint(gel_prop_plan* plan, int32_t B, int32_t Q, int32_t shared, const double* x, const double* disp, const double* lam,
+                          double* y, double* gx, double* gdisp) {
+  return propadj_host("gel_propagate_adjoint", plan, B, Q, shared, x, disp, lam, nullptr, y, gx, gdisp);
 }
 
 // ------------- Jacobian products from the compact values -------------

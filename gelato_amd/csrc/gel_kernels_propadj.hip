@@ -50,8 +50,12 @@ __device__ __forceinline__ size_t state_index(int M, int xi, int c) {
 }
 }  // namespace
 
-template <bool kChain>
-__global__ __launch_bounds__(kPropAdjThreads) void propadj_kernel(ProblemDev P, PropDev Pd, PropAdjArgs A) {
+// kEns = 1 (gel_propagate_adjoint_ensemble*): as proptan_kernel's -- an EnsDev behind the arguments (the pack Ens
+// holds exactly that one; none with kEns = 0, whose instantiations keep their argument list), and the lane's view of the tables
+// (ens_lane_tables) in every call that reads the wind: the inner checkpoints' value steps, F1 .. F3 and the four reversed stages.
+template <bool kChain, int kEns = 0, typename... Ens>
+__global__ __launch_bounds__(kPropAdjThreads) void propadj_kernel(ProblemDev P, PropDev Pd, PropAdjArgs A, Ens... ens) {
+  static_assert(sizeof...(Ens) == (kEns ? 1 : 0), "an EnsDev behind the arguments with kEns = 1, nothing otherwise");
   constexpr int T = kPropAdjThreads;
   __shared__ double Fs[3 * 11 * T];   // F1 .. F3 of the step in hand: [stage][component][lane]
   const long long nl = (long long)A.nb * A.Q;
@@ -63,6 +67,8 @@ __global__ __launch_bounds__(kPropAdjThreads) void propadj_kernel(ProblemDev P, 
   if (seg >= Pd.nseg || l >= nl) return;   // (idle lanes leave: they stay out of the calm-air vote of wind_eci_or_calm; no barrier follows)
   double* const Fl = Fs + threadIdx.x;     // the lane's column: no other lane reads or writes it
   const int v = (int)(l / A.Q), qf = (int)(l - (long long)v * A.Q);
+  Tables tbe = tb;   // under an ensemble: the lane's view (the wind part of its vector's member)
+  if constexpr (kEns != 0) tbe = ens_lane_view(P, tb, v, ens...);
   const int M = P.M, N = P.N;
   const double* const xb = A.x + (size_t)v * P.nvars;
   const double* const yb = A.y + (size_t)v * 11 * (size_t)M;
@@ -128,7 +134,7 @@ __global__ __launch_bounds__(kPropAdjThreads) void propadj_kernel(ProblemDev P, 
               u0 = us[(size_t)pp * 2 * (size_t)A.ld];
               u1 = us[((size_t)pp * 2 + 1) * (size_t)A.ld];
             }
-            section_rhs<true>(P, ph, tb, Pd.vp, sig[pp], to, tf, yt, u0, u1, F, fw);
+            section_rhs<true>(P, ph, kEns ? tbe : tb, Pd.vp, sig[pp], to, tf, yt, u0, u1, F, fw);
 #pragma unroll
             for (int c = 0; c < 11; c++) acc[c] = st ? __builtin_fma(w, F[c], acc[c]) : F[c];
           }
@@ -159,7 +165,7 @@ __global__ __launch_bounds__(kPropAdjThreads) void propadj_kernel(ProblemDev P, 
               u0 = us[(size_t)pp * 2 * (size_t)A.ld];
               u1 = us[((size_t)pp * 2 + 1) * (size_t)A.ld];
             }
-            section_rhs<true>(P, ph, tb, Pd.vp, sig[pp], to, tf, yt, u0, u1, F, fw);
+            section_rhs<true>(P, ph, kEns ? tbe : tb, Pd.vp, sig[pp], to, tf, yt, u0, u1, F, fw);
 #pragma unroll
             for (int c = 0; c < 11; c++) Fl[(st * 11 + c) * T] = F[c];
           }
@@ -189,7 +195,7 @@ __global__ __launch_bounds__(kPropAdjThreads) void propadj_kernel(ProblemDev P, 
           }
           double F[11], lx[11];
           RhsAdjoint g;
-          section_rhs_adjoint(P, ph, tb, Pd.vp, sig[pp], to, tf, yt, u0, u1, fw, lF, F, lx, g);
+          section_rhs_adjoint(P, ph, kEns ? tbe : tb, Pd.vp, sig[pp], to, tf, yt, u0, u1, fw, lF, F, lx, g);
           if (st == 3) {   // <lm, acc> / 6 with acc of the value lines
             double d = 0.0;
 #pragma unroll
@@ -322,7 +328,7 @@ __global__ __launch_bounds__(kPropAdjSampleThreads) void prop_sample_t_kernel(Pr
   if (bad) *(volatile int32_t*)P.flag = 1;
 }
 
-hipError_t launch_propadj_slab(const ProblemDev& P, const PropDev& Pd, const PropAdjArgs& A, hipStream_t s) {
+hipError_t launch_propadj_slab(const ProblemDev& P, const PropDev& Pd, const PropAdjArgs& A, const EnsDev& ens, hipStream_t s) {
   if (A.nb <= 0 || A.Q <= 0) return hipSuccess;
   if (Pd.restart) return hipErrorInvalidValue;
   const long long nl = (long long)A.nb * A.Q;
@@ -332,8 +338,13 @@ hipError_t launch_propadj_slab(const ProblemDev& P, const PropDev& Pd, const Pro
   const long long sgrid = (nl + kPropAdjSampleThreads - 1) / kPropAdjSampleThreads * ((long long)P.N + 1);
   if (grid <= 0) return hipSuccess;
   if (grid > 0x7fffffffLL || sgrid > 0x7fffffffLL) return hipErrorInvalidValue;
-  auto* const kern = Pd.chain ? propadj_kernel<true> : propadj_kernel<false>;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kPropAdjThreads), 0, s, P, Pd, A);
+  if (ens.tables) {
+    auto* const kern = Pd.chain ? propadj_kernel<true, 1, EnsDev> : propadj_kernel<false, 1, EnsDev>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kPropAdjThreads), 0, s, P, Pd, A, ens);
+  } else {
+    auto* const kern = Pd.chain ? propadj_kernel<true> : propadj_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kPropAdjThreads), 0, s, P, Pd, A);
+  }
   if (const hipError_t e = hipGetLastError()) return e;
   hipLaunchKernelGGL(prop_sample_t_kernel, dim3((unsigned)sgrid), dim3(kPropAdjSampleThreads), 0, s, P, Pd, nl,
                      (const double*)A.gws, (const double*)A.gS, A.gld, A.gx);

@@ -38,8 +38,14 @@ __device__ __forceinline__ size_t state_index(int M, int xi, int c) {
 }
 }  // namespace
 
-template <bool kChain>
-__global__ __launch_bounds__(kPropThreads) void proptan_kernel(ProblemDev P, PropDev Pd, PropTanArgs A) {
+// kEns = 1 (gel_propagate_tangent_ensemble*): the kernel takes an EnsDev behind its arguments -- the pack Ens holds
+// exactly that one argument, and none with kEns = 0, whose instantiations keep their argument list -- and the lane looks the wind
+// up in the table its vector is assigned (ens_lane_tables; -1: the handle's own).  The view replaces tb in the ONE call that reads
+// the wind, so the value, the slope of the interval the value lookup took (dw3) and the clamps all come from the member's rows.
+// Every lookup searches (wind_ned2_centre): the interval is that of the member's handle, and so are the bits.
+template <bool kChain, int kEns = 0, typename... Ens>
+__global__ __launch_bounds__(kPropThreads) void proptan_kernel(ProblemDev P, PropDev Pd, PropTanArgs A, Ens... ens) {
+  static_assert(sizeof...(Ens) == (kEns ? 1 : 0), "an EnsDev behind the arguments with kEns = 1, nothing otherwise");
   const long long nl = (long long)A.nb * A.P;
   const long long ngrp = (nl + kPropThreads - 1) / kPropThreads;
   const int seg = kChain ? 0 : (int)(blockIdx.x / ngrp);
@@ -48,6 +54,8 @@ __global__ __launch_bounds__(kPropThreads) void proptan_kernel(ProblemDev P, Pro
   const long long l = grp * kPropThreads + (long long)threadIdx.x;
   if (seg >= Pd.nseg || l >= nl) return;   // (idle lanes leave: they stay out of the calm-air vote of wind_eci_or_calm; no barrier follows)
   const int v = (int)(l / A.P), p = (int)(l - (long long)v * A.P);
+  Tables tbe = tb;   // under an ensemble: the lane's view (the wind part of its vector's member)
+  if constexpr (kEns != 0) tbe = ens_lane_view(P, tb, v, ens...);
   const size_t ls = A.shared ? (size_t)p : (size_t)l;   // the lane's seed set
   bool bad = false;
   double yv[11], dyv[11];
@@ -145,7 +153,7 @@ __global__ __launch_bounds__(kPropThreads) void proptan_kernel(ProblemDev P, Pro
               d.du1 = dus[((size_t)pp * 2 + 1) * (size_t)A.dld];
             }
           }
-          section_rhs_tangent(P, ph, tb, Pd.vp, sig[pp], to, tf, yt, u0, u1, fw, dyt, d, F, dF);
+          section_rhs_tangent(P, ph, kEns ? tbe : tb, Pd.vp, sig[pp], to, tf, yt, u0, u1, fw, dyt, d, F, dF);
 #pragma unroll
           for (int c = 0; c < 11; c++) {
             acc[c] = st ? __builtin_fma(w, F[c], acc[c]) : F[c];
@@ -171,7 +179,7 @@ __global__ __launch_bounds__(kPropThreads) void proptan_kernel(ProblemDev P, Pro
   if (bad) *(volatile int32_t*)P.flag = 1;
 }
 
-hipError_t launch_proptan_slab(const ProblemDev& P, const PropDev& Pd, const PropTanArgs& A, hipStream_t s) {
+hipError_t launch_proptan_slab(const ProblemDev& P, const PropDev& Pd, const PropTanArgs& A, const EnsDev& ens, hipStream_t s) {
   if (A.nb <= 0 || A.P <= 0) return hipSuccess;
   const long long nl = (long long)A.nb * A.P;
   if (A.ld < A.nb || (A.dx && A.dld < (A.shared ? (long long)A.P : nl))) return hipErrorInvalidValue;
@@ -179,8 +187,13 @@ hipError_t launch_proptan_slab(const ProblemDev& P, const PropDev& Pd, const Pro
   const long long grid = Pd.chain ? ngrp : ngrp * Pd.nseg;
   if (grid <= 0) return hipSuccess;
   if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
-  auto* const kern = Pd.chain ? proptan_kernel<true> : proptan_kernel<false>;
-  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kPropThreads), 0, s, P, Pd, A);
+  if (ens.tables) {
+    auto* const kern = Pd.chain ? proptan_kernel<true, 1, EnsDev> : proptan_kernel<false, 1, EnsDev>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kPropThreads), 0, s, P, Pd, A, ens);
+  } else {
+    auto* const kern = Pd.chain ? proptan_kernel<true> : proptan_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kPropThreads), 0, s, P, Pd, A);
+  }
   return hipGetLastError();
 }
 

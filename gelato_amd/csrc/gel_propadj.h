@@ -28,7 +28,10 @@ struct PropAdjArgs {
   long long ld, gld;
 };
 
-// propadj_kernel (state rows of gx, gdisp, gws, gS), then prop_sample_t_kernel (control and time entries of gx)
-hipError_t launch_propadj_slab(const ProblemDev& P, const PropDev& Pd, const PropAdjArgs& A, hipStream_t s);
+// propadj_kernel (state rows of gx, gdisp, gws, gS), then prop_sample_t_kernel (control and time entries of gx).  ens: the wind
+// ensemble with the SLAB's part of the assignment (a lane's vector is lane / Q), or ens.tables == null: the instantiations without
+// an ensemble, launched as before.  With an ensemble A.y must be the ensemble flight's (prop_kernel<*, *, 1> under
+// the same assignment): the checkpoints
+hipError_t launch_propadj_slab(const ProblemDev& P, const PropDev& Pd, const PropAdjArgs& A, const EnsDev& ens, hipStream_t s);
 
 }  // namespace gel

@@ -22,6 +22,8 @@ struct PropTanArgs {
   long long ld, dld;
 };
 
-hipError_t launch_proptan_slab(const ProblemDev& P, const PropDev& Pd, const PropTanArgs& A, hipStream_t s);
+// ens: the wind ensemble with the SLAB's part of the assignment (ens.member = the entry of the slab's first vector; a lane's vector
+// is lane / P), or ens.tables == null: the instantiations without an ensemble, launched as before
+hipError_t launch_proptan_slab(const ProblemDev& P, const PropDev& Pd, const PropTanArgs& A, const EnsDev& ens, hipStream_t s);
 
 }  // namespace gel

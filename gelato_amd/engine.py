@@ -224,14 +224,17 @@ class PropagationPlan:
             raise ValueError("%s: %s, not %s" % (name, want, a.shape))
         return np.ascontiguousarray(a)
 
-    def tangent(self, X, dX=None, dispersion=None, ddispersion=None, shared=False):
+    def tangent(self, X, dX=None, dispersion=None, ddispersion=None, shared=False, ensemble=None):
         """The flight of apply() and its exact derivative along seed directions (gel_propagate_tangent).
         X [B, nvars] (or [nvars]); dX: None, or the directions in x, [B, P, nvars] ([P, nvars] with shared=True: one set for every
         vector); dispersion: None or [B, S, 4]; ddispersion: None, or the directions in the factors, [B, P, S, 4] ([P, S, 4] shared).
-        At least one of dX / ddispersion.  -> (Y [B, 11 M]: apply()'s Y bit for bit, dY [B, P, 11 M], status)"""
+        At least one of dX / ddispersion.  ensemble: None, or a WindEnsemble of this engine assigned B vectors: every vector's
+        flight AND derivative under the wind table its entry selects (gel_propagate_tangent_ensemble).
+        -> (Y [B, 11 M]: apply()'s Y bit for bit, dY [B, P, 11 M], status)"""
         self._live()
         X = _f64(X).reshape(-1, self.nvars)
         B = X.shape[0]
+        ens = _ensemble_ptr(ensemble, self._owner)
         if dX is None and ddispersion is None:
             raise ValueError("tangent: at least one of dX and ddispersion")
         shared = bool(shared)
@@ -257,15 +260,17 @@ class PropagationPlan:
         Y = np.empty((B, 11 * self.M))
         dY = np.empty((B, P, 11 * self.M))
         opt = lambda a: _d(a) if a is not None else None   # noqa: E731
-        rc = check(lib().gel_propagate_tangent(self._p, B, P, int(shared), _d(X), opt(disp), opt(dx), opt(dd), _d(Y), _d(dY)))
+        rc = check(lib().gel_propagate_tangent_ensemble(self._p, B, P, int(shared), _d(X), opt(disp), opt(dx), opt(dd), ens, _d(Y), _d(dY)))
         return Y, dY, rc
 
-    def tangent_device(self, B, P, d_x, d_y, d_dy, d_dx=0, d_dispersion=0, d_ddispersion=0, shared=False):
+    def tangent_device(self, B, P, d_x, d_y, d_dy, d_dx=0, d_dispersion=0, d_ddispersion=0, shared=False, ensemble=None):
         """device buffers: d_y [B][11 M], d_dy [B][P][11 M], d_dx / d_ddispersion as tangent() lays them out or 0 (not both),
-        d_dispersion [B][S][4] or 0; asynchronous on the engine's own stream; status through Engine.sync()"""
+        d_dispersion [B][S][4] or 0; ensemble: None or a WindEnsemble of this engine assigned B vectors; asynchronous on the engine's
+        own stream; status through Engine.sync()"""
         self._live()
-        check(lib().gel_propagate_tangent_device(self._p, int(B), int(P), int(bool(shared)), d_x, d_dispersion or None, d_dx or None,
-                                                 d_ddispersion or None, d_y, d_dy))
+        check(lib().gel_propagate_tangent_ensemble_device(self._p, int(B), int(P), int(bool(shared)), d_x, d_dispersion or None,
+                                                          d_dx or None, d_ddispersion or None, _ensemble_ptr(ensemble, self._owner),
+                                                          d_y, d_dy))
 
     def tangent_info(self, B, P, shared=False):
         """{"sample_set_bytes", "lanes_per_slab", "slabs"} of a tangent call NOW (works on host-only handles)"""
@@ -274,14 +279,17 @@ class PropagationPlan:
         check(lib().gel_prop_tangent_info(self._p, int(B), int(P), int(bool(shared)), info))
         return dict(zip(("sample_set_bytes", "lanes_per_slab", "slabs"), (int(v) for v in info)))
 
-    def adjoint(self, X, Lam, dispersion=None, shared=False):
+    def adjoint(self, X, Lam, dispersion=None, shared=False, ensemble=None):
         """The flight of apply() and the gradients of Q functionals of it in one backward pass (gel_propagate_adjoint):
         the transpose of the linear map tangent() applies.  X [B, nvars] (or [nvars]); Lam: the functionals as weights on Y,
         [B, Q, 11 M] ([Q, 11 M] with shared=True: one set for every vector); dispersion: None or [B, S, 4].  Chain and section plans.
+        ensemble: None, or a WindEnsemble of this engine assigned B vectors: every vector's flight AND gradients under the wind
+        table its entry selects (gel_propagate_adjoint_ensemble).
         -> (Y [B, 11 M]: apply()'s Y bit for bit, GX [B, Q, nvars], GD [B, Q, S, 4], status)"""
         self._live()
         X = _f64(X).reshape(-1, self.nvars)
         B = X.shape[0]
+        ens = _ensemble_ptr(ensemble, self._owner)
         shared = bool(shared)
         lam = np.asarray(Lam)
         if lam.dtype != np.float64:
@@ -306,16 +314,17 @@ class PropagationPlan:
         Y = np.empty((B, 11 * self.M))
         GX = np.empty((B, Q, self.nvars))
         GD = np.empty((B, Q, self.S, nd))
-        rc = check(lib().gel_propagate_adjoint(self._p, B, Q, int(shared), _d(X), _d(disp) if disp is not None else None, _d(lam), _d(Y),
-                                               _d(GX), _d(GD)))
+        rc = check(lib().gel_propagate_adjoint_ensemble(self._p, B, Q, int(shared), _d(X), _d(disp) if disp is not None else None, _d(lam),
+                                                        ens, _d(Y), _d(GX), _d(GD)))
         return Y, GX, GD, rc
 
-    def adjoint_device(self, B, Q, d_x, d_lam, d_y, d_gx, d_gdisp=0, d_dispersion=0, shared=False):
+    def adjoint_device(self, B, Q, d_x, d_lam, d_y, d_gx, d_gdisp=0, d_dispersion=0, shared=False, ensemble=None):
         """device buffers: d_lam as adjoint() lays Lam out, d_y [B][11 M], d_gx [B][Q][nvars], d_gdisp [B][Q][S][4] or 0,
-        d_dispersion [B][S][4] or 0; asynchronous on the engine's own stream; status through Engine.sync()"""
+        d_dispersion [B][S][4] or 0; ensemble: None or a WindEnsemble of this engine assigned B vectors; asynchronous on the engine's
+        own stream; status through Engine.sync()"""
         self._live()
-        check(lib().gel_propagate_adjoint_device(self._p, int(B), int(Q), int(bool(shared)), d_x, d_dispersion or None, d_lam or None, d_y,
-                                                 d_gx, d_gdisp or None))
+        check(lib().gel_propagate_adjoint_ensemble_device(self._p, int(B), int(Q), int(bool(shared)), d_x, d_dispersion or None,
+                                                          d_lam or None, _ensemble_ptr(ensemble, self._owner), d_y, d_gx, d_gdisp or None))
 
     def adjoint_info(self, B, Q, shared=False):
         """{"lane_bytes", "lanes_per_slab", "slabs"} of an adjoint call NOW (works on host-only handles)"""

@@ -221,11 +221,18 @@ def jacobian_seeds(num_nodes, attitude_hold, wrt=("initial", "dispersion", "time
     return cols, dX, dD
 
 
-def flight_jacobian(xdict_or_X, pdict, unitdict, steps=4, wrt=("initial", "dispersion", "times"), dispersion=None, engine=None):
+def flight_jacobian(xdict_or_X, pdict, unitdict, steps=4, wrt=("initial", "dispersion", "times"), dispersion=None, engine=None,
+                    ensemble=None):
     """The exact Jacobian of the flight fly() reports (one chain, RK4 with 2 * steps steps per node interval) with respect to the
     lift-off state, the 4 S dispersion factors, the S + 1 knot times and optionally a constant bias of every free phase's controls
     (wrt; jacobian_seeds): the tangent-linear propagation (PropagationPlan.tangent) along shared unit seeds --
     derivatives of the discrete map, without sampling noise, where montecarlo.dispersion_sensitivity regresses over a batch.
+    ensemble: None, or a WindEnsemble of the engine assigned B vectors, as fly() takes it: every vector's flight and its derivative
+    under the wind table its entry selects.  B vectors under B members give one Jacobian per sounding, each of
+    which feeds the linear covariance of that day's insertion state:
+        ens = engine.wind_ensemble(soundings); ens.assign(np.arange(B))
+        J = flight_jacobian(np.tile(x, (B, 1)), None, None, wrt=("dispersion",), engine=engine, ensemble=ens)
+        cov = [montecarlo.linear_covariance(J["terminal"]["velocity"][b], sigma) for b in range(B)]
     -> {"columns": names [P], "status", "y" [B, 11 M], "dy" [B, P, 11 M], "x_flown" [B, nvars],
         "terminal": {group: [B, 1 | 3 | 3 | 4, P]}: the last state node's derivative in physical units (kg, m, m/s, 1),
         "rows" [B, R, P]: the engine's row table's derivative, Engine.con_matvec applied to [dy | du | dt] at x_flown -- only
@@ -245,7 +252,8 @@ def flight_jacobian(xdict_or_X, pdict, unitdict, steps=4, wrt=("initial", "dispe
     P = len(cols)
     plan = engine.propagation_plan(steps=2 * steps, restart="chain")
     try:
-        Y, dY, rc = plan.tangent(X, dX=dX if dX.any() else None, dispersion=dispersion, ddispersion=dD if dD.any() else None, shared=True)
+        Y, dY, rc = plan.tangent(X, dX=dX if dX.any() else None, dispersion=dispersion, ddispersion=dD if dD.any() else None, shared=True,
+                                 ensemble=ensemble)
     finally:
         plan.close()
     x_flown = X.copy()
@@ -270,13 +278,16 @@ def flight_jacobian(xdict_or_X, pdict, unitdict, steps=4, wrt=("initial", "dispe
 GRADIENT_OF = ("terminal", "rows")
 
 
-def flight_gradient(xdict_or_X, pdict, unitdict, steps=4, of=("terminal",), dispersion=None, engine=None):
+def flight_gradient(xdict_or_X, pdict, unitdict, steps=4, of=("terminal",), dispersion=None, engine=None, ensemble=None):
     """The gradients of functionals of the flight fly() reports (one chain, RK4 with 2 * steps steps per node interval) with respect to
     EVERY input in one backward pass: the adjoint flight (PropagationPlan.adjoint), where flight_jacobian pays one
     lane per column.  of = ("terminal",): the 11 components of the last state node in physical units (kg, m, m/s, 1);
     of = ("rows", mu): mu [R] or [Q, R] multipliers on the engine's row table at x_flown -- Engine.con_rmatvec carries them to
     [dy | du | dt]: the state part becomes the functional's weights on y, the u and t parts are added to the result (the mirror of
     what flight_jacobian does with con_matvec).
+    ensemble: None, or a WindEnsemble of the engine assigned B vectors, as fly() takes it: the flight that yields x_flown and the
+    adjoint both run under every vector's own wind table.  The row table and con_rmatvec are evaluated AT x_flown
+    and read no wind table, so of=("rows", mu) passes through them unchanged: the ensemble enters through x_flown alone.
     -> {"functionals": names [Q], "status", "y" [B, 11 M], "x_flown" [B, nvars],
         "gx" [B, Q, nvars]: the gradient with respect to the decision vector (its own units): the lift-off state, both state rows of
                             every knot, ALL controls and the knot times; +0.0 where the flight does not read x,
@@ -319,7 +330,7 @@ def flight_gradient(xdict_or_X, pdict, unitdict, steps=4, of=("terminal",), disp
             mu = mu.reshape(-1, R)
             Q = mu.shape[0]
             names = ["rows:mu[%d]" % q for q in range(Q)]
-            Y0, _err, rc0 = plan.apply(X, want_err=False, dispersion=dispersion)
+            Y0, _err, rc0 = plan.apply(X, want_err=False, dispersion=dispersion, ensemble=ensemble)
             x_fl = X.copy()
             x_fl[:, :11 * M] = Y0
             _con, jfn, rc1 = engine.rows_eval(x_fl, want_jac=True)
@@ -330,7 +341,7 @@ def flight_gradient(xdict_or_X, pdict, unitdict, steps=4, of=("terminal",), disp
             extra = g[:, :, 11 * M:]          # the rows' own dependence on u and t
             scale = np.ones(Q)
             shared = False
-        Y, GX, GD, rc = plan.adjoint(X, lam, dispersion=dispersion, shared=shared)
+        Y, GX, GD, rc = plan.adjoint(X, lam, dispersion=dispersion, shared=shared, ensemble=ensemble)
     finally:
         plan.close()
     GX = GX * scale[None, :, None]

@@ -653,7 +653,8 @@ int gel_propagate_dispersed_device(gel_prop_plan* plan, int32_t B, const double*
  *      has tangent zero, as in that flag's t columns.  Knot (chain): dy where djump == 0, else dy + djump.  Quaternions are not
  *      renormalised; a hold phase has zero quaternion rows, an engine-off phase a zero mass row.  The tangent is linear in the
  *      seed with no additive constant: a zero seed gives dy == 0, a seed times 2^k gives dy times 2^k bit for bit.  Direction p's
- *      bits depend neither on P, nor on B, nor on the slab size.  There is no err output.
+ *      bits depend neither on P, nor on B, nor on the slab size.  There is no err output.  Under a wind ensemble:
+ *      gel_propagate_tangent_ensemble* below.
  *      Status: a non-finite y or dy raises the source handle's status as gel_propagate* does; the other (vector, direction)
  *      slices stay valid.  Refusals (GEL_ERR_ARG): P < 1; B P > 2^31 - 1; both seeds NULL; shared not 0 or 1; a host-only handle;
  *      seeds whose control samples for 64 vectors do not fit the plan's 1 GB workspace.  B = 0 succeeds and touches nothing.
@@ -679,7 +680,7 @@ int gel_prop_tangent_info(const gel_prop_plan* plan, int32_t B, int32_t P, int32
  *      does not read (state rows that start no segment and lie at no chain knot, a hold phase's controls) are +0.0; every element
  *      of gx and gdisp is written by every call.
  *      Chain (GEL_PROP_CHAIN) and section plans.  GEL_PROP_RESTART_NODE plans are refused: neighbouring node segments share a stage
- *      point, whose control multiplier would need a second accumulation path.  Wind ensembles are out of scope.
+ *      point, whose control multiplier would need a second accumulation path.  Under a wind ensemble: gel_propagate_adjoint_ensemble* below.
  *      The value flight runs first; its y(node j) is the checkpoint interval j restarts from.  Then every (vector, functional) walks
  *      backwards -- phases S - 1 .. 0 (chain), intervals n - 1 .. 0, steps k - 1 .. 0 -- and every step is the transpose of the
  *      tangent's step, term by term in this order (l = the multiplier of the step's end state; F1 .. F3 recomputed with the value's
@@ -848,6 +849,37 @@ int gel_output_table_batch_ensemble_device(gel_problem* p, int32_t B, const doub
                                            const double* d_disp /* or NULL */, gel_wind_ensemble* ens /* or NULL */, double launch_lat_deg,
                                            double launch_lon_deg, int32_t ncols, const int32_t* cols /* host pointer, or NULL */,
                                            double* d_out /* or NULL */, double* d_env /* or NULL */, double* d_peaks /* or NULL */);
+
+/* ---- the tangent and the adjoint flight under a wind ensemble: gel_propagate_tangent* and gel_propagate_adjoint*
+ *      with every flight's derivative taken under the wind table its vector is assigned.  Every wind lookup of vector b runs through
+ *      the member's rows, slopes and Kw in all three places: the value right-hand side, its tangent (the slope of the interval the
+ *      value lookup took, zero in the clamped ends) and the adjoint's recomputation of F1 .. F3; atmosphere, CA table and everything
+ *      else stay the handle's.  The adjoint's value flight is gel_propagate_ensemble*'s: its checkpoints are that flight's bits.
+ *      THE CONTRACT, for y, dy, gx and gdisp, without a tolerance (the contract above, extended): a vector with member[b] = e gets bit
+ *      for bit what gel_propagate_tangent* / gel_propagate_adjoint* return for the same x, disp row and seeds / lam on a handle
+ *      created from the same problem with wind_table = tables[e]; a vector with member[b] = -1 gets that call's bits on this handle;
+ *      y is also gel_propagate_ensemble*'s y.  A (vector, direction) or (vector, functional) slice depends neither on B, P or Q, nor
+ *      on its place in the batch, nor on the slab size, nor on shared, nor on what its neighbours are assigned.  The parents'
+ *      linearity carries over: a zero seed or lam gives zeros, a seed or lam times 2^k gives the outputs times 2^k bit for bit.
+ *      Calls: ens == NULL is exactly gel_propagate_tangent* / gel_propagate_adjoint* (those ARE these calls with NULL).  Refusals
+ *      (GEL_ERR_ARG, the reason in gel_last_error, all decided before a buffer or the device is looked at): the parent call's, and
+ *      an ensemble created on another handle than the plan's or whose assignment does not hold exactly B vectors; a host-only
+ *      handle; the adjoint still refuses GEL_PROP_RESTART_NODE plans.  B = 0 succeeds and touches nothing.  gel_prop_tangent_info /
+ *      gel_prop_adjoint_info hold unchanged: the ensemble adds no per-lane workspace.  No stream argument: the calls enqueue on the
+ *      handle's own stream and report through gel_sync(src, NULL), like their parents.
+ *      Status: a non-finite wind entry of a member makes its own flights' y, dy, gx and gdisp non-finite and raises GEL_NONFINITE;
+ *      the other vectors' slices stay valid. ---- */
+int gel_propagate_tangent_ensemble(gel_prop_plan* plan, int32_t B, int32_t P, int32_t shared, const double* x, const double* disp /* or NULL */,
+                                   const double* dx /* or NULL */, const double* ddisp /* or NULL */, gel_wind_ensemble* ens /* or NULL */,
+                                   double* y, double* dy);
+int gel_propagate_tangent_ensemble_device(gel_prop_plan* plan, int32_t B, int32_t P, int32_t shared, const double* d_x,
+                                          const double* d_disp /* or NULL */, const double* d_dx /* or NULL */,
+                                          const double* d_ddisp /* or NULL */, gel_wind_ensemble* ens /* or NULL */, double* d_y, double* d_dy);
+int gel_propagate_adjoint_ensemble(gel_prop_plan* plan, int32_t B, int32_t Q, int32_t shared, const double* x, const double* disp /* or NULL */,
+                                   const double* lam, gel_wind_ensemble* ens /* or NULL */, double* y, double* gx, double* gdisp /* or NULL */);
+int gel_propagate_adjoint_ensemble_device(gel_prop_plan* plan, int32_t B, int32_t Q, int32_t shared, const double* d_x,
+                                          const double* d_disp /* or NULL */, const double* d_lam, gel_wind_ensemble* ens /* or NULL */,
+                                          double* d_y, double* d_gx, double* d_gdisp /* or NULL */);
 
 /* ---- exact quantiles over the vectors of a batch: what a Monte-Carlo batch is read by -- the 99.865 % value of
  *      every flight's peak, the 0.135 % / 99.865 % band of the terminal row, the 2.5 .. 97.5 % band of every column along the

@@ -8,6 +8,11 @@ mixed-6x64 and stress-12x128 at B = 65536, from device events after a warm-up, t
              ens-blocked   E members of Kw rows, propagate.assign_members(order="blocked"): a workgroup's lanes on one or two tables
              ens-cyclic    the same members, order="cyclic": every wavefront on all E tables
     table    34 and 5 columns, table + envelope + peaks, under the same factors: disp, ens-blocked, ens-cyclic
+    tangent  mixed-6x64, chain, k = 1, P = 16 shared seeds (the first columns of propagate.jacobian_seeds), under the same factors
+             (gel_propagate_tangent_ensemble_device): disp = the call without an ensemble, ens-own, ens-blocked,
+             ens-cyclic
+    adjoint  the same with Q = 11 shared terminal functionals (gel_propagate_adjoint_ensemble_device)
+ENS_BENCH_LEGS (flight,table,tangent,adjoint) and ENS_BENCH_WORKLOADS (mixed-6x64,stress-12x128) select.
 ENS_BENCH_PARENT=path/to/libgelato_amd.so adds "disp@parent": the dispersed call of ANOTHER build of the library (the parent
 commit's), loaded beside this one into the same process through the symbols both have, on the same buffers in the same turns.
 Prints one JSON line.
@@ -79,9 +84,11 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("ensemble_bench: no GPU visible")
     parent_path = os.environ.get("ENS_BENCH_PARENT")
+    legs = os.environ.get("ENS_BENCH_LEGS", "flight,table,tangent,adjoint").split(",")
+    workloads = os.environ.get("ENS_BENCH_WORKLOADS", "mixed-6x64,stress-12x128").split(",")
     out = {"B": B, "turns": turns, "E": nE, "Kw": Kw, "cases": [], "build": _lib.build_info(), "parent": parent_path}
     T = wind_members(nE, Kw)
-    for wl in ("mixed-6x64", "stress-12x128"):
+    for wl in workloads:
         pd, ud, _, xd = problem.make_problem(wl)
         prob = con_dynamics.problem_arrays(pd, ud)
         ps, S, lc = pd["ps_params"], pd["num_sections"], pd["LaunchCondition"]
@@ -113,7 +120,7 @@ def main():
             out["cases"].append(rec)
             print({k: v for k, v in rec.items() if k != "call_s_all"}, file=sys.stderr, flush=True)   # progress
 
-        for k in (1, 4):
+        for k in (1, 4) if "flight" in legs else ():
             for mode in ("section", "chain"):
                 plan = E.propagation_plan(steps=k, restart=mode)
                 calls = {"disp": lambda: plan.apply_device(B, dX.data_ptr(), dY.data_ptr(), de.data_ptr(), dD.data_ptr())}
@@ -128,10 +135,11 @@ def main():
                     assert par.L.gel_sync(par.h, None) == 0
                     par.L.gel_prop_plan_destroy(pplan)
                 plan.close()
-        dO = torch.empty((B, M, 34), dtype=torch.float64, device="cuda")
+        tab = "table" in legs
+        dO = torch.empty((B if tab else 0, M, 34), dtype=torch.float64, device="cuda")
         dV = torch.empty((M, 34, 8), dtype=torch.float64, device="cuda")
-        dP = torch.empty((B, 34, 4), dtype=torch.float64, device="cuda")
-        for cols in (None, FIVE):
+        dP = torch.empty((B if tab else 0, 34, 4), dtype=torch.float64, device="cuda")
+        for cols in (None, FIVE) if "table" in legs else ():
             def table(en):
                 return lambda: E.output_table_batch_device(B, dX.data_ptr(), lc["lat"], lc["lon"], d_dispersion=dD.data_ptr(), columns=cols,
                                                            d_out=dO.data_ptr(), d_env=dV.data_ptr(), d_peaks=dP.data_ptr(), ensemble=en)
@@ -144,11 +152,47 @@ def main():
             run(calls, {"workload": wl, "what": "table", "ncols": 34 if cols is None else len(cols), "M": M})
             if par:
                 assert par.L.gel_sync(par.h, None) == 0
+        del dO, dV, dP
+        torch.cuda.empty_cache()
+        # the derivative calls under the ensemble against the same calls without one: shared seeds / functionals
+        if wl == "mixed-6x64" and ("tangent" in legs or "adjoint" in legs):
+            P, Q, nv = 16, 11, E.nvars
+            _cols, sX, sD = propagate.jacobian_seeds(E.num_nodes, prob["attitude_hold"])
+            last = M - 1
+            idx = [last] + [M + 3 * last + c for c in range(3)] + [4 * M + 3 * last + c for c in range(3)] + [7 * M + 4 * last + c for c in range(4)]
+            lam = np.zeros((Q, 11 * M))
+            lam[np.arange(Q), idx] = 1.0
+            tX, tD, tL = torch.from_numpy(sX[:P].copy()).cuda(), torch.from_numpy(sD[:P].copy()).cuda(), torch.from_numpy(lam).cuda()
+            plan = E.propagation_plan(steps=1, restart="chain")
+            if "tangent" in legs:
+                ddY = torch.empty((B, P, 11 * M), dtype=torch.float64, device="cuda")
+
+                def tangent(en):
+                    return lambda: plan.tangent_device(B, P, dX.data_ptr(), dY.data_ptr(), ddY.data_ptr(), d_dx=tX.data_ptr(),
+                                                       d_dispersion=dD.data_ptr(), d_ddispersion=tD.data_ptr(), shared=True, ensemble=en)
+                calls = {"disp": tangent(None)}
+                calls.update({name: tangent(en) for name, en in ens.items()})
+                run(calls, {"workload": wl, "what": "tangent", "k": 1, "mode": "chain", "P": P, "info": plan.tangent_info(B, P, True)})
+                del ddY
+                torch.cuda.empty_cache()
+            if "adjoint" in legs:
+                gX = torch.empty((B, Q, nv), dtype=torch.float64, device="cuda")
+                gD = torch.empty((B, Q, S, 4), dtype=torch.float64, device="cuda")
+
+                def adjoint(en):
+                    return lambda: plan.adjoint_device(B, Q, dX.data_ptr(), tL.data_ptr(), dY.data_ptr(), gX.data_ptr(), d_gdisp=gD.data_ptr(),
+                                                       d_dispersion=dD.data_ptr(), shared=True, ensemble=en)
+                calls = {"disp": adjoint(None)}
+                calls.update({name: adjoint(en) for name, en in ens.items()})
+                run(calls, {"workload": wl, "what": "adjoint", "k": 1, "mode": "chain", "Q": Q, "info": plan.adjoint_info(B, Q, True)})
+                del gX, gD
+            plan.close()
+            del tX, tD, tL
         for en in ens.values():
             en.close()
         if par:
             par.L.gel_problem_destroy(par.h)
-        del dX, dD, dY, de, dO, dV, dP
+        del dX, dD, dY, de
         torch.cuda.empty_cache()
         E.close()
     print(json.dumps(out))
