@@ -3408,6 +3408,9 @@ static int propadj_refuse(const char* who, const gel_prop_plan* plan, int32_t B,
   if (shared != 0 && shared != 1) return fail(GEL_ERR_ARG, w + ": shared is neither 0 nor 1");
   if (plan->flags & GEL_PROP_RESTART_NODE)
     return fail(GEL_ERR_ARG, w + ": a GEL_PROP_RESTART_NODE plan has no adjoint flight (neighbouring node segments share a stage point)");
+  int64_t lane_steps = 0;   // a lane walks every phase, in section mode too (the inner checkpoints are the lane's)
+  for (const gel::PropPhaseDev& q : plan->ph) lane_steps += (int64_t)q.k * q.n;
+  if (lane_steps > gel::kPropMaxLaneSteps) return fail(GEL_ERR_ARG, w + ": the sum of steps[s] n_s exceeds 2^20 RK4 steps in one lane");
   if (!propadj_slab(plan, Q))
     return fail(GEL_ERR_ARG, w + ": the workspace of 64 vectors (control samples, and per functional the stage points' multipliers) exceeds the 1 GB cap");
   return GEL_OK;

@@ -3,8 +3,11 @@
 // prop_kernel's (launch_prop_slab runs before these kernels); its y is both the call's output and the checkpoint set: y(node j) is the
 // start of node interval j.
 //
-//   propadj_kernel<kChain>   one lane = one (vector, functional, segment): lane l of a slab is functional l % Q of vector l / Q.  A
-//                            workgroup = kPropAdjThreads = 64 consecutive lanes of ONE segment: the phase, n and k are wave-uniform.
+//   propadj_kernel<kChain>   one lane = one (vector, functional): lane l of a slab is functional l % Q of vector l / Q.  A
+//                            workgroup = kPropAdjThreads = 64 consecutive lanes, all in the same phase: n and k are wave-uniform.
+//                            In section mode too the lane walks ALL phases, one after the other, with lm starting at zero in each:
+//                            the inner checkpoints [k_max - 1][11] are the lane's, and one thread per (lane, phase) would have S
+//                            threads write and read the same cells at once.
 //                            The tables are read where the handle keeps them, in global memory, as proptan_kernel reads them.  The
 //                            lane walks BACKWARDS: phases S - 1 .. 0 (chain), intervals n - 1 .. 0, steps k - 1 .. 0.  No atomics:
 //                            every output cell has one writer.
@@ -59,12 +62,9 @@ __global__ __launch_bounds__(kPropAdjThreads) void propadj_kernel(ProblemDev P, 
   constexpr int T = kPropAdjThreads;
   __shared__ double Fs[3 * 11 * T];   // F1 .. F3 of the step in hand: [stage][component][lane]
   const long long nl = (long long)A.nb * A.Q;
-  const long long ngrp = (nl + T - 1) / T;
-  const int seg = kChain ? 0 : (int)(blockIdx.x / ngrp);
-  const long long grp = blockIdx.x - seg * ngrp;
   const Tables tb = table_view(P.tables, P.Kw, P.Kc);   // the handle's tables where they lie (global memory): no LDS copy
-  const long long l = grp * T + (long long)threadIdx.x;
-  if (seg >= Pd.nseg || l >= nl) return;   // (idle lanes leave: they stay out of the calm-air vote of wind_eci_or_calm; no barrier follows)
+  const long long l = (long long)blockIdx.x * T + (long long)threadIdx.x;
+  if (l >= nl) return;   // (idle lanes leave: they stay out of the calm-air vote of wind_eci_or_calm; no barrier follows)
   double* const Fl = Fs + threadIdx.x;     // the lane's column: no other lane reads or writes it
   const int v = (int)(l / A.Q), qf = (int)(l - (long long)v * A.Q);
   Tables tbe = tb;   // under an ensemble: the lane's view (the wind part of its vector's member)
@@ -79,8 +79,12 @@ __global__ __launch_bounds__(kPropAdjThreads) void propadj_kernel(ProblemDev P, 
   double lm[11];
 #pragma unroll
   for (int c = 0; c < 11; c++) lm[c] = 0.0;
-  int s = kChain ? Pd.S - 1 : load_const(&Pd.seg_phase[seg]);
+  int s = Pd.S - 1;
   do {
+    if (!kChain) {   // every phase is a segment of its own: nothing is carried across the knot
+#pragma unroll
+      for (int c = 0; c < 11; c++) lm[c] = 0.0;
+    }
     PhaseDev ph = load_phase(P.phases + s);
     const int n = load_const(&Pd.ph[s].n), k = load_const(&Pd.ph[s].k), sampled = load_const(&Pd.ph[s].sampled);
     const double* const sig = Pd.mat + load_const(&Pd.ph[s].sg);
@@ -269,7 +273,7 @@ __global__ __launch_bounds__(kPropAdjThreads) void propadj_kernel(ProblemDev P, 
       bad |= nonfinite(g2);
       bad |= nonfinite(g3);
     }
-  } while (kChain && --s >= 0);
+  } while (--s >= 0);
   if (bad) *(volatile int32_t*)P.flag = 1;
 }
 
@@ -333,8 +337,7 @@ hipError_t launch_propadj_slab(const ProblemDev& P, const PropDev& Pd, const Pro
   if (Pd.restart) return hipErrorInvalidValue;
   const long long nl = (long long)A.nb * A.Q;
   if (A.ld < A.nb || A.gld < nl || !A.ck) return hipErrorInvalidValue;
-  const long long ngrp = (nl + kPropAdjThreads - 1) / kPropAdjThreads;
-  const long long grid = Pd.chain ? ngrp : ngrp * Pd.nseg;
+  const long long grid = (nl + kPropAdjThreads - 1) / kPropAdjThreads;   // one lane per (vector, functional) in either mode
   const long long sgrid = (nl + kPropAdjSampleThreads - 1) / kPropAdjSampleThreads * ((long long)P.N + 1);
   if (grid <= 0) return hipSuccess;
   if (grid > 0x7fffffffLL || sgrid > 0x7fffffffLL) return hipErrorInvalidValue;

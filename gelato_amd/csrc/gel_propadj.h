@@ -24,7 +24,8 @@ struct PropAdjArgs {
   const double* ws;      // the control samples [stage point][2][ld], ld >= nb
   double* gws;           // the stage points' control adjoints [stage point][2][gld], gld >= nb Q: every cell stored once
   double* gS;            // the adjoint of S h's factor S of every (phase, lane): [S][gld]
-  double* ck;            // inner checkpoints, the starts of steps 1 .. k - 1 of the interval in hand: [k_max - 1][11][gld] (never null)
+  double* ck;            // inner checkpoints, the starts of steps 1 .. k - 1 of the interval in hand: [k_max - 1][11][gld] (never null);
+                         // a lane's column has ONE user: the lane's thread, which walks all its phases (section mode too)
   long long ld, gld;
 };
 

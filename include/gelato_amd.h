@@ -682,7 +682,8 @@ int gel_prop_tangent_info(const gel_prop_plan* plan, int32_t B, int32_t P, int32
  *      Chain (GEL_PROP_CHAIN) and section plans.  GEL_PROP_RESTART_NODE plans are refused: neighbouring node segments share a stage
  *      point, whose control multiplier would need a second accumulation path.  Under a wind ensemble: gel_propagate_adjoint_ensemble* below.
  *      The value flight runs first; its y(node j) is the checkpoint interval j restarts from.  Then every (vector, functional) walks
- *      backwards -- phases S - 1 .. 0 (chain), intervals n - 1 .. 0, steps k - 1 .. 0 -- and every step is the transpose of the
+ *      backwards -- phases S - 1 .. 0 (on a section plan too, where l starts at zero in every phase), intervals n - 1 .. 0, steps
+ *      k - 1 .. 0 -- and every step is the transpose of the
  *      tangent's step, term by term in this order (l = the multiplier of the step's end state; F1 .. F3 recomputed with the value's
  *      own lines from the step's start: the node's checkpoint, or an inner checkpoint -- per node interval the k - 1 value steps to
  *      the starts of its later steps are integrated once more and kept per lane):
@@ -702,8 +703,9 @@ int gel_prop_tangent_info(const gel_prop_plan* plan, int32_t B, int32_t P, int32
  *      Q, nor on B, nor on the vector's position in the batch, nor on the slab size, nor on shared.
  *      Status: a non-finite y, gx or gdisp raises the source handle's status as gel_propagate* does; the other (vector, functional)
  *      slices stay valid.  Refusals (GEL_ERR_ARG, decided before a buffer is looked at, the reason in gel_last_error): Q < 1;
- *      B Q > 2^31 - 1; lam == NULL; shared not 0 or 1; a host-only handle; a GEL_PROP_RESTART_NODE plan; a workspace that does not fit
- *      the plan's 1 GB cap for 64 vectors.  B = 0 succeeds and touches nothing.
+ *      B Q > 2^31 - 1; lam == NULL; shared not 0 or 1; a host-only handle; a GEL_PROP_RESTART_NODE plan; a plan whose sum of steps[s] n_s
+ *      exceeds 2^20 (one (vector, functional) walks every phase, so a section plan is held to the chain's limit here); a workspace
+ *      that does not fit the plan's 1 GB cap for 64 vectors.  B = 0 succeeds and touches nothing.
  *      The workspace holds one sample set per vector and, per (vector, functional), the stage points' control multipliers (as many
  *      bytes again), one double per phase and 88 (max steps[s] - 1) bytes of inner checkpoints; a larger batch is walked in slabs, GEL_PROP_SLAB (vectors) as above.  The device form
  *      takes no stream argument: it enqueues on the handle's own stream and reports through gel_sync(src, NULL). ---- */

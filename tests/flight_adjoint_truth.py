@@ -70,11 +70,12 @@ def groups(prob):
 
 
 def adjoint(prob, mode, k, x, mats, hs, st, lam, mutate=None, value_err=None, num=float):
-    """The adjoint of the flight (chain or section mode, k steps per node interval) of the vector x for the functional lam [M, 11] from
+    """The adjoint of the flight (chain or section mode, k steps per node interval: one number, or one per phase) of the vector x for the functional lam [M, 11] from
     the per-stage data st (flight_tangent_truth.recursion's) -> (gx [nvars], gd [S, 4]), and (Egx, Egd) behind them where value_err
     [T, 11] is given (fp64 only).  x, lam and st in the arithmetic `num` converts to."""
     nn, S, N, M = tt.layout(prob)
     nv = 11 * M + 2 * N + S + 1
+    ks = tt.steps_of(k, S)
     ut = num(float(prob["units"][4]))
     t0 = 11 * M + 2 * N
     dt = object if num is not float else float
@@ -83,11 +84,11 @@ def adjoint(prob, mode, k, x, mats, hs, st, lam, mutate=None, value_err=None, nu
     Egx, Egd = np.zeros(nv), np.zeros((S, 4))
     gS, EgS = [zero] * S, [0.0] * S
     want_E = value_err is not None
-    T0 = [4 * k * sum(nn[:s]) for s in range(S)]
+    T0 = [4 * sum(ks[r] * nn[r] for r in range(s)) for s in range(S)]
     fl = lambda a: np.abs(np.asarray(a, dtype=float))   # noqa: E731
     lm, El = np.full(11, zero, dtype=dt), np.zeros(11)
     for s in reversed(range(S)):
-        n = nn[s]
+        n, k = nn[s], ks[s]
         ua = sum(nn[:s])
         xa = ua + s
         if not (mode == "chain" and s < S - 1):

@@ -108,13 +108,23 @@ def segments(prob, mode):
     return [(s, mode == "chain" and s > 0) for s in range(S)]
 
 
+def steps_of(k, S):
+    """k as one number of RK4 steps per node interval, or one per phase -> [S] integers"""
+    if np.ndim(k) == 0:
+        return [int(k)] * S
+    ks = [int(v) for v in k]
+    assert len(ks) == S, (ks, S)
+    return ks
+
+
 def recursion(prob, mode, k, x, mats, hs, st, dx, dd, mutate=None, value_err=None, num=float):
-    """The tangent of the flight (chain or section mode, k steps per node interval) of the vector x along the seed (dx [nvars],
+    """The tangent of the flight (chain or section mode, k steps per node interval: one number, or one per phase) of the vector x along the seed (dx [nvars],
     dd [S, 4]) from the per-stage data st = {"F" [T, 11], "J" [T, 11, 11], "Pu" [T, 11, 2], "Pf" [T, 11, 4], "Jw" [T, 3, 3]: the part
     of J[4:7, 1:4] that comes through the wind's slope} in stage order -> dy [M, 11] (and the bound E [M, 11] where value_err
     [T, 11] = what the values of F may differ by is given; fp64 only).  mats[s] = the plan's matrices of phase s; hs[s] its steps;
     x, dx, dd and st in the arithmetic `num` converts to (float, or mpmath.mpf with object arrays)."""
     nn, S, N, M = layout(prob)
+    ks = steps_of(k, S)
     ut = num(float(prob["units"][4]))
     t0 = 11 * M + 2 * N
     dy_out = np.zeros((M, 11), dtype=object if num is not float else float)
@@ -124,7 +134,7 @@ def recursion(prob, mode, k, x, mats, hs, st, dx, dd, mutate=None, value_err=Non
     Eb = np.zeros(11)
     want_E = value_err is not None
     for s, carried in segments(prob, mode):
-        n = nn[s]
+        n, k = nn[s], ks[s]
         ua = sum(nn[:s])
         xa = ua + s
         rows0 = state_rows(M, xa)
@@ -196,21 +206,23 @@ def recursion(prob, mode, k, x, mats, hs, st, dx, dd, mutate=None, value_err=Non
 
 
 def recursion_steps(flight):
-    """RK4 steps of one of the stored flights"""
+    """RK4 steps of a flight (case, mode, steps per node interval: one number, or one per phase)"""
     prob, _X, _d = case(flight[0])
-    return flight[2] * sum(layout(prob)[0])
+    nn = layout(prob)[0]
+    return sum(k * n for k, n in zip(steps_of(flight[2], len(nn)), nn))
 
 
 def plan_tables(E, k, mode="chain"):
-    """(mats [S], hs [S]) of a plan of k steps per node interval: the matrices as the library builds them and the steps as its
-    host code forms them (one subtraction, one division)"""
-    plan = E.propagation_plan(steps=k, restart=mode)
+    """(mats [S], hs [S]) of a plan of k steps per node interval (one number, or one per phase): the matrices as the library builds
+    them and the steps as its host code forms them (one subtraction, one division)"""
+    ks = steps_of(k, E.S)
+    plan = E.propagation_plan(steps=ks, restart=mode)
     mats = [plan.matrices(s) for s in range(E.S)]
     plan.close()
     hs = []
     for s in range(E.S):
         tx = np.concatenate([[-1.0], E.tau(s)])
-        hs.append((tx[1:] - tx[:-1]) / k)
+        hs.append((tx[1:] - tx[:-1]) / ks[s])
     return mats, hs
 
 

@@ -51,6 +51,7 @@ class Ctx:
     """everything a flight reads besides x and the factors, as exact mpf of the fp64 numbers the device holds"""
 
     def __init__(self, name, mode, k):
+        """k: RK4 steps per node interval, one number or one per phase"""
         import flight_tangent_truth as tt
         import interp_truth as it
         self.X = mj._setup()
@@ -58,6 +59,7 @@ class Ctx:
         self.prob, self.Xb, self.disp = tt.case(name)
         self.E = it.engine(self.prob)
         self.nn, self.S, self.N, self.M = tt.layout(self.prob)
+        self.ks = tt.steps_of(k, self.S)
         self.mats, self.hs = tt.plan_tables(self.E, k, mode)
         um, up, uv, uu, ut = [float(v) for v in self.prob["units"]]
         self.units = [M_(um), M_(up), M_(uv)]
@@ -121,8 +123,8 @@ class Ctx:
             hold = bool(self.prob["attitude_hold"][s])
             for j in range(n):
                 Sh = S_ * M_(self.hs[s][j])
-                for i in range(self.k):
-                    p = 2 * (self.k * j + i)
+                for i in range(self.ks[s]):
+                    p = 2 * (self.ks[s] * j + i)
                     acc, Fp = None, None
                     for sg in range(4):
                         pp = p + ((sg + 1) >> 1)
@@ -229,8 +231,8 @@ def value_errors(C, x, fac, stages, Fs):
         n = C.nn[s]
         pd = ft.dispersed_prob(C.prob, s, fac[s])
         for j in range(n):
-            for i in range(C.k):
-                p = 2 * (C.k * j + i)
+            for i in range(C.ks[s]):
+                p = 2 * (C.ks[s] * j + i)
                 for sg in range(4):
                     pp = p + ((sg + 1) >> 1)
                     _s, z, u, _t = stages[T]
