@@ -50,6 +50,9 @@ def case(name):
     "example@CASE": the example over the tables of tests/table_cases.py.  (reference_area = 0), engines on, phase 0 held and phases 1, 2 free; random states that jump at every knot."""
     import flight_truth as ft
     import interp_truth as it
+    if name.startswith("kinks"):   # tests/kink_flight.py: every phase starts on another branch of the right-hand side
+        import kink_flight
+        return kink_flight.kink_problem("ends" if name == "kinks@ENDS" else None)
     if name.startswith("example"):
         prob, x0 = it.named("example")
         if "@" in name:            # "example@CASE": over the wind and CA tables of table_cases.CASES[CASE]
@@ -118,7 +121,7 @@ def steps_of(k, S):
 
 
 def recursion(prob, mode, k, x, mats, hs, st, dx, dd, mutate=None, value_err=None, num=float):
-    """The tangent of the flight (chain or section mode, k steps per node interval: one number, or one per phase) of the vector x along the seed (dx [nvars],
+    """The tangent of the flight (chain, section or node mode, k steps per node interval: one number, or one per phase) of the vector x along the seed (dx [nvars],
     dd [S, 4]) from the per-stage data st = {"F" [T, 11], "J" [T, 11, 11], "Pu" [T, 11, 2], "Pf" [T, 11, 4], "Jw" [T, 3, 3]: the part
     of J[4:7, 1:4] that comes through the wind's slope} in stage order -> dy [M, 11] (and the bound E [M, 11] where value_err
     [T, 11] = what the values of F may differ by is given; fp64 only).  mats[s] = the plan's matrices of phase s; hs[s] its steps;
@@ -160,6 +163,9 @@ def recursion(prob, mode, k, x, mats, hs, st, dx, dd, mutate=None, value_err=Non
         m = mats[s]
         du_nodes = dx[11 * M + 2 * ua:11 * M + 2 * (ua + n)].reshape(n, 2)
         for j in range(n):
+            if mode == "node" and j > 0:        # every node interval starts from the collocated row: its seed, E = 0
+                dy = dx[state_rows(M, xa + j)].copy()
+                Eb = np.zeros(11)
             Sh = S_ * hs[s][j]
             dSh = dS * hs[s][j]
             for i in range(k):

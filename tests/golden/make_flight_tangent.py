@@ -122,6 +122,8 @@ class Ctx:
             Uc = [[x[11 * M + 2 * (ua + q) + c] for c in range(2)] for q in range(n)]
             hold = bool(self.prob["attitude_hold"][s])
             for j in range(n):
+                if self.mode == "node" and j > 0:
+                    y = [x[i] for i in tt.state_rows(M, xa + j)]
                 Sh = S_ * M_(self.hs[s][j])
                 for i in range(self.ks[s]):
                     p = 2 * (self.ks[s] * j + i)
