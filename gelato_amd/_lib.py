@@ -191,6 +191,12 @@ SIGNATURES = {
     "gel_propagate_tangent_ensemble_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 7),
     "gel_propagate_adjoint_ensemble": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp, C.c_void_p, _dp, _dp, _dp]),
     "gel_propagate_adjoint_ensemble_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 7),
+    "gel_prop_wind_rows": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_int32)]),
+    "gel_propagate_tangent_wind": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp, _dp, _dp, C.c_void_p, _dp, _dp]),
+    "gel_propagate_tangent_wind_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 8),
+    "gel_propagate_adjoint_wind": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, _dp, _dp, _dp, C.c_void_p, _dp, _dp, _dp, _dp]),
+    "gel_propagate_adjoint_wind_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 8),
+    "gel_prop_adjoint_wind_info": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _lp]),
     "gel_output_table_batch_ensemble": (C.c_int, [C.c_void_p, C.c_int32, _dp, _dp, _dp, C.c_void_p, C.c_double, C.c_double, C.c_int32, _ip,
                                                   _dp, _dp, _dp]),
     "gel_output_table_batch_ensemble_device": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double,

@@ -3251,15 +3251,22 @@ static int64_t proptan_slab(const gel_prop_plan* pl, int64_t P, bool shared) {
   return vs;
 }
 
+// the row count of the wind seeds and of gwind (gel_prop_wind_rows): every table a lane of the call may read fits
+static int32_t prop_wind_rows(const gel_prop_plan* plan, const gel_wind_ensemble* ens) {
+  return std::max<int32_t>(plan->src->dev.Kw, ens ? ens->Kw : 0);
+}
+
+// wind_call: one of gel_propagate_tangent_wind*, which take a third seed (dwind; NULL in the parents' calls)
 static int proptan_check(const char* who, const gel_prop_plan* plan, int32_t B, int32_t P, int32_t shared, const void* x, const void* dx,
-                         const void* ddisp, const gel_wind_ensemble* ens, const void* y, const void* dy) {
+                         const void* ddisp, const void* dwind, bool wind_call, const gel_wind_ensemble* ens, const void* y, const void* dy) {
   const std::string w(who);
   if (!plan) return fail(GEL_ERR_ARG, w + ": null plan");
   if (B < 0) return fail(GEL_ERR_ARG, w + ": B < 0");
   if (P < 1) return fail(GEL_ERR_ARG, w + ": P < 1");
   if ((int64_t)B * P > 0x7fffffffLL) return fail(GEL_ERR_ARG, w + ": B P exceeds 2^31 - 1 lanes");
   if (shared != 0 && shared != 1) return fail(GEL_ERR_ARG, w + ": shared is neither 0 nor 1");
-  if (!dx && !ddisp) return fail(GEL_ERR_ARG, w + ": both seeds (dx, ddisp) are NULL");
+  if (!dx && !ddisp && !dwind)
+    return fail(GEL_ERR_ARG, w + (wind_call ? ": all three seeds (dx, ddisp, dwind) are NULL" : ": both seeds (dx, ddisp) are NULL"));
   if (B > 0 && (!x || !y || !dy)) return fail(GEL_ERR_ARG, w + ": x, y or dy is NULL with B > 0");
   if (int rc = ens_check(who, ens, plan->src, B)) return rc;
   if (plan->src->device == GEL_DEVICE_NONE) return fail(GEL_ERR_ARG, w + ": the plan's handle is host-only (GEL_DEVICE_NONE)");
@@ -3282,9 +3289,10 @@ int gel_prop_tangent_info(const gel_prop_plan* plan, int32_t B, int32_t P, int32
 // the launches of one call on stream s, slab after slab: the control samples of the slab's vectors, those of its seeds (the shared
 // seeds' once, before the first slab), the integration
 static int proptan_enqueue(gel_prop_plan* plan, int32_t B, int32_t P, int32_t shared, const double* d_x, const double* d_disp,
-                           const double* d_dx, const double* d_ddisp, const gel_wind_ensemble* ens, double* d_y, double* d_dy,
-                           hipStream_t s) {
+                           const double* d_dx, const double* d_ddisp, const double* d_dwind, const gel_wind_ensemble* ens, double* d_y,
+                           double* d_dy, hipStream_t s) {
   gel_problem* p = plan->src;
+  const int32_t Kg = prop_wind_rows(plan, ens);
   const int64_t vs = proptan_slab(plan, P, shared != 0), ldv = std::min<int64_t>(vs, ((int64_t)B + 63) / 64 * 64);
   const int64_t dld = d_dx ? (shared ? ((int64_t)P + 63) / 64 * 64 : ldv * P) : 0;
   const size_t set = 2 * (size_t)plan->sampled_pts, need = (size_t)(ldv + dld) * set;
@@ -3320,19 +3328,22 @@ static int proptan_enqueue(gel_prop_plan* plan, int32_t B, int32_t P, int32_t sh
     a.y = d_y + (size_t)v0 * ny;
     a.dy = d_dy + l0 * ny;
     a.ws = ws; a.dws = dws; a.ld = ldv; a.dld = dld;
-    HIPCHK(gel::launch_proptan_slab(p->dev, plan->dev, a, ens_dev(ens, v0), s));
+    gel::WindSeedDev wd{};   // (the seeds are read where the caller keeps them: no workspace)
+    if (d_dwind) { wd.dwind = shared ? d_dwind : d_dwind + l0 * 2 * (size_t)Kg; wd.Kg = Kg; }
+    HIPCHK(gel::launch_proptan_slab(p->dev, plan->dev, a, ens_dev(ens, v0), wd, s));
   }
   return GEL_OK;
 }
 
 // (the refusals name the entry point the caller used: with an ensemble the _ensemble one)
 static int proptan_device(const char* who, gel_prop_plan* plan, int32_t B, int32_t P, int32_t shared, const double* d_x, const double* d_disp,
-                          const double* d_dx, const double* d_ddisp, gel_wind_ensemble* ens, double* d_y, double* d_dy) {
-  if (int rc = proptan_check(who, plan, B, P, shared, d_x, d_dx, d_ddisp, ens, d_y, d_dy)) return rc;
+                          const double* d_dx, const double* d_ddisp, gel_wind_ensemble* ens, double* d_y, double* d_dy,
+                          const double* d_dwind = nullptr, bool wind_call = false) {
+  if (int rc = proptan_check(who, plan, B, P, shared, d_x, d_dx, d_ddisp, d_dwind, wind_call, ens, d_y, d_dy)) return rc;
   if (B == 0) return GEL_OK;
   gel_problem* p = plan->src;
   HIPCHK(hipSetDevice(p->device));
-  return proptan_enqueue(plan, B, P, shared, d_x, d_disp, d_dx, d_ddisp, ens, d_y, d_dy, p->stream.get());
+  return proptan_enqueue(plan, B, P, shared, d_x, d_disp, d_dx, d_ddisp, d_dwind, ens, d_y, d_dy, p->stream.get());
 }
 
 int gel_propagate_tangent_ensemble_device(gel_prop_plan* plan, int32_t B, int32_t P, int32_t shared, const double* d_x, const double* d_disp,
@@ -3346,8 +3357,9 @@ int gel_propagate_tangent_device(gel_prop_plan* plan, int32_t B, int32_t P, int3
 }
 
 static int proptan_host(const char* who, gel_prop_plan* plan, int32_t B, int32_t P, int32_t shared, const double* x, const double* disp,
-                        const double* dx, const double* ddisp, gel_wind_ensemble* ens, double* y, double* dy) {
-  if (int rc = proptan_check(who, plan, B, P, shared, x, dx, ddisp, ens, y, dy)) return rc;
+                        const double* dx, const double* ddisp, gel_wind_ensemble* ens, double* y, double* dy, const double* dwind = nullptr,
+                        bool wind_call = false) {
+  if (int rc = proptan_check(who, plan, B, P, shared, x, dx, ddisp, dwind, wind_call, ens, y, dy)) return rc;
   if (B == 0) return GEL_OK;
   gel_problem* p = plan->src;
   HIPCHK(hipSetDevice(p->device));
@@ -3356,9 +3368,10 @@ static int proptan_host(const char* who, gel_prop_plan* plan, int32_t B, int32_t
   // (x, y, disp as gel_propagate_dispersed lays them out; the new buffers behind them; the ensemble's members and assignment are
   // resident: the arena holds what it held)
   return staged_call(p, 0, {staged_in(x, (size_t)B * nv), staged_out(y, (size_t)B * ny), staged_in(disp, (size_t)B * nd),
-                            staged_in(dx, seeds * nv), staged_in(ddisp, seeds * nd), staged_out(dy, (size_t)B * P * ny)},
+                            staged_in(dx, seeds * nv), staged_in(ddisp, seeds * nd), staged_out(dy, (size_t)B * P * ny),
+                            staged_in(dwind, seeds * 2 * (size_t)prop_wind_rows(plan, ens))},
                      [&](const gel::ProblemDev&, double* const* a) {
-                       return proptan_enqueue(plan, B, P, shared, a[0], a[2], a[3], a[4], ens, a[1], a[5], p->stream.get());
+                       return proptan_enqueue(plan, B, P, shared, a[0], a[2], a[3], a[4], a[6], ens, a[1], a[5], p->stream.get());
                      });
 }
 
@@ -3372,6 +3385,26 @@ int gel_propagate_tangent(gel_prop_plan* plan, int32_t B, int32_t P, int32_t sha
   return proptan_host("gel_propagate_tangent", plan, B, P, shared, x, disp, dx, ddisp, nullptr, y, dy);
 }
 
+// the wind table's own direction beside dx and ddisp; dwind == NULL: the calls above
+int gel_propagate_tangent_wind_device(gel_prop_plan* plan, int32_t B, int32_t P, int32_t shared, const double* d_x, const double* d_disp,
+                                      const double* d_dx, const double* d_ddisp, const double* d_dwind, gel_wind_ensemble* ens, double* d_y,
+                                      double* d_dy) {
+  return proptan_device("gel_propagate_tangent_wind_device", plan, B, P, shared, d_x, d_disp, d_dx, d_ddisp, ens, d_y, d_dy, d_dwind, true);
+}
+
+int gel_propagate_tangent_wind(gel_prop_plan* plan, int32_t B, int32_t P, int32_t shared, const double* x, const double* disp,
+                               const double* dx, const double* ddisp, const double* dwind, gel_wind_ensemble* ens, double* y, double* dy) {
+  return proptan_host("gel_propagate_tangent_wind", plan, B, P, shared, x, disp, dx, ddisp, ens, y, dy, dwind, true);
+}
+
+int gel_prop_wind_rows(const gel_prop_plan* plan, const gel_wind_ensemble* ens, int32_t* Kg) {
+  if (!plan) return fail(GEL_ERR_ARG, "gel_prop_wind_rows: null plan");
+  if (!Kg) return fail(GEL_ERR_ARG, "gel_prop_wind_rows: Kg is NULL");
+  if (ens && ens->src != plan->src) return fail(GEL_ERR_ARG, "gel_prop_wind_rows: the wind ensemble belongs to another handle");
+  *Kg = prop_wind_rows(plan, ens);
+  return GEL_OK;
+}
+
 // ------------- adjoint flight: gradients of the flown trajectory in one pass -------------
 // The workspace holds per vector of a slab one sample set (16 bytes per sampled stage point) and per lane (vector, functional) the
 // stage points' control multipliers (as many bytes again), one double per phase (the multiplier of S) and the inner checkpoints of
@@ -3383,10 +3416,13 @@ static int64_t propadj_kmax(const gel_prop_plan* pl) {
   for (const gel::PropPhaseDev& q : pl->ph) k = std::max<int64_t>(k, q.k);
   return k;
 }
-static int64_t propadj_lane_bytes(const gel_prop_plan* pl) { return 16 * pl->sampled_pts + 8 * (int64_t)pl->dev.S + 88 * (propadj_kmax(pl) - 1); }
+// Kg: the rows of the lane's wind column (16 Kg bytes), 0 where gwind is not wanted
+static int64_t propadj_lane_bytes(const gel_prop_plan* pl, int64_t Kg = 0) {
+  return 16 * pl->sampled_pts + 8 * (int64_t)pl->dev.S + 88 * (propadj_kmax(pl) - 1) + 16 * Kg;
+}
 
-static int64_t propadj_slab(const gel_prop_plan* pl, int64_t Q) {
-  const int64_t per_vec = 16 * pl->sampled_pts + Q * propadj_lane_bytes(pl);
+static int64_t propadj_slab(const gel_prop_plan* pl, int64_t Q, int64_t Kg = 0) {
+  const int64_t per_vec = 16 * pl->sampled_pts + Q * propadj_lane_bytes(pl, Kg);
   int64_t vs = std::min<int64_t>(kPropMaxSlab, kPropWsBytes / per_vec / 64 * 64);
   const int64_t grid_lanes = (int64_t)0x7fffffff / ((int64_t)pl->src->dims.N + 1) * gel::kPropAdjSampleThreads;
   vs = std::min<int64_t>(vs, std::min<int64_t>(grid_lanes, 0x7fffffff) / Q / 64 * 64);
@@ -3399,7 +3435,7 @@ static int64_t propadj_slab(const gel_prop_plan* pl, int64_t Q) {
 }
 
 // every refusal that is decided before a buffer is looked at
-static int propadj_refuse(const char* who, const gel_prop_plan* plan, int32_t B, int32_t Q, int32_t shared) {
+static int propadj_refuse(const char* who, const gel_prop_plan* plan, int32_t B, int32_t Q, int32_t shared, int64_t Kg = 0) {
   const std::string w(who);
   if (!plan) return fail(GEL_ERR_ARG, w + ": null plan");
   if (B < 0) return fail(GEL_ERR_ARG, w + ": B < 0");
@@ -3411,16 +3447,16 @@ static int propadj_refuse(const char* who, const gel_prop_plan* plan, int32_t B,
   int64_t lane_steps = 0;   // a lane walks every phase, in section mode too (the inner checkpoints are the lane's)
   for (const gel::PropPhaseDev& q : plan->ph) lane_steps += (int64_t)q.k * q.n;
   if (lane_steps > gel::kPropMaxLaneSteps) return fail(GEL_ERR_ARG, w + ": the sum of steps[s] n_s exceeds 2^20 RK4 steps in one lane");
-  if (!propadj_slab(plan, Q))
+  if (!propadj_slab(plan, Q, Kg))
     return fail(GEL_ERR_ARG, w + ": the workspace of 64 vectors (control samples, and per functional the stage points' multipliers) exceeds the 1 GB cap");
   return GEL_OK;
 }
 
 static int propadj_check(const char* who, const gel_prop_plan* plan, int32_t B, int32_t Q, int32_t shared, const void* x, const void* lam,
-                         const gel_wind_ensemble* ens, const void* y, const void* gx) {
+                         const gel_wind_ensemble* ens, const void* y, const void* gx, const void* gwind = nullptr) {
   const std::string w(who);
   if (plan && !lam) return fail(GEL_ERR_ARG, w + ": lam is NULL");
-  if (int rc = propadj_refuse(who, plan, B, Q, shared)) return rc;
+  if (int rc = propadj_refuse(who, plan, B, Q, shared, (plan && gwind) ? prop_wind_rows(plan, ens) : 0)) return rc;
   if (int rc = ens_check(who, ens, plan->src, B)) return rc;
   if (plan->src->device == GEL_DEVICE_NONE) return fail(GEL_ERR_ARG, w + ": the plan's handle is host-only (GEL_DEVICE_NONE)");
   if (B > 0 && (!x || !y || !gx)) return fail(GEL_ERR_ARG, w + ": x, y or gx is NULL with B > 0");
@@ -3441,13 +3477,15 @@ int gel_prop_adjoint_info(const gel_prop_plan* plan, int32_t B, int32_t Q, int32
 // ensemble gel_propagate_ensemble*'s launch, so that the checkpoints are that flight's bits), the backward walk, the transposed
 // sampler with the knot times
 static int propadj_enqueue(gel_prop_plan* plan, int32_t B, int32_t Q, int32_t shared, const double* d_x, const double* d_disp,
-                           const double* d_lam, const gel_wind_ensemble* ens, double* d_y, double* d_gx, double* d_gdisp, hipStream_t s) {
+                           const double* d_lam, const gel_wind_ensemble* ens, double* d_y, double* d_gx, double* d_gdisp, double* d_gwind,
+                           hipStream_t s) {
   gel_problem* p = plan->src;
-  const int64_t vs = propadj_slab(plan, Q), ldv = std::min<int64_t>(vs, ((int64_t)B + 63) / 64 * 64);
+  const int64_t Kg = d_gwind ? prop_wind_rows(plan, ens) : 0;
+  const int64_t vs = propadj_slab(plan, Q, Kg), ldv = std::min<int64_t>(vs, ((int64_t)B + 63) / 64 * 64);
   const int64_t gld = ldv * Q;
   const size_t set = 2 * (size_t)plan->sampled_pts;
   const size_t nck = 11 * (size_t)(propadj_kmax(plan) - 1);
-  const size_t need = (size_t)ldv * set + (size_t)gld * (set + (size_t)plan->dev.S + nck) + 1;   // (+ 1: ck is a valid pointer at k = 1 too)
+  const size_t need = (size_t)ldv * set + (size_t)gld * (set + (size_t)plan->dev.S + nck + 2 * (size_t)Kg) + 1;   // (+ 1: ck is a valid pointer at k = 1 too)
   if (plan->d_ws.capacity() < need) {
     HIPCHK(drain(p));   // an earlier call in flight still reads the old block
     HIPCHK(plan->d_ws.reserve(need));
@@ -3456,6 +3494,7 @@ static int propadj_enqueue(gel_prop_plan* plan, int32_t B, int32_t Q, int32_t sh
   double* const gws = ws + (size_t)ldv * set;    // the second region: the stage points' control multipliers
   double* const gS = gws + (size_t)gld * set;    // the third: the multiplier of S per (phase, lane)
   double* const ck = gS + (size_t)gld * (size_t)plan->dev.S;   // the fourth: the inner checkpoints of the interval in hand
+  double* const gww = ck + (size_t)gld * nck + 1;              // the fifth: the lanes' wind columns [Kg][2][gld] (only where gwind is wanted)
   const size_t nv = (size_t)p->dims.num_vars, ny = (size_t)11 * p->dims.M, nd = (size_t)p->dims.S * GEL_PROP_NDISP;
   for (int64_t v0 = 0; v0 < B; v0 += vs) {
     const int nb = (int)std::min<int64_t>(vs, B - v0);
@@ -3473,18 +3512,20 @@ static int propadj_enqueue(gel_prop_plan* plan, int32_t B, int32_t Q, int32_t sh
     a.gx = d_gx + l0 * nv;
     a.gdisp = d_gdisp ? d_gdisp + l0 * nd : nullptr;
     a.ws = ws; a.gws = gws; a.gS = gS; a.ck = ck; a.ld = ldv; a.gld = gld;
-    HIPCHK(gel::launch_propadj_slab(p->dev, plan->dev, a, e, s));
+    gel::WindGradDev wg{};
+    if (d_gwind) { wg.gww = gww; wg.gwind = d_gwind + l0 * 2 * (size_t)Kg; wg.Kg = (int32_t)Kg; }
+    HIPCHK(gel::launch_propadj_slab(p->dev, plan->dev, a, e, wg, s));
   }
   return GEL_OK;
 }
 
 static int propadj_device(const char* who, gel_prop_plan* plan, int32_t B, int32_t Q, int32_t shared, const double* d_x, const double* d_disp,
-                          const double* d_lam, gel_wind_ensemble* ens, double* d_y, double* d_gx, double* d_gdisp) {
-  if (int rc = propadj_check(who, plan, B, Q, shared, d_x, d_lam, ens, d_y, d_gx)) return rc;
+                          const double* d_lam, gel_wind_ensemble* ens, double* d_y, double* d_gx, double* d_gdisp, double* d_gwind = nullptr) {
+  if (int rc = propadj_check(who, plan, B, Q, shared, d_x, d_lam, ens, d_y, d_gx, d_gwind)) return rc;
   if (B == 0) return GEL_OK;
   gel_problem* p = plan->src;
   HIPCHK(hipSetDevice(p->device));
-  return propadj_enqueue(plan, B, Q, shared, d_x, d_disp, d_lam, ens, d_y, d_gx, d_gdisp, p->stream.get());
+  return propadj_enqueue(plan, B, Q, shared, d_x, d_disp, d_lam, ens, d_y, d_gx, d_gdisp, d_gwind, p->stream.get());
 }
 
 int gel_propagate_adjoint_ensemble_device(gel_prop_plan* plan, int32_t B, int32_t Q, int32_t shared, const double* d_x, const double* d_disp,
@@ -3498,8 +3539,8 @@ int gel_propagate_adjoint_device(gel_prop_plan* plan, int32_t B, int32_t Q, int3
 }
 
 static int propadj_host(const char* who, gel_prop_plan* plan, int32_t B, int32_t Q, int32_t shared, const double* x, const double* disp,
-                        const double* lam, gel_wind_ensemble* ens, double* y, double* gx, double* gdisp) {
-  if (int rc = propadj_check(who, plan, B, Q, shared, x, lam, ens, y, gx)) return rc;
+                        const double* lam, gel_wind_ensemble* ens, double* y, double* gx, double* gdisp, double* gwind = nullptr) {
+  if (int rc = propadj_check(who, plan, B, Q, shared, x, lam, ens, y, gx, gwind)) return rc;
   if (B == 0) return GEL_OK;
   gel_problem* p = plan->src;
   HIPCHK(hipSetDevice(p->device));
@@ -3507,9 +3548,10 @@ static int propadj_host(const char* who, gel_prop_plan* plan, int32_t B, int32_t
   const size_t lanes = (size_t)B * Q;
   // (x, y, disp as gel_propagate_dispersed lays them out; the new buffers behind them)
   return staged_call(p, 0, {staged_in(x, (size_t)B * nv), staged_out(y, (size_t)B * ny), staged_in(disp, (size_t)B * nd),
-                            staged_in(lam, (shared ? (size_t)Q : lanes) * ny), staged_out(gx, lanes * nv), staged_out(gdisp, lanes * nd)},
+                            staged_in(lam, (shared ? (size_t)Q : lanes) * ny), staged_out(gx, lanes * nv), staged_out(gdisp, lanes * nd),
+                            staged_out(gwind, lanes * 2 * (size_t)prop_wind_rows(plan, ens))},
                      [&](const gel::ProblemDev&, double* const* a) {
-                       return propadj_enqueue(plan, B, Q, shared, a[0], a[2], a[3], ens, a[1], a[4], a[5], p->stream.get());
+                       return propadj_enqueue(plan, B, Q, shared, a[0], a[2], a[3], ens, a[1], a[4], a[5], a[6], p->stream.get());
                      });
 }
 
@@ -3521,6 +3563,31 @@ int gel_propagate_adjoint_ensemble(gel_prop_plan* plan, int32_t B, int32_t Q, in
 int gel_propagate_adjoint(gel_prop_plan* plan, int32_t B, int32_t Q, int32_t shared, const double* x, const double* disp, const double* lam,
                           double* y, double* gx, double* gdisp) {
   return propadj_host("gel_propagate_adjoint", plan, B, Q, shared, x, disp, lam, nullptr, y, gx, gdisp);
+}
+
+// the gradient with respect to the wind table's rows beside gx and gdisp; gwind == NULL: the calls above
+int gel_propagate_adjoint_wind_device(gel_prop_plan* plan, int32_t B, int32_t Q, int32_t shared, const double* d_x, const double* d_disp,
+                                      const double* d_lam, gel_wind_ensemble* ens, double* d_y, double* d_gx, double* d_gdisp, double* d_gwind) {
+  return propadj_device("gel_propagate_adjoint_wind_device", plan, B, Q, shared, d_x, d_disp, d_lam, ens, d_y, d_gx, d_gdisp, d_gwind);
+}
+
+int gel_propagate_adjoint_wind(gel_prop_plan* plan, int32_t B, int32_t Q, int32_t shared, const double* x, const double* disp, const double* lam,
+                               gel_wind_ensemble* ens, double* y, double* gx, double* gdisp, double* gwind) {
+  return propadj_host("gel_propagate_adjoint_wind", plan, B, Q, shared, x, disp, lam, ens, y, gx, gdisp, gwind);
+}
+
+int gel_prop_adjoint_wind_info(const gel_prop_plan* plan, const gel_wind_ensemble* ens, int32_t B, int32_t Q, int32_t shared, int32_t want_gwind,
+                               int64_t* info) {
+  if (!info) return fail(GEL_ERR_ARG, "gel_prop_adjoint_wind_info: info is NULL");
+  if (plan && ens && ens->src != plan->src) return fail(GEL_ERR_ARG, "gel_prop_adjoint_wind_info: the wind ensemble belongs to another handle");
+  const int64_t Kg = plan ? prop_wind_rows(plan, ens) : 0, Kl = want_gwind ? Kg : 0;
+  if (int rc = propadj_refuse("gel_prop_adjoint_wind_info", plan, B, Q, shared, Kl)) return rc;
+  const int64_t vs = propadj_slab(plan, Q, Kl);
+  info[0] = propadj_lane_bytes(plan, Kl);
+  info[1] = vs * Q;
+  info[2] = (B + vs - 1) / vs;
+  info[3] = Kg;
+  return GEL_OK;
 }
 
 // ------------- Jacobian products from the compact values -------------

@@ -51,14 +51,29 @@ __device__ __forceinline__ size_t state_index(int M, int xi, int c) {
   return (c == 0) ? (size_t)xi : (c < 4) ? (size_t)M + 3 * (size_t)xi + (c - 1) : (c < 7) ? 4 * (size_t)M + 3 * (size_t)xi + (c - 4)
                                                                                       : 7 * (size_t)M + 4 * (size_t)xi + (c - 7);
 }
+template <typename A, typename... R>
+__device__ __forceinline__ const A& pack_first(const A& a, const R&...) { return a; }
+template <typename A>
+__device__ __forceinline__ const A& pack_last(const A& a) { return a; }
+template <typename A, typename B, typename... R>
+__device__ __forceinline__ const auto& pack_last(const A&, const B& b, const R&... r) { return pack_last(b, r...); }
 }  // namespace
 
 // kEns = 1 (gel_propagate_adjoint_ensemble*): as proptan_kernel's -- an EnsDev behind the arguments (the pack Ens
 // holds exactly that one; none with kEns = 0, whose instantiations keep their argument list), and the lane's view of the tables
 // (ens_lane_tables) in every call that reads the wind: the inner checkpoints' value steps, F1 .. F3 and the four reversed stages.
+//
+// kEns & 2 (gel_propagate_adjoint_wind*): a WindGradDev is the pack's LAST argument (behind the EnsDev where kEns = 3).
+// WIND ROWS: the lane owns column l of gww [Kg][2][gld] (lane-major like gws: the functionals of one vector sit on the same piece, so
+// their cells are neighbours), zeroed on the stream before the walk.  Every reversed air stage adds its (fw lwn, fw lwe) to the
+// cells of the piece's two rows (gel_wind_rows.h) by read-add-write, in walk order, by this lane alone: one writer, no atomics --
+// in section mode too, where the one lane walks every phase.  The rows lie below the LANE's Kw <= Kg.  After the walk the lane
+// copies its column out as gwind [lane][Kg][2]: every element is written, an untouched row is the +0.0 it was zeroed to.
+// kEns = 0 and 1 are the instantiations they were: the same argument lists, the same code.
 template <bool kChain, int kEns = 0, typename... Ens>
 __global__ __launch_bounds__(kPropAdjThreads) void propadj_kernel(ProblemDev P, PropDev Pd, PropAdjArgs A, Ens... ens) {
-  static_assert(sizeof...(Ens) == (kEns ? 1 : 0), "an EnsDev behind the arguments with kEns = 1, nothing otherwise");
+  static_assert(sizeof...(Ens) == (kEns & 1) + ((kEns >> 1) & 1), "an EnsDev with kEns & 1, then a WindGradDev with kEns & 2, nothing else");
+  constexpr bool kWind = (kEns & 2) != 0;
   constexpr int T = kPropAdjThreads;
   __shared__ double Fs[3 * 11 * T];   // F1 .. F3 of the step in hand: [stage][component][lane]
   const long long nl = (long long)A.nb * A.Q;
@@ -68,7 +83,9 @@ __global__ __launch_bounds__(kPropAdjThreads) void propadj_kernel(ProblemDev P, 
   double* const Fl = Fs + threadIdx.x;     // the lane's column: no other lane reads or writes it
   const int v = (int)(l / A.Q), qf = (int)(l - (long long)v * A.Q);
   Tables tbe = tb;   // under an ensemble: the lane's view (the wind part of its vector's member)
-  if constexpr (kEns != 0) tbe = ens_lane_view(P, tb, v, ens...);
+  if constexpr ((kEns & 1) != 0) tbe = ens_lane_view(P, tb, v, pack_first(ens...));
+  double* gwl = nullptr;   // the lane's column of gww
+  if constexpr (kWind) gwl = pack_last(ens...).gww + (size_t)l;
   const int M = P.M, N = P.N;
   const double* const xb = A.x + (size_t)v * P.nvars;
   const double* const yb = A.y + (size_t)v * 11 * (size_t)M;
@@ -138,7 +155,7 @@ __global__ __launch_bounds__(kPropAdjThreads) void propadj_kernel(ProblemDev P, 
               u0 = us[(size_t)pp * 2 * (size_t)A.ld];
               u1 = us[((size_t)pp * 2 + 1) * (size_t)A.ld];
             }
-            section_rhs<true>(P, ph, kEns ? tbe : tb, Pd.vp, sig[pp], to, tf, yt, u0, u1, F, fw);
+            section_rhs<true>(P, ph, (kEns & 1) ? tbe : tb, Pd.vp, sig[pp], to, tf, yt, u0, u1, F, fw);
 #pragma unroll
             for (int c = 0; c < 11; c++) acc[c] = st ? __builtin_fma(w, F[c], acc[c]) : F[c];
           }
@@ -169,7 +186,7 @@ __global__ __launch_bounds__(kPropAdjThreads) void propadj_kernel(ProblemDev P, 
               u0 = us[(size_t)pp * 2 * (size_t)A.ld];
               u1 = us[((size_t)pp * 2 + 1) * (size_t)A.ld];
             }
-            section_rhs<true>(P, ph, kEns ? tbe : tb, Pd.vp, sig[pp], to, tf, yt, u0, u1, F, fw);
+            section_rhs<true>(P, ph, (kEns & 1) ? tbe : tb, Pd.vp, sig[pp], to, tf, yt, u0, u1, F, fw);
 #pragma unroll
             for (int c = 0; c < 11; c++) Fl[(st * 11 + c) * T] = F[c];
           }
@@ -199,7 +216,27 @@ __global__ __launch_bounds__(kPropAdjThreads) void propadj_kernel(ProblemDev P, 
           }
           double F[11], lx[11];
           RhsAdjoint g;
-          section_rhs_adjoint(P, ph, kEns ? tbe : tb, Pd.vp, sig[pp], to, tf, yt, u0, u1, fw, lF, F, lx, g);
+          if constexpr (kWind) {
+            RhsWindAdjoint gw;
+            section_rhs_adjoint<true>(P, ph, (kEns & 1) ? tbe : tb, Pd.vp, sig[pp], to, tf, yt, u0, u1, fw, lF, F, lx, g, &gw);
+            if (ph.air) {   // (an air-less phase has no wind: gw is not written)
+              const size_t g1 = (size_t)A.gld;
+              double* const c0 = gwl + 2 * (size_t)gw.rows.i0 * g1;
+              if (gw.rows.i1 != gw.rows.i0) {
+                double* const c1 = gwl + 2 * (size_t)gw.rows.i1 * g1;
+                const double t1 = gw.rows.th, t0 = 1.0 - t1;
+                c0[0] = __builtin_fma(t0, gw.wn, c0[0]);
+                c0[g1] = __builtin_fma(t0, gw.we, c0[g1]);
+                c1[0] = __builtin_fma(t1, gw.wn, c1[0]);
+                c1[g1] = __builtin_fma(t1, gw.we, c1[g1]);
+              } else {
+                c0[0] = c0[0] + gw.wn;
+                c0[g1] = c0[g1] + gw.we;
+              }
+            }
+          } else {
+            section_rhs_adjoint(P, ph, kEns ? tbe : tb, Pd.vp, sig[pp], to, tf, yt, u0, u1, fw, lF, F, lx, g);
+          }
           if (st == 3) {   // <lm, acc> / 6 with acc of the value lines
             double d = 0.0;
 #pragma unroll
@@ -274,6 +311,15 @@ __global__ __launch_bounds__(kPropAdjThreads) void propadj_kernel(ProblemDev P, 
       bad |= nonfinite(g3);
     }
   } while (--s >= 0);
+  if constexpr (kWind) {
+    const WindGradDev& wg = pack_last(ens...);
+    double* const out = wg.gwind + (size_t)l * 2 * (size_t)wg.Kg;
+    for (int i = 0; i < 2 * wg.Kg; i++) {
+      const double gv = gwl[(size_t)i * (size_t)A.gld];
+      out[i] = gv;
+      bad |= nonfinite(gv);
+    }
+  }
   if (bad) *(volatile int32_t*)P.flag = 1;
 }
 
@@ -332,7 +378,8 @@ __global__ __launch_bounds__(kPropAdjSampleThreads) void prop_sample_t_kernel(Pr
   if (bad) *(volatile int32_t*)P.flag = 1;
 }
 
-hipError_t launch_propadj_slab(const ProblemDev& P, const PropDev& Pd, const PropAdjArgs& A, const EnsDev& ens, hipStream_t s) {
+hipError_t launch_propadj_slab(const ProblemDev& P, const PropDev& Pd, const PropAdjArgs& A, const EnsDev& ens, const WindGradDev& wg,
+                               hipStream_t s) {
   if (A.nb <= 0 || A.Q <= 0) return hipSuccess;
   if (Pd.restart) return hipErrorInvalidValue;
   const long long nl = (long long)A.nb * A.Q;
@@ -341,7 +388,18 @@ hipError_t launch_propadj_slab(const ProblemDev& P, const PropDev& Pd, const Pro
   const long long sgrid = (nl + kPropAdjSampleThreads - 1) / kPropAdjSampleThreads * ((long long)P.N + 1);
   if (grid <= 0) return hipSuccess;
   if (grid > 0x7fffffffLL || sgrid > 0x7fffffffLL) return hipErrorInvalidValue;
-  if (ens.tables) {
+  if (wg.gwind) {
+    // the rows must cover every table a lane may read: the handle's (no ensemble, or member -1) and the members'
+    if (!wg.gww || wg.Kg < P.Kw || (ens.tables && wg.Kg < ens.Kw)) return hipErrorInvalidValue;
+    if (const hipError_t e = hipMemsetAsync(wg.gww, 0, (size_t)wg.Kg * 2 * (size_t)A.gld * sizeof(double), s)) return e;
+    if (ens.tables) {
+      auto* const kern = Pd.chain ? propadj_kernel<true, 3, EnsDev, WindGradDev> : propadj_kernel<false, 3, EnsDev, WindGradDev>;
+      hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kPropAdjThreads), 0, s, P, Pd, A, ens, wg);
+    } else {
+      auto* const kern = Pd.chain ? propadj_kernel<true, 2, WindGradDev> : propadj_kernel<false, 2, WindGradDev>;
+      hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kPropAdjThreads), 0, s, P, Pd, A, wg);
+    }
+  } else if (ens.tables) {
     auto* const kern = Pd.chain ? propadj_kernel<true, 1, EnsDev> : propadj_kernel<false, 1, EnsDev>;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kPropAdjThreads), 0, s, P, Pd, A, ens);
   } else {

@@ -36,6 +36,12 @@ __device__ __forceinline__ size_t state_index(int M, int xi, int c) {
   return (c == 0) ? (size_t)xi : (c < 4) ? (size_t)M + 3 * (size_t)xi + (c - 1) : (c < 7) ? 4 * (size_t)M + 3 * (size_t)xi + (c - 4)
                                                                                       : 7 * (size_t)M + 4 * (size_t)xi + (c - 7);
 }
+template <typename A, typename... R>
+__device__ __forceinline__ const A& pack_first(const A& a, const R&...) { return a; }
+template <typename A>
+__device__ __forceinline__ const A& pack_last(const A& a) { return a; }
+template <typename A, typename B, typename... R>
+__device__ __forceinline__ const auto& pack_last(const A&, const B& b, const R&... r) { return pack_last(b, r...); }
 }  // namespace
 
 // kEns = 1 (gel_propagate_tangent_ensemble*): the kernel takes an EnsDev behind its arguments -- the pack Ens holds
@@ -43,9 +49,15 @@ __device__ __forceinline__ size_t state_index(int M, int xi, int c) {
 // up in the table its vector is assigned (ens_lane_tables; -1: the handle's own).  The view replaces tb in the ONE call that reads
 // the wind, so the value, the slope of the interval the value lookup took (dw3) and the clamps all come from the member's rows.
 // Every lookup searches (wind_ned2_centre): the interval is that of the member's handle, and so are the bits.
+//
+// kEns & 2 (gel_propagate_tangent_wind*): a WindSeedDev is the pack's LAST argument (behind the EnsDev where kEns = 3),
+// and the lane's direction also moves the values of the wind table its flight reads, by its seed dwind [Kg][2] in global memory
+// (per lane, or per direction with shared seeds).  The seed is read at the rows of the piece the value lookup took, which lie below
+// the LANE's Kw (the handle's, or its member's): rows of the seed at or beyond that are not read.  kEns = 0 and 1 are the
+// instantiations they were: the same argument lists, the same code.
 template <bool kChain, int kEns = 0, typename... Ens>
 __global__ __launch_bounds__(kPropThreads) void proptan_kernel(ProblemDev P, PropDev Pd, PropTanArgs A, Ens... ens) {
-  static_assert(sizeof...(Ens) == (kEns ? 1 : 0), "an EnsDev behind the arguments with kEns = 1, nothing otherwise");
+  static_assert(sizeof...(Ens) == (kEns & 1) + ((kEns >> 1) & 1), "an EnsDev with kEns & 1, then a WindSeedDev with kEns & 2, nothing else");
   const long long nl = (long long)A.nb * A.P;
   const long long ngrp = (nl + kPropThreads - 1) / kPropThreads;
   const int seg = kChain ? 0 : (int)(blockIdx.x / ngrp);
@@ -55,8 +67,13 @@ __global__ __launch_bounds__(kPropThreads) void proptan_kernel(ProblemDev P, Pro
   if (seg >= Pd.nseg || l >= nl) return;   // (idle lanes leave: they stay out of the calm-air vote of wind_eci_or_calm; no barrier follows)
   const int v = (int)(l / A.P), p = (int)(l - (long long)v * A.P);
   Tables tbe = tb;   // under an ensemble: the lane's view (the wind part of its vector's member)
-  if constexpr (kEns != 0) tbe = ens_lane_view(P, tb, v, ens...);
+  if constexpr ((kEns & 1) != 0) tbe = ens_lane_view(P, tb, v, pack_first(ens...));
   const size_t ls = A.shared ? (size_t)p : (size_t)l;   // the lane's seed set
+  const double* dwl = nullptr;   // the lane's wind seed [Kg][2]
+  if constexpr ((kEns & 2) != 0) {
+    const WindSeedDev& wd = pack_last(ens...);
+    dwl = wd.dwind + ls * 2 * (size_t)wd.Kg;
+  }
   bool bad = false;
   double yv[11], dyv[11];
   const int M = P.M, N = P.N;
@@ -153,7 +170,7 @@ __global__ __launch_bounds__(kPropThreads) void proptan_kernel(ProblemDev P, Pro
               d.du1 = dus[((size_t)pp * 2 + 1) * (size_t)A.dld];
             }
           }
-          section_rhs_tangent(P, ph, kEns ? tbe : tb, Pd.vp, sig[pp], to, tf, yt, u0, u1, fw, dyt, d, F, dF);
+          section_rhs_tangent<(kEns & 2) != 0>(P, ph, (kEns & 1) ? tbe : tb, Pd.vp, sig[pp], to, tf, yt, u0, u1, fw, dyt, d, F, dF, dwl);
 #pragma unroll
           for (int c = 0; c < 11; c++) {
             acc[c] = st ? __builtin_fma(w, F[c], acc[c]) : F[c];
@@ -179,7 +196,8 @@ __global__ __launch_bounds__(kPropThreads) void proptan_kernel(ProblemDev P, Pro
   if (bad) *(volatile int32_t*)P.flag = 1;
 }
 
-hipError_t launch_proptan_slab(const ProblemDev& P, const PropDev& Pd, const PropTanArgs& A, const EnsDev& ens, hipStream_t s) {
+hipError_t launch_proptan_slab(const ProblemDev& P, const PropDev& Pd, const PropTanArgs& A, const EnsDev& ens, const WindSeedDev& wd,
+                               hipStream_t s) {
   if (A.nb <= 0 || A.P <= 0) return hipSuccess;
   const long long nl = (long long)A.nb * A.P;
   if (A.ld < A.nb || (A.dx && A.dld < (A.shared ? (long long)A.P : nl))) return hipErrorInvalidValue;
@@ -187,7 +205,17 @@ hipError_t launch_proptan_slab(const ProblemDev& P, const PropDev& Pd, const Pro
   const long long grid = Pd.chain ? ngrp : ngrp * Pd.nseg;
   if (grid <= 0) return hipSuccess;
   if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
-  if (ens.tables) {
+  if (wd.dwind) {
+    // the seed's rows must cover every table a lane may read: the handle's (no ensemble, or member -1) and the members'
+    if (wd.Kg < P.Kw || (ens.tables && wd.Kg < ens.Kw)) return hipErrorInvalidValue;
+    if (ens.tables) {
+      auto* const kern = Pd.chain ? proptan_kernel<true, 3, EnsDev, WindSeedDev> : proptan_kernel<false, 3, EnsDev, WindSeedDev>;
+      hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kPropThreads), 0, s, P, Pd, A, ens, wd);
+    } else {
+      auto* const kern = Pd.chain ? proptan_kernel<true, 2, WindSeedDev> : proptan_kernel<false, 2, WindSeedDev>;
+      hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kPropThreads), 0, s, P, Pd, A, wd);
+    }
+  } else if (ens.tables) {
     auto* const kern = Pd.chain ? proptan_kernel<true, 1, EnsDev> : proptan_kernel<false, 1, EnsDev>;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kPropThreads), 0, s, P, Pd, A, ens);
   } else {

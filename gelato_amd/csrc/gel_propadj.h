@@ -29,10 +29,20 @@ struct PropAdjArgs {
   long long ld, gld;
 };
 
+// The wind rows' gradient of a slab: gww [Kg][2][gld] the lanes' columns (workspace, zeroed by the launch), gwind
+// [nb][Q][Kg][2] the result (the slab's first lane), or gwind == null: not wanted.  Kg >= the row count of every table a lane of the
+// launch may read.
+struct WindGradDev {
+  double* gww;
+  double* gwind;
+  int32_t Kg, pad;
+};
+
 // propadj_kernel (state rows of gx, gdisp, gws, gS), then prop_sample_t_kernel (control and time entries of gx).  ens: the wind
 // ensemble with the SLAB's part of the assignment (a lane's vector is lane / Q), or ens.tables == null: the instantiations without
 // an ensemble, launched as before.  With an ensemble A.y must be the ensemble flight's (prop_kernel<*, *, 1> under
-// the same assignment): the checkpoints
-hipError_t launch_propadj_slab(const ProblemDev& P, const PropDev& Pd, const PropAdjArgs& A, const EnsDev& ens, hipStream_t s);
+// the same assignment): the checkpoints.  wg.gwind == null: the instantiations without the wind rows, launched as before
+hipError_t launch_propadj_slab(const ProblemDev& P, const PropDev& Pd, const PropAdjArgs& A, const EnsDev& ens, const WindGradDev& wg,
+                               hipStream_t s);
 
 }  // namespace gel

@@ -22,8 +22,16 @@ struct PropTanArgs {
   long long ld, dld;
 };
 
+// The wind seeds of a slab: dwind [nb][P][Kg][2], shared: [P][Kg][2] (the slab's first lane, like dx), or
+// dwind == null: no wind seed.  Kg >= the row count of every table a lane of the launch may read.
+struct WindSeedDev {
+  const double* dwind;
+  int32_t Kg, pad;
+};
+
 // ens: the wind ensemble with the SLAB's part of the assignment (ens.member = the entry of the slab's first vector; a lane's vector
 // is lane / P), or ens.tables == null: the instantiations without an ensemble, launched as before
-hipError_t launch_proptan_slab(const ProblemDev& P, const PropDev& Pd, const PropTanArgs& A, const EnsDev& ens, hipStream_t s);
+hipError_t launch_proptan_slab(const ProblemDev& P, const PropDev& Pd, const PropTanArgs& A, const EnsDev& ens, const WindSeedDev& wd,
+                               hipStream_t s);
 
 }  // namespace gel

@@ -16,9 +16,14 @@
 // Out: lxt [11] = J^T lF in the units of the value call's state, and in RhsAdjoint the multipliers of the controls and of
 // ph.thrust, ph.mf_um, ph.area AS THE VALUE CALL HOLDS THEM (the caller multiplies by the handle's unscaled values, as the tangent
 // forms d.dthrust from them) and of the wind factor.
+//
+// kWind (gel_propagate_adjoint_wind*): also out, in gwd, the multipliers (fw lwn, fw lwe) of the seed the tangent's
+// kWind lines look up, with the rows and the weight of that lookup (gel_wind_rows.h); the caller splits them between the rows.
+// Not written in an air-less phase.  kWind = false forms none of this and is the function it was.
 #pragma once
 #include "gel_exact.h"
 #include "gel_section_rhs.h"
+#include "gel_wind_rows.h"
 
 namespace gel {
 
@@ -26,10 +31,15 @@ struct RhsAdjoint {
   double u0, u1;
   double thrust, mf, area, fw;
 };
+struct RhsWindAdjoint {
+  WindRows rows;
+  double wn, we;
+};
 
+template <bool kWind = false>
 GEL_DEV void section_rhs_adjoint(const ProblemDev& P, const PhaseDev& ph, const Tables& tb, double vp, double sig, double to,
                                  double tf, const double xt[11], double u0, double u1, double fw, const double lF[11],
-                                 double F[11], double lxt[11], RhsAdjoint& g) {
+                                 double F[11], double lxt[11], RhsAdjoint& g, RhsWindAdjoint* gwd = nullptr) {
   F[0] = ph.engine_on ? ph.mf_um : 0.0;
   g.mf = ph.engine_on ? lF[0] : 0.0;
 #pragma unroll
@@ -121,6 +131,11 @@ GEL_DEV void section_rhs_adjoint(const ProblemDev& P, const PhaseDev& ph, const 
     const double lwe = (-slon) * ldw[0] + clon * ldw[1];
     // dwn = wn dfw, dwe = we dfw with the interpolated (unscaled) wind
     g.fw = pp.wn * lwn + pp.we * lwe;
+    if constexpr (kWind) {
+      gwd->rows = wind_rows(tail.h, tail.piece, tb.wind, tb.Kw);
+      gwd->wn = fw * lwn;
+      gwd->we = fw * lwe;
+    }
   } else {
     double gv[3];
     gravity_eci(r, P.barC20, gv);

@@ -16,9 +16,15 @@
 // taken as gel_kernels_exact.hip takes it for the t columns of the velocity rows: zero (the rotations by the Earth angle cancel
 // off the axis, and on it the longitude is held, like the partials of p and of the longitude there).  The knot times therefore
 // enter a flight's tangent through the step S h alone.
+//
+// kWind (gel_propagate_tangent_wind*): the direction also moves the VALUES of the wind table, by the seed dwl [Kw][2]
+// (north, east per row; the altitudes stay).  The seed is looked up on the piece the value lookup took (gel_wind_rows.h), times fw,
+// and added to dwn / dwe beside the factor's term; where that product is zero the sum is not formed, so a zero seed leaves the
+// bits of the instantiation without it.  kWind = false reads none of this and is the function it was.
 #pragma once
 #include "gel_exact.h"
 #include "gel_section_rhs.h"
+#include "gel_wind_rows.h"
 
 namespace gel {
 
@@ -27,9 +33,10 @@ struct RhsDirection {
   double dthrust, dmf, darea, dfw;
 };
 
+template <bool kWind = false>
 GEL_DEV void section_rhs_tangent(const ProblemDev& P, const PhaseDev& ph, const Tables& tb, double vp, double sig, double to,
                                  double tf, const double xt[11], double u0, double u1, double fw, const double dxt[11],
-                                 const RhsDirection& d, double F[11], double dF[11]) {
+                                 const RhsDirection& d, double F[11], double dF[11], const double* dwl = nullptr) {
   F[0] = ph.engine_on ? ph.mf_um : 0.0;
   dF[0] = ph.engine_on ? d.dmf : 0.0;
 #pragma unroll
@@ -85,7 +92,13 @@ GEL_DEV void section_rhs_tangent(const ProblemDev& P, const PhaseDev& ph, const 
     wind_eci_tangent(r, pp.inv_p, clon, slon, pc.sl, pc.cl, wn, we, s0, s1, dh, dsl, dcl, dw3);
     const double dhd = dh[0] * dr[0] + dh[1] * dr[1] + dh[2] * dr[2];
     // the wind factor's direction: (wn N + we E) dfw with the value's axes
-    const double dwn = pp.wn * d.dfw, dwe = pp.we * d.dfw;
+    double dwn = pp.wn * d.dfw, dwe = pp.we * d.dfw;
+    if constexpr (kWind) {   // the table's own direction: the seed on the value's piece, times the factor
+      const WindRows wr = wind_rows(tail.h, tail.piece, tb.wind, tb.Kw);
+      const double sn = wind_rows_seed(wr, dwl, 0) * fw, se = wind_rows_seed(wr, dwl, 1) * fw;
+      dwn = (sn == 0.0) ? dwn : dwn + sn;
+      dwe = (se == 0.0) ? dwe : dwe + se;
+    }
     const double dw[3] = {dw3[0][0] * dr[0] + dw3[1][0] * dr[1] + dw3[2][0] * dr[2] + (dwn * (-pc.sl * clon) + dwe * (-slon)),
                           dw3[0][1] * dr[0] + dw3[1][1] * dr[1] + dw3[2][1] * dr[2] + (dwn * (-pc.sl * slon) + dwe * clon),
                           dw3[0][2] * dr[0] + dw3[1][2] * dr[1] + dw3[2][2] * dr[2] + dwn * pc.cl};

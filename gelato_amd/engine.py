@@ -224,21 +224,31 @@ class PropagationPlan:
             raise ValueError("%s: %s, not %s" % (name, want, a.shape))
         return np.ascontiguousarray(a)
 
-    def tangent(self, X, dX=None, dispersion=None, ddispersion=None, shared=False, ensemble=None):
+    def wind_rows(self, ensemble=None):
+        """Kg: the rows of a wind seed / of GW (gel_prop_wind_rows): the handle's Kw, under an ensemble the larger
+        of that and the ensemble's (works on host-only handles)"""
+        self._live()
+        kg = C.c_int32(0)
+        check(lib().gel_prop_wind_rows(self._p, _ensemble_ptr(ensemble, self._owner), C.byref(kg)))
+        return int(kg.value)
+
+    def tangent(self, X, dX=None, dispersion=None, ddispersion=None, shared=False, ensemble=None, dwind=None):
         """The flight of apply() and its exact derivative along seed directions (gel_propagate_tangent).
         X [B, nvars] (or [nvars]); dX: None, or the directions in x, [B, P, nvars] ([P, nvars] with shared=True: one set for every
         vector); dispersion: None or [B, S, 4]; ddispersion: None, or the directions in the factors, [B, P, S, 4] ([P, S, 4] shared).
-        At least one of dX / ddispersion.  ensemble: None, or a WindEnsemble of this engine assigned B vectors: every vector's
+        At least one of dX / ddispersion / dwind.  ensemble: None, or a WindEnsemble of this engine assigned B vectors: every vector's
         flight AND derivative under the wind table its entry selects (gel_propagate_tangent_ensemble).
+        dwind: None, or the directions in the VALUES of the wind table the flight reads, [B, P, Kg, 2] ([P, Kg, 2] shared), north and
+        east per row, Kg = wind_rows(ensemble) (gel_propagate_tangent_wind); None is the call without it.
         -> (Y [B, 11 M]: apply()'s Y bit for bit, dY [B, P, 11 M], status)"""
         self._live()
         X = _f64(X).reshape(-1, self.nvars)
         B = X.shape[0]
         ens = _ensemble_ptr(ensemble, self._owner)
-        if dX is None and ddispersion is None:
-            raise ValueError("tangent: at least one of dX and ddispersion")
+        if dX is None and ddispersion is None and dwind is None:
+            raise ValueError("tangent: at least one of dX, ddispersion and dwind")
         shared = bool(shared)
-        lead = np.asarray(dX if dX is not None else ddispersion)
+        lead = np.asarray(dX if dX is not None else ddispersion if ddispersion is not None else dwind)
         if lead.ndim < (2 if shared else 3):
             raise ValueError("tangent: seeds are [P, ...] with shared=True, else [B, P, ...]")
         P = int(lead.shape[0] if shared else lead.shape[1])
@@ -260,14 +270,23 @@ class PropagationPlan:
         Y = np.empty((B, 11 * self.M))
         dY = np.empty((B, P, 11 * self.M))
         opt = lambda a: _d(a) if a is not None else None   # noqa: E731
-        rc = check(lib().gel_propagate_tangent_ensemble(self._p, B, P, int(shared), _d(X), opt(disp), opt(dx), opt(dd), ens, _d(Y), _d(dY)))
+        if dwind is None:
+            rc = check(lib().gel_propagate_tangent_ensemble(self._p, B, P, int(shared), _d(X), opt(disp), opt(dx), opt(dd), ens, _d(Y), _d(dY)))
+            return Y, dY, rc
+        dw = self._seed(dwind, "dwind", B, P, shared, (self.wind_rows(ensemble), 2))
+        rc = check(lib().gel_propagate_tangent_wind(self._p, B, P, int(shared), _d(X), opt(disp), opt(dx), opt(dd), _d(dw), ens, _d(Y), _d(dY)))
         return Y, dY, rc
 
-    def tangent_device(self, B, P, d_x, d_y, d_dy, d_dx=0, d_dispersion=0, d_ddispersion=0, shared=False, ensemble=None):
-        """device buffers: d_y [B][11 M], d_dy [B][P][11 M], d_dx / d_ddispersion as tangent() lays them out or 0 (not both),
-        d_dispersion [B][S][4] or 0; ensemble: None or a WindEnsemble of this engine assigned B vectors; asynchronous on the engine's
-        own stream; status through Engine.sync()"""
+    def tangent_device(self, B, P, d_x, d_y, d_dy, d_dx=0, d_dispersion=0, d_ddispersion=0, shared=False, ensemble=None, d_dwind=0):
+        """device buffers: d_y [B][11 M], d_dy [B][P][11 M], d_dx / d_ddispersion / d_dwind as tangent() lays them out or 0 (not
+        all), d_dispersion [B][S][4] or 0; ensemble: None or a WindEnsemble of this engine assigned B vectors; asynchronous on the
+        engine's own stream; status through Engine.sync()"""
         self._live()
+        if d_dwind:
+            check(lib().gel_propagate_tangent_wind_device(self._p, int(B), int(P), int(bool(shared)), d_x, d_dispersion or None,
+                                                          d_dx or None, d_ddispersion or None, d_dwind,
+                                                          _ensemble_ptr(ensemble, self._owner), d_y, d_dy))
+            return
         check(lib().gel_propagate_tangent_ensemble_device(self._p, int(B), int(P), int(bool(shared)), d_x, d_dispersion or None,
                                                           d_dx or None, d_ddispersion or None, _ensemble_ptr(ensemble, self._owner),
                                                           d_y, d_dy))
@@ -279,13 +298,17 @@ class PropagationPlan:
         check(lib().gel_prop_tangent_info(self._p, int(B), int(P), int(bool(shared)), info))
         return dict(zip(("sample_set_bytes", "lanes_per_slab", "slabs"), (int(v) for v in info)))
 
-    def adjoint(self, X, Lam, dispersion=None, shared=False, ensemble=None):
+    def adjoint(self, X, Lam, dispersion=None, shared=False, ensemble=None, want_wind=False):
         """The flight of apply() and the gradients of Q functionals of it in one backward pass (gel_propagate_adjoint):
         the transpose of the linear map tangent() applies.  X [B, nvars] (or [nvars]); Lam: the functionals as weights on Y,
         [B, Q, 11 M] ([Q, 11 M] with shared=True: one set for every vector); dispersion: None or [B, S, 4].  Chain and section plans.
         ensemble: None, or a WindEnsemble of this engine assigned B vectors: every vector's flight AND gradients under the wind
         table its entry selects (gel_propagate_adjoint_ensemble).
-        -> (Y [B, 11 M]: apply()'s Y bit for bit, GX [B, Q, nvars], GD [B, Q, S, 4], status)"""
+        want_wind: also the gradients with respect to the VALUES of the wind table every flight reads (gel_propagate_adjoint_wind;
+        DESIGN.md 3.23), GW [B, Q, Kg, 2], Kg = wind_rows(ensemble): rows at or beyond a vector's own table, and rows no stage of its
+        flight touched, are +0.0.
+        -> (Y [B, 11 M]: apply()'s Y bit for bit, GX [B, Q, nvars], GD [B, Q, S, 4], status), with want_wind
+        (Y, GX, GD, status, GW)"""
         self._live()
         X = _f64(X).reshape(-1, self.nvars)
         B = X.shape[0]
@@ -314,21 +337,36 @@ class PropagationPlan:
         Y = np.empty((B, 11 * self.M))
         GX = np.empty((B, Q, self.nvars))
         GD = np.empty((B, Q, self.S, nd))
+        if want_wind:
+            GW = np.empty((B, Q, self.wind_rows(ensemble), 2))
+            rc = check(lib().gel_propagate_adjoint_wind(self._p, B, Q, int(shared), _d(X), _d(disp) if disp is not None else None, _d(lam),
+                                                        ens, _d(Y), _d(GX), _d(GD), _d(GW)))
+            return Y, GX, GD, rc, GW
         rc = check(lib().gel_propagate_adjoint_ensemble(self._p, B, Q, int(shared), _d(X), _d(disp) if disp is not None else None, _d(lam),
                                                         ens, _d(Y), _d(GX), _d(GD)))
         return Y, GX, GD, rc
 
-    def adjoint_device(self, B, Q, d_x, d_lam, d_y, d_gx, d_gdisp=0, d_dispersion=0, shared=False, ensemble=None):
+    def adjoint_device(self, B, Q, d_x, d_lam, d_y, d_gx, d_gdisp=0, d_dispersion=0, shared=False, ensemble=None, d_gwind=0):
         """device buffers: d_lam as adjoint() lays Lam out, d_y [B][11 M], d_gx [B][Q][nvars], d_gdisp [B][Q][S][4] or 0,
-        d_dispersion [B][S][4] or 0; ensemble: None or a WindEnsemble of this engine assigned B vectors; asynchronous on the engine's
-        own stream; status through Engine.sync()"""
+        d_gwind [B][Q][Kg][2] or 0, d_dispersion [B][S][4] or 0; ensemble: None or a WindEnsemble of this engine assigned B vectors;
+        asynchronous on the engine's own stream; status through Engine.sync()"""
         self._live()
+        if d_gwind:
+            check(lib().gel_propagate_adjoint_wind_device(self._p, int(B), int(Q), int(bool(shared)), d_x, d_dispersion or None,
+                                                          d_lam or None, _ensemble_ptr(ensemble, self._owner), d_y, d_gx, d_gdisp or None,
+                                                          d_gwind))
+            return
         check(lib().gel_propagate_adjoint_ensemble_device(self._p, int(B), int(Q), int(bool(shared)), d_x, d_dispersion or None,
                                                           d_lam or None, _ensemble_ptr(ensemble, self._owner), d_y, d_gx, d_gdisp or None))
 
-    def adjoint_info(self, B, Q, shared=False):
-        """{"lane_bytes", "lanes_per_slab", "slabs"} of an adjoint call NOW (works on host-only handles)"""
+    def adjoint_info(self, B, Q, shared=False, want_wind=False, ensemble=None):
+        """{"lane_bytes", "lanes_per_slab", "slabs"} of an adjoint call NOW (works on host-only handles); with want_wind those of a
+        call that also returns GW (16 Kg bytes per lane more), and "wind_rows": Kg"""
         self._live()
+        if want_wind:
+            info = (C.c_int64 * 4)()
+            check(lib().gel_prop_adjoint_wind_info(self._p, _ensemble_ptr(ensemble, self._owner), int(B), int(Q), int(bool(shared)), 1, info))
+            return dict(zip(("lane_bytes", "lanes_per_slab", "slabs", "wind_rows"), (int(v) for v in info)))
         info = (C.c_int64 * 3)()
         check(lib().gel_prop_adjoint_info(self._p, int(B), int(Q), int(bool(shared)), info))
         return dict(zip(("lane_bytes", "lanes_per_slab", "slabs"), (int(v) for v in info)))
@@ -401,6 +439,7 @@ class WindEnsemble:
             raise ValueError("members: -1 or 0 .. %d, not %d .. %d" % (self.E - 1, int(m.min()), int(m.max())))
         m = np.ascontiguousarray(m, dtype=np.int32)
         check(lib().gel_wind_ensemble_assign(self._p, int(m.size), m.ctypes.data_as(_ip)))
+        self.members = m.copy()   # the assignment in force (what flight_gradient(wind=True) names the altitudes by)
         return self
 
 
@@ -430,6 +469,7 @@ class Engine:
         wind, ca = _f64(prob["wind_table"]), _f64(prob["ca_table"])
         units = _f64(prob["units"])
         self.units = units.copy()   # (mass, position, velocity, u, t)
+        self.wind_altitudes = wind.reshape(-1, 3)[:, 0].copy()   # of the handle's own wind table (flight_gradient(wind=True))
         self.prob = {k: np.array(prob[k]) for k in ("num_nodes", "thrust", "massflow", "reference_area", "nozzle_area",
                                                     "engine_on", "attitude_hold")}
         d = GelProblemDesc()

@@ -390,3 +390,28 @@ def linear_covariance(J, sigma):
     C = np.einsum("...ip,...jp->...ij", A, A)
     lo = np.tril(np.ones(C.shape[-2:], dtype=bool))
     return np.where(lo, C, np.swapaxes(C, -1, -2))
+
+
+def wind_linear_prediction(gwind, base_table, tables):
+    """The first-order change of every functional under other wind tables, without flying them:
+    sum over rows and components of gwind * (W_e - W_0).  gwind [..., Kg, 2]: propagate.flight_gradient(wind=True)["gwind"] (or
+    PropagationPlan.adjoint(want_wind=True)'s GW) taken under base_table; base_table [Kw, 3] (altitude, north, east), Kw <= Kg;
+    tables [E, Kw, 3] (one table: [Kw, 3]).  Every table must have the base's altitudes, bit for bit: the gradient holds the
+    altitudes fixed, and another grid is another map (ValueError).  -> [E, ...]: the leading axes of gwind behind the table's.
+    Host numpy."""
+    g = np.asarray(gwind, dtype=np.float64)
+    base = np.asarray(base_table, dtype=np.float64)
+    T = np.asarray(tables, dtype=np.float64)
+    if base.ndim != 2 or base.shape[1] != 3:
+        raise ValueError("base_table: [Kw, 3]")
+    if T.ndim == 2:
+        T = T[None]
+    if T.ndim != 3 or T.shape[1:] != base.shape:
+        raise ValueError("tables: [E, Kw, 3] with the base's Kw = %d rows" % base.shape[0])
+    Kw = base.shape[0]
+    if g.ndim < 2 or g.shape[-1] != 2 or g.shape[-2] < Kw:
+        raise ValueError("gwind: [..., Kg, 2] with Kg >= the base's %d rows" % Kw)
+    if not np.array_equal(T[:, :, 0], np.broadcast_to(base[:, 0], T.shape[:2])):
+        raise ValueError("tables: a member's altitudes differ from the base table's (the gradient holds the altitudes fixed)")
+    dW = T[:, :, 1:] - base[None, :, 1:]                      # [E, Kw, 2]
+    return np.einsum("...kc,ekc->e...", g[..., :Kw, :], dW)

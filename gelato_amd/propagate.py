@@ -278,7 +278,7 @@ def flight_jacobian(xdict_or_X, pdict, unitdict, steps=4, wrt=("initial", "dispe
 GRADIENT_OF = ("terminal", "rows")
 
 
-def flight_gradient(xdict_or_X, pdict, unitdict, steps=4, of=("terminal",), dispersion=None, engine=None, ensemble=None):
+def flight_gradient(xdict_or_X, pdict, unitdict, steps=4, of=("terminal",), dispersion=None, engine=None, ensemble=None, wind=False):
     """The gradients of functionals of the flight fly() reports (one chain, RK4 with 2 * steps steps per node interval) with respect to
     EVERY input in one backward pass: the adjoint flight (PropagationPlan.adjoint), where flight_jacobian pays one
     lane per column.  of = ("terminal",): the 11 components of the last state node in physical units (kg, m, m/s, 1);
@@ -293,7 +293,12 @@ def flight_gradient(xdict_or_X, pdict, unitdict, steps=4, of=("terminal",), disp
                             every knot, ALL controls and the knot times; +0.0 where the flight does not read x,
         "gdisp" [B, Q, S, 4]: with respect to the factors,
         "columns" names [P] and "jacobian" [B, Q, P]: the entries flight_jacobian's columns name (jacobian_seeds with all four groups:
-                            "initial:*", "dispersion:*[s]", "time[i]", and "u*_bias[s]" = the sum over the phase's nodes)}"""
+                            "initial:*", "dispersion:*[s]", "time[i]", and "u*_bias[s]" = the sum over the phase's nodes)}
+    wind=True adds the gradient with respect to the VALUES of the wind table every flight reads:
+        "gwind" [B, Q, Kg, 2]: north and east per row, in the functional's units per m/s (scaled like gx for of=("terminal",)); rows
+                            beyond a vector's own table and rows no stage touched are zero,
+        "wind_altitudes":   the rows' altitudes: [Kg] the engine's table's, or under an ensemble [B, Kg] those of every vector's
+                            member (NaN beyond its rows).  montecarlo.wind_linear_prediction reads both."""
     steps = int(steps)
     if steps < 1:
         raise ValueError("steps: at least 1")
@@ -341,7 +346,11 @@ def flight_gradient(xdict_or_X, pdict, unitdict, steps=4, of=("terminal",), disp
             extra = g[:, :, 11 * M:]          # the rows' own dependence on u and t
             scale = np.ones(Q)
             shared = False
-        Y, GX, GD, rc = plan.adjoint(X, lam, dispersion=dispersion, shared=shared, ensemble=ensemble)
+        GW = None
+        if wind:
+            Y, GX, GD, rc, GW = plan.adjoint(X, lam, dispersion=dispersion, shared=shared, ensemble=ensemble, want_wind=True)
+        else:
+            Y, GX, GD, rc = plan.adjoint(X, lam, dispersion=dispersion, shared=shared, ensemble=ensemble)
     finally:
         plan.close()
     GX = GX * scale[None, :, None]
@@ -352,5 +361,21 @@ def flight_gradient(xdict_or_X, pdict, unitdict, steps=4, of=("terminal",), disp
     x_flown[:, :11 * M] = Y
     cols, dX, dD = jacobian_seeds(engine.num_nodes, engine.prob["attitude_hold"], JACOBIAN_GROUPS)
     jac = np.einsum("bqv,pv->bqp", GX, dX) + np.einsum("bqsf,psf->bqp", GD, dD)
-    return {"functionals": names, "status": max(status, int(rc)), "y": Y, "x_flown": x_flown, "gx": GX, "gdisp": GD, "columns": cols,
-            "jacobian": jac}
+    out = {"functionals": names, "status": max(status, int(rc)), "y": Y, "x_flown": x_flown, "gx": GX, "gdisp": GD, "columns": cols,
+           "jacobian": jac}
+    if wind:
+        out["gwind"] = GW * scale[None, :, None, None]
+        own = engine.wind_altitudes
+        Kg = GW.shape[2]
+        if ensemble is None:
+            out["wind_altitudes"] = own.copy()
+        else:
+            alt = np.full((B, Kg), np.nan)
+            rows = {-1: own}
+            for b, e in enumerate(ensemble.members):
+                e = int(e)
+                if e not in rows:
+                    rows[e] = ensemble.member(e)["rows"][:, 0].copy()
+                alt[b, :rows[e].size] = rows[e]
+            out["wind_altitudes"] = alt
+    return out

@@ -883,6 +883,44 @@ int gel_propagate_adjoint_ensemble_device(gel_prop_plan* plan, int32_t B, int32_
                                           const double* d_disp /* or NULL */, const double* d_lam, gel_wind_ensemble* ens /* or NULL */,
                                           double* d_y, double* d_gx, double* d_gdisp /* or NULL */);
 
+/* ---- wind-profile sensitivities of the flight: the derivative of the flown trajectory with respect to the VALUES
+ *      of the wind table its flight reads -- W [Kw][2], north and east per row -- with the table's altitudes x fixed.  The map is
+ *      what is coded: the lookup W[i] + (h - x[i]) slope[i] on the piece i with x[i] < h <= x[i + 1], slope staged as
+ *      (W[i + 1] - W[i]) / (x[i + 1] - x[i]), row 0 for h <= x[0] and row Kw - 1 for h > x[Kw - 1], the result times the wind factor
+ *      fw.  It is linear in W, so along a seed dW the tangent is that lookup applied to the seed on the piece the value took:
+ *        th = (h - x[i]) / (x[i + 1] - x[i]);   fma(th, dW[i + 1] - dW[i], dW[i]) inside;   the end row's seed in a clamped end;
+ *      times fw, added to the tangent of the interpolated wind beside wn dfw (not added where it is zero: a zero seed changes no
+ *      bit).  The adjoint is the transpose: every reversed air stage's (fw lwn, fw lwe) goes to rows i and i + 1 with the weights
+ *      1 - th and th, in a clamped end wholly to the end row.  An air-less phase contributes nothing.
+ *      Rows: Kg = gel_prop_wind_rows = the handle's Kw, under an ensemble max(handle's Kw, ensemble's Kw).  A lane's table has
+ *      Kw <= Kg rows (the handle's, or its vector's member's): seed rows at or beyond Kw are not read, gwind rows there are +0.0.
+ *      dwind [B][P][Kg][2], shared = 1: [P][Kg][2].  gwind [B][Q][Kg][2]: every element is written by every call; a row no stage
+ *      touched is +0.0.  The tangent accepts any non-empty subset of the seeds dx, ddisp, dwind.
+ *      dwind == NULL / gwind == NULL IS gel_propagate_tangent_ensemble* / gel_propagate_adjoint_ensemble*: the same kernels, the same
+ *      bits.  With gwind wanted, y, gx and gdisp are still those bits; with dwind given and zero, dy is.  A slice's bits depend
+ *      neither on B, P / Q, its place in the batch, shared, the form of the call nor the slab size; a seed or lam times 2^k gives the
+ *      outputs times 2^k bit for bit; under an ensemble a vector with member e gets the bits of a handle created with
+ *      wind_table = tables[e].  Accumulation: each (vector, functional) owns one column of a workspace [Kg][2][lanes], zeroed on the
+ *      stream, updated by read-add-write in walk order by that lane alone (no atomics); 16 Kg bytes per lane more workspace
+ *      (gel_prop_adjoint_wind_info: info[0 .. 2] as gel_prop_adjoint_info with that counted where want_gwind != 0, info[3] = Kg).
+ *      Refusals: the parents', decided before a buffer or the device is looked at, with the call's name in gel_last_error.  A
+ *      non-finite gwind entry raises GEL_NONFINITE like gx.  No stream argument, as in the parents. ---- */
+int gel_prop_wind_rows(const gel_prop_plan* plan, const gel_wind_ensemble* ens /* or NULL */, int32_t* Kg);
+int gel_propagate_tangent_wind(gel_prop_plan* plan, int32_t B, int32_t P, int32_t shared, const double* x, const double* disp /* or NULL */,
+                               const double* dx /* or NULL */, const double* ddisp /* or NULL */, const double* dwind /* or NULL */,
+                               gel_wind_ensemble* ens /* or NULL */, double* y, double* dy);
+int gel_propagate_tangent_wind_device(gel_prop_plan* plan, int32_t B, int32_t P, int32_t shared, const double* d_x,
+                                      const double* d_disp /* or NULL */, const double* d_dx /* or NULL */, const double* d_ddisp /* or NULL */,
+                                      const double* d_dwind /* or NULL */, gel_wind_ensemble* ens /* or NULL */, double* d_y, double* d_dy);
+int gel_propagate_adjoint_wind(gel_prop_plan* plan, int32_t B, int32_t Q, int32_t shared, const double* x, const double* disp /* or NULL */,
+                               const double* lam, gel_wind_ensemble* ens /* or NULL */, double* y, double* gx, double* gdisp /* or NULL */,
+                               double* gwind /* or NULL */);
+int gel_propagate_adjoint_wind_device(gel_prop_plan* plan, int32_t B, int32_t Q, int32_t shared, const double* d_x,
+                                      const double* d_disp /* or NULL */, const double* d_lam, gel_wind_ensemble* ens /* or NULL */,
+                                      double* d_y, double* d_gx, double* d_gdisp /* or NULL */, double* d_gwind /* or NULL */);
+int gel_prop_adjoint_wind_info(const gel_prop_plan* plan, const gel_wind_ensemble* ens /* or NULL */, int32_t B, int32_t Q, int32_t shared,
+                               int32_t want_gwind, int64_t* info /* [4] */);
+
 /* ---- exact quantiles over the vectors of a batch: what a Monte-Carlo batch is read by -- the 99.865 % value of
  *      every flight's peak, the 0.135 % / 99.865 % band of the terminal row, the 2.5 .. 97.5 % band of every column along the
  *      trajectory, and which flight that is.  src [B][ld]: columns 0 .. W - 1 of every row are read.  Everything below is per column
