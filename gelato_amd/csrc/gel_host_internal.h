@@ -1,6 +1,7 @@
-// gel_host_internal.h -- what more than one of the host files gel_host*.hip needs, and nothing else.  Nothing declared here is part
-// of the library's C surface (include/gelato_amd.h): the functions live in namespace gelhost and the whole header has hidden
-// visibility, so that none of them becomes a dynamic symbol.
+// gel_host_internal.h -- what more than one of the host files gel_host*.hip needs and no HIP call is behind, and nothing else (the
+// handle and what makes HIP calls: gel_host_handle.h, which includes this header).  Nothing declared here is part of the library's
+// C surface (include/gelato_amd.h): the functions live in namespace gelhost and the whole header has hidden visibility, so that
+// none of them becomes a dynamic symbol.
 #pragma once
 #include <string>
 #include <vector>

@@ -1,4 +1,4 @@
-"""The host-buffer entry points share one staged-call helper and one pair of arenas per handle (gel_host.hip staged_call, DESIGN.md
+"""The host-buffer entry points share one staged-call helper and one pair of arenas per handle (gel_host_handle.h staged_call, DESIGN.md
 3.5): what seven private working sets could not get wrong and a shared one can -- a pointer kept across a growth, two carve-outs
 that overlap, one form's output landing in another's input -- and the parts of the helper the older tests do not reach: both sides
 of the zero-copy limit, optional outputs that are absent, the status rule on the zero-copy branch.
@@ -16,7 +16,7 @@ import stream_harness as H
 
 pytestmark = pytest.mark.gpu
 
-ZERO_COPY_BYTES = 1 << 20       # gel_host.hip kZeroCopyBytes: a call moving at most this much takes the zero-copy branch
+ZERO_COPY_BYTES = 1 << 20       # gel_host_handle.h kZeroCopyBytes: a call moving at most this much takes the zero-copy branch
 FORMS = ["rows", "mesh", "aero"]
 
 
