@@ -21,12 +21,17 @@ The adjoint is the transpose: a reversed stage's lw = Pw^T lF (lF as in flight_a
 i + 1 with the weights 1 - th and th, in a clamped end wholly to the end row.  Its bound Eg, per row and component:
   e(lw) as flight_adjoint_truth's err(Pf);   Eg[row] += fw weight e(lw) + 4u |contribution|, and at the end (T + 2) u sum |contributions|
   for the T stages' read-add-write in walk order.
+
+The flights of tests/golden/g36_flight_wind_plans.npz (PLAN_FLIGHTS; tests/golden/make_flight_wind_plans.py, tests/test_flight_wind_plans*.py)
+run through the same two recursions: a node plan (every node interval restarts from the collocated row), the example under
+mixed_steps.E_STEPS in chain and section mode, and the example over the two-row table.
 """
 import os
 
 import numpy as np
 
 import flight_tangent_truth as tt
+import mixed_steps as ms
 
 U = tt.U
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -38,6 +43,18 @@ FLIGHTS = (("example", "chain", 1), ("example", "section", 2), ("example@LONG", 
 SEEDS = ("bump_north", "east_all", "scale", "row_first", "row_last", "dense", "mixed")
 MUTATIONS = ("shift_piece", "no_fw", "ends_dropped", "theta_swapped")
 NQ = 12   # the eleven terminal rows and one dense functional
+# the flights of tests/golden/g36_flight_wind_plans.npz (tests/golden/make_flight_wind_plans.py; tests/test_flight_wind_plans*.py):
+# a node plan (the tangent alone: the adjoint refuses node plans) | step counts that differ by phase, chain and section (inner
+# checkpoints in air phases, k = 2 and k = 3) | the shortest table a handle takes: Kw = 2, one piece, both ends clamp onto its rows
+G36 = os.path.join(HERE, "golden", "g36_flight_wind_plans.npz")
+PLAN_FLIGHTS = {"W-node": ("example", "node", 1), "W-E-chain": ("example", "chain", ms.E_STEPS), "W-E-section": ("example", "section", ms.E_STEPS),
+                "W-MIN": ("example@MIN", "chain", 1)}
+PLAN_NAMES = tuple(PLAN_FLIGHTS)
+PLAN_ADJOINT = ("W-E-chain", "W-E-section", "W-MIN")
+PLAN_E = ("W-E-chain", "W-E-section")
+# g36's counts: the bump row, air stages on the piece below / above it, air stages under / over the table with Pw != 0, air stages,
+# air stages inside the table with Pw != 0, air stages of phases with k = 2 / k = 3, air stages of node intervals j >= 1
+COUNTS = ("bump", "lo", "hi", "below", "above", "air", "inside", "air_k2", "air_k3", "air_j1")
 
 
 def key(flight):
@@ -161,6 +178,9 @@ def tangent(prob, mode, k, x, mats, hs, st, fws, dx, dd, dW, mutate=None, value_
         m = mats[s]
         du_nodes = dx[11 * M + 2 * ua:11 * M + 2 * (ua + n)].reshape(n, 2)
         for j in range(n):
+            if mode == "node" and j > 0:        # every node interval starts from the collocated row: its seed, E = 0
+                dy = dx[tt.state_rows(M, xa + j)].copy()
+                Eb = np.zeros(11)
             Sh = S_ * hs[s][j]
             dSh = dS * hs[s][j]
             for i in range(k):
@@ -285,6 +305,32 @@ def load(flight):
     g = np.load(G35)
     k = key(flight)
     return {name[len(k):]: g[name] for name in g.files if name.startswith(k)}
+
+
+def load_plan(name):
+    """the stored truth of one of PLAN_NAMES -> dict without the flight's prefix"""
+    g = np.load(G36)
+    k = name + "_"
+    return {n[len(k):]: g[n] for n in g.files if n.startswith(k)}
+
+
+def node_rows(nn):
+    """(the state rows xa, xa + 1 of every phase: its start and the end of its first node interval, where a node plan and a section
+    plan agree; the rows past them, where a node plan restarted from the collocated row and a section plan went on)"""
+    first, later = [], []
+    for s, n in enumerate(nn):
+        xa = sum(nn[:s]) + s
+        first += [xa, xa + 1]
+        later += list(range(xa + 2, xa + n + 1))
+    return np.array(first), np.array(later)
+
+
+def miss_bounded(a, ref, bound):
+    """the largest |a - ref| / bound over the entries that HAVE a bound: what the teeth are measured by (an entry that differs
+    under a zero bound would make `miss` infinite and the teeth trivial)"""
+    d = np.abs(np.asarray(a, dtype=float) - ref)
+    ok = (bound > 0) & np.isfinite(d)
+    return float((d[ok] / bound[ok]).max()) if ok.any() else 0.0
 
 
 def miss(a, ref, bound):

@@ -29,11 +29,10 @@ def _case(name):
     return _CASE[name]
 
 
-@pytest.mark.parametrize("name", ms.NAMES)
-def test_plan_matrices_are_the_uniform_plans(name):
-    """(a) for every phase s the stage points, the control matrix and the copy list of the mixed plan are, bit for bit, those of the
-    uniform plan steps = steps[s]; so are the step fractions of tt.plan_tables.  In the flight's mode and in the node mode."""
-    prob, E, X, disp, mode, steps, (mats, hs) = _case(name)
+def check_plan_matrices(name, E, mode, steps, mats, hs):
+    """for every phase s the stage points, the control matrix and the copy list of the plan with these per-phase steps are, bit for
+    bit, those of the uniform plan steps = steps[s]; so are the step fractions of tt.plan_tables.  In the given mode and in the node
+    mode.  (shared with tests/test_flight_wind_plans_cpu.py)"""
     uniform = {}
     for md in (mode, "node"):
         plan = E.propagation_plan(steps=list(steps), restart=md)
@@ -53,6 +52,14 @@ def test_plan_matrices_are_the_uniform_plans(name):
                 assert np.array_equal(_bits(hs[s]), _bits(uhs[s])), (name, s)
                 assert all(np.array_equal(_bits(mats[s][key]), _bits(m[key])) for key in ("pts", "Wu")) and np.array_equal(mats[s]["copy_u"], m["copy_u"])
         plan.close()
+
+
+@pytest.mark.parametrize("name", ms.NAMES)
+def test_plan_matrices_are_the_uniform_plans(name):
+    """(a) for every phase s the stage points, the control matrix and the copy list of the mixed plan are, bit for bit, those of the
+    uniform plan steps = steps[s]; so are the step fractions of tt.plan_tables.  In the flight's mode and in the node mode."""
+    prob, E, X, disp, mode, steps, (mats, hs) = _case(name)
+    check_plan_matrices(name, E, mode, steps, mats, hs)
 
 
 @pytest.mark.parametrize("name", ms.NAMES)
