@@ -13,12 +13,9 @@
 #include <hip/hip_runtime.h>
 
 #include "gel_interp.h"
+#include "gel_flight_step.h"   // nonfinite
 
 namespace gel {
-
-namespace {
-__device__ __forceinline__ bool nonfinite(double v) { return !(__builtin_fabs(v) <= 1.79769313486231570815e308); }
-}  // namespace
 
 template <int VB>
 __global__ __launch_bounds__(kInterpThreads) void interp_kernel(InterpDev Id, int B, const double* __restrict__ x,

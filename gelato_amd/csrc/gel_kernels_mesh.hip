@@ -19,11 +19,9 @@
 #include "gel_tables.h"
 #include "gel_section_rhs.h"
 #include "gel_mesh.h"
+#include "gel_flight_step.h"   // nan_max
 
 namespace gel {
-
-// running maximum that keeps a NaN once it has seen one (fmax would drop it)
-GEL_DEV double nan_max(double acc, double v) { return (v > acc || v != v) ? v : acc; }
 
 __global__ __launch_bounds__(kMeshMaxThreads) void mesh_kernel(ProblemDev P, MeshDev Md, int B, const double* __restrict__ x,
                                                                double* __restrict__ err, double* __restrict__ diff) {

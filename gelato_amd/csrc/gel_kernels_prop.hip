@@ -8,7 +8,7 @@
 //                        stored transposed: one coalesced load per column), into the plan's workspace [stage point][2][vector]
 //   prop_kernel          one lane = one (vector, segment); a wavefront = 64 consecutive vectors of ONE segment, so the phase and
 //                        the step count are wave-uniform and the two control samples of a stage are one coalesced load each.
-//                        The step is written down in gel_prop.h.  The loop lengths n and k come from the plan's tables, which
+//                        The step is written down in gel_prop.h; its pieces are gel_flight_step.h's.  The loop lengths n and k come from the plan's tables, which
 //                        creation bounds (k n <= 2^20): a launch always ends.
 //                        Template parameters: kChain (GEL_PROP_CHAIN) one lane = one vector through ALL phases, the state carried
 //                        across the knots; kDisp (gel_propagate_dispersed*) per (vector, phase) factors of thrust, mass flow,
@@ -20,20 +20,9 @@
 
 #include "gel_tables.h"
 #include "gel_section_rhs.h"
-#include "gel_prop.h"
+#include "gel_flight_step.h"
 
 namespace gel {
-
-namespace {
-__device__ __forceinline__ bool nonfinite(double v) { return !(__builtin_fabs(v) <= 1.79769313486231570815e308); }
-// running maximum that keeps a NaN once it has seen one (fmax would drop it)
-__device__ __forceinline__ double nan_max(double acc, double v) { return (v > acc || v != v) ? v : acc; }
-// component c of state row xi of a packed vector (x, or y: the same layout)
-__device__ __forceinline__ size_t state_index(int M, int xi, int c) {
-  return (c == 0) ? (size_t)xi : (c < 4) ? (size_t)M + 3 * (size_t)xi + (c - 1) : (c < 7) ? 4 * (size_t)M + 3 * (size_t)xi + (c - 4)
-                                                                                      : 7 * (size_t)M + 4 * (size_t)xi + (c - 7);
-}
-}  // namespace
 
 __global__ __launch_bounds__(kPropSampleThreads) void prop_sample_kernel(ProblemDev P, PropDev Pd, int nb, const double* __restrict__ x,
                                                                          double* __restrict__ ws, long long ld) {
@@ -124,26 +113,14 @@ __global__ __launch_bounds__(kPropThreads) void prop_kernel(ProblemDev P, PropDe
   if constexpr (kEns) tbe = ens_lane_tables(P, tb, Ens, Ens.member[v]);
   int s = kChain ? 0 : load_const(&Pd.seg_phase[seg]);
   do {
-    PhaseDev ph = load_phase(P.phases + s);
-    const int n = load_const(&Pd.ph[s].n), k = load_const(&Pd.ph[s].k), sampled = load_const(&Pd.ph[s].sampled);
-    const int j0 = (!kChain && Pd.restart) ? seg - load_const(&Pd.ph[s].seg0) : 0, j1 = (!kChain && Pd.restart) ? j0 + 1 : n;
-    const double* const sig = Pd.mat + load_const(&Pd.ph[s].sg);
-    const double* const hs = Pd.mat + load_const(&Pd.ph[s].hs);
-    const double* const us = ws + (size_t)load_const(&Pd.ph[s].pt0) * 2 * (size_t)ld + v;
-    const int M = P.M, N = P.N;
+    const int M = P.M;
     const double* const xb = x + (size_t)v * P.nvars;
     double* const yb = y + (size_t)v * 11 * (size_t)M;
-    const double to = xb[11 * M + 2 * N + s], tf = xb[11 * M + 2 * N + s + 1];
-    const double S = (tf - to) * P.ut / 2.0;
-    double fw = 1.0;
-    if (kDisp && (!kEns || disp)) {   // (null only under an ensemble: factors of one, which change no bit)
-      const double* const fac = disp + ((size_t)v * Pd.S + s) * kPropNDisp;
-      const double f_thrust = fac[0], f_mf = fac[1], f_area = fac[2];
-      fw = fac[3];
-      ph.thrust = ph.thrust * f_thrust;
-      ph.mf_um = ph.mf_um * f_mf;
-      ph.area = ph.area * f_area;
-    }
+    FlightPhase f = load_flight_phase(P, Pd, s, xb);
+    const PhaseDev& ph = f.ph;
+    const int j0 = (!kChain && Pd.restart) ? seg - load_const(&Pd.ph[s].seg0) : 0, j1 = (!kChain && Pd.restart) ? j0 + 1 : f.n;
+    const double* const us = ws + f.pt0 * 2 * (size_t)ld + v;
+    if (kDisp && (!kEns || disp)) apply_factors(f, disp + ((size_t)v * Pd.S + s) * kPropNDisp);   // (null only under an ensemble: factors of one)
 
     if (kChain && s > 0) {
       // across the knot the collocated jump x(first node of s) - x(last node of s - 1) is added to the carried state; a zero jump
@@ -162,30 +139,25 @@ __global__ __launch_bounds__(kPropThreads) void prop_kernel(ProblemDev P, PropDe
       for (int c = 0; c < 11; c++) { yb[state_index(M, ph.xa, c)] = yv[c]; bad |= nonfinite(yv[c]); }
     }
     for (int j = j0; j < j1; j++) {
-      const double Sh = S * hs[j], Sh2 = Sh * 0.5, Sh6 = Sh / 6.0;
-      for (int i = 0; i < k; i++) {
-        const int p = 2 * (k * j + i);
+      const double Sh = f.S * f.hs[j], Sh2 = Sh * 0.5, Sh6 = Sh / 6.0;
+      for (int i = 0; i < f.k; i++) {
+        const int p = 2 * (f.k * j + i);
         double acc[11], F[11];
 #pragma unroll
         for (int c = 0; c < 11; c++) acc[c] = F[c] = 0.0;
 #pragma nounroll
         for (int st = 0; st < 4; st++) {
-          const int pp = p + ((st + 1) >> 1);                 // stage points p, p + 1, p + 1, p + 2
-          const double a = (st == 3) ? Sh : Sh2;
-          const double w = (st == 3) ? 1.0 : 2.0;
+          const Stage g = rk4_stage(p, st, Sh, Sh2);
           double yt[11];
 #pragma unroll
-          for (int c = 0; c < 11; c++) yt[c] = st ? __builtin_fma(a, F[c], yv[c]) : yv[c];
-          double u0 = 0.0, u1 = 0.0;
-          if (sampled) {
-            u0 = us[(size_t)pp * 2 * (size_t)ld];
-            u1 = us[((size_t)pp * 2 + 1) * (size_t)ld];
-          }
-          if constexpr (kEns) section_rhs<true, true>(P, ph, tbe, Pd.vp, sig[pp], to, tf, yt, u0, u1, F, fw, &wbr);
-          else if constexpr (kDisp) section_rhs<true>(P, ph, tb, Pd.vp, sig[pp], to, tf, yt, u0, u1, F, fw);
-          else section_rhs(P, ph, tb, Pd.vp, sig[pp], to, tf, yt, u0, u1, F);
+          for (int c = 0; c < 11; c++) yt[c] = st ? __builtin_fma(g.a, F[c], yv[c]) : yv[c];
+          double u0, u1;
+          stage_controls(us, (size_t)ld, f.sampled, g.pp, u0, u1);
+          if constexpr (kEns) section_rhs<true, true>(P, ph, tbe, Pd.vp, f.sig[g.pp], f.to, f.tf, yt, u0, u1, F, f.fw, &wbr);
+          else if constexpr (kDisp) section_rhs<true>(P, ph, tb, Pd.vp, f.sig[g.pp], f.to, f.tf, yt, u0, u1, F, f.fw);
+          else section_rhs(P, ph, tb, Pd.vp, f.sig[g.pp], f.to, f.tf, yt, u0, u1, F);
 #pragma unroll
-          for (int c = 0; c < 11; c++) acc[c] = st ? __builtin_fma(w, F[c], acc[c]) : F[c];
+          for (int c = 0; c < 11; c++) acc[c] = st ? __builtin_fma(g.w, F[c], acc[c]) : F[c];
         }
 #pragma unroll
         for (int c = 0; c < 11; c++) yv[c] = __builtin_fma(Sh6, acc[c], yv[c]);

@@ -14,7 +14,7 @@
 //   prop_sample_t_kernel     the transposed control sampler and the knot times' finishing step: one lane = one (lane of the slab,
 //                            control node), plus one row of lanes for the S + 1 times.
 //
-// ONE STEP, REVERSED (value lines: gel_prop.h; lm = the multiplier of the step's END state on entry, of its START state on exit):
+// ONE STEP, REVERSED (value lines: gel_prop.h, on gel_flight_step.h's stage helpers; lm = the multiplier of the step's END state on entry, of its START state on exit):
 //   restart   per interval, once: from y(node j) the k - 1 value steps to the starts of steps 1 .. k - 1, kept per lane in the
 //             workspace (inner checkpoints); per step: F1 .. F3 with the value's own fma lines (kept in LDS): yt has the bits the
 //             flight had
@@ -40,24 +40,10 @@
 
 #include "gel_tables.h"
 #include "gel_section_rhs_adj.h"
-#include "gel_prop.h"
+#include "gel_flight_step.h"
 #include "gel_propadj.h"
 
 namespace gel {
-
-namespace {
-__device__ __forceinline__ bool nonfinite(double v) { return !(__builtin_fabs(v) <= 1.79769313486231570815e308); }
-__device__ __forceinline__ size_t state_index(int M, int xi, int c) {
-  return (c == 0) ? (size_t)xi : (c < 4) ? (size_t)M + 3 * (size_t)xi + (c - 1) : (c < 7) ? 4 * (size_t)M + 3 * (size_t)xi + (c - 4)
-                                                                                      : 7 * (size_t)M + 4 * (size_t)xi + (c - 7);
-}
-template <typename A, typename... R>
-__device__ __forceinline__ const A& pack_first(const A& a, const R&...) { return a; }
-template <typename A>
-__device__ __forceinline__ const A& pack_last(const A& a) { return a; }
-template <typename A, typename B, typename... R>
-__device__ __forceinline__ const auto& pack_last(const A&, const B& b, const R&... r) { return pack_last(b, r...); }
-}  // namespace
 
 // kEns = 1 (gel_propagate_adjoint_ensemble*): as proptan_kernel's -- an EnsDev behind the arguments (the pack Ens
 // holds exactly that one; none with kEns = 0, whose instantiations keep their argument list), and the lane's view of the tables
@@ -144,20 +130,15 @@ __global__ __launch_bounds__(kPropAdjThreads) void propadj_kernel(ProblemDev P, 
           for (int c = 0; c < 11; c++) acc[c] = F[c] = 0.0;
 #pragma nounroll
           for (int st = 0; st < 4; st++) {
-            const int pp = pf + ((st + 1) >> 1);
-            const double a = (st == 3) ? Sh : Sh2;
-            const double w = (st == 3) ? 1.0 : 2.0;
+            const Stage g = rk4_stage(pf, st, Sh, Sh2);
             double yt[11];
 #pragma unroll
-            for (int c = 0; c < 11; c++) yt[c] = st ? __builtin_fma(a, F[c], yv[c]) : yv[c];
-            double u0 = 0.0, u1 = 0.0;
-            if (sampled) {
-              u0 = us[(size_t)pp * 2 * (size_t)A.ld];
-              u1 = us[((size_t)pp * 2 + 1) * (size_t)A.ld];
-            }
-            section_rhs<true>(P, ph, (kEns & 1) ? tbe : tb, Pd.vp, sig[pp], to, tf, yt, u0, u1, F, fw);
+            for (int c = 0; c < 11; c++) yt[c] = st ? __builtin_fma(g.a, F[c], yv[c]) : yv[c];
+            double u0, u1;
+            stage_controls(us, (size_t)A.ld, sampled, g.pp, u0, u1);
+            section_rhs<true>(P, ph, (kEns & 1) ? tbe : tb, Pd.vp, sig[g.pp], to, tf, yt, u0, u1, F, fw);
 #pragma unroll
-            for (int c = 0; c < 11; c++) acc[c] = st ? __builtin_fma(w, F[c], acc[c]) : F[c];
+            for (int c = 0; c < 11; c++) acc[c] = st ? __builtin_fma(g.w, F[c], acc[c]) : F[c];
           }
 #pragma unroll
           for (int c = 0; c < 11; c++) {
@@ -168,6 +149,7 @@ __global__ __launch_bounds__(kPropAdjThreads) void propadj_kernel(ProblemDev P, 
       }
       for (int i = k - 1; i >= 0; i--) {
         // ---- forward: the step's start (the node's checkpoint, or the interval's inner checkpoint), then F1 .. F3 ----
+        const int pb = 2 * (k * j + i);
         double yv[11];
 #pragma unroll
         for (int c = 0; c < 11; c++) yv[c] = i ? ckl[((size_t)(i - 1) * 11 + c) * (size_t)A.gld] : yb[state_index(M, ph.xa + j, c)];
@@ -177,43 +159,36 @@ __global__ __launch_bounds__(kPropAdjThreads) void propadj_kernel(ProblemDev P, 
           for (int c = 0; c < 11; c++) F[c] = 0.0;
 #pragma nounroll
           for (int st = 0; st < 3; st++) {
-            const int pp = 2 * (k * j + i) + ((st + 1) >> 1);
+            const Stage g = rk4_stage(pb, st, Sh, Sh2);
             double yt[11];
 #pragma unroll
-            for (int c = 0; c < 11; c++) yt[c] = st ? __builtin_fma(Sh2, F[c], yv[c]) : yv[c];
-            double u0 = 0.0, u1 = 0.0;
-            if (sampled) {
-              u0 = us[(size_t)pp * 2 * (size_t)A.ld];
-              u1 = us[((size_t)pp * 2 + 1) * (size_t)A.ld];
-            }
-            section_rhs<true>(P, ph, (kEns & 1) ? tbe : tb, Pd.vp, sig[pp], to, tf, yt, u0, u1, F, fw);
+            for (int c = 0; c < 11; c++) yt[c] = st ? __builtin_fma(g.a, F[c], yv[c]) : yv[c];
+            double u0, u1;
+            stage_controls(us, (size_t)A.ld, sampled, g.pp, u0, u1);
+            section_rhs<true>(P, ph, (kEns & 1) ? tbe : tb, Pd.vp, sig[g.pp], to, tf, yt, u0, u1, F, fw);
 #pragma unroll
             for (int c = 0; c < 11; c++) Fl[(st * 11 + c) * T] = F[c];
           }
         }
         // ---- the four stages, reversed ----
-        const int pb = 2 * (k * j + i);
         double lacc[11], lsum[11], lyt[11], gstep = 0.0, mid0 = 0.0, mid1 = 0.0;
 #pragma unroll
         for (int c = 0; c < 11; c++) { lacc[c] = Sh6 * lm[c]; lsum[c] = 0.0; lyt[c] = 0.0; }
 #pragma nounroll
         for (int st = 3; st >= 0; st--) {
-          const int pp = pb + ((st + 1) >> 1);
-          const double a = (st == 3) ? Sh : Sh2;    // yt = y + a F_prev
+          const Stage sg = rk4_stage(pb, st, Sh, Sh2);          // its point, and a of yt = y + a F_prev; the weight is the reversed walk's own
+          const int pp = sg.pp;
           const double an = (st == 2) ? Sh : Sh2;   // the next stage's a: what its lyt brings to this stage's lF
           const double w = (st == 0) ? 1.0 : 2.0;
           double yt[11], lF[11];
 #pragma unroll
           for (int c = 0; c < 11; c++) {
             const double Fp = st ? Fl[((st - 1) * 11 + c) * T] : 0.0;
-            yt[c] = st ? __builtin_fma(a, Fp, yv[c]) : yv[c];
+            yt[c] = st ? __builtin_fma(sg.a, Fp, yv[c]) : yv[c];
             lF[c] = (st == 3) ? lacc[c] : __builtin_fma(an, lyt[c], w * lacc[c]);
           }
-          double u0 = 0.0, u1 = 0.0;
-          if (sampled) {
-            u0 = us[(size_t)pp * 2 * (size_t)A.ld];
-            u1 = us[((size_t)pp * 2 + 1) * (size_t)A.ld];
-          }
+          double u0, u1;
+          stage_controls(us, (size_t)A.ld, sampled, pp, u0, u1);
           double F[11], lx[11];
           RhsAdjoint g;
           if constexpr (kWind) {

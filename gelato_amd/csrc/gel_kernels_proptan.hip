@@ -15,7 +15,7 @@
 // Loop lengths come from the plan's tables (k n <= 2^20): a launch always ends.  The right-hand side and its tangent are
 // section_rhs_tangent (gel_section_rhs_tan.h).
 //
-// THE STEP'S TANGENT, in this order (value lines: gel_prop.h; F, dF: the previous stage's):
+// THE STEP'S TANGENT, in this order (value lines: gel_prop.h, on gel_flight_step.h's pieces; F, dF: the previous stage's):
 //   dS   = (dtf - dto) * unit_t / 2.0;  dSh = dS * hs[j];  dSh2 = dSh * 0.5;  dSh6 = dSh / 6.0
 //   dyt  = fma(da, F, fma(a, dF, dy))          a = Sh2, Sh2, Sh and da = dSh2, dSh2, dSh for stages 2, 3, 4; stage 1: dyt = dy
 //   dacc = fma(w, dF, dacc)                    w = 2, 2, 1; stage 1: dacc = dF
@@ -25,24 +25,10 @@
 
 #include "gel_tables.h"
 #include "gel_section_rhs_tan.h"
-#include "gel_prop.h"
+#include "gel_flight_step.h"
 #include "gel_proptan.h"
 
 namespace gel {
-
-namespace {
-__device__ __forceinline__ bool nonfinite(double v) { return !(__builtin_fabs(v) <= 1.79769313486231570815e308); }
-__device__ __forceinline__ size_t state_index(int M, int xi, int c) {
-  return (c == 0) ? (size_t)xi : (c < 4) ? (size_t)M + 3 * (size_t)xi + (c - 1) : (c < 7) ? 4 * (size_t)M + 3 * (size_t)xi + (c - 4)
-                                                                                      : 7 * (size_t)M + 4 * (size_t)xi + (c - 7);
-}
-template <typename A, typename... R>
-__device__ __forceinline__ const A& pack_first(const A& a, const R&...) { return a; }
-template <typename A>
-__device__ __forceinline__ const A& pack_last(const A& a) { return a; }
-template <typename A, typename B, typename... R>
-__device__ __forceinline__ const auto& pack_last(const A&, const B& b, const R&... r) { return pack_last(b, r...); }
-}  // namespace
 
 // kEns = 1 (gel_propagate_tangent_ensemble*): the kernel takes an EnsDev behind its arguments -- the pack Ens holds
 // exactly that one argument, and none with kEns = 0, whose instantiations keep their argument list -- and the lane looks the wind
@@ -83,19 +69,13 @@ __global__ __launch_bounds__(kPropThreads) void proptan_kernel(ProblemDev P, Pro
   double* const dyb = A.dy + (size_t)l * 11 * (size_t)M;
   int s = kChain ? 0 : load_const(&Pd.seg_phase[seg]);
   do {
-    PhaseDev ph = load_phase(P.phases + s);
-    const int n = load_const(&Pd.ph[s].n), k = load_const(&Pd.ph[s].k), sampled = load_const(&Pd.ph[s].sampled);
-    const int j0 = (!kChain && Pd.restart) ? seg - load_const(&Pd.ph[s].seg0) : 0, j1 = (!kChain && Pd.restart) ? j0 + 1 : n;
-    const double* const sig = Pd.mat + load_const(&Pd.ph[s].sg);
-    const double* const hs = Pd.mat + load_const(&Pd.ph[s].hs);
-    const size_t pt0 = (size_t)load_const(&Pd.ph[s].pt0);
-    const double* const us = A.ws + pt0 * 2 * (size_t)A.ld + v;
-    const double* const dus = A.dws + pt0 * 2 * (size_t)A.dld + ls;
-    const double to = xb[11 * M + 2 * N + s], tf = xb[11 * M + 2 * N + s + 1];
-    const double S = (tf - to) * P.ut / 2.0;
+    FlightPhase f = load_flight_phase(P, Pd, s, xb);
+    const PhaseDev& ph = f.ph;
+    const int j0 = (!kChain && Pd.restart) ? seg - load_const(&Pd.ph[s].seg0) : 0, j1 = (!kChain && Pd.restart) ? j0 + 1 : f.n;
+    const double* const us = A.ws + f.pt0 * 2 * (size_t)A.ld + v;
+    const double* const dus = A.dws + f.pt0 * 2 * (size_t)A.dld + ls;
     double dS = 0.0;
     if (dxb) dS = (dxb[11 * M + 2 * N + s + 1] - dxb[11 * M + 2 * N + s]) * P.ut / 2.0;
-    double fw = 1.0;
     RhsDirection d;
     d.du0 = d.du1 = d.dthrust = d.dmf = d.darea = d.dfw = 0.0;
     if (A.ddisp) {   // (before the factors scale the record: the tangents of thrust f0, mf_um f1 and area f2 along df)
@@ -105,14 +85,7 @@ __global__ __launch_bounds__(kPropThreads) void proptan_kernel(ProblemDev P, Pro
       d.darea = ph.area * df[2];
       d.dfw = df[3];
     }
-    if (A.disp) {
-      const double* const fac = A.disp + ((size_t)v * Pd.S + s) * kPropNDisp;
-      const double f_thrust = fac[0], f_mf = fac[1], f_area = fac[2];
-      fw = fac[3];
-      ph.thrust = ph.thrust * f_thrust;
-      ph.mf_um = ph.mf_um * f_mf;
-      ph.area = ph.area * f_area;
-    }
+    if (A.disp) apply_factors(f, A.disp + ((size_t)v * Pd.S + s) * kPropNDisp);
 
     if (kChain && s > 0) {
 #pragma unroll
@@ -142,39 +115,38 @@ __global__ __launch_bounds__(kPropThreads) void proptan_kernel(ProblemDev P, Pro
       }
     }
     for (int j = j0; j < j1; j++) {
-      const double Sh = S * hs[j], Sh2 = Sh * 0.5, Sh6 = Sh / 6.0;
-      const double dSh = dS * hs[j], dSh2 = dSh * 0.5, dSh6 = dSh / 6.0;
-      for (int i = 0; i < k; i++) {
-        const int pb = 2 * (k * j + i);
+      const double Sh = f.S * f.hs[j], Sh2 = Sh * 0.5, Sh6 = Sh / 6.0;
+      const double dSh = dS * f.hs[j], dSh2 = dSh * 0.5, dSh6 = dSh / 6.0;
+      for (int i = 0; i < f.k; i++) {
+        const int pb = 2 * (f.k * j + i);
         double acc[11], F[11], dacc[11], dF[11];
 #pragma unroll
         for (int c = 0; c < 11; c++) acc[c] = F[c] = dacc[c] = dF[c] = 0.0;
 #pragma nounroll
         for (int st = 0; st < 4; st++) {
-          const int pp = pb + ((st + 1) >> 1);                 // stage points p, p + 1, p + 1, p + 2
-          const double a = (st == 3) ? Sh : Sh2, da = (st == 3) ? dSh : dSh2;
-          const double w = (st == 3) ? 1.0 : 2.0;
+          const Stage g = rk4_stage(pb, st, Sh, Sh2);
+          const double da = (st == 3) ? dSh : dSh2;
           double yt[11], dyt[11];
 #pragma unroll
           for (int c = 0; c < 11; c++) {
-            yt[c] = st ? __builtin_fma(a, F[c], yv[c]) : yv[c];
-            dyt[c] = st ? __builtin_fma(da, F[c], __builtin_fma(a, dF[c], dyv[c])) : dyv[c];
+            yt[c] = st ? __builtin_fma(g.a, F[c], yv[c]) : yv[c];
+            dyt[c] = st ? __builtin_fma(da, F[c], __builtin_fma(g.a, dF[c], dyv[c])) : dyv[c];
           }
           double u0 = 0.0, u1 = 0.0;
           d.du0 = d.du1 = 0.0;
-          if (sampled) {
-            u0 = us[(size_t)pp * 2 * (size_t)A.ld];
-            u1 = us[((size_t)pp * 2 + 1) * (size_t)A.ld];
+          if (f.sampled) {   // (stage_controls' reads with the seed's nested inside; two calls in a row compile to a section-mode tangent 2 - 4 % slower)
+            u0 = us[(size_t)g.pp * 2 * (size_t)A.ld];
+            u1 = us[((size_t)g.pp * 2 + 1) * (size_t)A.ld];
             if (dxb) {
-              d.du0 = dus[(size_t)pp * 2 * (size_t)A.dld];
-              d.du1 = dus[((size_t)pp * 2 + 1) * (size_t)A.dld];
+              d.du0 = dus[(size_t)g.pp * 2 * (size_t)A.dld];
+              d.du1 = dus[((size_t)g.pp * 2 + 1) * (size_t)A.dld];
             }
           }
-          section_rhs_tangent<(kEns & 2) != 0>(P, ph, (kEns & 1) ? tbe : tb, Pd.vp, sig[pp], to, tf, yt, u0, u1, fw, dyt, d, F, dF, dwl);
+          section_rhs_tangent<(kEns & 2) != 0>(P, ph, (kEns & 1) ? tbe : tb, Pd.vp, f.sig[g.pp], f.to, f.tf, yt, u0, u1, f.fw, dyt, d, F, dF, dwl);
 #pragma unroll
           for (int c = 0; c < 11; c++) {
-            acc[c] = st ? __builtin_fma(w, F[c], acc[c]) : F[c];
-            dacc[c] = st ? __builtin_fma(w, dF[c], dacc[c]) : dF[c];
+            acc[c] = st ? __builtin_fma(g.w, F[c], acc[c]) : F[c];
+            dacc[c] = st ? __builtin_fma(g.w, dF[c], dacc[c]) : dF[c];
           }
         }
 #pragma unroll

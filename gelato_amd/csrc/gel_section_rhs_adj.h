@@ -2,9 +2,9 @@
 // applied to one multiplier lF [11], for the adjoint flight (gel_kernels_propadj.hip).
 //
 // Values: the lines of section_rhs_tangent, on the same arguments in the same order, so F has section_rhs<true>'s bits.  Partials:
-// the ones section_rhs_tangent forms (dg, dw3, dh, AirTangent, the quadratic thrust direction, the bilinear quaternion rate), with
-// gel_exact.h's conventions at kinks; every line of the tangent is transposed where it stands, the 3 x 3 blocks contracted from the
-// other side (over the component instead of over the position direction).  aero_force_tangent() is linear in (da, drho, dinv_a): its
+// the ones section_rhs_tangent reads -- the air branch's from the same linearise_air (gel_section_rhs_lin.h), then dg, the quadratic
+// thrust direction and the bilinear quaternion rate; every line of the tangent is transposed where it stands, the 3 x 3 blocks
+// contracted from the other side (over the component instead of over the position direction).  aero_force_tangent() is linear in (da, drho, dinv_a): its
 // transpose is WRITTEN OUT here (not probed with unit inputs), term by term:
 //   dF_i = -(dk a_i + kk da_i)                 ->  l_dk = -<lFa, a>;  l_da_i = -kk lFa_i
 //   dk   = area / 2 (drho ca s + rho cas dM s + rho ca ds)   (0 where |a| = 0)
@@ -21,8 +21,7 @@
 // kWind lines look up, with the rows and the weight of that lookup (gel_wind_rows.h); the caller splits them between the rows.
 // Not written in an air-less phase.  kWind = false forms none of this and is the function it was.
 #pragma once
-#include "gel_exact.h"
-#include "gel_section_rhs.h"
+#include "gel_section_rhs_lin.h"
 #include "gel_wind_rows.h"
 
 namespace gel {
@@ -61,62 +60,33 @@ GEL_DEV void section_rhs_adjoint(const ProblemDev& P, const PhaseDev& ph, const 
   g.area = 0.0;
   g.fw = 0.0;
   if (ph.air) {
-    const double v3[3] = {xt[4] * P.uv, xt[5] * P.uv, xt[6] * P.uv};
-    PosCentre pc;
-    PosCentreTail tail;
-    const PosPart pp = pos_part<true, PosCentreSink>(r, tb, P.barC20, nullptr, PosCentreSink{&pc}, &tail);
-    const EarthAngle ea = earth_angle(sig * (tf - to) / 2 + (tf + to) / 2);
-    double w[3], Fa[3];
-    const double wn = pp.wn * fw, we = pp.we * fw;
-    wind_eci_or_calm(r, ea, pp.shp, pp.chp, pp.inv_p, wn, we, w);
-    aero_force(r, v3, pp.rho, pp.inv_a, w, ph.area, tb, Fa);
-    const double T = ph.thrust - ph.nozzle * pp.P;
-    const double Td[3] = {T * dir[0], T * dir[1], T * dir[2]};
-    accel(Td, Fa, inv_m, pp.g, P.inv_uv, f);
-    // ---- the partials, as section_rhs_tangent forms them ----
-    const double a[3] = {(v3[0] + kOmega * r[1]) - w[0], (v3[1] - kOmega * r[0]) - w[1], v3[2] - w[2]};
-    const double s2 = a[0] * a[0] + a[1] * a[1] + a[2] * a[2];
-    const double s = fsqrt(fmax(s2, 1.0e-200));
-    const double mach = s * pp.inv_a;
-    const double ca = interp_tab(mach, tb.ca, tb.cas, tb.Kc, 2, 1);
-    const double cas = interp_tab_slope(mach, tb.ca, tb.cas, tb.Kc, 2);
-    const double kk = (s2 > 0.0) ? 0.5 * pp.rho * ph.area * ca * s : 0.0;
-    double dsl[3], dcl[3], dalt[3], dh[3];
-    geodetic_tangent(r, pp.inv_p, pc, dsl, dcl, dalt);
-#pragma unroll
-    for (int k = 0; k < 3; k++) dh[k] = (pc.G * pc.G) * dalt[k];
-    const double Tk = pp.P / (pp.rho * tb.atm[33 + tail.k]);
-    const AirTangent at = atmosphere_tangent(tail.h, Tk, pp.P, pp.rho, pp.inv_a, tb.atm);
-    const bool in = tail.piece >= 0;
-    const double s0 = in ? tb.winds[2 * tail.piece] * fw : 0.0, s1 = in ? tb.winds[2 * tail.piece + 1] * fw : 0.0;
-    const double clon = (pp.inv_p > 0.0) ? r[0] * pp.inv_p : ea.c, slon = (pp.inv_p > 0.0) ? r[1] * pp.inv_p : ea.s;
-    double dw3[3][3];
-    wind_eci_tangent(r, pp.inv_p, clon, slon, pc.sl, pc.cl, wn, we, s0, s1, dh, dsl, dcl, dw3);
+    AirLinearisation L;
+    linearise_air(P, ph, tb, sig, to, tf, xt, r, dir, inv_m, fw, L, f);
     // ---- the transpose ----
     // df_c: -(tm_c / m) dm
     ldm = 0.0;
 #pragma unroll
-    for (int c = 0; c < 3; c++) ldm -= (((Td[c] + Fa[c]) * inv_m) * inv_m) * mu[c];
+    for (int c = 0; c < 3; c++) ldm -= (((L.Td[c] + L.Fa[c]) * inv_m) * inv_m) * mu[c];
     // X_c = (dT dir_c + T ddir_c) + (dFa_c - dka a_c)
     const double lT = nu[0] * dir[0] + nu[1] * dir[1] + nu[2] * dir[2];
-    const double na = nu[0] * a[0] + nu[1] * a[1] + nu[2] * a[2];
+    const double na = nu[0] * L.a[0] + nu[1] * L.a[1] + nu[2] * L.a[2];
 #pragma unroll
-    for (int c = 0; c < 3; c++) ldir[c] = T * nu[c];
+    for (int c = 0; c < 3; c++) ldir[c] = L.T * nu[c];
     // dka = rho darea ca s / 2;  dT = dthrust - nozzle dP dhd
-    g.area = (s2 > 0.0) ? (0.5 * pp.rho * ca * s) * (-na) : 0.0;
+    g.area = (L.s2 > 0.0) ? (0.5 * L.pp.rho * L.ca * L.s) * (-na) : 0.0;
     g.thrust = lT;
-    double lhd = -(ph.nozzle * at.dP) * lT;
+    double lhd = -(ph.nozzle * L.at.dP) * lT;
     // aero_force_tangent transposed (the head of this file); lFa = nu
-    double lda[3] = {-kk * nu[0], -kk * nu[1], -kk * nu[2]};
-    if (s2 > 0.0) {
+    double lda[3] = {-L.kk * nu[0], -L.kk * nu[1], -L.kk * nu[2]};
+    if (L.s2 > 0.0) {
       const double h = 0.5 * ph.area * (-na);
-      const double lrho = h * (ca * s), lM = h * (pp.rho * cas * s);
-      const double ls = h * (pp.rho * ca) + pp.inv_a * lM;
-      const double linv_a = s * lM;
+      const double lrho = h * (L.ca * L.s), lM = h * (L.pp.rho * L.cas * L.s);
+      const double ls = h * (L.pp.rho * L.ca) + L.pp.inv_a * lM;
+      const double linv_a = L.s * lM;
 #pragma unroll
-      for (int i = 0; i < 3; i++) lda[i] += (a[i] / s) * ls;
+      for (int i = 0; i < 3; i++) lda[i] += (L.a[i] / L.s) * ls;
       // drho = at.drho dhd, dinv_a = at.dinv_a dhd
-      lhd += at.drho * lrho + at.dinv_a * linv_a;
+      lhd += L.at.drho * lrho + L.at.dinv_a * linv_a;
     }
     // da = (dv uv + Omega x dr) - dw
 #pragma unroll
@@ -126,13 +96,13 @@ GEL_DEV void section_rhs_adjoint(const ProblemDev& P, const PhaseDev& ph, const 
     const double ldw[3] = {-lda[0], -lda[1], -lda[2]};
     // dw_i = sum_k dw3[k][i] dr_k + (dwn N_i + dwe E_i);  dhd = <dh, dr>
 #pragma unroll
-    for (int k = 0; k < 3; k++) ldr[k] += (dw3[k][0] * ldw[0] + dw3[k][1] * ldw[1] + dw3[k][2] * ldw[2]) + dh[k] * lhd;
-    const double lwn = (-pc.sl * clon) * ldw[0] + (-pc.sl * slon) * ldw[1] + pc.cl * ldw[2];
-    const double lwe = (-slon) * ldw[0] + clon * ldw[1];
+    for (int k = 0; k < 3; k++) ldr[k] += (L.dw3[k][0] * ldw[0] + L.dw3[k][1] * ldw[1] + L.dw3[k][2] * ldw[2]) + L.dh[k] * lhd;
+    const double lwn = (-L.pc.sl * L.clon) * ldw[0] + (-L.pc.sl * L.slon) * ldw[1] + L.pc.cl * ldw[2];
+    const double lwe = (-L.slon) * ldw[0] + L.clon * ldw[1];
     // dwn = wn dfw, dwe = we dfw with the interpolated (unscaled) wind
-    g.fw = pp.wn * lwn + pp.we * lwe;
+    g.fw = L.pp.wn * lwn + L.pp.we * lwe;
     if constexpr (kWind) {
-      gwd->rows = wind_rows(tail.h, tail.piece, tb.wind, tb.Kw);
+      gwd->rows = wind_rows(L.tail.h, L.tail.piece, tb.wind, tb.Kw);
       gwd->wn = fw * lwn;
       gwd->we = fw * lwe;
     }

@@ -1,10 +1,9 @@
 // gel_section_rhs_tan.h -- the right-hand side F of gel_section_rhs.h together with its tangent dF along ONE direction, for the
 // tangent-linear propagation (gel_kernels_proptan.hip).
 //
-// Values: the functions section_rhs<true> calls, on the same arguments in the same order (pos_part's CENTRE form and
-// wind_ned2_centre are the same value expressions), so F has section_rhs<true>'s bits.  Tangents: gel_exact.h's helpers -- written
-// for the three unit position directions -- contracted with the direction's position part; their conventions at kinks (table
-// knots, clamps, atmosphere layers, r < b, |v_air| = 0, the polar axis) are gel_exact.h's and are not restated here.
+// Values: the functions section_rhs<true> calls, on the same arguments in the same order, so F has section_rhs<true>'s bits; the air
+// branch's are linearise_air's (gel_section_rhs_lin.h), which also forms the partials -- gel_exact.h's helpers, written for the
+// three unit position directions.  Here they are contracted with the direction's position part.
 //
 // The direction (everything in the units of the value call):
 //   dxt [11]   the state: mass | position 3 | velocity 3 | quaternion 4, normalised
@@ -22,8 +21,7 @@
 // and added to dwn / dwe beside the factor's term; where that product is zero the sum is not formed, so a zero seed leaves the
 // bits of the instantiation without it.  kWind = false reads none of this and is the function it was.
 #pragma once
-#include "gel_exact.h"
-#include "gel_section_rhs.h"
+#include "gel_section_rhs_lin.h"
 #include "gel_wind_rows.h"
 
 namespace gel {
@@ -57,62 +55,32 @@ GEL_DEV void section_rhs_tangent(const ProblemDev& P, const PhaseDev& ph, const 
   double dg[3][3];
   gravity_tangent(r, P.barC20, dg);
   if (ph.air) {
-    const double v3[3] = {xt[4] * P.uv, xt[5] * P.uv, xt[6] * P.uv};
-    PosCentre pc;
-    PosCentreTail tail;
-    const PosPart pp = pos_part<true, PosCentreSink>(r, tb, P.barC20, nullptr, PosCentreSink{&pc}, &tail);
-    const EarthAngle ea = earth_angle(sig * (tf - to) / 2 + (tf + to) / 2);
-    double w[3], Fa[3];
-    const double wn = pp.wn * fw, we = pp.we * fw;
-    wind_eci_or_calm(r, ea, pp.shp, pp.chp, pp.inv_p, wn, we, w);
-    aero_force(r, v3, pp.rho, pp.inv_a, w, ph.area, tb, Fa);
-    const double T = ph.thrust - ph.nozzle * pp.P;
-    const double Td[3] = {T * dir[0], T * dir[1], T * dir[2]};
-    accel(Td, Fa, inv_m, pp.g, P.inv_uv, f);
-    // ---- the tangent ----
-    // the air-relative velocity and the force's factors, as aero_force() forms them
-    const double a[3] = {(v3[0] + kOmega * r[1]) - w[0], (v3[1] - kOmega * r[0]) - w[1], v3[2] - w[2]};
-    const double s2 = a[0] * a[0] + a[1] * a[1] + a[2] * a[2];
-    const double s = fsqrt(fmax(s2, 1.0e-200));
-    const double mach = s * pp.inv_a;
-    const double ca = interp_tab(mach, tb.ca, tb.cas, tb.Kc, 2, 1);
-    const double cas = interp_tab_slope(mach, tb.ca, tb.cas, tb.Kc, 2);
-    const double kk = (s2 > 0.0) ? 0.5 * pp.rho * ph.area * ca * s : 0.0;
-    // altitude -> atmosphere, wind; latitude / longitude -> wind axes (the three unit directions, then the contraction)
-    double dsl[3], dcl[3], dalt[3], dh[3];
-    geodetic_tangent(r, pp.inv_p, pc, dsl, dcl, dalt);
-#pragma unroll
-    for (int k = 0; k < 3; k++) dh[k] = (pc.G * pc.G) * dalt[k];
-    const double Tk = pp.P / (pp.rho * tb.atm[33 + tail.k]);
-    const AirTangent at = atmosphere_tangent(tail.h, Tk, pp.P, pp.rho, pp.inv_a, tb.atm);
-    const bool in = tail.piece >= 0;
-    const double s0 = in ? tb.winds[2 * tail.piece] * fw : 0.0, s1 = in ? tb.winds[2 * tail.piece + 1] * fw : 0.0;
-    const double clon = (pp.inv_p > 0.0) ? r[0] * pp.inv_p : ea.c, slon = (pp.inv_p > 0.0) ? r[1] * pp.inv_p : ea.s;
-    double dw3[3][3];
-    wind_eci_tangent(r, pp.inv_p, clon, slon, pc.sl, pc.cl, wn, we, s0, s1, dh, dsl, dcl, dw3);
-    const double dhd = dh[0] * dr[0] + dh[1] * dr[1] + dh[2] * dr[2];
+    AirLinearisation L;
+    linearise_air(P, ph, tb, sig, to, tf, xt, r, dir, inv_m, fw, L, f);
+    // ---- the contraction with the direction ----
+    const double dhd = L.dh[0] * dr[0] + L.dh[1] * dr[1] + L.dh[2] * dr[2];
     // the wind factor's direction: (wn N + we E) dfw with the value's axes
-    double dwn = pp.wn * d.dfw, dwe = pp.we * d.dfw;
+    double dwn = L.pp.wn * d.dfw, dwe = L.pp.we * d.dfw;
     if constexpr (kWind) {   // the table's own direction: the seed on the value's piece, times the factor
-      const WindRows wr = wind_rows(tail.h, tail.piece, tb.wind, tb.Kw);
+      const WindRows wr = wind_rows(L.tail.h, L.tail.piece, tb.wind, tb.Kw);
       const double sn = wind_rows_seed(wr, dwl, 0) * fw, se = wind_rows_seed(wr, dwl, 1) * fw;
       dwn = (sn == 0.0) ? dwn : dwn + sn;
       dwe = (se == 0.0) ? dwe : dwe + se;
     }
-    const double dw[3] = {dw3[0][0] * dr[0] + dw3[1][0] * dr[1] + dw3[2][0] * dr[2] + (dwn * (-pc.sl * clon) + dwe * (-slon)),
-                          dw3[0][1] * dr[0] + dw3[1][1] * dr[1] + dw3[2][1] * dr[2] + (dwn * (-pc.sl * slon) + dwe * clon),
-                          dw3[0][2] * dr[0] + dw3[1][2] * dr[1] + dw3[2][2] * dr[2] + dwn * pc.cl};
+    const double dw[3] = {L.dw3[0][0] * dr[0] + L.dw3[1][0] * dr[1] + L.dw3[2][0] * dr[2] + (dwn * (-L.pc.sl * L.clon) + dwe * (-L.slon)),
+                          L.dw3[0][1] * dr[0] + L.dw3[1][1] * dr[1] + L.dw3[2][1] * dr[2] + (dwn * (-L.pc.sl * L.slon) + dwe * L.clon),
+                          L.dw3[0][2] * dr[0] + L.dw3[1][2] * dr[1] + L.dw3[2][2] * dr[2] + dwn * L.pc.cl};
     const double da[3] = {(dxt[4] * P.uv + kOmega * dr[1]) - dw[0], (dxt[5] * P.uv - kOmega * dr[0]) - dw[1], dxt[6] * P.uv - dw[2]};
     double dFa[3];
-    aero_force_tangent(a, s2, s, pp.rho, pp.inv_a, ph.area, ca, cas, kk, da, at.drho * dhd, at.dinv_a * dhd, dFa);
+    aero_force_tangent(L.a, L.s2, L.s, L.pp.rho, L.pp.inv_a, ph.area, L.ca, L.cas, L.kk, da, L.at.drho * dhd, L.at.dinv_a * dhd, dFa);
     // the reference area enters k = rho area CA |a| / 2 linearly
-    const double dka = (s2 > 0.0) ? 0.5 * pp.rho * d.darea * ca * s : 0.0;
-    const double dT = d.dthrust - ph.nozzle * (at.dP * dhd);
+    const double dka = (L.s2 > 0.0) ? 0.5 * L.pp.rho * d.darea * L.ca * L.s : 0.0;
+    const double dT = d.dthrust - ph.nozzle * (L.at.dP * dhd);
 #pragma unroll
     for (int c = 0; c < 3; c++) {
-      const double tm = (Td[c] + Fa[c]) * inv_m;   // (thrust + aero) / m, whose mass derivative is -tm / m
+      const double tm = (L.Td[c] + L.Fa[c]) * inv_m;   // (thrust + aero) / m, whose mass derivative is -tm / m
       const double dgc = dg[0][c] * dr[0] + dg[1][c] * dr[1] + dg[2][c] * dr[2];
-      df[c] = (((dT * dir[c] + T * ddir[c]) + (dFa[c] - dka * a[c])) * inv_m - (tm * inv_m) * dm + dgc) * P.inv_uv;
+      df[c] = (((dT * dir[c] + L.T * ddir[c]) + (dFa[c] - dka * L.a[c])) * inv_m - (tm * inv_m) * dm + dgc) * P.inv_uv;
     }
   } else {
     double g[3];
