@@ -33,7 +33,11 @@ namespace gel {
 // The MFMA D.X path first uses the wave's region as the 64 x 17 staging tile of its result.
 // Q, V, DJJ: inputs the velocity sweeps re-read; LV: D.X row of the velocity defect; FP: results of the
 // position sweeps waiting for the centre value.  19 slots = 9.5 KB per wavefront: 16 wavefronts per CU fit
-// the 160 KB LDS.
+// the 160 KB LDS.  An aerodynamic phase with derivatives reuses them as it goes (eval_body, "Order of this branch"):
+//   Q0-2 f_c, Q3 / DJJ thrust direction x, y          once the quaternion and D[j][j+1] are spent
+//   LV0 1/T, LV1 sweep margin, LV2 1/p of the centre  once the velocity defect is stored (AERO: LV0 free, LV1 1/hypot(z Ra, p Rb), LV2 q_c)
+//   FP0-7 PosCentre's early members p, 1/hypot(z Ra, p Rb), 1/hypot(zz, pp), sin lat, cos lat, 1/cos lat, N, G
+//                                                     (AERO: FP0 / FP1 hold cos(alpha_c), alpha_c instead of p, 1/hypot)
 enum ParkSlot { PK_Q0 = 0, PK_Q1, PK_Q2, PK_Q3, PK_V0, PK_V1, PK_V2, PK_DJJ, PK_LV0, PK_LV1, PK_LV2,
                 PK_FP0, PK_FP1, PK_FP2, PK_FP3, PK_FP4, PK_FP5, PK_FP6, PK_FP7, PK_COUNT };
 constexpr int kStageLd = 17;                     // padded row of the staging tile: conflict-free row reads
@@ -111,6 +115,10 @@ typedef double gel_double4 __attribute__((ext_vector_type(4)));
 #define GEL_DX_HOLD7 1  // hold-type phases: D.X without the quaternion columns (two column tiles per wavefront instead of three)
 #endif
 
+#ifndef GEL_POS_REPARK
+#define GEL_POS_REPARK 1  // slots LV0 / LV1, free since the wind takes sin / cos of the latitude from FP3 / FP4: the centre's 1 / T and sweep
+                          // margin, taken once (AERO: 1 / hypot(z Ra, p Rb) in LV1); 0: every position sweep re-derives them (A/B)
+#endif
 #ifndef GEL_STORE_AUX
 #define GEL_STORE_AUX 2  // cache policy of the Jacobian stores: 2 = nt (A/B: 0 plain, 1 sc0, 16 sc1, 18 sc1+nt)
 #endif
@@ -1200,7 +1208,9 @@ __device__ __forceinline__ void eval_body(const ProblemDev P, int B, const doubl
       // Order of this branch (register and park discipline; the kernel runs 4 waves/SIMD on 128 VGPRs and a spilled value
       // would be reloaded through vmcnt, i.e. behind every Jacobian store in flight):
       // (1) the centre evaluation; the intermediates of its position part that the position sweeps will need (PosCentre) go to
-      //     the park as soon as they exist -- FP0-7 at once, LV0-2 once the velocity defect has been stored;
+      //     the park as soon as they exist -- FP0-7 at once (sin / cos of the latitude, which the wind's rotation reads as well, among
+      //     them); once the velocity defect has been stored its slots take 1/p (LV2) and the centre's 1/T and sweep margin (LV0 / LV1,
+      //     pos_centre_tail() once: GEL_POS_REPARK; AERO: LV1 takes 1/hypot(z Ra, p Rb), LV2 an aero row's centre value);
       // (2) the light sweeps (velocity, quaternion, mass) and the t columns, while the centre's wind, force, gravity and
       //     thrust are in registers, where they then die; the centre value f_c and the thrust direction go to Q0-3 / DJJ;
       // (3) the three position sweeps in exact-difference form (pos_delta(): the change of altitude, atmosphere and wind from
@@ -1287,9 +1297,10 @@ __device__ __forceinline__ void eval_body(const ProblemDev P, int B, const doubl
 #else
 #define GEL_CA_BRACKET nullptr
 #endif
-      // AERO: p and 1/hypot(z Ra, p Rb) are NOT parked (nor is 1/p, below): the position sweeps form them again from the node
-      // position (geodetic_p_ih: the statements that produced them, 30 operations per sweep), and their three slots hold the aero
-      // rows' centre values cos(alpha), alpha and q instead of ten more registers across the sweeps
+      // AERO: p and 1/hypot(z Ra, p Rb) are NOT parked in their own slots (nor is 1/p, below): those three slots hold the aero
+      // rows' centre values cos(alpha), alpha and q instead of ten more registers across the sweeps.  The position sweeps form p and
+      // 1/p again from the node position (the head of geodetic_p_ih: the statements that produced them); 1/hypot waits in LV1, which
+      // the half-latitude pair used to take (GEL_POS_REPARK=0: formed again as well, 30 operations per sweep in all)
       struct ParkSink { lds_double* park; GEL_DEV void put(int i, double v) const { if (!(AERO && (i == PCS_P || i == PCS_IH))) park[(PK_FP0 + i) * 64] = v; } };
       constexpr int PK_ACC = PK_FP0 + PCS_P, PK_AAC = PK_FP0 + PCS_IH, PK_AQC = PK_LV2;   // AERO: cos(alpha_c), alpha_c, q_c
       static_assert(PCS_COUNT == 8 && PK_FP7 == PK_FP0 + 7, "PosCentre's early members fill FP0-7");
@@ -1310,7 +1321,7 @@ __device__ __forceinline__ void eval_body(const ProblemDev P, int B, const doubl
         }
         EarthAngle ea{1.0, 0.0, 1.0, 0.0};
         if (have_eh) ea = full_angle(eh);
-        wind_eci_or_calm(r, ea, pp.shp, pp.chp, pp.inv_p, pp.wn, pp.we, w);
+        wind_eci_or_calm(r, ea, pp.sl, pp.cl, pp.inv_p, pp.wn, pp.we, w);
 #pragma unroll
         for (int c = 0; c < 3; c++) v[c] = PARK_GET(PK_V0 + c) * P.uv;
         aero_force(r, v, pp.rho, pp.inv_a, w, ph.area, tb, F, GEL_CA_BRACKET);
@@ -1346,10 +1357,30 @@ __device__ __forceinline__ void eval_body(const ProblemDev P, int B, const doubl
             }
           }
         }
-        if (JAC) {   // the half-latitude pair and 1/p wait in the slots of the D.X row for the position sweeps
+        if (JAC) {   // what waits in the slots of the D.X row for the position sweeps
           asm volatile("" ::: "memory");
-          PARK_SET(PK_LV0, pp.shp); PARK_SET(PK_LV1, pp.chp);
           if (!AERO) PARK_SET(PK_LV2, pp.inv_p);
+#if GEL_POS_REPARK
+          // (the lead of the latency form runs no position sweep.  A problem created with GEL_FLAG_FD_RECOMPUTE parks them too and never
+          // reads them -- its sweeps all recompute: a dozen wasted operations in the audit form, which is not for speed, instead of
+          // one more scalar test on the path that is)
+          if (!SPLIT || part) {
+            if (AERO) {
+              // 1/hypot(z Ra, p Rb), whose own slot holds an aero row's centre value (below): the statements that produced it, once
+              // here instead of once per sweep.  (p is not kept: the sweeps form 1/p again, and the same iteration gives p.)
+              double p_, ip_, ih_;
+              geodetic_p_ih(r[0], r[1], r[2], p_, ip_, ih_);
+              PARK_SET(PK_LV1, ih_);
+            } else {
+              // 1/T and the sweep margin of the centre (pos_centre_tail: the centre's wind and the slopes it also returns are not
+              // kept -- the sweeps form them again)
+              PosCentre pcx;
+              double wn_, we_;
+              pos_centre_tail(pt, pp.rho, pp.P, tb, pcx, wn_, we_);
+              PARK_SET(PK_LV0, pcx.air.iT); PARK_SET(PK_LV1, pcx.margin);
+            }
+          }
+#endif
         }
         if (JAC && lead && !P.fd_recompute) GEL_MASS_CLOSED(tm);   // first: (T d + F) / m dies here
         // velocity sweeps: only the aerodynamic force changes.  Latency form of a WHOLE evaluation (P.split_vel: the optimiser's
@@ -1422,7 +1453,7 @@ __device__ __forceinline__ void eval_body(const ProblemDev P, int B, const doubl
 #pragma unroll
           for (int c = 0; c < 3; c++) va[c] = PARK_GET(PK_V0 + c) * P.uv;
           // the wind in ECI with con_aero's Earth angle (aero_body: wind_eci_or_calm at the centre).  What the rotation needs of the
-          // centre's position part is taken from where it lies by now -- the half-latitude pair from the park, 1/p and the wind
+          // centre's position part is taken from where it lies by now -- sin / cos of the latitude from the park (FP3 / FP4), 1/p and the wind
           // components formed again (geodetic_p_ih, pos_centre_tail: bit-identical) -- instead of five values kept in registers
           // across the centre evaluation
           if (have_eh) {   // a windy lane of the centre is on the polar axis (wave-uniform): the node's time in seconds (lib/con_aero.py:45)
@@ -1436,7 +1467,7 @@ __device__ __forceinline__ void eval_body(const ProblemDev P, int B, const doubl
             geodetic_p_ih(ra[0], ra[1], ra[2], p_, ip_, ih_);
             EarthAngle e2{1.0, 0.0, 1.0, 0.0};
             if (have_aeh) e2 = full_angle(GEL_AEH);
-            wind_eci(ra, e2, PARK_GET(PK_LV0), PARK_GET(PK_LV1), ip_, wn_, we_, wa);
+            wind_eci(ra, e2, PARK_GET(PK_FP0 + PCS_SL), PARK_GET(PK_FP0 + PCS_CL), ip_, wn_, we_, wa);
           } else {
             wa[0] = 0.0; wa[1] = 0.0; wa[2] = 0.0;
           }
@@ -1502,7 +1533,7 @@ __device__ __forceinline__ void eval_body(const ProblemDev P, int B, const doubl
     GEL_NEED_EARTH_ANGLE((pq).inv_p, (pq).wn, (pq).we);                                                       \
     EarthAngle ea{1.0, 0.0, 1.0, 0.0};                                                                        \
     if (have_eh) ea = full_angle(eh);                                                                         \
-    wind_eci_or_calm(rp, ea, (pq).shp, (pq).chp, (pq).inv_p, (pq).wn, (pq).we, wq_);                          \
+    wind_eci_or_calm(rp, ea, (pq).sl, (pq).cl, (pq).inv_p, (pq).wn, (pq).we, wq_);                          \
     const double vq_[3] = {PARK_GET(PK_V0) * P.uv, PARK_GET(PK_V1) * P.uv, PARK_GET(PK_V2) * P.uv};           \
     aero_force(rp, vq_, (pq).rho, (pq).inv_a, wq_, ph.area, tb, Fp_, GEL_CA_BRACKET);                         \
     const double Tp_ = ph.thrust - ph.nozzle * (pq).P;                                                        \
@@ -1522,7 +1553,7 @@ __device__ __forceinline__ void eval_body(const ProblemDev P, int B, const doubl
     GEL_AERO_NEED_EA((pq).inv_p, (pq).wn, (pq).we);                                                           \
     EarthAngle ea_{1.0, 0.0, 1.0, 0.0};                                                                       \
     if (have_aeh) ea_ = full_angle(GEL_AEH);                                                                  \
-    wind_eci_or_calm(rp, ea_, (pq).shp, (pq).chp, (pq).inv_p, (pq).wn, (pq).we, wq_);                         \
+    wind_eci_or_calm(rp, ea_, (pq).sl, (pq).cl, (pq).inv_p, (pq).wn, (pq).we, wq_);                         \
     const double vq_[3] = {PARK_GET(PK_V0) * P.uv, PARK_GET(PK_V1) * P.uv, PARK_GET(PK_V2) * P.uv};           \
     const double nv2_ = aero_vair2(rp, vq_, wq_, a_);                                                         \
     const double dd_[3] = {PARK_GET(PK_Q3), PARK_GET(PK_DJJ), dir2};                                          \
@@ -1542,13 +1573,18 @@ __device__ __forceinline__ void eval_body(const ProblemDev P, int B, const doubl
   pc.N = PARK_GET(PK_FP0 + PCS_N); pc.G = PARK_GET(PK_FP0 + PCS_G);                                                    \
   PosPart pcv;                                                                                                         \
   pcv.rho = cen_rho; pcv.P = cen_P; pcv.inv_a = cen_inv_a;                                                             \
-  pcv.shp = PARK_GET(PK_LV0); pcv.chp = PARK_GET(PK_LV1);                                                              \
-  if (AERO) {                                                                                                          \
+  pcv.sl = pc.sl; pcv.cl = pc.cl;                                                                                      \
+  if (AERO && GEL_POS_REPARK) {   /* p and 1/p are formed again (one iteration gives both); 1/hypot, unused, is not */    \
+    double ih_;                                                                                                        \
+    geodetic_p_ih(fresh_product(re[0], P.up), fresh_product(re[1], P.up), fresh_product(re[2], P.up), pc.p, pcv.inv_p, ih_); \
+    pc.ih = PARK_GET(PK_LV1);                                                                                          \
+  } else if (AERO) {                                                                                                   \
     geodetic_p_ih(fresh_product(re[0], P.up), fresh_product(re[1], P.up), fresh_product(re[2], P.up), pc.p, pcv.inv_p, pc.ih); \
   } else {                                                                                                             \
     pc.p = PARK_GET(PK_FP0 + PCS_P); pc.ih = PARK_GET(PK_FP0 + PCS_IH); pcv.inv_p = PARK_GET(PK_LV2);                  \
   }                                                                                                                    \
-  pos_centre_tail(pt, cen_rho, cen_P, tb, pc, pcv.wn, pcv.we)
+  if (GEL_POS_REPARK && !AERO) pos_centre_tail_kept(pt, PARK_GET(PK_LV0), PARK_GET(PK_LV1), tb, pc, pcv.wn, pcv.we);   \
+  else pos_centre_tail(pt, cen_rho, cen_P, tb, pc, pcv.wn, pcv.we)
         unsigned todo = 0;   // sweeps with a lane the difference form does not cover (wave-uniform)
         unsigned long long coo_okm = 0;   // COO-direct output: the verdict of the difference form, kept for the recomputing pass (the LDS tile
                                           // of the first pass's stores has overwritten the parked PosCentre by then)
@@ -1633,7 +1669,7 @@ __device__ __forceinline__ void eval_body(const ProblemDev P, int B, const doubl
           const double r[3] = {fresh_product(re[0], P.up), fresh_product(re[1], P.up), fresh_product(re[2], P.up)};
           const PosPart p2 = pos_part(r, tb, P.barC20);
           const double T2 = ph.thrust - ph.nozzle * p2.P;
-          PARK_SET(PK_FP0, p2.shp); PARK_SET(PK_FP1, p2.chp); PARK_SET(PK_FP2, p2.inv_p); PARK_SET(PK_FP3, p2.wn); PARK_SET(PK_FP4, p2.we);
+          PARK_SET(PK_FP0, p2.sl); PARK_SET(PK_FP1, p2.cl); PARK_SET(PK_FP2, p2.inv_p); PARK_SET(PK_FP3, p2.wn); PARK_SET(PK_FP4, p2.we);
           PARK_SET(PK_FP5, p2.rho); PARK_SET(PK_FP6, p2.inv_a);
           PARK_SET(PK_LV0, p2.g[0]); PARK_SET(PK_LV1, p2.g[1]); PARK_SET(PK_LV2, p2.g[2]);
           PARK_SET(PK_Q0, T2 * PARK_GET(PK_Q3)); PARK_SET(PK_Q1, T2 * PARK_GET(PK_DJJ)); PARK_SET(PK_Q2, T2 * dir2);

@@ -1531,10 +1531,10 @@ int gel_table_limits(int32_t wind_rows, int32_t ca_rows, int32_t n, int64_t* inf
 }
 
 int gel_point_eval(int32_t kind, int32_t n, const double* in, const double* aux, int32_t aux_rows, double* out) {
-  static const int nin[16] = {1, 3, 3, 6, 7, 1, 1, 2, 2, 8, 8, 8, 7, 4, 1, 5}, nout[16] = {5, 3, 3, 3, 3, 3, 1, 4, 6, 8, 16, 4, 3, 7, 2, 18};
-  if (kind < 0 || kind > 15 || n < 0 || !in || !out) return fail(GEL_ERR_ARG, "bad argument");
+  static const int nin[17] = {1, 3, 3, 6, 7, 1, 1, 2, 2, 8, 8, 8, 7, 4, 1, 5, 5}, nout[17] = {5, 3, 3, 3, 3, 3, 1, 4, 6, 8, 16, 4, 3, 7, 2, 18, 54};
+  if (kind < 0 || kind > 16 || n < 0 || !in || !out) return fail(GEL_ERR_ARG, "bad argument");
   if (n == 0) return GEL_OK;
-  const bool tabulated = kind == 5 || kind == 6 || kind == 9 || kind == 10 || kind == 15;
+  const bool tabulated = kind == 5 || kind == 6 || kind == 9 || kind == 10 || kind == 15 || kind == 16;
   int rc = tabulated ? check_launch_lds("gel_point_eval", gel::point_lds_bytes(aux_rows), 5 * (size_t)std::max(aux_rows, 0), 5 * (size_t)std::max(aux_rows, 0), false) : GEL_OK;
   if (rc) return rc;
   rc = need_device();
@@ -1542,13 +1542,13 @@ int gel_point_eval(int32_t kind, int32_t n, const double* in, const double* aux,
   double atm[gel::kAtmTableDoubles];
   size_t naux = 0;
   const double* hax = aux;
-  std::vector<double> ext;  // kinds 5 / 6 / 9 / 10: the table rows followed by their per-interval slopes; kind 15: the atmosphere table before them
+  std::vector<double> ext;  // kinds 5 / 6 / 9 / 10: the table rows followed by their per-interval slopes; kinds 15 / 16: the atmosphere table before them
   if (kind == 0) { gel::fill_atmosphere_table(atm); hax = atm; naux = gel::kAtmTableDoubles; aux_rows = 0; }
   else if (kind == 2) { if (!aux) return fail(GEL_ERR_ARG, "kind 2 needs aux[0] = barC20"); naux = 1; aux_rows = 0; }
   else if (tabulated) {
-    const int w = (kind == 5 || kind == 10 || kind == 15) ? 3 : 2;
-    if (!aux || aux_rows < 2) return fail(GEL_ERR_ARG, "kinds 5, 6, 9, 10 and 15 need a table of at least two rows");
-    if (kind == 15) { gel::fill_atmosphere_table(atm); ext.assign(atm, atm + gel::kAtmTableDoubles); }   // atmosphere | wind rows | slopes
+    const int w = (kind == 5 || kind == 10 || kind == 15 || kind == 16) ? 3 : 2;
+    if (!aux || aux_rows < 2) return fail(GEL_ERR_ARG, "kinds 5, 6, 9, 10, 15 and 16 need a table of at least two rows");
+    if (kind == 15 || kind == 16) { gel::fill_atmosphere_table(atm); ext.assign(atm, atm + gel::kAtmTableDoubles); }   // atmosphere | wind rows | slopes
     for (int k = 1; k < aux_rows; k++)
       if (!(aux[(size_t)w * k] > aux[(size_t)w * (k - 1)])) return fail(GEL_ERR_ARG, "table abscissae must increase strictly");
     std::vector<double> slopes;

@@ -169,7 +169,7 @@ __global__ void rhs_vel_air_kernel(RhsArgs A) {
   const PosPart pp = pos_part(r, tb, A.barC20);
   const EarthAngle ea = earth_angle(A.t[i]);
   double w[3], F[3], dir[3], f[3];
-  wind_eci(r, ea, pp.shp, pp.chp, pp.inv_p, pp.wn, pp.we, w);
+  wind_eci(r, ea, pp.sl, pp.cl, pp.inv_p, pp.wn, pp.we, w);
   aero_force(r, v, pp.rho, pp.inv_a, w, A.area, tb, F);
   thrust_dir(q, dir);
   const double T = A.thrust - A.nozzle * pp.P;
@@ -207,7 +207,7 @@ __global__ void point_kernel(int kind, int n, const double* in, const double* au
   // kinds 5 / 6: rows followed by the per-interval slopes (built by the host entry point)
   const int naux = (kind == 5 || kind == 10) ? 3 * aux_rows + 2 * (aux_rows - 1)
                    : (kind == 6 || kind == 9) ? 2 * aux_rows + (aux_rows - 1)
-                   : (kind == 15) ? kAtmDoubles + 3 * aux_rows + 2 * (aux_rows - 1) : (kind == 0 ? kAtmDoubles : 0);
+                   : (kind == 15 || kind == 16) ? kAtmDoubles + 3 * aux_rows + 2 * (aux_rows - 1) : (kind == 0 ? kAtmDoubles : 0);
   for (int i = threadIdx.x; i < naux; i += blockDim.x) lds[i] = aux[i];
   __syncthreads();
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -241,9 +241,7 @@ __global__ void point_kernel(int kind, int n, const double* in, const double* au
       double sl, cl, p, ip, w[3];
       geodetic_sincos_p(r[0], r[1], r[2], sl, cl, p, ip);
       const EarthAngle ea = earth_angle(a[3]);
-      double chp, irt;
-      fsqrt_rsqrt(0.5 * (1.0 + cl), chp, irt);
-      wind_eci(r, ea, (0.5 * sl) * irt, chp, ip, a[4], a[5], w);
+      wind_eci(r, ea, sl, cl, ip, a[4], a[5], w);
       out[3 * i] = w[0]; out[3 * i + 1] = w[1]; out[3 * i + 2] = w[2];
     } break;
     case 4: {
@@ -315,11 +313,52 @@ __global__ void point_kernel(int kind, int n, const double* in, const double* au
       PosPart pp = pos_part<true, PosCentreSink, false>(r, tb, 0.0, nullptr, PosCentreSink{&pc}, &pt);
       pos_centre_tail(pt, pp.rho, pp.P, tb, pc, pp.wn, pp.we);
       PosPart pq;
-      const bool ok = pos_delta(r, kk, a[4], pp, pc, tb, pq);
+      double dlat;
+      const bool ok = pos_delta(r, kk, a[4], pp, pc, tb, pq, &dlat);
+      // the half-latitude pair of the centre and of the perturbed point, which the position part no longer carries (the wind takes
+      // sin / cos of the latitude itself): formed here as pos_part() and pos_delta() used to
+      double shp, chp, shq, chq;
+      half_lat_pair(pp.sl, pp.cl, shp, chp);
+      half_lat_step(shp, chp, dlat, shq, chq);
       double* o = out + 18 * i;
-      o[0] = pp.rho; o[1] = pp.P; o[2] = pp.inv_a; o[3] = pp.wn; o[4] = pp.we; o[5] = pp.shp; o[6] = pp.chp; o[7] = pp.inv_p;
-      o[8] = pq.rho; o[9] = pq.P; o[10] = pq.inv_a; o[11] = pq.wn; o[12] = pq.we; o[13] = pq.shp; o[14] = pq.chp; o[15] = pq.inv_p;
+      o[0] = pp.rho; o[1] = pp.P; o[2] = pp.inv_a; o[3] = pp.wn; o[4] = pp.we; o[5] = shp; o[6] = chp; o[7] = pp.inv_p;
+      o[8] = pq.rho; o[9] = pq.P; o[10] = pq.inv_a; o[11] = pq.wn; o[12] = pq.we; o[13] = shq; o[14] = chq; o[15] = pq.inv_p;
       o[16] = ok ? 1.0 : 0.0; o[17] = pc.margin;
+    } break;
+    case 16: {  // kind 15's 18 outputs for kk = 0, 1, 2 from ONE centre, chained as the fused kernel chains its three position sweeps:
+                // 1/T and the margin taken once (pos_centre_tail) and kept, each sweep re-deriving only the wind slopes and the
+                // centre's wind (pos_centre_tail_kept); in = r[3] (m), (unused), dlt; out = [kk][18]
+      Tables tb;
+      tb.atm = lds; tb.wind = lds + kAtmDoubles; tb.winds = tb.wind + 3 * aux_rows; tb.ca = nullptr; tb.cas = nullptr;
+      tb.Kw = aux_rows; tb.Kc = 0;
+      const double* a = in + 5 * i;
+      const double r[3] = {a[0], a[1], a[2]};
+      PosCentre pc0;
+      PosCentreTail pt;
+      const PosPart pp = pos_part<true, PosCentreSink, false>(r, tb, 0.0, nullptr, PosCentreSink{&pc0}, &pt);
+      double iT, margin;
+      {
+        PosCentre pcx;
+        double wn_, we_;
+        pos_centre_tail(pt, pp.rho, pp.P, tb, pcx, wn_, we_);
+        iT = pcx.air.iT; margin = pcx.margin;
+      }
+      double shp, chp;
+      half_lat_pair(pp.sl, pp.cl, shp, chp);
+#pragma unroll 1
+      for (int kk = 0; kk < 3; kk++) {
+        PosCentre pc = pc0;
+        PosPart pcv = pp;
+        pos_centre_tail_kept(pt, iT, margin, tb, pc, pcv.wn, pcv.we);
+        PosPart pq;
+        double dlat, shq, chq;
+        const bool ok = pos_delta(r, kk, a[4], pcv, pc, tb, pq, &dlat);
+        half_lat_step(shp, chp, dlat, shq, chq);
+        double* o = out + 54 * i + 18 * kk;
+        o[0] = pcv.rho; o[1] = pcv.P; o[2] = pcv.inv_a; o[3] = pcv.wn; o[4] = pcv.we; o[5] = shp; o[6] = chp; o[7] = pcv.inv_p;
+        o[8] = pq.rho; o[9] = pq.P; o[10] = pq.inv_a; o[11] = pq.wn; o[12] = pq.we; o[13] = shq; o[14] = chq; o[15] = pq.inv_p;
+        o[16] = ok ? 1.0 : 0.0; o[17] = pc.margin;
+      }
     } break;
     default: break;
   }
@@ -343,19 +382,16 @@ __global__ void point_kernel(int kind, int n, const double* in, const double* au
 struct AeroPos {            // depends on position only
   double rho;               // density at the node
   double wn, we;            // wind, NED
-  double shp, chp, inv_p;   // NED half-latitude pair, 1/p
+  double sl, cl, inv_p;     // sin, cos of the geodetic latitude, 1/p
 };
 
 GEL_DEV AeroPos aero_pos_part(const double r[3], const Tables& tb) {
   AeroPos o;
-  double lat, p, sl, cl;
+  double lat, p;
   geodetic_lat_p(r[0], r[1], r[2], lat, p, o.inv_p);
-  fsincos(lat, &sl, &cl);
-  const double h = geopotential_altitude(geodetic_alt_from(p, sl, cl));
+  fsincos(lat, &o.sl, &o.cl);
+  const double h = geopotential_altitude(geodetic_alt_from(p, o.sl, o.cl));
   wind_ned2(h, tb.wind, tb.winds, tb.Kw, o.wn, o.we);
-  double irt;
-  fsqrt_rsqrt(0.5 * (1.0 + cl), o.chp, irt);
-  o.shp = (0.5 * sl) * irt;
   o.rho = atmosphere(h, tb.atm).rho;      // wrapper_utils.hpp:163-175
   return o;
 }
@@ -524,7 +560,7 @@ __device__ __forceinline__ void aero_body(const ProblemDev P, int nnodes, const 
     pp = pos_part<true, PosCentreSink, false>(r, tb, 0.0, nullptr, PosCentreSink{&pc}, &pt);
     pos_centre_tail(pt, pp.rho, pp.P, tb, pc, pp.wn, pp.we);
     GEL_AERO_NEED_EA(pp.inv_p, pp.wn, pp.we);
-    wind_eci_or_calm(r, ea, pp.shp, pp.chp, pp.inv_p, pp.wn, pp.we, w);
+    wind_eci_or_calm(r, ea, pp.sl, pp.cl, pp.inv_p, pp.wn, pp.we, w);
     const double nv2 = aero_vair2(r, v, w, a0);
     thrust_dir(q, dir);
     const double ind = frsqrt(fmax(dir[0] * dir[0] + dir[1] * dir[1] + dir[2] * dir[2], 1.0e-300));
@@ -625,7 +661,7 @@ __device__ __forceinline__ void aero_body(const ProblemDev P, int nnodes, const 
         const double r[3] = {fresh_product(re[0], P.up), fresh_product(re[1], P.up), fresh_product(re[2], P.up)};
         const double vq[3] = {xb[4 * M + 3 * xi] * P.uv, xb[4 * M + 3 * xi + 1] * P.uv, xb[4 * M + 3 * xi + 2] * P.uv};
         double wq[3], aq[3];
-        wind_eci_chain(r, eq, pp.shp, pp.chp, pp.inv_p, pp.wn, pp.we, wq);   // the reference's chain: see wind_eci_chain_or_calm()
+        wind_eci_chain(r, eq, pp.sl, pp.cl, pp.inv_p, pp.wn, pp.we, wq);   // the reference's chain: see wind_eci_chain_or_calm()
         const double nvq = aero_vair2(r, vq, wq, aq);
         const double dq[3] = {AP_GET(AP_DIR), AP_GET(AP_DIR + 1), AP_GET(AP_DIR + 2)};
         GEL_AERO_EMIT(-1, 2, c, aq, nvq, dq, AP_GET(AP_IND), pp.rho, false, false, false);
@@ -639,7 +675,7 @@ __device__ __forceinline__ void aero_body(const ProblemDev P, int nnodes, const 
   do {                                                                                               \
     double wq_[3], a_[3];                                                                            \
     GEL_AERO_NEED_EA((pq).inv_p, (pq).wn, (pq).we);                                                  \
-    wind_eci_or_calm(rp, ea, (pq).shp, (pq).chp, (pq).inv_p, (pq).wn, (pq).we, wq_);                 \
+    wind_eci_or_calm(rp, ea, (pq).sl, (pq).cl, (pq).inv_p, (pq).wn, (pq).we, wq_);                 \
     const double vq_[3] = {xb[4 * M + 3 * xi] * P.uv, xb[4 * M + 3 * xi + 1] * P.uv, xb[4 * M + 3 * xi + 2] * P.uv}; \
     const double nv2_ = aero_vair2(rp, vq_, wq_, a_);                                                \
     const double dd_[3] = {AP_GET(AP_DIR), AP_GET(AP_DIR + 1), AP_GET(AP_DIR + 2)};                  \

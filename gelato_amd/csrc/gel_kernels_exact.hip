@@ -95,7 +95,7 @@ __global__ __launch_bounds__(kExactBlock) void exact_jac_kernel(ProblemDev P, in
     const PosPart pp = pos_part<true, PosCentreSink>(r, tb, P.barC20, nullptr, PosCentreSink{&pc}, &tail);
     const EarthAngle ea = earth_angle(tn);
     double wv[3], F[3];
-    wind_eci_or_calm(r, ea, pp.shp, pp.chp, pp.inv_p, pp.wn, pp.we, wv);
+    wind_eci_or_calm(r, ea, pp.sl, pp.cl, pp.inv_p, pp.wn, pp.we, wv);
     const double v[3] = {ve[0] * P.uv, ve[1] * P.uv, ve[2] * P.uv};
     aero_force(r, v, pp.rho, pp.inv_a, wv, ph.area, tb, F);
     T = ph.thrust - ph.nozzle * pp.P;

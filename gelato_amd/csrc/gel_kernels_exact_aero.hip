@@ -54,7 +54,7 @@ __global__ __launch_bounds__(kExactAeroBlock) void exact_aero_kernel(ProblemDev 
   // PSparams.time_nodes (SectionParameters.py:77-81): node 0 is t0 itself; t in seconds here (con_aero.py:45)
   const EarthAngle ea = earth_angle(((Nd.k == 0) ? to : (tau * (tf - to) / 2 + (tf + to) / 2)) * P.ut);
   double w[3], a[3], dir[3];
-  wind_eci_or_calm(r, ea, pp.shp, pp.chp, pp.inv_p, pp.wn, pp.we, w);
+  wind_eci_or_calm(r, ea, pp.sl, pp.cl, pp.inv_p, pp.wn, pp.we, w);
   const double nv2 = aero_vair2(r, v, w, a);
   thrust_dir(q, dir);
   const double ind = frsqrt(fmax(dir[0] * dir[0] + dir[1] * dir[1] + dir[2] * dir[2], 1.0e-300));

@@ -26,7 +26,7 @@ struct PosPart {
   double rho, P, inv_a;  // atmosphere at the node: density, pressure, 1 / speed of sound
   double wn, we;     // wind, NED
   double g[3];       // gravity, ECI
-  double shp, chp;   // sin, cos of half the geodetic latitude (for the NED quaternion)
+  double sl, cl;     // sin, cos of the geodetic latitude (the local north axis of the wind's rotation)
   double inv_p;      // 1 / sqrt(x^2 + y^2)
 };
 
@@ -83,13 +83,7 @@ GEL_DEV PosPart pos_part(const double r[3], const Tables& tb, double barC20, Bra
     geodetic_sincos_p(r[0], r[1], r[2], sl, cl, p, o.inv_p, &ih, &ihy);
     sink.put(PCS_IH, ih); sink.put(PCS_IHY, ihy); sink.put(PCS_P, p);
   } else geodetic_sincos_p(r[0], r[1], r[2], sl, cl, p, o.inv_p);
-  // half-angle pair of the NED quaternion (src/Coordinate.cpp:89-90): cos(lat/2) = sqrt((1+cos lat)/2)
-  // (cos lat >= 0), sin(lat/2) = sin lat / (2 cos(lat/2)); root and reciprocal root from one iteration
-  {
-    double irt;
-    fsqrt_rsqrt(0.5 * (1.0 + cl), o.chp, irt);
-    o.shp = (0.5 * sl) * irt;
-  }
+  o.sl = sl; o.cl = cl;
   // src/Earth.cpp:58-59 (geodetic_alt_from(), spelled out for the exports)
   const double N = fdiv(kRa, fsqrt(1.0 - kE2 * sl * sl));
   const double q = fdiv(p, cl);
@@ -126,6 +120,17 @@ GEL_DEV void pos_centre_tail(const PosCentreTail& t, double rho, double P, const
   pc.air.iT = rho * tb.atm[33 + t.k] * frcp(P);
   pc.air.h = t.h; pc.air.k = t.k;
 }
+// The same for a sweep whose caller took 1/T and the margin ONCE at the centre (pos_centre_tail(): the values are the centre's, not
+// the sweep's, and neither expression contracts, so a kept value has the bits of a re-derived one) and kept them -- the fused
+// kernel, in the two park slots the half-latitude pair used to take: only the wind slopes and the centre's wind are re-derived.
+GEL_DEV void pos_centre_tail_kept(const PosCentreTail& t, double iT, double margin, const Tables& tb, PosCentre& pc, double& wn,
+                                  double& we) {
+  double wm;
+  wind_piece(t.h, t.piece, tb.wind, tb.winds, tb.Kw, wn, we, pc.s0, pc.s1, wm);
+  pc.margin = margin;
+  pc.air.iT = iT;
+  pc.air.h = t.h; pc.air.k = t.k;
+}
 
 // ---------------------------------------------------------------------------
 // Exact-difference form of pos_part() for a position sweep: component kk of r moved by dlt = r'_kk - r_kk (an exact
@@ -135,7 +140,7 @@ GEL_DEV void pos_centre_tail(const PosCentreTail& t, double rho, double P, const
 //   p = sqrt(x^2 + y^2)          d(p^2) = dlt (2 x_k + dlt),  dp = p (sqrt(1 + u) - 1),  u = d(p^2)/p^2
 //   sin/cos(theta) = a/h, b/h    dh2 = da (2a + da) + db (2b + db),  d(1/h) = (1/h)((1 + uh)^-1/2 - 1)
 //   lat = atan2(zz, pp)          dlat = atan((dzz pp - zz dpp)/(zz zz' + pp pp'))   (tan of a difference)
-//   sin, cos, half-angle pair    angle-addition with sin(dlat) = dlat, 1 - cos(dlat) = dlat^2/2
+//   sin, cos of the latitude     angle-addition with sin(dlat) = dlat, 1 - cos(dlat) = dlat^2/2
 //   alt = p/cos(lat) - N         d(p/cl) = (dp cl - p dcl)/(cl cl'),  dN = N ((1 + uw)^-1/2 - 1)
 //   h = r0 alt/(r0 + alt)        dh = r0^2 dalt/((r0 + alt)(r0 + alt'))
 //   atmosphere, wind             atmosphere_delta(); linear piece of the table
@@ -154,7 +159,9 @@ GEL_DEV void pos_centre_tail(const PosCentreTail& t, double rho, double P, const
 // Returns false for a lane whose perturbed point leaves the centre's atmosphere layer / table piece / geopotential branch
 // or sits too close to the polar axis for the series: the caller then recomputes the wavefront's sweep in full.
 // ---------------------------------------------------------------------------
-GEL_DEV bool pos_delta(const double r[3], int kk, double dlt, const PosPart& c, const PosCentre& pc, const Tables& tb, PosPart& o) {
+// dlat_out (point hook 15 only): the change of the latitude itself, for half_lat_step().
+GEL_DEV bool pos_delta(const double r[3], int kk, double dlt, const PosPart& c, const PosCentre& pc, const Tables& tb, PosPart& o,
+                       double* dlat_out = nullptr) {
   // kk is a constant where the sweeps are unrolled (wave-uniform otherwise): a step along z leaves p alone, a step along x or y
   // leaves z alone, and the terms that the other direction would contribute -- products with an exact zero, sums with it -- are
   // not formed (same values; only the sign of an exact zero can differ)
@@ -195,10 +202,8 @@ GEL_DEV bool pos_delta(const double r[3], int kk, double dlt, const PosPart& c, 
   const double dlat = ((dzz * pc.cl - dpp * pc.sl) * pc.ihy) * (1.0 + e * (e - 1.0));
   const double hl2 = 0.5 * dlat * dlat;
   const double dsl = pc.cl * dlat - pc.sl * hl2, dcl = -(pc.sl * dlat + pc.cl * hl2);
-  // half-angle pair of the NED quaternion
-  const double hd = 0.5 * dlat, hd2 = 0.5 * hd * hd;
-  o.shp = c.shp + (c.chp * hd - c.shp * hd2);
-  o.chp = c.chp - (c.shp * hd + c.chp * hd2);
+  o.sl = pc.sl + dsl; o.cl = pc.cl + dcl;
+  if (dlat_out) *dlat_out = dlat;
   // altitude (src/Earth.cpp:58-59)
   const double v = dcl * pc.icl;
   const double dq = ((dp - (pc.p * pc.icl) * dcl) * pc.icl) * (1.0 + v * (v - 1.0));
@@ -250,8 +255,8 @@ GEL_DEV EarthAngle earth_angle(double t) {
 // ECI longitude omega t, and the Earth angle is the longitude: (cos lon, sin lon) = (e.c, e.s).  Those lanes alone read e; a
 // caller whose lanes are all off the axis need not form it.
 // The reference re-runs the Bowring latitude on the rotated position (Coordinate.cpp:86); a rotation about z leaves
-// (sqrt(x^2+y^2), z) and therefore the latitude unchanged, so pos_part's half-latitude pair is reused, and sin / cos lat formed
-// from it by the double-angle identities.  The roundings are pinned (fresh_mul, explicit fma): every kernel that calls this
+// (sqrt(x^2+y^2), z) and therefore the latitude unchanged, so pos_part's (sin lat, cos lat) -- at a sweep's perturbed point
+// pos_delta()'s -- are used as they are.  The roundings are pinned (fresh_mul, explicit fma): every kernel that calls this
 // gets the same bits whatever surrounds the call.
 // GEL_WIND_CHAIN=1 (ablation; needs the Earth angle in every windy lane, so it also turns the fused kernels' on-axis vote
 // back into the any-lane-windy one): the reference's quaternion chain operation by operation (wind_eci_chain()) -- the longitude taken from
@@ -270,8 +275,25 @@ GEL_DEV bool wind_needs_angle(double inv_p, double wn, double we) {
 #endif
 }
 // the reference's chain, operation by operation: GEL_WIND_CHAIN, and the t0 / tf sweeps of GEL_FLAG_FD_RECOMPUTE (below)
-GEL_DEV void wind_eci_chain(const double r[3], const EarthAngle& e, double s_hp, double c_hp, double inv_p, double wn,
+// Half-latitude pair of the NED quaternion (src/Coordinate.cpp:89-90) from (sin lat, cos lat): cos(lat/2) = sqrt((1+cos lat)/2)
+// (cos lat >= 0), sin(lat/2) = sin lat / (2 cos(lat/2)); root and reciprocal root from one iteration.  Only the reference's chain
+// (wind_eci_chain()) and point hook 15 read the pair: the position part carries (sin lat, cos lat) themselves.
+GEL_DEV void half_lat_pair(double sl, double cl, double& s_hp, double& c_hp) {
+  double irt;
+  fsqrt_rsqrt(0.5 * (1.0 + cl), c_hp, irt);
+  s_hp = (0.5 * sl) * irt;
+}
+// ... and the pair at lat + dlat by angle addition with sin(dlat / 2) = dlat / 2, 1 - cos(dlat / 2) = dlat^2 / 8: what the position
+// sweeps carried while the wind took the pair (point hook 15 reports it; tests/test_delta_model.py measures it)
+GEL_DEV void half_lat_step(double s_hp, double c_hp, double dlat, double& s_hp1, double& c_hp1) {
+  const double hd = 0.5 * dlat, hd2 = 0.5 * hd * hd;
+  s_hp1 = s_hp + (c_hp * hd - s_hp * hd2);
+  c_hp1 = c_hp - (s_hp * hd + c_hp * hd2);
+}
+GEL_DEV void wind_eci_chain(const double r[3], const EarthAngle& e, double sl, double cl, double inv_p, double wn,
                             double we, double w[3]) {
+  double s_hp, c_hp;
+  half_lat_pair(sl, cl, s_hp, c_hp);
   // eci2ecef(pos, t): src/Coordinate.cpp:51-59
   const double px = r[0] * e.c + r[1] * e.s;
   const double py = -r[0] * e.s + r[1] * e.c;
@@ -299,16 +321,14 @@ GEL_DEV void wind_eci_chain(const double r[3], const EarthAngle& e, double s_hp,
   w[1] = q0 * t2 + q1 * t3 - q2 * t0 - q3 * t1;
   w[2] = q0 * t3 - q1 * t2 + q2 * t1 - q3 * t0;
 }
-GEL_DEV void wind_eci(const double r[3], const EarthAngle& e, double s_hp, double c_hp, double inv_p, double wn,
+GEL_DEV void wind_eci(const double r[3], const EarthAngle& e, double sl, double cl, double inv_p, double wn,
                       double we, double w[3]) {
 #if GEL_WIND_CHAIN
-  wind_eci_chain(r, e, s_hp, c_hp, inv_p, wn, we, w);
+  wind_eci_chain(r, e, sl, cl, inv_p, wn, we, w);
 #else
   const bool off_axis = inv_p > 0.0;
   const double clon = off_axis ? r[0] * inv_p : e.c;
   const double slon = off_axis ? r[1] * inv_p : e.s;
-  const double sl = fresh_mul(2.0 * s_hp, c_hp);
-  const double cl = fresh_mul(c_hp - s_hp, c_hp + s_hp);
   const double nh = -fresh_mul(wn, sl);   // the north component's horizontal part, along (cos lon, sin lon)
   w[0] = __builtin_fma(nh, clon, -fresh_mul(we, slon));
   w[1] = __builtin_fma(nh, slon, fresh_mul(we, clon));
@@ -320,7 +340,7 @@ GEL_DEV void wind_eci(const double r[3], const EarthAngle& e, double s_hp, doubl
 // measured part of a wind table, as in the shipped example from 23 km up) the rotation of the zero vector is the zero
 // vector, so the call is skipped -- six times per node in the fused kernel (~110 instructions each with the quaternion
 // chain, GEL_WIND_CHAIN; some 20 with the local axes).  Non-finite components are not zero and take the full path.
-GEL_DEV void wind_eci_or_calm(const double r[3], const EarthAngle& e, double s_hp, double c_hp, double inv_p, double wn,
+GEL_DEV void wind_eci_or_calm(const double r[3], const EarthAngle& e, double sl, double cl, double inv_p, double wn,
                               double we, double w[3]) {
 #if GEL_CALM_SHORTCUT
   if (__builtin_amdgcn_ballot_w64(!(wn == 0.0 && we == 0.0)) == 0) {   // wave-uniform branch
@@ -328,13 +348,13 @@ GEL_DEV void wind_eci_or_calm(const double r[3], const EarthAngle& e, double s_h
     return;
   }
 #endif
-  wind_eci(r, e, s_hp, c_hp, inv_p, wn, we, w);
+  wind_eci(r, e, sl, cl, inv_p, wn, we, w);
 }
 // The t0 / tf sweeps of GEL_FLAG_FD_RECOMPUTE (the audit form: what the reference's own sweeps give) move nothing but the Earth
 // angle, which the local-axes form does not read off the polar axis -- it would return the centre's bits and the columns would be
 // exact zeros, which the reference's are not: its two runs of the chain differ by their rounding.  These sweeps therefore
 // evaluate the perturbed point with the reference's chain and the perturbed angle, like the reference does.
-GEL_DEV void wind_eci_chain_or_calm(const double r[3], const EarthAngle& e, double s_hp, double c_hp, double inv_p, double wn,
+GEL_DEV void wind_eci_chain_or_calm(const double r[3], const EarthAngle& e, double sl, double cl, double inv_p, double wn,
                                     double we, double w[3]) {
 #if GEL_CALM_SHORTCUT
   if (__builtin_amdgcn_ballot_w64(!(wn == 0.0 && we == 0.0)) == 0) {   // wave-uniform branch
@@ -342,7 +362,7 @@ GEL_DEV void wind_eci_chain_or_calm(const double r[3], const EarthAngle& e, doub
     return;
   }
 #endif
-  wind_eci_chain(r, e, s_hp, c_hp, inv_p, wn, we, w);
+  wind_eci_chain(r, e, sl, cl, inv_p, wn, we, w);
 }
 
 // aerodynamic force (ECI): src/pybind_dynamics.cpp:48-59 given the shared parts.

@@ -39,9 +39,9 @@ GEL_DEV void section_rhs(const ProblemDev& P, const PhaseDev& ph, const Tables& 
     double w[3], Fa[3];
     if constexpr (kDisp) {
       const double wn = pp.wn * fw, we = pp.we * fw;
-      wind_eci_or_calm(r, ea, pp.shp, pp.chp, pp.inv_p, wn, we, w);
+      wind_eci_or_calm(r, ea, pp.sl, pp.cl, pp.inv_p, wn, we, w);
     } else {
-      wind_eci_or_calm(r, ea, pp.shp, pp.chp, pp.inv_p, pp.wn, pp.we, w);
+      wind_eci_or_calm(r, ea, pp.sl, pp.cl, pp.inv_p, pp.wn, pp.we, w);
     }
     aero_force(r, v3, pp.rho, pp.inv_a, w, ph.area, tb, Fa);
     const double T = ph.thrust - ph.nozzle * pp.P;

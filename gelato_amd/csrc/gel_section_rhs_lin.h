@@ -34,7 +34,7 @@ GEL_DEV void linearise_air(const ProblemDev& P, const PhaseDev& ph, const Tables
   double w[3];
   L.wn = pp.wn * fw;
   L.we = pp.we * fw;
-  wind_eci_or_calm(r, L.ea, pp.shp, pp.chp, pp.inv_p, L.wn, L.we, w);
+  wind_eci_or_calm(r, L.ea, pp.sl, pp.cl, pp.inv_p, L.wn, L.we, w);
   aero_force(r, v3, pp.rho, pp.inv_a, w, ph.area, tb, L.Fa);
   L.T = ph.thrust - ph.nozzle * pp.P;
 #pragma unroll

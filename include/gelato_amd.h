@@ -1079,6 +1079,10 @@ int gel_dynamics_quaternion(int32_t n, const double* quat_eci2body, const double
  *           aux [K][3]: [rho, P, 1/a, wn, we, sin(lat/2), cos(lat/2), 1/p] of the centre, the same eight of the perturbed point,
  *           pos_delta's return value (1.0: the difference form holds, 0.0: the caller recomputes), the centre's margin [m]
  *                                                                   in [n][5]   out [n][18]
+ *           (the half-latitude pair is formed for this hook alone: the position part carries sin / cos of the latitude itself)
+ *  kind 16: (r, -, dlt)   -> kind 15's 18 outputs for kk = 0, 1, 2 from ONE centre, as the fused kernel chains its three position
+ *           sweeps: 1/T and the margin taken once (pos_centre_tail) and kept, every sweep re-deriving only the wind slopes and the
+ *           centre's wind (pos_centre_tail_kept); bit for bit kind 15's             in [n][5]   out [n][3][18]
  */
 int gel_point_eval(int32_t kind, int32_t n, const double* in, const double* aux, int32_t aux_rows, double* out);
 
@@ -1090,7 +1094,7 @@ int gel_point_eval(int32_t kind, int32_t n, const double* in, const double* aux,
  *  rows), which also covers the launches that keep nothing behind the tables (exact Jacobians, propagation, output table:
  *  T <= 8192); gel_mesh_error[_device] for the estimate, whose workgroup takes as many vectors of a phase as fit beside the
  *  tables and needs room for one (T <= 8170 - 13 n, below the aero limit only from n = 491 on; the handle stays usable for
- *  everything else); gel_dynamics_velocity (T <= 8192) and gel_point_eval kinds 5, 6, 9, 10, 15 (88 + 5 aux_rows <= 8192) for theirs.
+ *  everything else); gel_dynamics_velocity (T <= 8192) and gel_point_eval kinds 5, 6, 9, 10, 15, 16 (88 + 5 aux_rows <= 8192) for theirs.
  *  gel_table_limits (needs no GPU): info[0] = T, info[1] = the T that fits the fused kernel, [2] the aero and callback kernels,
  *  [3] one vector of the collocation error estimate of a phase of n nodes (-1 if n is outside 2 .. 511), [4] the launches with nothing
  *  behind the tables, [5] = the cap in bytes, [6] the vectors a workgroup of the estimate takes of such a phase beside these tables

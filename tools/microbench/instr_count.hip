@@ -27,10 +27,10 @@ K(k_atmos, Air p = atmosphere(a[12], tb.atm); o[0]=p.rho;o[1]=p.P;o[2]=p.inv_a;)
 K(k_wind, double wn, we; wind_ned2(a[12], tb.wind, tb.winds, tb.Kw, wn, we); o[0]=wn;o[1]=we;)
 K(k_interp, o[0]=interp_tab(a[13], tb.ca, tb.cas, tb.Kc, 2, 1);)
 K(k_gravity, double r[3]={a[0],a[1],a[2]}; double g[3]; gravity_eci(r,-0.484165371736e-3,g); o[0]=g[0];o[1]=g[1];o[2]=g[2];)
-K(k_pos_part, double r[3]={a[0],a[1],a[2]}; PosPart p = pos_part(r, tb, -0.484165371736e-3); o[0]=p.rho;o[1]=p.P;o[2]=p.inv_a;o[3]=p.wn;o[4]=p.we;o[5]=p.g[0];o[6]=p.g[1];o[7]=p.g[2];o[8]=p.shp;o[9]=p.chp;o[10]=p.inv_p;)
+K(k_pos_part, double r[3]={a[0],a[1],a[2]}; PosPart p = pos_part(r, tb, -0.484165371736e-3); o[0]=p.rho;o[1]=p.P;o[2]=p.inv_a;o[3]=p.wn;o[4]=p.we;o[5]=p.g[0];o[6]=p.g[1];o[7]=p.g[2];o[8]=p.sl;o[9]=p.cl;o[10]=p.inv_p;)
 K(k_earth, EarthAngle e = earth_angle(a[14]); o[0]=e.c;o[1]=e.s;o[2]=e.ch;o[3]=e.sh;)
 K(k_wind_eci, double r[3]={a[0],a[1],a[2]}; EarthAngle e{0.999,0.01,0.9999,0.005}; double w[3]; wind_eci(r,e,0.36,0.93,1.0/4.7e6,10.0,-5.0,w); o[0]=w[0];o[1]=w[1];o[2]=w[2];)
-K(k_aero, double r[3]={a[0],a[1],a[2]}; double v[3]={a[3],a[4],a[5]}; EarthAngle e{0.999,0.01,0.9999,0.005}; double w[3]={1,2,3}; double F[3]; aero_force(r,v,0.5,1.0/300.0,e,w,2.21,tb,F); o[0]=F[0];o[1]=F[1];o[2]=F[2];)
+K(k_aero, double r[3]={a[0],a[1],a[2]}; double v[3]={a[3],a[4],a[5]}; EarthAngle e{0.999,0.01,0.9999,0.005}; double w[3]={1,2,3}; double F[3]; aero_force(r,v,0.5,1.0/300.0,w,2.21,tb,F); o[0]=F[0];o[1]=F[1];o[2]=F[2];)
 K(k_thrustdir, double q[4]={a[5],a[6],a[7],a[8]}; double d[3]; thrust_dir(q,d); o[0]=d[0];o[1]=d[1];o[2]=d[2];)
 int main() {
   const int n = 64 * 1024;
