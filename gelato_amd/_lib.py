@@ -227,7 +227,7 @@ def build(force=False):
     src_dir = os.path.join(_HERE, "csrc")
     if force and os.path.exists(SO_PATH):
         os.remove(SO_PATH)
-    subprocess.check_call(["make", "-s", "-j8", "-C", src_dir])   # fifteen translation units with kernels (the fused kernels, the AERO instantiation, the three exact Jacobians, the mesh error estimate, the two Jacobian products, the interpolation, the propagation, its tangent and its adjoint, the batched output table, the batch quantiles, the batch co-moments) and the host side, gel_host*.hip: one file per subsystem (the core with the one-vector path, the forward difference, the constraints, the mesh estimate and interpolation, the flights, the Jacobian products, the Monte-Carlo statistics, the LGR generators), sharing gel_host_handle.h and gel_host_internal.h
+    subprocess.check_call(["make", "-s", "-j8", "-C", src_dir])   # every unit the Makefile lists: gel_kernels*.hip (the kernels) and gel_host*.hip
     if not os.path.exists(SO_PATH):
         raise RuntimeError("building %s failed" % SO_PATH)
     _write_build_info()

@@ -90,17 +90,14 @@ struct AeroPhaseDev {
 // first column (in units of n doubles) of a block inside a spec-major block: con 0, position 1, velocity 4, quaternion 7, (t 11)
 constexpr int kAeroSpecCols = 11, kAeroSpecColsWithT = 13;
 
-// knot / terminal / user rows (lib/con_init_terminal_knot.py, example/user_constraints.py): see gel_kernels.hip rows_kernel
+// knot / terminal / user rows (lib/con_init_terminal_knot.py, example/user_constraints.py): see gel_rows_body.h rows_body
 struct LinRowDev { int32_t idx0, idx1; double coef0, coef1, c0; };  // (coef0 x[idx0] + coef1 x[idx1]) + c0; idx1 < 0: one term
-// f(position, velocity of state node `node`[, knot time x_t[tcol]]) mapped by `mode` (gel_kernels.hip rows_kernel):
+// f(position, velocity of state node `node`[, knot time x_t[tcol]]) mapped by `mode` (gel_rows_body.h rows_body):
 // value: mode & 3 == 0: f / p[0] - p[1];  == 1: (f - p[1]) / p[0];  bit 3: negated
 // difference: bit 2 clear: (value(x + dx e_c) - value(x)) / dx;  set: ((f(x + dx e_c) - f(x)) / dx) / p[0], negated with bit 3
 struct FnRowDev { int32_t fn, node, tcol, mode; double p[8]; };
 
-#ifndef GEL_LONG_PHASE_FROM
-#define GEL_LONG_PHASE_FROM 68
-#endif
-constexpr int kLongPhaseFrom = GEL_LONG_PHASE_FROM;   // phases of this many nodes and more take the slab loop of the cooperative form (gel_eval_kernel.h)
+constexpr int kLongPhaseFrom = 68;   // phases of this many nodes and more take the slab loop of the cooperative form (gel_eval_kernel.h)
 
 struct ProblemDev {
   int32_t S, N, M, nvars;

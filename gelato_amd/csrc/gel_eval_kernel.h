@@ -1,4 +1,4 @@
-// gel_eval_kernel.h -- the fused evaluation kernel (included by gel_kernels.hip).
+// gel_eval_kernel.h -- the fused evaluation kernel (included by gel_kernels.hip and gel_kernels_aero.hip, the two units that instantiate eval_body).
 //
 // One wavefront = one (decision vector b, phase, 64-node chunk) work item; one
 // lane = one collocation node.  The phase is wave-uniform: its parameters sit in
@@ -72,64 +72,21 @@ static_assert(wave_lds_doubles(false, true, true) >= kParkRes && wave_lds_double
 //   s_qq+8 +8 quat/u   s_qq+16 +4 quat/t (t0)
 constexpr int kSlotPT = 0, kSlotVM = 3, kSlotVP = 6;
 
-#ifndef GEL_MIN_WAVES_PER_SIMD
-#define GEL_MIN_WAVES_PER_SIMD 4  // 121-128 VGPRs: 4 waves/SIMD (16 per CU, matching the LDS budget); 5 spills heavily
-#endif
-#ifndef GEL_MIN_WAVES_PER_SIMD_PACKJAC
-#define GEL_MIN_WAVES_PER_SIMD_PACKJAC 4  // two vectors per wavefront with derivatives (the per-half scalars are vector values there)
-#endif
-#ifndef GEL_MIN_WAVES_PER_SIMD_RES
-#define GEL_MIN_WAVES_PER_SIMD_RES 5  // residual-only, two vectors per wavefront: 94 VGPRs, 25 KB of LDS per workgroup
-                                      // (6: 80 VGPRs + 48 B of scratch per lane, 3 x 32 residual-only 29 % SLOWER, pooled A/B round 4)
-#endif
+// Tunables of the fused kernel (closed experiments with the other values: tools/ablations/r09_switches.patch)
+constexpr int kMinWaves = 4;         // waves/SIMD of every form but the two below: 121-128 VGPRs (16 per CU, matching the LDS budget); 5 spills heavily
+constexpr int kMinWavesPackJac = 4;  // two vectors per wavefront with derivatives (the per-half scalars are vector values there)
+constexpr int kMinWavesPackRes = 5;  // residual-only, two vectors per wavefront: 94 VGPRs, 25 KB of LDS per workgroup (6: 80 VGPRs + 48 B of
+                                     // scratch per lane, 3 x 32 residual-only 29 % SLOWER, pooled A/B round 4)
+constexpr int kARing = 4;            // LDS-staged cooperative D.X, one vector per wavefront: A slabs in flight, a ring of four, the first four
+                                     // requested before the operand barrier.  In-process A/B at mixed-6x64 (tools/ab_inproc.py, round 5, 0.1 %
+                                     // spread): against all 17 of a 64-node phase at once -1.2 %; 2 / 3 / 5 / 8 in flight +0.4 .. +0.6 % over 4,
+                                     // 6 level; residual-only launch at 6x64 +11 % over 1
+constexpr int kJacStoreAux = 2;      // cache policy of the Jacobian stores: 2 = nt (A/B: 0 plain, 1 sc0, 16 sc1, 18 sc1+nt)
+constexpr int kAeroStoreAux = 2;     // cache policy of the fused kernel's aero-row stores: streamed (nt) like the Jacobian values.  In part A of the
+                                     // record a spec's row of a column is the phase's n nodes -- at n = 64 one store is eight whole 64-byte
+                                     // lines.  In-process A/B at mixed-6x64: nt -0.8 % against ordinary stores.
 
 typedef double gel_double4 __attribute__((ext_vector_type(4)));
-
-#ifndef GEL_CA_CACHE
-#define GEL_CA_CACHE 1  // the Mach interval of a node's first CA lookup serves its other aerodynamic-force evaluations
-#endif
-#ifndef GEL_XLDS_A_PF_JAC
-#define GEL_XLDS_A_PF_JAC 4   // LDS-staged cooperative D.X, one vector per wavefront: A slabs in flight, fused launch.  A ring of four,
-                              // the first four requested before the operand barrier.  In-process A/B at mixed-6x64 (tools/ab_inproc.py,
-                              // round 5, 0.1 % spread): against all 17 of a 64-node phase at once (round 4's choice, made with a
-                              // harness that could not see it) -1.2 %; 2 / 3 / 5 / 8 in flight +0.4 .. +0.6 % over 4, 6 level
-#endif
-#ifndef GEL_XLDS_A_PF_RES
-#define GEL_XLDS_A_PF_RES 4  // ... residual-only launch (6x64: +11 % over 1; the fused launch does not care: +-1 % for 1..8)
-#endif
-#ifndef GEL_PACK_A_PRELOAD
-#define GEL_PACK_A_PRELOAD 1  // two vectors per wavefront: all (<= 9) A slabs of D.X requested before the operand barrier
-#endif
-
-
-#ifndef GEL_XCD_RANGES
-#define GEL_XCD_RANGES 1   // cooperative launches, work-item major order: every XCD takes contiguous runs of vector groups
-#endif
-#ifndef GEL_XCD_BLOCK
-#define GEL_XCD_BLOCK 0    // groups per run (a power of two), 0: an eighth of the batch
-#endif
-#ifndef GEL_FRONT_BATCH
-#define GEL_FRONT_BATCH 1  // cooperative forms: the kernel arguments of the walk to the phase record in one round trip, one chunk-record fetch
-#endif
-#ifndef GEL_DX_HOLD7
-#define GEL_DX_HOLD7 1  // hold-type phases: D.X without the quaternion columns (two column tiles per wavefront instead of three)
-#endif
-
-#ifndef GEL_POS_REPARK
-#define GEL_POS_REPARK 1  // slots LV0 / LV1, free since the wind takes sin / cos of the latitude from FP3 / FP4: the centre's 1 / T and sweep
-                          // margin, taken once (AERO: 1 / hypot(z Ra, p Rb) in LV1); 0: every position sweep re-derives them (A/B)
-#endif
-#ifndef GEL_STORE_AUX
-#define GEL_STORE_AUX 2  // cache policy of the Jacobian stores: 2 = nt (A/B: 0 plain, 1 sc0, 16 sc1, 18 sc1+nt)
-#endif
-
-#ifndef GEL_AERO_STORE_AUX
-#define GEL_AERO_STORE_AUX 2  // cache policy of the fused kernel's aero-row stores: streamed (nt) like the Jacobian values.  In part A of the
-                              // record a spec's row of a column is the phase's n nodes -- at n = 64 one store is eight whole 64-byte
-                              // lines (in gel_eval_aero_all's layout the rows are n + 1 doubles long and every store of nodes 1 .. n
-                              // began 8 bytes into a line and ended 8 bytes into another: the fused launch took 4.95 ms instead of
-                              // 4.46).  In-process A/B at mixed-6x64: nt -0.8 % against ordinary stores.
-#endif
 
 // JAC: also the FD Jacobian.  MFMA: D.X on the matrix pipe (v_mfma_f64_16x16x4_f64) instead of VALU FMAs.
 // SPLIT (latency form for a handful of decision vectors, e.g. the optimiser's B = 1 callback): every work item
@@ -163,7 +120,7 @@ __device__ __forceinline__ void eval_body(const ProblemDev P, int B, const doubl
   int fB = B, f_chunk0 = P.chunk0, f_vmajor = P.vmajor, f_nchunks = P.nchunks;
   const int4* f_chunks = P.chunks;
   const PhaseDev* f_phases = P.phases;
-  if (GEL_FRONT_BATCH && MFMA && !SPLIT) asm volatile("" : "+s"(fB), "+s"(f_chunk0), "+s"(f_vmajor), "+s"(f_nchunks), "+s"(f_chunks), "+s"(f_phases));
+  if (MFMA && !SPLIT) asm volatile("" : "+s"(fB), "+s"(f_chunk0), "+s"(f_vmajor), "+s"(f_nchunks), "+s"(f_chunks), "+s"(f_phases));
   const int park_off = P.park_off;
   // the cooperative forms meet at a barrier (operand image / hand-over) before any table lookup: no barrier of its own
   constexpr bool kSplitStage = MFMA && !SPLIT;   // cooperative forms: table entry requested now, written before their first barrier
@@ -240,19 +197,19 @@ __device__ __forceinline__ void eval_body(const ProblemDev P, int B, const doubl
     // XCD-contiguous vector groups: workgroup p runs on XCD p % 8, so with the groups dealt in dispatch order every XCD touched
     // every eighth group of the batch -- every page of x / res / jvar that is being worked on, eight times over.  Within a block of
     // 8 G groups, XCD j instead takes the G consecutive groups j G .. (j + 1) G - 1 (for every work item alike: the same XCD comes
-    // back to the same vectors' rows): each XCD's translations and lines cover an eighth of the pages.  G = GEL_XCD_BLOCK groups,
-    // or a whole eighth of the batch (0: in-process A/B at B = 65536, mixed-6x64 -2.2 %, dense -4.6 %, 12 x 128 -1.0 %; runs of 64 / 512
+    // back to the same vectors' rows): each XCD's translations and lines cover an eighth of the pages.  G = a whole
+    // eighth of the batch (in-process A/B at B = 65536, mixed-6x64 -2.2 %, dense -4.6 %, 12 x 128 -1.0 %; runs of 64 / 512
     // groups -1.8 / -2.1 %, 0 / -0.7 %); the groups behind the last full block keep the dispatch order.  (Applied to the group index
     // the order ends with: the chunks of a long phase stay together on their XCD.)
-    if (GEL_XCD_RANGES && !f_vmajor) {   // (the vector-group major order of the small-phase meshes: +1.0 % with it at 3 x 32, left alone)
-      const unsigned G = GEL_XCD_BLOCK ? (unsigned)GEL_XCD_BLOCK : (nb >> 3), blk8 = 8u * G;
+    if (!f_vmajor) {   // (the vector-group major order of the small-phase meshes: +1.0 % with it at 3 x 32, left alone)
+      const unsigned G = nb >> 3, blk8 = 8u * G;
       if (G != 0) {
-        const unsigned bq = bg / blk8, inb = bg - bq * blk8;   // blk8 a power of two when GEL_XCD_BLOCK is one: shifts
+        const unsigned bq = bg / blk8, inb = bg - bq * blk8;
         if ((bq + 1u) * blk8 <= nb) bg = bq * blk8 + (p & 7u) * G + (inb >> 3);
       }
     }
     q = (int)(it - pos + c);
-    ck_same = GEL_FRONT_BATCH && nc <= 1;
+    ck_same = nc <= 1;
     b0 = (int)bg * kVecWg;                             // first vector of the workgroup
   } else {
     q = (int)(item / B);
@@ -304,15 +261,13 @@ __device__ __forceinline__ void eval_body(const ProblemDev P, int B, const doubl
 #define GEL_UNI(v) (PACK ? (v) : wave_uniform(v))
   // The phase's two knot times: requested here, TAKEN (v_readfirstlane: the first wait of the wavefront) only once every other
   // load of phase A has been requested -- one HBM round trip instead of two in a row in front of the D.X product.
-#ifndef GEL_KNOT_VLOAD
-#define GEL_KNOT_VLOAD 1   // the knot times by a VECTOR load (the index made opaque): a wave-uniform address becomes a scalar load, which the
-                           // compiler -- short of scalar registers here -- waits for on the spot (to park the pair in a VGPR's lanes): an HBM
-                           // round trip IN FRONT of the requests for the state rows, the very thing the comment above is about
-#endif
+  // By a VECTOR load (the index made opaque): a wave-uniform address becomes a scalar load, which the compiler -- short of scalar
+  // registers here -- waits for on the spot (to park the pair in a VGPR's lanes): an HBM round trip IN FRONT of the requests for the
+  // state rows, the very thing the comment above is about
   int sec_ld = sec;
   // (the residual-only forms have the scalar registers to let the pair wait with the others; the latency form reads x from pinned
   // host memory, where the pair as a vector load cost a one-vector evaluation with derivatives 2.5 us: 31.6-34.3 -> 36.2-37.1)
-  if (GEL_KNOT_VLOAD && JAC && !SPLIT) asm volatile("" : "+v"(sec_ld));
+  if (JAC && !SPLIT) asm volatile("" : "+v"(sec_ld));
   const double to_ld = xt[sec_ld], tf_ld = xt[sec_ld + 1];
   double to = 0.0, tf = 0.0, fds = 0.0, fdt = 0.0;
   const double dx = P.dx, ut = P.ut;
@@ -371,7 +326,7 @@ __device__ __forceinline__ void eval_body(const ProblemDev P, int B, const doubl
     const double _v = (val);                                                            \
     gel_u2 _d;                                                                          \
     __builtin_memcpy(&_d, &_v, 8);                                                      \
-    __builtin_amdgcn_raw_buffer_store_b64(_d, jrs, jvo, (byteoff), NTS ? GEL_STORE_AUX : 0); \
+    __builtin_amdgcn_raw_buffer_store_b64(_d, jrs, jvo, (byteoff), NTS ? kJacStoreAux : 0); \
     if (!rb) GEL_CHK(_v);                                                                 \
   } while (0)
 #define EMIT(slot, val) EMIT_AT(((int)(slot) - (SPLIT ? (((int)(slot) >= kSlotVP) ? sub_hi : sub_lo) : 0)) * cw8, val)
@@ -388,7 +343,7 @@ __device__ __forceinline__ void eval_body(const ProblemDev P, int B, const doubl
     const double _v = (val);                                                            \
     gel_u2 _d;                                                                          \
     __builtin_memcpy(&_d, &_v, 8);                                                      \
-    __builtin_amdgcn_raw_buffer_store_b64(_d, ars, jvo, (byteoff), GEL_AERO_STORE_AUX); \
+    __builtin_amdgcn_raw_buffer_store_b64(_d, ars, jvo, (byteoff), kAeroStoreAux); \
   } while (0)
 // (latency form: the rows go to pinned host memory -- streamed, so that they cross PCIe while the wavefront computes on instead of
 // waiting in L2 for the end of the kernel; throughput form: the strided rows' partial lines want to meet in L2 first)
@@ -401,15 +356,12 @@ __device__ __forceinline__ void eval_body(const ProblemDev P, int B, const doubl
   // driver places a process's 14 GB of buffers (+-3 % between processes of one build; pooled A/B of round 4: +-1 % against the
   // strided form) -- the launch is bound by package power, and the bytes are the same.  Measured on the way (same box, round 4):
   // the residual rows are 17 % of the stored bytes and, removed entirely, 9-10 % of the launch (3.41 -> 3.06 ms; without any store
-  // 2.43 ms).  Ragged chunks (lanes past the phase have left) keep the strided form.  -DGEL_RES_XPOSE=0: strided everywhere (A/B).
-#ifndef GEL_RES_XPOSE
-#define GEL_RES_XPOSE 1
-#endif
+  // 2.43 ms).  Ragged chunks (lanes past the phase have left) keep the strided form.
   // Two vectors per wavefront (PACK): the tile holds half 0's rows then half 1's ([w * lane + c] does that by itself); row i of
   // the tile belongs to the vector of half (64 i + lane) / (32 w), so a lane may store the OTHER half's values: only in a
   // wavefront whose two vectors both exist (no ghost half) and whose phase has exactly 32 nodes.
   constexpr int kTileOff = JAC ? PK_FP0 * 64 : kParkRes;     // phase A: slots FP0.. are not in use yet (residual-only: behind the park)
-  constexpr bool kCanXpose = (GEL_RES_XPOSE != 0) && (kWL >= kTileOff + 4 * 64);
+  constexpr bool kCanXpose = kWL >= kTileOff + 4 * 64;
   // whole lines, written once and never read by this kernel: non-temporal like the Jacobian values (the strided form's partial
   // lines want to meet in L2 first: written non-temporally they cost 4 % more HBM writes, round 2)
 #define RSTORE_LINE(ptr, val) __builtin_nontemporal_store((val), (ptr))
@@ -556,7 +508,7 @@ __device__ __forceinline__ void eval_body(const ProblemDev P, int B, const doubl
         // quaternion columns of D.X: their vectors are packed seven columns each (mass | position | velocity) -- 28 columns in TWO
         // column tiles per wavefront instead of 44 in three, a third of the phase's matrix instructions less (one vector per wavefront only).
         // A column's sums do not depend on its neighbours in the tile: the columns that are formed keep their bits.
-        const bool h7 = GEL_DX_HOLD7 && !PACK && ph.hold;   // wave-uniform (one work item per workgroup); PACK: not taken (3 x 32 residual-only +1.1 % with it)
+        const bool h7 = !PACK && ph.hold;   // wave-uniform (one work item per workgroup); PACK: not taken (3 x 32 residual-only +1.1 % with it)
         const int ncv = h7 ? 7 : 11;               // columns per vector
         const int ncols = ncv * kVecWg;
         const int ct0 = PACK ? (h7 ? 2 : 3) * (wv >> 1) : 0;
@@ -573,10 +525,10 @@ __device__ __forceinline__ void eval_body(const ProblemDev P, int B, const doubl
         // ksteps <= kSlabK: the phase is one slab
         // Every load of phase A is REQUESTED before anything waits: the A slabs first (they do not depend on x: L2), then the
         // state rows (HBM), and only then the first s_waitcnt of the wavefront.  A slabs: all k-steps of the phase at once
-        // (kAAll), or a ring of kAPF in flight.
-        constexpr int kAPF = JAC ? GEL_XLDS_A_PF_JAC : GEL_XLDS_A_PF_RES;
+        // (kAAll: two vectors per wavefront, all <= 9 of them), or a ring of kAPF in flight.
+        constexpr int kAPF = kARing;
         constexpr int kAllN = PACK ? 9 : kSlabK;
-        constexpr bool kAAll = PACK ? (GEL_PACK_A_PRELOAD != 0) : (kAPF >= kSlabK);
+        constexpr bool kAAll = PACK || kAPF >= kSlabK;
         double a_all[kAAll ? kAllN : 1], a_ring[kAAll ? 1 : kAPF];
         if (kAAll) {
 #pragma unroll
@@ -730,7 +682,7 @@ __device__ __forceinline__ void eval_body(const ProblemDev P, int B, const doubl
         static_assert(!COOP || PACK || !LONGP || kRingOff + 64 * kPipeK <= kWL, "two images and the A ring must fit the wave's region");
         constexpr int kBP = kPipeRows, kBV = 4 * kPipeRows, kBQ = 7 * kPipeRows;   // blocks of an image
         lds_double* regions = (lds_double*)lds + park_off;
-        const bool h7 = GEL_DX_HOLD7 && ph.hold;   // hold-type phase: seven columns per vector in two column tiles (see the one-slab form)
+        const bool h7 = ph.hold;   // hold-type phase: seven columns per vector in two column tiles (see the one-slab form)
         const int ncv = h7 ? 7 : 11, ncols = 4 * ncv;
         int xoff[3], xstr[3];
 #pragma unroll
@@ -1210,7 +1162,7 @@ __device__ __forceinline__ void eval_body(const ProblemDev P, int B, const doubl
       // (1) the centre evaluation; the intermediates of its position part that the position sweeps will need (PosCentre) go to
       //     the park as soon as they exist -- FP0-7 at once (sin / cos of the latitude, which the wind's rotation reads as well, among
       //     them); once the velocity defect has been stored its slots take 1/p (LV2) and the centre's 1/T and sweep margin (LV0 / LV1,
-      //     pos_centre_tail() once: GEL_POS_REPARK; AERO: LV1 takes 1/hypot(z Ra, p Rb), LV2 an aero row's centre value);
+      //     pos_centre_tail() once; AERO: LV1 takes 1/hypot(z Ra, p Rb), LV2 an aero row's centre value);
       // (2) the light sweeps (velocity, quaternion, mass) and the t columns, while the centre's wind, force, gravity and
       //     thrust are in registers, where they then die; the centre value f_c and the thrust direction go to Q0-3 / DJJ;
       // (3) the three position sweeps in exact-difference form (pos_delta(): the change of altitude, atmosphere and wind from
@@ -1231,18 +1183,6 @@ __device__ __forceinline__ void eval_body(const ProblemDev P, int B, const doubl
       // half-angle pair, formed on first need like the defect's
       EarthHalf aeh{1.0, 0.0};
       bool have_aeh = false;
-#ifndef GEL_AEH
-#define GEL_AEH aeh
-#endif
-#ifndef GEL_X_NOPOS
-#define GEL_X_NOPOS 0
-#endif
-#ifndef GEL_X_NOQUAT
-#define GEL_X_NOQUAT 0
-#endif
-#ifndef GEL_X_NOVEL
-#define GEL_X_NOVEL 0
-#endif
       const bool aero_on = AERO && akinds != 0;                 // wave-uniform
       const bool a_need_alpha = AERO && (akinds & 5) != 0;      // an alpha or q-alpha row
 #define GEL_AERO_NEED_EA(ip_, wn_, we_)                                                                                \
@@ -1257,7 +1197,7 @@ __device__ __forceinline__ void eval_body(const ProblemDev P, int B, const doubl
   } while (0)
       // One gradient entry of every kind of this phase, -(f_p - f_c) / dx / limit (lib/con_aero.py:437-463), from the perturbed
       // point's air-relative velocity a_ (squared norm nv2_), body axis d_ (1 / |d| = ind_) and density: aero_body's GEL_AERO_EMIT
-      // (gel_kernels.hip), expression for expression.  blk: 0 position, 1 velocity, 2 quaternion; okl_: this lane writes.
+      // (gel_aero_body.h), expression for expression.  blk: 0 position, 1 velocity, 2 quaternion; okl_: this lane writes.
       // A kind this phase does not have (akinds) is not branched around: its block base points at the record's dump area and its
       // scale factors are zero (gel_host.hip) -- three scalar tests and branches less per entry, nothing written where it counts.
       // the phase's aero record, fetched ONCE per group of entries (scalar loads, one round trip -- fetched where each store needs
@@ -1291,16 +1231,12 @@ __device__ __forceinline__ void eval_body(const ProblemDev P, int B, const doubl
       if (okl_) AEMIT(ab_[kind] + (((blk) == 0 ? 1 : ((blk) == 1 ? 4 : 7)) + (col)) * n8_ + j08_, gv);                 \
     }                                                                                                                  \
   } while (0)
-#if GEL_CA_CACHE
-      Bracket ca_br = no_bracket();   // the node's Mach interval, shared by all of its aerodynamic-force evaluations
+      Bracket ca_br = no_bracket();   // the Mach interval of a node's first CA lookup serves its other aerodynamic-force evaluations
 #define GEL_CA_BRACKET (JAC ? &ca_br : (Bracket*)nullptr)   // a residual-only launch looks up once
-#else
-#define GEL_CA_BRACKET nullptr
-#endif
       // AERO: p and 1/hypot(z Ra, p Rb) are NOT parked in their own slots (nor is 1/p, below): those three slots hold the aero
       // rows' centre values cos(alpha), alpha and q instead of ten more registers across the sweeps.  The position sweeps form p and
       // 1/p again from the node position (the head of geodetic_p_ih: the statements that produced them); 1/hypot waits in LV1, which
-      // the half-latitude pair used to take (GEL_POS_REPARK=0: formed again as well, 30 operations per sweep in all)
+      // the half-latitude pair used to take
       struct ParkSink { lds_double* park; GEL_DEV void put(int i, double v) const { if (!(AERO && (i == PCS_P || i == PCS_IH))) park[(PK_FP0 + i) * 64] = v; } };
       constexpr int PK_ACC = PK_FP0 + PCS_P, PK_AAC = PK_FP0 + PCS_IH, PK_AQC = PK_LV2;   // AERO: cos(alpha_c), alpha_c, q_c
       static_assert(PCS_COUNT == 8 && PK_FP7 == PK_FP0 + 7, "PosCentre's early members fill FP0-7");
@@ -1338,29 +1274,16 @@ __device__ __forceinline__ void eval_body(const ProblemDev P, int B, const doubl
           accel_parts(Tdc, F, inv_m, pp.g, inv_uv, tm, fc);
         }
         if (rb) {  // velocity defect (:216-289); its D.X row leaves slots LV0-2, which then serve as the tile of the transposed store
-#ifndef GEL_RES_XPOSE_VEL_AIR
-#define GEL_RES_XPOSE_VEL_AIR 1   // the velocity defect of an aerodynamic phase through the tile as well (with the max-ilp scheduling
-                                  // strategy the three values live at the register peak cost no scratch any more): in-process A/B
-                                  // -0.35 % at mixed-6x64, level at dense / 12 x 128 (round 5)
-#endif
-          if (!JAC || GEL_RES_XPOSE_VEL_AIR) {
-            double cv[3];
+          // through the tile like the other rows (with the max-ilp scheduling strategy the three values live at the register peak cost
+          // no scratch any more): in-process A/B -0.35 % at mixed-6x64, level at dense / 12 x 128 (round 5)
+          double cv[3];
 #pragma unroll
-            for (int c = 0; c < 3; c++) cv[c] = PARK_GET(PK_LV0 + c) - fc[c] * (tf - to) * hT;
-            RSTORE_ROWS(wave_lds + PK_LV0 * 64, 3, rs_v, cv);
-          } else {
-#pragma unroll
-            for (int c = 0; c < 3; c++) {
-              const double cv = PARK_GET(PK_LV0 + c) - fc[c] * (tf - to) * hT;
-              RSTORE(rs_v + 3 * gn + c, cv);
-              GEL_CHK(cv);
-            }
-          }
+          for (int c = 0; c < 3; c++) cv[c] = PARK_GET(PK_LV0 + c) - fc[c] * (tf - to) * hT;
+          RSTORE_ROWS(wave_lds + PK_LV0 * 64, 3, rs_v, cv);
         }
         if (JAC) {   // what waits in the slots of the D.X row for the position sweeps
           asm volatile("" ::: "memory");
           if (!AERO) PARK_SET(PK_LV2, pp.inv_p);
-#if GEL_POS_REPARK
           // (the lead of the latency form runs no position sweep.  A problem created with GEL_FLAG_FD_RECOMPUTE parks them too and never
           // reads them -- its sweeps all recompute: a dozen wasted operations in the audit form, which is not for speed, instead of
           // one more scalar test on the path that is)
@@ -1380,7 +1303,6 @@ __device__ __forceinline__ void eval_body(const ProblemDev P, int B, const doubl
               PARK_SET(PK_LV0, pcx.air.iT); PARK_SET(PK_LV1, pcx.margin);
             }
           }
-#endif
         }
         if (JAC && lead && !P.fd_recompute) GEL_MASS_CLOSED(tm);   // first: (T d + F) / m dies here
         // velocity sweeps: only the aerodynamic force changes.  Latency form of a WHOLE evaluation (P.split_vel: the optimiser's
@@ -1446,7 +1368,7 @@ __device__ __forceinline__ void eval_body(const ProblemDev P, int B, const doubl
         if (aero_on) {
           // ---- aero rows, centre (lib/con_aero.py:39-87,127-139): the air-relative velocity with con_aero's Earth angle, alpha, q;
           //      then the sweeps whose inputs are at hand here -- quaternion (only the body axis changes) and velocity (only the
-          //      air-relative velocity) -- and the t columns (exact zeros: aero_body, gel_kernels.hip)
+          //      air-relative velocity) -- and the t columns (exact zeros: aero_body, gel_aero_body.h)
           asm volatile("" ::: "memory");
           const double ra[3] = {fresh_product(re[0], P.up), fresh_product(re[1], P.up), fresh_product(re[2], P.up)};
           double va[3], wa[3], a0[3];
@@ -1466,7 +1388,7 @@ __device__ __forceinline__ void eval_body(const ProblemDev P, int B, const doubl
             pos_centre_tail(pt, pp.rho, pp.P, tb, pcx, wn_, we_);
             geodetic_p_ih(ra[0], ra[1], ra[2], p_, ip_, ih_);
             EarthAngle e2{1.0, 0.0, 1.0, 0.0};
-            if (have_aeh) e2 = full_angle(GEL_AEH);
+            if (have_aeh) e2 = full_angle(aeh);
             wind_eci(ra, e2, PARK_GET(PK_FP0 + PCS_SL), PARK_GET(PK_FP0 + PCS_CL), ip_, wn_, we_, wa);
           } else {
             wa[0] = 0.0; wa[1] = 0.0; wa[2] = 0.0;
@@ -1489,7 +1411,7 @@ __device__ __forceinline__ void eval_body(const ProblemDev P, int B, const doubl
             GEL_CHK(cv);
             // (the t0 / tf columns: exact zeros, not stored -- gel_aero_record_map names them -1)
           }
-          if (a_need_alpha && !GEL_X_NOQUAT) {
+          if (a_need_alpha) {
             const double q[4] = {PARK_GET(PK_Q0), PARK_GET(PK_Q1), PARK_GET(PK_Q2), PARK_GET(PK_Q3)};
 #pragma unroll
             for (int c = 0; c < 4; c++) {
@@ -1503,7 +1425,7 @@ __device__ __forceinline__ void eval_body(const ProblemDev P, int B, const doubl
             }
           }
 #pragma unroll
-          for (int c = 0; c < (GEL_X_NOVEL ? 0 : 3); c++) {
+          for (int c = 0; c < 3; c++) {
             double vp[3], a[3];
 #pragma unroll
             for (int d = 0; d < 3; d++) vp[d] = ((d == c) ? PARK_GET(PK_V0 + d) + dx : PARK_GET(PK_V0 + d)) * P.uv;
@@ -1552,7 +1474,7 @@ __device__ __forceinline__ void eval_body(const ProblemDev P, int B, const doubl
     double wq_[3], a_[3];                                                                                     \
     GEL_AERO_NEED_EA((pq).inv_p, (pq).wn, (pq).we);                                                           \
     EarthAngle ea_{1.0, 0.0, 1.0, 0.0};                                                                       \
-    if (have_aeh) ea_ = full_angle(GEL_AEH);                                                                  \
+    if (have_aeh) ea_ = full_angle(aeh);                                                                  \
     wind_eci_or_calm(rp, ea_, (pq).sl, (pq).cl, (pq).inv_p, (pq).wn, (pq).we, wq_);                         \
     const double vq_[3] = {PARK_GET(PK_V0) * P.uv, PARK_GET(PK_V1) * P.uv, PARK_GET(PK_V2) * P.uv};           \
     const double nv2_ = aero_vair2(rp, vq_, wq_, a_);                                                         \
@@ -1574,16 +1496,14 @@ __device__ __forceinline__ void eval_body(const ProblemDev P, int B, const doubl
   PosPart pcv;                                                                                                         \
   pcv.rho = cen_rho; pcv.P = cen_P; pcv.inv_a = cen_inv_a;                                                             \
   pcv.sl = pc.sl; pcv.cl = pc.cl;                                                                                      \
-  if (AERO && GEL_POS_REPARK) {   /* p and 1/p are formed again (one iteration gives both); 1/hypot, unused, is not */    \
+  if (AERO) {   /* p and 1/p are formed again (one iteration gives both); 1/hypot, unused, is not */                      \
     double ih_;                                                                                                        \
     geodetic_p_ih(fresh_product(re[0], P.up), fresh_product(re[1], P.up), fresh_product(re[2], P.up), pc.p, pcv.inv_p, ih_); \
     pc.ih = PARK_GET(PK_LV1);                                                                                          \
-  } else if (AERO) {                                                                                                   \
-    geodetic_p_ih(fresh_product(re[0], P.up), fresh_product(re[1], P.up), fresh_product(re[2], P.up), pc.p, pcv.inv_p, pc.ih); \
   } else {                                                                                                             \
     pc.p = PARK_GET(PK_FP0 + PCS_P); pc.ih = PARK_GET(PK_FP0 + PCS_IH); pcv.inv_p = PARK_GET(PK_LV2);                  \
   }                                                                                                                    \
-  if (GEL_POS_REPARK && !AERO) pos_centre_tail_kept(pt, PARK_GET(PK_LV0), PARK_GET(PK_LV1), tb, pc, pcv.wn, pcv.we);   \
+  if (!AERO) pos_centre_tail_kept(pt, PARK_GET(PK_LV0), PARK_GET(PK_LV1), tb, pc, pcv.wn, pcv.we);   \
   else pos_centre_tail(pt, cen_rho, cen_P, tb, pc, pcv.wn, pcv.we)
         unsigned todo = 0;   // sweeps with a lane the difference form does not cover (wave-uniform)
         unsigned long long coo_okm = 0;   // COO-direct output: the verdict of the difference form, kept for the recomputing pass (the LDS tile
@@ -1615,7 +1535,7 @@ __device__ __forceinline__ void eval_body(const ProblemDev P, int B, const doubl
             // form -- a lane's entries do not depend on which other nodes (or, with two vectors per wavefront, which other
             // decision vector) share its wavefront
             GEL_POS_SWEEP_EMIT(k, f, ok);
-            if (aero_on && !GEL_X_NOPOS) GEL_AERO_POS(k, rp, pq, ok);
+            if (aero_on) GEL_AERO_POS(k, rp, pq, ok);
           }
         }
         if (todo) {
@@ -1643,7 +1563,7 @@ __device__ __forceinline__ void eval_body(const ProblemDev P, int B, const doubl
             double f[3];
             GEL_POS_SWEEP_F(rp, pq, f);
             GEL_POS_SWEEP_EMIT(k, f, !ok);
-            if (aero_on && !GEL_X_NOPOS) GEL_AERO_POS(k, rp, pq, !ok);
+            if (aero_on) GEL_AERO_POS(k, rp, pq, !ok);
           }
         }
 #undef GEL_AERO_POS
@@ -1805,7 +1725,7 @@ __device__ __forceinline__ void signal_done(const ProblemDev& P) {
 // cost 4.4 %)
 // AERO = true: the aero path constraints' rows of the aerodynamic phases' nodes ride along (P.aero_ph / aero_out / aero_ld)
 template <bool JAC, bool MFMA, bool SPLIT = false, bool PACK = false, bool LONGP = true, bool NTS = true, bool AERO = false>
-__global__ __launch_bounds__(kBlock, (!JAC && PACK) ? GEL_MIN_WAVES_PER_SIMD_RES : ((JAC && PACK) ? GEL_MIN_WAVES_PER_SIMD_PACKJAC : GEL_MIN_WAVES_PER_SIMD)) void eval_kernel(ProblemDev P, int B, const double* __restrict__ x,
+__global__ __launch_bounds__(kBlock, (!JAC && PACK) ? kMinWavesPackRes : ((JAC && PACK) ? kMinWavesPackJac : kMinWaves)) void eval_kernel(ProblemDev P, int B, const double* __restrict__ x,
                                                       double* __restrict__ res, double* __restrict__ jvar) {
   eval_body<JAC, MFMA, SPLIT, PACK, 9, LONGP, NTS, AERO>(P, B, x, res, jvar, blockIdx.x);
   if constexpr (SPLIT) signal_done(P);   // latency form only: the throughput forms never signal

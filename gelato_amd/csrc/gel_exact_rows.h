@@ -1,4 +1,4 @@
-// gel_exact_rows.h -- forward-mode (value, tangent) forms of the node functions of the row table (gel_kernels.hip node_fn,
+// gel_exact_rows.h -- forward-mode (value, tangent) forms of the node functions of the row table (gel_rows_body.h node_fn,
 // iip_faa, distance_vincenty) for the exact row Jacobian (gel_kernels_exact_rows.hip, GEL_FLAG_EXACT_ROWS_JAC).
 //
 // Every function is restated statement for statement on a scalar fp64 dual number (value, tangent along ONE direction).  The
@@ -73,7 +73,6 @@ GEL_DEV Dual datan2(Dual y, Dual x) {
   const double r2 = x.v * x.v + y.v * y.v;
   return {atan2(y.v, x.v), (r2 > 0.0) ? (x.v * y.d - y.v * x.d) / r2 : 0.0};
 }
-GEL_DEV Dual dfabs(Dual a) { return (a.v < 0.0) ? -a : a; }
 
 // geodetic_full (gel_physics.h, Bowring one step) with tangents: the values by the same helper calls, hence the same bits
 GEL_DEV void geodetic_full_dual(Dual x, Dual y, Dual z, Dual& lat, Dual& lon, Dual& alt) {
@@ -103,7 +102,7 @@ GEL_DEV void geodetic_full_dual(Dual x, Dual y, Dual z, Dual& lat, Dual& lon, Du
   alt = {altv, (dp - p * icl * dcl) * icl - dN};
 }
 
-// iip_faa (gel_kernels.hip) on duals: the (0, 0) fill returns zero tangents
+// iip_faa (gel_output_row.h) on duals: the (0, 0) fill returns zero tangents
 GEL_DEV void iip_faa_dual(const Dual pe[3], const Dual ve[3], Dual& lat_deg, Dual& lon_deg) {
   const double a = 6378137.0, f = 1.0 / 298.257223563, b = a * (1.0 - f), e2 = 2.0 * f - f * f;
   lat_deg = {0.0, 0.0}; lon_deg = {0.0, 0.0};
@@ -145,7 +144,7 @@ GEL_DEV void iip_faa_dual(const Dual pe[3], const Dual ve[3], Dual& lat_deg, Dua
   lon_deg = lam * 180.0 / kPi;
 }
 
-// distance_vincenty (gel_kernels.hip) from a fixed origin to a dual target; the loop runs on the value part
+// distance_vincenty (gel_output_row.h) from a fixed origin to a dual target; the loop runs on the value part
 GEL_DEV Dual distance_vincenty_dual(double lat_o, double lon_o, Dual lat_t, Dual lon_t) {
   const double Ra = 6378137.0, f = 1.0 / 298.257223563, Rb = Ra * (1.0 - f);
   const double lat1 = lat_o * kPi / 180.0, lon1 = lon_o * kPi / 180.0;
@@ -180,7 +179,7 @@ GEL_DEV Dual distance_vincenty_dual(double lat_o, double lon_o, Dual lat_t, Dual
   return Rb * A * (sigma - ds);
 }
 
-// node_fn (gel_kernels.hip) on duals: functions 0 .. 15 of one knot state
+// node_fn (gel_rows_body.h) on duals: functions 0 .. 15 of one knot state
 GEL_DEV Dual node_fn_dual(int fn, const Dual r[3], const Dual v[3], Dual t, const double* p) {
   if (fn >= 9) {
     Dual sn, cs;

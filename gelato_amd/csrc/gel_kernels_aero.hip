@@ -19,13 +19,10 @@ bool eval_aero_fusable(const ProblemDev& P, int B) {
 hipError_t launch_eval_aero(const ProblemDev& P, int B, const double* d_x, double* d_res, double* d_jvar, hipStream_t s) {
   if (B <= 0) return hipSuccess;
   if (!eval_aero_fusable(P, B) || !P.aero_ph || !P.aero_out || !d_res || !d_jvar) return hipErrorInvalidValue;
-  // grid and LDS as launch_coop() of gel_kernels.hip (one vector per wavefront, four per workgroup)
-  const unsigned nb = (unsigned)((B + 3) / 4);
-  const unsigned grid = P.vmajor ? (unsigned)P.nchunks * 8u * ((nb + 7u) / 8u) : (unsigned)P.nchunks * nb;
+  const unsigned grid = coop_grid(P, B, 4);   // one vector per wavefront, four per workgroup
   const size_t lds = eval_lds_bytes_max(P.Kw, P.Kc);
   hipLaunchKernelGGL((eval_kernel<true, true, false, false, true, true, true>), dim3(grid), dim3(kBlock), lds, s, P, B, d_x, d_res, d_jvar);
   return hipGetLastError();
 }
-
 
 }  // namespace gel

@@ -16,7 +16,7 @@
 // the table-interval, atmosphere-layer, polar-axis and zero-air-speed conventions are those of gel_exact.h.  The t0 / tf columns
 // are exact zeros (the air-relative velocity does not depend on the Earth angle).
 //
-// Outputs: the addressing of aero_body (gel_kernels.hip) for all three forms -- the dense per-kind arrays (ld = 0), the per-vector
+// Outputs: the addressing of aero_body (gel_aero_body.h) for all three forms -- the dense per-kind arrays (ld = 0), the per-vector
 // records' part B (ld != 0, gel_eval_aero_all's block layout) and part A (ld != 0, sm: spec-major, no t columns).
 #include <hip/hip_runtime.h>
 
@@ -87,7 +87,7 @@ __global__ __launch_bounds__(kExactAeroBlock) void exact_aero_kernel(ProblemDev 
 #pragma unroll
   for (int c = 0; c < 3; c++) { ep[c] *= kep; upp[c] *= kup; }
 
-  // ---- outputs: aero_body's addressing (gel_kernels.hip AeroOut)
+  // ---- outputs: aero_body's addressing (gel_aero_body.h AeroOut)
   double* base[3];
   int32_t rowst[3];   // distance between a block's columns (doubles)
 #pragma unroll

@@ -1,5 +1,5 @@
 // gel_output_row.h -- one row of the post-processing table (output_result.py:37-263): the derived quantities
-// of ONE state node, in the order of include/gelato_amd.h gel_output_column.  output_kernel (gel_kernels.hip: one decision vector,
+// of ONE state node, in the order of include/gelato_amd.h gel_output_column.  output_kernel (gel_kernels_rows.hip: one decision vector,
 // gel_output_table) and the batched kernels (gel_kernels_outbatch.hip: gel_output_table_batch*) call the same
 // function, so a row has the same bits in both: written for agreement with the reference's formulas (same operation order, libm
 // calls where the reference has them).  iip_faa and distance_vincenty, which node_fn of the row table shares, live here too.

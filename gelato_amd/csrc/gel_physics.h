@@ -159,16 +159,12 @@ GEL_DEV double frsqrt(double x) {
 // One Horner step p * w + c with the coefficient as a SCALAR operand.  hipcc compiles __builtin_fma(p, w, literal) to
 // v_fmac_f64 with the literal first moved into the destination VGPR pair -- two v_mov_b32 per term, which on a
 // kernel bound by vector issue doubles the cost of every polynomial.  With the coefficient in an SGPR pair (two s_mov_b32
-// on the scalar unit) the step is the one v_fma_f64.  Same operation, same bits.  -DGEL_HORNER_VGPR restores the plain form.
-#ifndef GEL_HORNER_VGPR
+// on the scalar unit) the step is the one v_fma_f64.  Same operation, same bits.
 GEL_DEV double horner(double p, double w, double c) {
   double r;
   asm("v_fma_f64 %0, %1, %2, %3" : "=v"(r) : "v"(p), "v"(w), "s"(c));
   return r;
 }
-#else
-GEL_DEV double horner(double p, double w, double c) { return __builtin_fma(p, w, c); }
-#endif
 
 // exp(x) for the arguments of this path (pressure ratios: |x| <= 40; the thermosphere's temperature law: -3 < x <= 0).  The library's own
 // algorithm (ocml expD: n = rint(x log2 e), t = x - n ln 2 in two parts, degree-11 polynomial, ldexp) with its coefficients as scalar
@@ -375,14 +371,6 @@ GEL_DEV void geodetic_sincos_p(double x, double y, double z, double& sl, double&
 GEL_DEV double geodetic_alt_from(double p, double sl, double cl) {
   const double N = fdiv(kRa, fsqrt(1.0 - kE2 * sl * sl));
   return fdiv(p, cl) - N;
-}
-
-GEL_DEV double geodetic_altitude(double x, double y, double z) {
-  double lat, p, ip;
-  geodetic_lat_p(x, y, z, lat, p, ip);
-  double sl, cl;
-  fsincos(lat, &sl, &cl);
-  return geodetic_alt_from(p, sl, cl);
 }
 
 GEL_DEV void geodetic_full(double x, double y, double z, double& lat, double& lon, double& alt) {

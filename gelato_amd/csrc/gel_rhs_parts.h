@@ -15,10 +15,6 @@
 #pragma once
 #include "gel_physics.h"
 
-#ifndef GEL_CALM_SHORTCUT
-#define GEL_CALM_SHORTCUT 1
-#endif
-
 namespace gel {
 
 // depends on position only
@@ -29,22 +25,6 @@ struct PosPart {
   double sl, cl;     // sin, cos of the geodetic latitude (the local north axis of the wind's rotation)
   double inv_p;      // 1 / sqrt(x^2 + y^2)
 };
-
-// Bowring's one-step geodetic latitude (src/Earth.cpp:49-57) delivered as (sin lat, cos lat): the
-// reference forms lat = atan2(zz, pp) and then only ever uses sin/cos of it (and of lat/2), so the pair is
-// taken directly as zz/hypot, pp/hypot -- the same two numbers up to rounding, without the atan2 -> sincos
-// round trip.  Likewise sin/cos(theta) of theta = atan2(z Ra, p Rb).
-GEL_DEV void geodetic_sincos(double x, double y, double z, double& sl, double& cl, double& p) {
-  p = sqrt(x * x + y * y);
-  const double a = z * kRa, b = p * kRb;
-  const double ih = 1.0 / sqrt(a * a + b * b);
-  const double st = a * ih, ct = b * ih;
-  const double zz = z + kEp2 * kRb * (st * st * st);
-  const double pp = p - kE2 * kRa * (ct * ct * ct);
-  const double ihy = 1.0 / sqrt(zz * zz + pp * pp);
-  sl = zz * ihy;
-  cl = pp * ihy;
-}
 
 // What the exact-difference position sweeps (pos_delta) need of the centre evaluation besides PosPart.
 struct PosCentre {
@@ -258,23 +238,14 @@ GEL_DEV EarthAngle earth_angle(double t) {
 // (sqrt(x^2+y^2), z) and therefore the latitude unchanged, so pos_part's (sin lat, cos lat) -- at a sweep's perturbed point
 // pos_delta()'s -- are used as they are.  The roundings are pinned (fresh_mul, explicit fma): every kernel that calls this
 // gets the same bits whatever surrounds the call.
-// GEL_WIND_CHAIN=1 (ablation; needs the Earth angle in every windy lane, so it also turns the fused kernels' on-axis vote
-// back into the any-lane-windy one): the reference's quaternion chain operation by operation (wind_eci_chain()) -- the longitude taken from
-// the rotated position as (cos lon, sin lon) = (px, py)/p, its half-angle pair by the half-angle identities on the branch
-// that has no cancellation (lon/2 in (-pi/2, pi/2], so cos(lon/2) >= 0), ~90 instructions.
-#ifndef GEL_WIND_CHAIN
-#define GEL_WIND_CHAIN 0
-#endif
 // does this lane's wind_eci() read the Earth angle?  (the vote the fused kernels take before they form it)
 GEL_DEV bool wind_needs_angle(double inv_p, double wn, double we) {
   const bool windy = !(wn == 0.0 && we == 0.0);
-#if GEL_WIND_CHAIN
-  return windy;
-#else
   return windy && !(inv_p > 0.0);
-#endif
 }
-// the reference's chain, operation by operation: GEL_WIND_CHAIN, and the t0 / tf sweeps of GEL_FLAG_FD_RECOMPUTE (below)
+// The reference's quaternion chain, operation by operation (wind_eci_chain(): the t0 / tf sweeps of GEL_FLAG_FD_RECOMPUTE, below) --
+// the longitude taken from the rotated position as (cos lon, sin lon) = (px, py)/p, its half-angle pair by the half-angle identities
+// on the branch that has no cancellation (lon/2 in (-pi/2, pi/2], so cos(lon/2) >= 0), ~90 instructions.
 // Half-latitude pair of the NED quaternion (src/Coordinate.cpp:89-90) from (sin lat, cos lat): cos(lat/2) = sqrt((1+cos lat)/2)
 // (cos lat >= 0), sin(lat/2) = sin lat / (2 cos(lat/2)); root and reciprocal root from one iteration.  Only the reference's chain
 // (wind_eci_chain()) and point hook 15 read the pair: the position part carries (sin lat, cos lat) themselves.
@@ -323,9 +294,6 @@ GEL_DEV void wind_eci_chain(const double r[3], const EarthAngle& e, double sl, d
 }
 GEL_DEV void wind_eci(const double r[3], const EarthAngle& e, double sl, double cl, double inv_p, double wn,
                       double we, double w[3]) {
-#if GEL_WIND_CHAIN
-  wind_eci_chain(r, e, sl, cl, inv_p, wn, we, w);
-#else
   const bool off_axis = inv_p > 0.0;
   const double clon = off_axis ? r[0] * inv_p : e.c;
   const double slon = off_axis ? r[1] * inv_p : e.s;
@@ -333,21 +301,17 @@ GEL_DEV void wind_eci(const double r[3], const EarthAngle& e, double sl, double 
   w[0] = __builtin_fma(nh, clon, -fresh_mul(we, slon));
   w[1] = __builtin_fma(nh, slon, fresh_mul(we, clon));
   w[2] = fresh_mul(wn, cl);
-#endif
 }
 
 // wind_eci unless the whole wavefront is in calm air: where both wind components are exactly zero (below / above the
 // measured part of a wind table, as in the shipped example from 23 km up) the rotation of the zero vector is the zero
-// vector, so the call is skipped -- six times per node in the fused kernel (~110 instructions each with the quaternion
-// chain, GEL_WIND_CHAIN; some 20 with the local axes).  Non-finite components are not zero and take the full path.
+// vector, so the call is skipped -- six times per node in the fused kernel (some 20 instructions each).  Non-finite components are not zero and take the full path.
 GEL_DEV void wind_eci_or_calm(const double r[3], const EarthAngle& e, double sl, double cl, double inv_p, double wn,
                               double we, double w[3]) {
-#if GEL_CALM_SHORTCUT
   if (__builtin_amdgcn_ballot_w64(!(wn == 0.0 && we == 0.0)) == 0) {   // wave-uniform branch
     w[0] = 0.0; w[1] = 0.0; w[2] = 0.0;
     return;
   }
-#endif
   wind_eci(r, e, sl, cl, inv_p, wn, we, w);
 }
 // The t0 / tf sweeps of GEL_FLAG_FD_RECOMPUTE (the audit form: what the reference's own sweeps give) move nothing but the Earth
@@ -356,12 +320,10 @@ GEL_DEV void wind_eci_or_calm(const double r[3], const EarthAngle& e, double sl,
 // evaluate the perturbed point with the reference's chain and the perturbed angle, like the reference does.
 GEL_DEV void wind_eci_chain_or_calm(const double r[3], const EarthAngle& e, double sl, double cl, double inv_p, double wn,
                                     double we, double w[3]) {
-#if GEL_CALM_SHORTCUT
   if (__builtin_amdgcn_ballot_w64(!(wn == 0.0 && we == 0.0)) == 0) {   // wave-uniform branch
     w[0] = 0.0; w[1] = 0.0; w[2] = 0.0;
     return;
   }
-#endif
   wind_eci_chain(r, e, sl, cl, inv_p, wn, we, w);
 }
 
@@ -426,7 +388,7 @@ GEL_DEV void quat_rate(const double q[4], double u0, double u1, double unit_u, d
 }
 
 // ---------------------------------------------------------------------------
-// Aero path constraints (lib/con_aero.py, src/wrapper_utils.hpp:89-206): the pieces aero_kernel (gel_kernels.hip) and the
+// Aero path constraints (lib/con_aero.py, src/wrapper_utils.hpp:89-206): the pieces aero_body (gel_aero_body.h) and the
 // aero rows of the fused kernel (gel_eval_kernel.h, AERO instantiation) share -- the same expressions, hence the same bits.
 // ---------------------------------------------------------------------------
 // air-relative velocity in ECI (wrapper_utils.hpp:93-100) and its SQUARED norm (q needs no root; alpha takes the reciprocal root)

@@ -9,10 +9,7 @@
 
 namespace gel {
 
-#ifndef GEL_BLOCK
-#define GEL_BLOCK 256
-#endif
-constexpr int kBlock = GEL_BLOCK;  // threads per workgroup of the fused kernel (a multiple of 64)
+constexpr int kBlock = 256;  // threads per workgroup of the fused kernel (a multiple of 64)
 static_assert(kAtmDoubles == kAtmTableDoubles, "atmosphere table size mismatch between host and device");
 
 GEL_DEV Tables table_view(const double* base, int Kw, int Kc) {

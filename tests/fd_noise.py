@@ -258,7 +258,7 @@ def aero_stated_tolerance(bound, ref):
 
 
 def aero_first_order_truncation(terms, rows, limit, kind, t, dx):
-    """What the engine's entries would move by if its alpha-difference (gel_kernels.hip aero_dalpha: t = t0 (1 - x + 2 x^2 - x^3),
+    """What the engine's entries would move by if its alpha-difference (gel_rhs_parts.h aero_dalpha: t = t0 (1 - x + 2 x^2 - x^3),
     x = cot(alpha_c) t0 / 2) were cut after its first term, t = t0, given the true differences t = alpha_p - alpha_c of every entry
     (from the oracle's alpha rows of the same nodes): the alpha part of an entry -- -t / (dx L) for the alpha kind, -q t / (dx L) for
     the q-alpha kind (q_p = q_c to first order) -- grows by the factor x.  q kind: zero."""

@@ -132,7 +132,7 @@ def vincenty(lat_o, lon_o, lat_t, lon_t, stop="1e-50"):
 
 
 def node_fn(fn, r, v, t, p, stop="1e-50"):
-    """gel_kernels.hip node_fn in exact arithmetic (r, v [SI], t [s], row parameters p as mpf)"""
+    """gel_rows_body.h node_fn in exact arithmetic (r, v [SI], t [s], row parameters p as mpf)"""
     if fn >= 9:
         sn, cs = mp.sin(OMEGA * t), mp.cos(OMEGA * t)
         pe = [r[0] * cs + r[1] * sn, -r[0] * sn + r[1] * cs, r[2]]

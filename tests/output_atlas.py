@@ -1,5 +1,5 @@
 """The output table's atlas: one synthetic problem and one decision vector whose state nodes are placed by hand, one node or
-more for every branch of the post-processing table (output_result.py:37-263; output_kernel in gel_kernels.hip), each carrying tags.
+more for every branch of the post-processing table (output_result.py:37-263; output_kernel in gel_kernels_rows.hip), each carrying tags.
 Plain numpy, no GPU.  tests/golden/make_output_atlas.py turns it into tests/golden/g26_output_atlas.npz (the inputs, the reference's
 own table, a 50-digit truth with its sensitivity scale and the margin of every branch predicate); the tests read that fixture and
 rebuild nothing but the handles.

@@ -1,5 +1,5 @@
 """GPU: the position part carries (sin lat, cos lat) instead of the half-latitude pair, and the fused kernel keeps the centre's 1/T and
-sweep margin in the two park slots the pair used to take (gel_eval_kernel.h GEL_POS_REPARK; AERO: 1/hypot(z Ra, p Rb)).
+sweep margin in the two park slots the pair used to take (gel_eval_kernel.h, the park slots LV0 / LV1; AERO: 1/hypot(z Ra, p Rb)).
 
   1  parked equals re-derived: point hook 16 chains one centre and the three sweeps as the fused kernel does -- 1/T and the margin taken
      once (pos_centre_tail), each sweep re-deriving only the wind slopes and the centre's wind (pos_centre_tail_kept) -- and must give

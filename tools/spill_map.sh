@@ -1,13 +1,15 @@
 #!/bin/bash
-# (here, no GPU) Where does an instantiation of the fused kernel spill?  Compiles gel_kernels.hip with line tables and lists every
-# scratch_load / scratch_store of the chosen kernel with the source line it belongs to.
+# (here, no GPU) Where does an instantiation of the fused kernel spill?  Compiles a unit (UNIT=gel_kernels_aero; default gel_kernels)
+# with the Makefile's flags for it plus line tables and lists every scratch_load / scratch_store of the chosen kernel with the
+# source line it belongs to.
 # usage: tools/spill_map.sh <mangled-name prefix> [extra -D flags]     e.g. _ZN3gel11eval_kernelILb1ELb1ELb0ELb0ELb1ELb1ELb1E
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 K="$1"; shift
+U="${UNIT:-gel_kernels}"
+CC=$(make -s -C "$ROOT/gelato_amd/csrc" print-flags TU=$U | sed 's/ -c -o .*//')
 D=$(mktemp -d /tmp/spillmap.XXXXXX)
-( cd "$D" && /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -fno-fast-math -ffp-contract=on -mllvm -disable-machine-licm \
-    -mllvm -amdgpu-sched-strategy=max-ilp -gline-tables-only -save-temps "$@" -c "$ROOT/gelato_amd/csrc/gel_kernels.hip" -o k.o 2>/dev/null )
-python3 - "$D/gel_kernels-hip-amdgcn-amd-amdhsa-gfx950.s" "$K" <<'EOF'
+( cd "$D" && $CC -gline-tables-only -save-temps "$@" -c "$ROOT/gelato_amd/csrc/$U.hip" -o k.o 2>/dev/null )
+python3 - "$D/$U-hip-amdgcn-amd-amdhsa-gfx950.s" "$K" <<'EOF'
 import re, sys
 lines = open(sys.argv[1]).read().split('\n')
 start = [i for i, l in enumerate(lines) if l.startswith(sys.argv[2])][0]
